@@ -4,6 +4,7 @@
     python bench.py --gpus 1 --steps 8 --warmup 2
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus 1 --steps 8 --warmup 2 --dump-outputs DIR
 
 Primary metric (BASELINE.json configs[1]): denoise-steps/sec of the production 256x256x27 tri-plane UNet
 (497M params) inside the 1000-step DDPM p_sample loop at batch 4 per GPU.  A "step" is one p_sample call:
@@ -13,6 +14,13 @@ Secondary metric (configs[2]) in the "render" object: Mrays/sec of the tri-plane
 only collective is the final all-gather of samples and images (north star), inside the timed region.
 "fit" object (not a BASELINE metric): tri-plane fitting iterations/sec at the reference's training
 configuration (2 subjects x 2048 rays x 128+128 samples; forward, HIP backward, Adam).
+
+`--steps K` is the number of timed steps (the loop starts again from x_T if warm-up + K outgrow its 1000 steps); `ms_per_step` in
+the line is the milliseconds one of them took.  `--dump-outputs DIR` writes what the last timed step handed its caller - the dict
+p_sample_loop_progressive yields: `sample` (x_{t-1}) and `pred_xstart`, B x 27 x 256 x 256 each, plus `sample_all_ranks` (the final
+gather) when N > 1 - as DIR/<name>.npy in float32, rank 0 only.  The inputs are seeded (weights, x_T, the device generator that draws
+the per-step noise), so two runs with the same arguments, e.g. of two builds, can be compared array for array.  Above 64 MB in all,
+every array is cut to the same fixed, seeded sample of its flattened elements.
 
 Prints ONE JSON line on rank 0.  `roofline` is measured live with HIP events (per-kernel-category events
 inside hl_unet_forward for the conv kernels; torch events around the stage launches for the ray-march
@@ -33,12 +41,33 @@ from bench_legs import *          # noqa: E402,F401,F403  (the legs; tests and s
 from bench_legs import UNET_GFLOP_PER_SAMPLE_STEP, dist_setup, bench_unet, collective_probe, e2e_chain, ddim50_parity, cpu_baseline_unet, e2e_slice, bench_train, \
     bench_render, bench_fit, cpu_baseline_render, cpu_baseline_fit   # noqa: E402
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(arrays, out_dir, budget=DUMP_BUDGET_BYTES, seed=0):
+    """Write every tensor of `arrays` as out_dir/<name>.npy (float64 stays float64, everything else becomes float32).  If they come to
+    more than `budget` bytes, each one is replaced by a fixed, seeded sample of its flattened elements (ascending positions), sized
+    in proportion so that the files stay within the budget."""
+    import numpy as np
+    arrays = {k: (v.detach().cpu() if v.dtype == torch.float64 else v.detach().cpu().float()) for k, v in arrays.items()}
+    total = sum(v.numel() * v.element_size() for v in arrays.values())
+    room = budget - 4096 * len(arrays)          # .npy headers
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in arrays.items():
+        if total > room:
+            keep = v.numel() * room // total
+            pick = torch.randperm(v.numel(), generator=torch.Generator().manual_seed(seed))[:keep].sort().values
+            v = v.reshape(-1)[pick]
+        np.save(os.path.join(out_dir, name + ".npy"), v.contiguous().numpy())
+
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=8)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (sample, pred_xstart) as DIR/<name>.npy, float32, at most 64 MB in all")
     ap.add_argument("--batch", type=int, default=4, help="subjects per GPU in the denoise loop (configs[1]: 4)")
     ap.add_argument("--views", type=int, default=36, help="512x512 views per GPU in the render leg (configs[2]: the whole 36-view orbit)")
     ap.add_argument("--sustained-steps", type=int, default=200,
@@ -60,6 +89,8 @@ def main():
                     help="issue the control encoder on the caller's stream instead of the side stream (used for the "
                          "per-kernel rocprof trace: concurrent kernels stretch each other's durations)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: become one - one rank per GPU under torch.distributed.run on this node (RCCL over
         # xGMI), same arguments; the ranks' output (rank 0 prints the JSON line) passes straight through.
@@ -80,7 +111,11 @@ def main():
     assert world == args.gpus, f"--gpus {args.gpus} but WORLD_SIZE={world}: launch with torch.distributed.run"
     dev = torch.device("cuda", local)
 
-    secs, roof, sd, model = bench_unet(args, rank, world, dev)
+    torch.cuda.manual_seed(1234)     # the device generator draws every step's noise: same arguments, same inputs, same outputs
+    secs, roof, sd, model, last = bench_unet(args, rank, world, dev)
+    if rank == 0 and last is not None:
+        dump_outputs(last, args.dump_outputs)
+    del last
     value = world * args.batch * args.steps / secs
     rccl = collective_probe(args, rank, world, dev) if world > 1 else None
     parity = None

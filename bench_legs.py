@@ -136,8 +136,12 @@ def bench_unet(args, rank, world, dev):
     x_T = torch.randn((B, 27, 256, 256), generator=g).to(dev)
     x_cond = torch.zeros((B, 27, 256, 256), device=dev)          # layer 0: zeros (triplane_sample_layered.py:124-129)
     y = torch.zeros((B,), dtype=torch.int64, device=dev)
-    it = diffusion.p_sample_loop_progressive(model, (B, 27, 256, 256), x_cond=x_cond, noise=x_T, clip_denoised=True,
-                                             model_kwargs={"y": y}, device=dev)
+
+    def loop():   # the 1000-step loop, started again from x_T when it ends: any --warmup + --steps (+ the legs below) fits
+        while True:
+            yield from diffusion.p_sample_loop_progressive(model, (B, 27, 256, 256), x_cond=x_cond, noise=x_T, clip_denoised=True,
+                                                           model_kwargs={"y": y}, device=dev)
+    it = loop()
     out = next(it)   # first step binds the state_dict (hl_unet_create) and sizes the workspace
     if args.no_overlap:
         _lib.check(_lib.lib().hl_unet_set_overlap(model._hip[0], 0))
@@ -154,6 +158,12 @@ def bench_unet(args, rank, world, dev):
     barrier(world)
     secs = max_over_ranks(time.perf_counter() - t0, world, dev)
     assert torch.isfinite(out["sample"]).all()
+    # what the last timed step handed its caller (bench.py --dump-outputs), copied to the host before any later step runs
+    last = None
+    if getattr(args, "dump_outputs", None):
+        last = {k: v.detach().cpu() for k, v in out.items()}
+        if world > 1:
+            last["sample_all_ranks"] = gathered.cpu()
     # ---- roofline leg: one more step with per-launch HIP events inside hl_unet_forward ----
     L = _lib.lib()
     handle = model._hip[0]
@@ -310,7 +320,7 @@ def bench_unet(args, rank, world, dev):
             "value": round(B * k3 / s3, 3), "unit": "denoise-steps/s", "steps": k3, "ms_per_step": round(s3 * 1e3 / k3, 3),
             "psnr_db_forward_vs_fp32": round(psnr(alt, ref), 1), "max_abs_diff_vs_fp32_forward": float((alt - ref).abs().max()),
             "psnr_db_ddim50_sample_vs_fp32": round(psnr(alt50, ref50), 1), "max_abs_diff_ddim50_sample": float((alt50 - ref50).abs().max())}
-    return secs, roof, sd, model
+    return secs, roof, sd, model, last
 
 
 def collective_probe(args, rank, world, dev, iters=3):

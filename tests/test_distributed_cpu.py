@@ -95,6 +95,66 @@ def test_world_size_2_gloo():
         assert all(oks), (rank, oks)
 
 
+def _worker8(rank, world, port, q):
+    """BASELINE configs[3] / [4] partitioning with stand-ins: 64 subjects, 8 per rank sampled as one batch of 8 per layer."""
+    os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1",
+                      MASTER_PORT=str(port))
+    import torch.distributed as dist
+    from humanliff_amd import distributed as hd
+    r, w, dev = hd.init_distributed("gloo")
+    assert (r, w) == (rank, world) and dev.type == "cpu"
+    nsub, n_layers, n_views, batch = 64, 2, 2, 8
+    calls, rendered = [], []
+
+    def sample_fn(x_cond, layer, ids):
+        calls.append((layer, tuple(ids)))
+        base = torch.tensor(ids, dtype=torch.float32).view(-1, 1, 1, 1)
+        return x_cond * 2 + base + layer
+
+    def render_fn(sid, sample, v):
+        rendered.append((sid, v))
+        return torch.full((2, 2, 3), (sid * 2 + v) / 200.0) + sample[:1, :2, :2].permute(1, 2, 0) * 0
+
+    smp, img = hd.sample_and_render(sample_fn, render_fn, nsub, n_layers, (2, 4, 4), batch, n_views, (2, 2, 3), dev, as_uint8=True,
+                                    images_root=0)
+    want = torch.empty(nsub, n_layers, 2, 4, 4)
+    for s in range(nsub):
+        x = torch.zeros(2, 4, 4)
+        for k in range(n_layers):
+            x = x * 2 + s + k
+            want[s, k] = x
+    block = list(range(rank * 8, rank * 8 + 8))
+    ok1 = calls == [(k, tuple(block)) for k in range(n_layers)]                     # one batch of 8 per layer, this rank's block only
+    ok2 = sorted(rendered) == [(s, v) for s in block for v in range(n_views)]        # the views of this rank's 8 subjects, nothing else
+    ok3 = torch.equal(smp, want)                                                     # every rank holds all samples in subject order
+    want_img = torch.tensor([[int(((s * 2 + v) / 200.0) * 255.0) for v in range(n_views)] for s in range(nsub)], dtype=torch.uint8)
+    ok4 = (img is None) if rank != 0 else (tuple(img.shape) == (nsub, n_views, 2, 2, 3) and img.dtype == torch.uint8 and
+                                            torch.equal(img[:, :, 0, 0, 0], want_img))
+    dist.barrier()
+    dist.destroy_process_group()
+    q.put((rank, ok1, ok2, ok3, ok4))
+
+
+@pytest.mark.timeout(300)
+def test_eight_ranks_sixty_four_subjects_gloo():
+    """The partitioning of BASELINE configs[3] / [4] - 64 subjects over 8 ranks - through humanliff_amd.distributed.sample_and_render with
+    arithmetic stand-ins for the network and the renderer: block sharding, call pattern, gathered order and root-only image assembly.
+    (The HIP path runs the same flow with four ranks on one GPU: tests/test_distributed_gpu.py.)"""
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    ps = [ctx.Process(target=_worker8, args=(r, 8, port, q)) for r in range(8)]
+    for p in ps:
+        p.start()
+    res = [q.get(timeout=250) for _ in ps]
+    for p in ps:
+        p.join(30)
+        assert p.exitcode == 0
+    assert sorted(r for r, *_ in res) == list(range(8))
+    for rank, *oks in res:
+        assert all(oks), (rank, oks)
+
+
 def test_single_process_paths():
     from humanliff_amd import distributed as hd
     idx, valid = hd.shard_indices(3, rank=0, world=1)

@@ -226,3 +226,28 @@ def test_bench_line_is_compact():
     ws = json.dumps(w)
     assert len(ws) < bench_line.MAX_LINE_BYTES and json.loads(ws) == w and "NaN" not in ws
     assert w["rccl"]["backend"] == "nccl" and w["rccl"]["image_gather_uint8_recv_gb_per_s_per_rank"] == 301.5
+
+
+def test_bench_dump_outputs_budget_and_sample(tmp_path):
+    """bench.py --dump-outputs: every array as <name>.npy in float32 (float64 kept); within the budget the arrays are written whole, above
+    it each one becomes the same seeded sample of its elements, so two runs (two builds) stay comparable array for array."""
+    import bench
+    g = torch.Generator().manual_seed(3)
+    arrays = {"sample": torch.randn((4, 3, 16, 16), generator=g), "pred_xstart": torch.randn((4, 3, 16, 16), generator=g).double(),
+              "half": torch.randn((2, 8), generator=g).half()}
+    bench.dump_outputs(arrays, str(tmp_path / "whole"))
+    for k, v in arrays.items():
+        a = np.load(tmp_path / "whole" / f"{k}.npy")
+        assert a.dtype == (np.float64 if v.dtype == torch.float64 else np.float32) and a.shape == tuple(v.shape)
+        assert np.array_equal(a, v.double().numpy() if v.dtype == torch.float64 else v.float().numpy())
+    budget = 4096 * 3 + 8000
+    for d in ("cut_a", "cut_b"):
+        bench.dump_outputs(arrays, str(tmp_path / d), budget=budget)
+    total = 0
+    for k, v in arrays.items():
+        a, b = np.load(tmp_path / "cut_a" / f"{k}.npy"), np.load(tmp_path / "cut_b" / f"{k}.npy")
+        assert a.ndim == 1 and 0 < a.size < v.numel() and np.array_equal(a, b)
+        flat = (v.double() if v.dtype == torch.float64 else v.float()).reshape(-1).numpy()
+        assert np.isin(a, flat).all()
+        total += os.path.getsize(tmp_path / "cut_a" / f"{k}.npy")
+    assert total <= budget
