@@ -12,6 +12,7 @@ PyTorch fallback (a missing library or a CPU tensor raises).
 """
 import ctypes as C
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -460,9 +461,14 @@ class Renderer(nn.Module):
             out[i:j] = untile_rows(tmp, j - i, N)
         return (-out).reshape(N, N, N)
 
-    def extract_geometry(self, tp_input, tri_planes=None, resolution=512, threshold=0.0):
-        """Reference signature (renderer.py:290).  The density field comes from the HIP kernel; smoothing and
-        marching cubes stay on the CPU in PyMCubes, as in the reference (an external dependency, not rebuilt)."""
+    def extract_geometry(self, tp_input, tri_planes=None, resolution=512, threshold=0.0, mesher=None):
+        """Reference signature (renderer.py:290).  The density field comes from the HIP kernel.  mesher=None: smoothing and
+        marching cubes on the CPU in PyMCubes, as in the reference (an external dependency, not rebuilt).  mesher="hip": both on
+        the device (NeRF/geometry.py, DESIGN.md "Mesh extraction"); a field without a sign change gives empty (0,3) arrays."""
+        if mesher == "hip":
+            return self._extract_geometry_hip(tp_input, tri_planes, resolution, threshold)
+        if mesher is not None:
+            raise ValueError(f"extract_geometry: mesher must be None (PyMCubes) or 'hip', got {mesher!r}")
         try:
             import mcubes
         except ImportError as e:
@@ -473,6 +479,21 @@ class Renderer(nn.Module):
         b = tp_input['world_bounds'].reshape(-1, 2, 3)[0].detach().cpu().numpy()
         vertices = vertices / (resolution - 1.0) * (b[1] - b[0])[None, :] + b[0][None, :]
         return vertices, triangles
+
+    def _extract_geometry_hip(self, tp_input, tri_planes, resolution, threshold):
+        from . import geometry
+        u = Renderer.density_grid(self, tp_input, tri_planes, resolution)      # (this class's: the recon twin overrides it without tri_planes)
+        try:
+            field = geometry.smooth(u)
+        except geometry.NoSignChange:        # nothing to mesh
+            return np.zeros((0, 3), dtype=np.float64), np.zeros((0, 3), dtype=np.int64)
+        del u
+        verts, tris = geometry.marching_cubes(field, threshold)
+        del field
+        b = tp_input['world_bounds'].reshape(-1, 2, 3)[0].detach().to(verts.device)
+        ext, lo = (b[1] - b[0]).double(), b[0].double()      # (the reference's numpy expression: extent in the bounds' dtype, then fp64)
+        verts = verts / (resolution - 1.0) * ext[None, :] + lo[None, :]
+        return verts.cpu().numpy(), tris.cpu().numpy()
 
 
 def render(chunk=1024 * 32, rays_o=None, rays_d=None, near=0., far=1., tri_planes=None, tp_input=None, renderer=None,

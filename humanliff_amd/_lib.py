@@ -133,6 +133,17 @@ SIGNATURES = {
     "hl_debug_set_h16_min_blocks": (_i, [C.c_long]),
     "hl_debug_set_single_op_scale_source": (_i, [_i]),
     "hl_debug_set_mt19937_piece": (_i, [C.c_int64]),
+    "hl_smooth_workspace_bytes": (_sz, [_i, _i, _i]),
+    "hl_smooth_prepare": (_i, [_p, _i, _i, _i, _i, C.c_double, _p, _p, _p, _sz, _p]),
+    "hl_smooth_band": (_i, [_p, _i, _i, _i, C.c_double, _i64, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "hl_smooth_sweep_scratch_bytes": (_sz, [_i64]),
+    "hl_smooth_sweeps": (_i, [_p, _p, _p, _i64, _i, _p, _p, _p, _sz, _p]),
+    "hl_smooth_scatter": (_i, [_p, _p, _i64, _p, _p]),
+    "hl_mc_workspace_bytes": (_sz, [_i, _i, _i]),
+    "hl_mc_count": (_i, [_p, _i, _i, _i, C.c_double, _p, _p, _sz, _p]),
+    "hl_mc_emit": (_i, [_p, _i, _i, _i, C.c_double, _p, _p, _p, _sz, _p]),
+    "hl_mc_max_triangles": (_i, []),
+    "hl_mc_case_table": (_i, [_p, _p]),
 }
 
 

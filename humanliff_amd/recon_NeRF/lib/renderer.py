@@ -36,6 +36,7 @@ class Renderer(_Renderer):
     def density_grid(self, tp_input, resolution=512, **kw):
         return super().density_grid(tp_input, self._own_planes(tp_input)[:1], resolution, **kw)
 
-    def extract_geometry(self, tp_input, resolution, threshold=0.0):
-        """recon_NeRF/lib/renderer.py:304 (no tri_planes argument: the module's own, first subject of the batch)."""
-        return super().extract_geometry(tp_input, self._own_planes(tp_input)[:1], resolution, threshold)
+    def extract_geometry(self, tp_input, resolution, threshold=0.0, mesher=None):
+        """recon_NeRF/lib/renderer.py:304 (no tri_planes argument: the module's own, first subject of the batch); `mesher` as in
+        NeRF.Renderer.extract_geometry."""
+        return super().extract_geometry(tp_input, self._own_planes(tp_input)[:1], resolution, threshold, mesher=mesher)

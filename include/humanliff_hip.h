@@ -539,6 +539,38 @@ int hl_mt19937_uniform(const uint32_t *state, int pos, float *out, int64_t n, ui
  * range; longer requests continue from the state the piece before left).  words <= 0 restores the default.  The unit tests run the chaining with small pieces. */
 int hl_debug_set_mt19937_piece(int64_t words);
 
+/* ---- mesh extraction (mcubes.smooth + mcubes.marching_cubes behind extract_geometry, NeRF/renderer.py:290-321) ----------
+ * Contract: DESIGN.md "Mesh extraction".  Volumes are (nx, ny, nz) C order (x slowest) with nx*ny*nz*5 < 2^31.  The host reads
+ * the device `counts` between the phases to size the next buffers; every reduction is integer or fixed-order (bit-reproducible).
+ *
+ * Constrained smoothing (Lempitsky 2010 as PyMCubes' smooth_constrained):
+ *   hl_smooth_prepare: binarize vol > 0 (fp32, or fp64 if is_fp64), exact signed distance d (edt(b) - 0.5 on b, -edt(~b) + 0.5
+ *     off b) into d_out (fp64 volume); counts[0] = band size (|d| <= band_radius), counts[1] = voxels with vol > 0.
+ *   hl_smooth_band (ws as left by hl_smooth_prepare): the nb band variables - lin (int32 voxel index), nbr (int32 6 x nb: slot of
+ *     the -x, +x, -y, +y, -z, +z band neighbour or -1), start value x = d, bounds lower / upper.
+ *   hl_smooth_sweeps: n_sweeps damped (w = 1/2) projected Jacobi sweeps on A = Q^T Q in place on x, then (energy != NULL)
+ *     energy[0] = x^T A x / 2 of the result; n_sweeps = 0 gives the energy alone.
+ *   hl_smooth_scatter: out[lin[s]] = x[s]. */
+size_t hl_smooth_workspace_bytes(int nx, int ny, int nz);
+int hl_smooth_prepare(const void *vol, int is_fp64, int nx, int ny, int nz, double band_radius, double *d_out, int64_t *counts,
+                      void *ws, size_t ws_bytes, void *stream);
+int hl_smooth_band(const double *d, int nx, int ny, int nz, double band_radius, int64_t nb, int32_t *lin, int32_t *nbr, double *x,
+                   double *lower, double *upper, void *ws, size_t ws_bytes, void *stream);
+size_t hl_smooth_sweep_scratch_bytes(int64_t nb);
+int hl_smooth_sweeps(const int32_t *nbr, const double *lower, const double *upper, int64_t nb, int n_sweeps, double *x, double *energy,
+                     void *scratch, size_t scratch_bytes, void *stream);
+int hl_smooth_scatter(const double *x, const int32_t *lin, int64_t nb, double *out, void *stream);
+/* Marching cubes at `iso` on an fp64 volume (corner above when value > iso):
+ *   hl_mc_count: classify every voxel and scan; counts[0] = vertices V, counts[1] = triangles T.
+ *   hl_mc_emit (ws as left by hl_mc_count): verts fp64 (V,3) in index coordinates, ordered by edge key
+ *     ((i*ny + j)*nz + k)*3 + axis; tris int64 (T,3), by cube then case-table order, normals toward the above side.
+ *   hl_mc_case_table: host copy of the baked table, h_tris 256 x hl_mc_max_triangles() x 3 cube edges (-1 padded), h_ntri 256. */
+size_t hl_mc_workspace_bytes(int nx, int ny, int nz);
+int hl_mc_count(const double *vol, int nx, int ny, int nz, double iso, int64_t *counts, void *ws, size_t ws_bytes, void *stream);
+int hl_mc_emit(const double *vol, int nx, int ny, int nz, double iso, double *verts, int64_t *tris, void *ws, size_t ws_bytes, void *stream);
+int hl_mc_max_triangles(void);
+int hl_mc_case_table(int8_t *h_tris, uint8_t *h_ntri);
+
 #ifdef __cplusplus
 }
 #endif

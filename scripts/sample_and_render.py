@@ -28,6 +28,9 @@ def main():
     ap.add_argument("--res", type=int, default=256)
     ap.add_argument("--batch", type=int, default=4, help="subjects sampled together on one GPU")
     ap.add_argument("--float-images", action="store_true", help="gather fp32 images instead of uint8")
+    ap.add_argument("--meshes", help="write one PLY mesh per subject and layer here (extract_geometry, mesher='hip'; "
+                                     "triplane_sample_layered.py:201-207)")
+    ap.add_argument("--mesh-res", type=int, default=512, help="density lattice resolution of the meshes (the reference's 512)")
     args = ap.parse_args()
     rank, world, dev = hd.init_distributed()
     cfg = dict(bench.F4, timestep_respacing=f"ddim{args.ddim}")
@@ -69,6 +72,16 @@ def main():
         print(f"ranks {world}: {args.subjects} subjects x {args.layers} layers x DDIM-{args.ddim} ({steps} denoise steps) + "
               f"{args.subjects * args.views} views {H}x{W} ({rays / 1e6:.1f} Mrays) + gathers in {t2 - t0:.2f} s; "
               f"samples {tuple(samples.shape)} images {tuple(images.shape)} {images.dtype} mean {float(images.float().mean()):.4f}")
+        if args.meshes:
+            from humanliff_amd.NeRF.geometry import write_ply
+            os.makedirs(args.meshes, exist_ok=True)
+            for sid in range(args.subjects):
+                for layer in range(args.layers):
+                    planes = samples[sid, layer].to(dev).clamp(-1, 1).reshape(1, 3, 9, 256, 256)
+                    v, t = r.extract_geometry(tp, planes, resolution=args.mesh_res, threshold=0, mesher="hip")
+                    path = os.path.join(args.meshes, f"subject{sid:03d}_layer{layer}.ply")
+                    write_ply(path, v, t)
+                    print(f"{path}: {len(v)} vertices, {len(t)} triangles")
 
 
 if __name__ == "__main__":
