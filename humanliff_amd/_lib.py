@@ -108,6 +108,11 @@ SIGNATURES = {
     "hl_unet_dispatch_census_ex": (_i, [_p, _p, _i]),
     "hl_unet_profile_dominant": (_i, [_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     "hl_diffusion_step": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _i64, _i, _i, _i, _p, _p]),
+    "hl_diffusion_q_sample": (_i, [_p, _p, _p, _p, _p, _i64, _i, _i, _p]),
+    "hl_diffusion_reverse_step": (_i, [_i, _p, _p, _p, _p, _p, _p, _i64, _i, _i, _i, _p]),
+    "hl_diffusion_vb_scratch_bytes": (_sz, [_i64, _i]),
+    "hl_diffusion_vb_terms": (_i, [_i, _i, _i, _p, _p, _p, _p, _p, _i64, _p, _p, _i64, _i, _i, _p, _p, _p, _i64, _i64, _p, _sz, _p]),
+    "hl_diffusion_prior_bpd": (_i, [_p, _p, _i64, _i, _i, _p, _p, _sz, _p]),
     "hl_conv2d_nhwc": (_i, [_p, _i, _i, _i, _i, _p, _p, _i, _i, _i, _i, _p, _p, _i, _p, _p, _p, _sz, _p]),
     "hl_conv2d_nhwc_mode": (_i, [_i, _p, _i, _i, _i, _i, _p, _p, _i, _i, _i, _i, _p, _p, _i, _p, _p, _p, _sz, _p]),
     "hl_conv2d_nhwc_gn": (_i, [_i, _p, _i, _i, _i, _i, _p, _p, _i, _i, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p, _p, C.POINTER(C.c_int), _p, _sz, _p]),

@@ -13,6 +13,7 @@ Sampling covers EPSILON and START_X prediction with fixed (FIXED_LARGE - the shi
 same fused kernel.  training_losses covers every LossType of the reference (MSE / RESCALED_MSE incl. the hybrid variational-bound term of
 learned variances, KL / RESCALED_KL) as differentiable tensor algebra around the model call.
 """
+import ctypes as C
 import enum
 import math
 
@@ -126,6 +127,10 @@ class GaussianDiffusion:
             return hit
         f32 = lambda a: th.from_numpy(np.asarray(a)).float()  # noqa: E731  (fp64 -> fp32 like _extract_into_tensor)
         T = self.num_timesteps
+        if kind == "eval":
+            hit = self._eval_table(f32).to(device)
+            self._tables[key] = hit
+            return hit
         tab = th.zeros((T, 8), dtype=th.float32)
         tab[:, 0] = f32(self.sqrt_recip_alphas_cumprod)
         tab[:, 1] = f32(self.sqrt_recipm1_alphas_cumprod)
@@ -145,6 +150,27 @@ class GaussianDiffusion:
         hit = tab.to(device)
         self._tables[key] = hit
         return hit
+
+    def _eval_table(self, f32):
+        """(T,16) fp32 table of the evaluation kernels (column layout in include/humanliff_hip.h, hl_diffusion_q_sample)."""
+        tab = th.zeros((self.num_timesteps, 16), dtype=th.float32)
+        tab[:, 0] = f32(self.sqrt_recip_alphas_cumprod)
+        tab[:, 1] = f32(self.sqrt_recipm1_alphas_cumprod)
+        tab[:, 2] = f32(self.posterior_mean_coef1)
+        tab[:, 3] = f32(self.posterior_mean_coef2)
+        tab[:, 4] = f32(1.0 / self.posterior_mean_coef1)
+        tab[:, 5] = f32(self.posterior_mean_coef2 / self.posterior_mean_coef1)
+        tab[:, 6] = f32(self.posterior_log_variance_clipped)
+        tab[:, 7] = f32(np.log(self.betas))
+        if self.model_var_type in (ModelVarType.FIXED_LARGE, ModelVarType.FIXED_SMALL):
+            tab[:, 8] = f32(self._fixed_variance()[1])
+        tab[:, 9] = f32(self.sqrt_alphas_cumprod)
+        tab[:, 10] = f32(self.sqrt_one_minus_alphas_cumprod)
+        abn = f32(self.alphas_cumprod_next)                                   # th.sqrt of the fp32 cast, like ddim_reverse_sample (:562-565)
+        tab[:, 11] = th.sqrt(abn)
+        tab[:, 12] = th.sqrt(1 - abn)
+        tab[:, 13] = f32(self.log_one_minus_alphas_cumprod)
+        return tab
 
     def _step(self, mode, x, eps, noise, t, clip, eta=0.0, want_x0=True, x0_given=False, logvar=None, xprev_given=False):
         if not x.is_cuda:
@@ -437,3 +463,146 @@ class GaussianDiffusion:
         terms["mse"] = mean_flat((target - out) ** 2)
         terms["loss"] = terms["mse"] + terms["vb"] if "vb" in terms else terms["mse"]
         return terms
+
+    # ---- DDIM inversion and the variational bound in bits per dimension (fused HIP kernels, hl_diffusion_eval.hip) -----------------------
+    # The reference's ddim_reverse_sample / _vb_terms_bpd call the model WITHOUT a condition (:545-552, 668-670).  Here `x_cond` is a
+    # keyword-only extension of ddim_reverse_sample and calc_bpd_loop: the default None keeps the reference's call, a controlnet model
+    # (which needs its condition, unet.py) gets it through x_cond.  The bodies run under no_grad (calc_bpd_loop's model call does in the
+    # reference too), so the UNet takes its inference kernels; there is no CPU path.
+    def _raw_model_out(self, model, x, t, x_cond, model_kwargs):
+        """The model call -> (mean-type half, variance half or None), both views into one contiguous fp32 output."""
+        B, Cc = x.shape[:2]
+        assert t.shape == (B,)
+        out = model(x, self._scale_timesteps(t), x_cond, **(model_kwargs or {}))
+        out = out.to(th.float32).contiguous()
+        if self.model_var_type in (ModelVarType.LEARNED, ModelVarType.LEARNED_RANGE):
+            assert out.shape == (B, Cc * 2, *x.shape[2:])
+            return out, True
+        assert out.shape == x.shape
+        return out, False
+
+    def _reverse(self, model, x, t, x_cond, clip_denoised, denoised_fn, model_kwargs):
+        out, learned = self._raw_model_out(model, x, t, x_cond, model_kwargs)
+        B, Cc = x.shape[:2]
+        if learned:
+            out = out[:, :Cc]
+        if self.model_mean_type == ModelMeanType.EPSILON and denoised_fn is None:
+            mode, arg, clip = 0, out, clip_denoised
+        else:
+            # START_X / PREVIOUS_X / a denoised_fn: the processed pred_xstart (process_xstart, :293-304) goes in as x0
+            if self.model_mean_type == ModelMeanType.START_X:
+                x0 = out
+            elif self.model_mean_type == ModelMeanType.PREVIOUS_X:
+                x0 = self._predict_xstart_from_xprev(x, t, out)
+            else:
+                x0 = self._predict_xstart_from_eps(x, t, out)
+            if denoised_fn is not None:
+                x0 = denoised_fn(x0)
+            if clip_denoised:
+                x0 = x0.clamp(-1, 1)
+            mode, arg, clip = 1, x0, False
+        xf = x.to(th.float32).contiguous()
+        af = arg.to(th.float32).contiguous()
+        sample, x0 = th.empty_like(xf), th.empty_like(xf)
+        tab = self._table("eval", x.device)
+        tt = t.to(device=x.device, dtype=th.int64).contiguous()
+        with _lib.on(x.device):
+            _lib.check(_lib.lib().hl_diffusion_reverse_step(mode, _lib.ptr(xf), _lib.ptr(af), _lib.ptr(tab), _lib.ptr(tt), _lib.ptr(sample),
+                                                            _lib.ptr(x0), xf.numel() // B, B, self.num_timesteps, 1 if clip else 0,
+                                                            _lib.stream_ptr()), "hl_diffusion_reverse_step")
+        return {"sample": sample, "pred_xstart": x0}
+
+    def ddim_reverse_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None, eta=0.0, *, x_cond=None):
+        """x_t -> x_{t+1} along the deterministic DDIM ODE (:531-567): one model call and one fused kernel."""
+        assert eta == 0.0, "Reverse ODE only for deterministic path"
+        if not x.is_cuda:
+            raise RuntimeError("ddim_reverse_sample needs CUDA(HIP) tensors; there is no CPU path")
+        self._check_timesteps(t)
+        with th.no_grad():
+            return self._reverse(model, x, t, x_cond, clip_denoised, denoised_fn, model_kwargs)
+
+    def ddim_reverse_sample_loop_progressive(self, model, x_start, *, x_cond=None, clip_denoised=True, denoised_fn=None, model_kwargs=None,
+                                             device=None, progress=False):
+        """ddim_reverse_sample for t = 0 ... T-1: yields ddim_sample's dict after every step; the last sample is the x_T that
+        ddim_sample_loop maps back onto x_start.  (The reference has the step only; this is that step in ascending order.)"""
+        img = x_start if device is None else x_start.to(device)
+        if not img.is_cuda:
+            raise RuntimeError("ddim_reverse_sample_loop needs CUDA(HIP) tensors; there is no CPU path")
+        T, B = self.num_timesteps, img.shape[0]
+        t_all = th.arange(T, device=img.device, dtype=th.int64)[:, None].expand(T, B).contiguous()
+        model = self._loop_model(model)
+        order = range(T)
+        if progress:
+            from tqdm.auto import tqdm
+            order = tqdm(order)
+        for i in order:
+            with th.no_grad():
+                out = self._reverse(model, img, t_all[i], x_cond, clip_denoised, denoised_fn, model_kwargs)
+            yield out
+            img = out["sample"]
+
+    def ddim_reverse_sample_loop(self, model, x_start, *, x_cond=None, clip_denoised=True, denoised_fn=None, model_kwargs=None,
+                                 device=None, progress=False):
+        final = None
+        for final in self.ddim_reverse_sample_loop_progressive(model, x_start, x_cond=x_cond, clip_denoised=clip_denoised,
+                                                               denoised_fn=denoised_fn, model_kwargs=model_kwargs, device=device,
+                                                               progress=progress):
+            pass
+        return final["sample"]
+
+    def _eval_scratch(self, x):
+        B = x.shape[0]
+        nbytes = _lib.lib().hl_diffusion_vb_scratch_bytes(x.numel() // B, B)
+        return th.empty(((nbytes + 7) // 8,), dtype=th.float64, device=x.device), nbytes
+
+    def _prior_bpd(self, x_start):
+        """KL(q(x_T | x_0) || N(0, 1)) in bits per dimension, per sample (:774-790); one fused reduction."""
+        if not x_start.is_cuda:
+            raise RuntimeError("_prior_bpd needs CUDA(HIP) tensors; there is no CPU path")
+        xs = x_start.to(th.float32).contiguous()
+        B = xs.shape[0]
+        out = th.empty((B,), dtype=th.float32, device=xs.device)
+        scratch, nbytes = self._eval_scratch(xs)
+        tab = self._table("eval", xs.device)
+        with _lib.on(xs.device):
+            _lib.check(_lib.lib().hl_diffusion_prior_bpd(_lib.ptr(xs), _lib.ptr(tab), xs.numel() // B, B, self.num_timesteps, _lib.ptr(out),
+                                                         _lib.ptr(scratch, th.float64), nbytes, _lib.stream_ptr()), "hl_diffusion_prior_bpd")
+        return out
+
+    _MEAN_CODE = {ModelMeanType.EPSILON: 0, ModelMeanType.START_X: 1, ModelMeanType.PREVIOUS_X: 2}
+    _VAR_CODE = {ModelVarType.FIXED_LARGE: 0, ModelVarType.FIXED_SMALL: 0, ModelVarType.LEARNED: 1, ModelVarType.LEARNED_RANGE: 2}
+
+    def calc_bpd_loop(self, model, x_start, clip_denoised=True, model_kwargs=None, *, x_cond=None):
+        """The whole variational bound in bits per dimension (:792-848): per timestep (t = T-1 ... 0) one th.randn_like draw, the fused
+        q_sample, the model call, and ONE kernel that writes the vb term, the x_0 MSE and the eps MSE of every sample into column T-1-t
+        of the (B, T) results (the reference stacks its per-step lists in loop order, t descending).  Returns the reference's dict: total_bpd, prior_bpd (B,), vb, xstart_mse, mse (B, T)."""
+        if not x_start.is_cuda:
+            raise RuntimeError("calc_bpd_loop needs CUDA(HIP) tensors; there is no CPU path")
+        model = self._loop_model(model)
+        dev, B, T = x_start.device, x_start.shape[0], self.num_timesteps
+        xs = x_start.to(th.float32).contiguous()
+        n = xs.numel() // B
+        tab = self._table("eval", dev)
+        t_all = th.arange(T, device=dev, dtype=th.int64)[:, None].expand(T, B).contiguous()
+        vb, xstart_mse, mse = (th.empty((B, T), dtype=th.float32, device=dev) for _ in range(3))
+        scratch, nbytes = self._eval_scratch(xs)
+        L, st = _lib.lib(), _lib.stream_ptr(dev)
+        mean_code, var_code = self._MEAN_CODE[self.model_mean_type], self._VAR_CODE[self.model_var_type]
+        with th.no_grad(), _lib.on(dev):
+            for t in range(T - 1, -1, -1):
+                t_batch = t_all[t]
+                noise = th.randn_like(x_start).to(th.float32).contiguous()
+                x_t = th.empty_like(xs)
+                _lib.check(L.hl_diffusion_q_sample(_lib.ptr(xs), _lib.ptr(noise), _lib.ptr(tab), _lib.ptr(t_batch), _lib.ptr(x_t), n, B, T, st),
+                           "hl_diffusion_q_sample")
+                out, learned = self._raw_model_out(model, x_t, t_batch, x_cond, model_kwargs)
+                # learned variances: the two halves of each sample's 2C channels, read at a stride of 2n
+                var = C.c_void_p(out.data_ptr() + n * out.element_size()) if learned else None
+                _lib.check(L.hl_diffusion_vb_terms(mean_code, var_code, 1 if clip_denoised else 0, _lib.ptr(xs), _lib.ptr(x_t),
+                                                   _lib.ptr(noise), _lib.ptr(out), var, out.numel() // B, _lib.ptr(tab),
+                                                   _lib.ptr(t_batch), n, B, T, _lib.ptr(vb), _lib.ptr(xstart_mse), _lib.ptr(mse), T, T - 1 - t,
+                                                   _lib.ptr(scratch, th.float64), nbytes, st), "hl_diffusion_vb_terms")
+            prior_bpd = self._prior_bpd(xs)
+        total_bpd = vb.sum(dim=1) + prior_bpd
+        return {"total_bpd": total_bpd, "prior_bpd": prior_bpd, "vb": vb, "xstart_mse": xstart_mse, "mse": mse}
+

@@ -425,6 +425,50 @@ int hl_diffusion_step(int mode, const float *x, const float *eps, const float *n
                       const int64_t *t, float *sample, float *pred_xstart, int64_t n_per_sample, int B, int T, int clip,
                       const float *log_variance, void *stream);
 
+/* Likelihood evaluation (calc_bpd_loop, _prior_bpd, gaussian_diffusion.py:653-687, 774-848) and DDIM inversion (ddim_reverse_sample,
+ * :531-567).  coef: the (T, 16) fp32 eval table the host mirror builds from the float64 schedule (each entry the fp32 cast of the fp64 value,
+ * like _extract_into_tensor), one row per kept timestep:
+ *   [0] sqrt_recip_acp  [1] sqrt_recipm1_acp  [2] posterior_mean_coef1  [3] posterior_mean_coef2  [4] 1/coef1  [5] coef2/coef1
+ *   [6] posterior_log_variance_clipped  [7] log(beta)  [8] the fixed model log-variance (FIXED_LARGE / FIXED_SMALL; 0 for learned)
+ *   [9] sqrt_acp  [10] sqrt(1 - acp)  [11] sqrt(acp_next)  [12] sqrt(1 - acp_next)  (both in fp32 from fp32 acp_next, as the reference;
+ *   acp_next of the last row is 0)  [13] log(1 - acp)  [14..15] 0
+ * t: (B) int64 row indices.  A t outside [0, T) never reads outside the table: row 0 is read and that sample's outputs become NaN (the
+ * Python binding raises IndexError first, like the reference).  n_per_sample = C*H*W.  Elementwise arithmetic is in the reference's fp32
+ * op order; each kernel has an f32x4 path (n % 4 == 0, 16-byte aligned pointers) and a scalar path. */
+/* x_t = sqrt_acp[t] * x_start + sqrt(1 - acp[t]) * noise */
+int hl_diffusion_q_sample(const float *x_start, const float *noise, const float *coef, const int64_t *t, float *x_t,
+                          int64_t n_per_sample, int B, int T, void *stream);
+/* One reverse DDIM step x_t -> x_{t+1} (eta = 0):
+ *   mode 0:  x0 = clip(r*x - rm1*eps)      mode 1: x0 = eps (pred_xstart already processed by the caller; `clip` ignored)
+ *   e = (r*x - x0) / rm1;  sample = x0 * sqrt(acp_next) + sqrt(1 - acp_next) * e;  pred_xstart (may be NULL) = x0 */
+int hl_diffusion_reverse_step(int mode, const float *x, const float *eps, const float *coef, const int64_t *t, float *sample,
+                              float *pred_xstart, int64_t n_per_sample, int B, int T, int clip, void *stream);
+#define HL_MEAN_EPSILON 0
+#define HL_MEAN_START_X 1
+#define HL_MEAN_PREVIOUS_X 2
+#define HL_VAR_FIXED 0
+#define HL_VAR_LEARNED 1
+#define HL_VAR_LEARNED_RANGE 2
+/* Bytes of fp64 scratch hl_diffusion_vb_terms / hl_diffusion_prior_bpd need for B samples of n_per_sample elements. */
+size_t hl_diffusion_vb_scratch_bytes(int64_t n_per_sample, int B);
+/* One timestep of calc_bpd_loop after the model call.  model_out: the mean-type half of the model output, sample b at model_out + b*out_stride
+ * (out_stride = n_per_sample, or 2*n_per_sample for the first half of a learned-variance model's 2C channels); model_var: the variance half
+ * (NULL exactly when var_type == HL_VAR_FIXED), same stride.  Per element:
+ *   x0 = EPSILON: r*x_t - rm1*out | START_X: out | PREVIOUS_X: out/coef1 - coef2/coef1 * x_t;  clip -> clamp(x0, -1, 1)
+ *   mean = PREVIOUS_X: out | else coef1*x0 + coef2*x_t
+ *   lv = FIXED: [8] | LEARNED: var | LEARNED_RANGE: frac*[7] + (1-frac)*[6], frac = (var + 1)/2
+ *   term = t == 0: -discretized_gaussian_log_likelihood(x_start; mean, 0.5*lv) | else normal_kl(coef1*x_start + coef2*x_t, [6], mean, lv)
+ *   xm = (x0 - x_start)^2;  mse = ((r*x_t - x0)/rm1 - noise)^2
+ * The per-sample means over n_per_sample are summed in fp64 in a fixed order (per-workgroup partials in `scratch`, then one fixed-order pass;
+ * no atomics: bit-reproducible) and written as fp32 to vb[b*ld + j] (mean term / ln 2), xstart_mse[b*ld + j], mse[b*ld + j]. */
+int hl_diffusion_vb_terms(int mean_type, int var_type, int clip, const float *x_start, const float *x_t, const float *noise,
+                          const float *model_out, const float *model_var, int64_t out_stride, const float *coef, const int64_t *t,
+                          int64_t n_per_sample, int B, int T, float *vb, float *xstart_mse, float *mse, int64_t ld, int64_t j,
+                          void *scratch, size_t scratch_bytes, void *stream);
+/* prior_bpd[b] = mean over the sample of normal_kl(sqrt_acp[T-1]*x_start, log(1 - acp[T-1]), 0, 0) / ln 2, same fixed-order reduction. */
+int hl_diffusion_prior_bpd(const float *x_start, const float *coef, int64_t n_per_sample, int B, int T, float *prior_bpd,
+                           void *scratch, size_t scratch_bytes, void *stream);
+
 /* Single ops of the UNet path, exposed for parity tests and profiling (NHWC fp32). */
 int hl_conv2d_nhwc(const float *in, int N, int H, int W, int Cin, const float *w_oihw, const float *bias, int Cout,
                    int ks, int stride, int upsample, const float *coefA, const float *coefB, int silu,
