@@ -128,6 +128,14 @@ SIGNATURES = {
     "hl_groupnorm_train_backward": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "hl_upsample2_backward_nhwc": (_i, [_p, _i, _i, _i, _i, _p, _p]),
     "hl_zero_stuff2_nhwc": (_i, [_p, _i, _i, _i, _i, _p, _p]),
+    "hl_triplane_agg_forward": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p]),
+    "hl_triplane_agg_backward": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _sz, _p]),
+    "hl_layernorm_train_forward": (_i, [_p, _i64, _i, _p, _p, C.c_float, _p, _p, _p]),
+    "hl_layernorm_backward_scratch_bytes": (_sz, [_i64, _i]),
+    "hl_layernorm_train_backward": (_i, [_p, _p, _p, _i64, _i, _p, _p, _p, _p, _p, _sz, _p]),
+    "hl_geglu_forward": (_i, [_p, _i64, _i, _p, _p]),
+    "hl_geglu_backward": (_i, [_p, _p, _i64, _i, _p, _p]),
+    "hl_groupnorm_train_forward_eps": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _i, C.c_float, _p, _p, _p, _p, _p, _sz, _p]),
     "hl_groupnorm_coef": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "hl_attention_nhwc": (_i, [_p, _i, _i, _i, _i, _p, _p]),
     "hl_attention_nhwc_mode": (_i, [_i, _p, _i, _i, _i, _i, _p, _p]),

@@ -5,8 +5,9 @@ The torch modules declared here only own the parameters (so reference checkpoint
 load_state_dict and .to(device) works).  forward() hands the parameter pointers to the C ABI
 (hl_unet_create / hl_unet_forward); there is no PyTorch implementation of the math and no CPU path.
 Supported configuration: dims=2, use_scale_shift_norm True / False, cond_type in {"controlnet", "AdaGN", "cross_attention", "concat", ""},
-use_3d_aware False or True (sampling only; not with AdaGN / cross_attention).  Under no_grad / eval() forward() is the fused inference path; with gradients enabled on a model in training
-mode it is the differentiable path of unet_train.py (HIP forward and backward kernels behind autograd.Functions).
+use_3d_aware False or True (not with AdaGN / cross_attention).  Under no_grad / eval() forward() is the fused inference path; with gradients enabled on a model in training
+mode it is the differentiable path of unet_train.py (HIP forward and backward kernels behind autograd.Functions), for every one of these
+configurations (the 3-D-aware ResBlock needs use_scale_shift_norm=True, as in the reference).
 """
 import ctypes as C
 
@@ -364,10 +365,6 @@ class UNetModel(nn.Module):
             # training call (train_util.py:236 reaches this through the DDP wrapper): gradients are wanted, take the differentiable path -
             # the same network as a chain of autograd.Functions whose forward and backward are HIP kernels (unet_train.py).
             # Sampling never gets here: the loops run under no_grad and the scripts call model.eval()
-            if self.use_3d_aware or self.cond_type == "cross_attention":
-                # (documented limit: these two configurations have no differentiable HIP path - also not for a gradient with respect to x
-                #  alone; under no_grad / with x.requires_grad False they sample on the fused inference kernels)
-                raise NotImplementedError("the HIP training path does not cover use_3d_aware=True / cond_type='cross_attention' (sampling does)")
             from .unet_train import forward_train
             if self.training and self._any_param_requires_grad():
                 # an optimizer step follows; fused optimizers do not bump Tensor._version (see _bind).  A guidance call (eval mode, gradient

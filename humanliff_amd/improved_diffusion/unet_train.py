@@ -16,8 +16,16 @@ include/humanliff_hip.h), activations NHWC fp32:
     _Attention     forward   hl_attention_nhwc (fp32 flash-style kernel)
                    backward  hl_attention_nhwc_backward (csrc/hl_attention_bwd.hip: fp32 MFMA, probabilities recomputed, deterministic; round 4 -
                              rounds 2-3 used five torch.bmm here)
-The (N, 768)-sized embedding MLP (time_embed, label_emb, the ResBlocks' emb_layers: 0.004 % of the FLOPs), residual adds and channel
-concatenations are torch tensor ops.  No convolution, normalisation or attention runs through MIOpen / torch.nn.functional.
+    use_3d_aware=True and cond_type='cross_attention' (csrc/hl_unet_train_xf.hip):
+    _TriplaneAgg   the 3-D-aware ResBlock's plane aggregation + SiLU (unet.py:208-214): hl_triplane_agg_forward / _backward
+    _LayerNorm     the SpatialTransformer's nn.LayerNorm: hl_layernorm_train_forward / _backward
+    _GEGLU         its feed-forward gate: hl_geglu_forward / _backward
+    _GroupNormAct  with eps (its GroupNorm, eps 1e-6): hl_groupnorm_train_forward_eps, backward unchanged
+    The SpatialTransformer's Linear layers are 1x1 _Convs; its self-attention is _Attention on a qkv weight stacked from to_q / to_k / to_v;
+    its cross-attention to the ONE context token is to_out(to_v(context)) on (N, C) in torch (the softmax over one key is exactly 1).
+The (N, 768)-sized embedding MLP (time_embed, label_emb, the ResBlocks' emb_layers: 0.004 % of the FLOPs), the condition's Linear
+(AdaGN / cross_attention; AdaGN's two small convolutions too), residual adds, channel concatenations and the tri-plane roll-out are torch
+tensor ops.  No convolution of the network, normalisation or attention runs through MIOpen / torch.nn.functional.
 
 UNetModel.forward takes this path when gradients are enabled on a model in training mode (unet.py); the samplers (no_grad, eval) never
 do.  The PyTorch-op twin (tests/unet_autograd_twin.py, test infrastructure) remains as the CPU-checkable statement of the same function that the gradient tests compare
@@ -91,7 +99,8 @@ def _pad_c(x, mult):
 class _Conv(th.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b, stride, ups):
-        w4 = w.unsqueeze(-1) if w.dim() == 3 else w              # Conv1d k=1 (attention qkv / proj_out) is a 1x1 conv
+        # Conv1d k=1 (attention qkv / proj_out) and nn.Linear (the SpatialTransformer's projections) are 1x1 convs; b may be None
+        w4 = w.reshape(*w.shape, *(1,) * (4 - w.dim())) if w.dim() < 4 else w
         ks = w4.shape[2]
         Cin = w4.shape[1]
         wp = w4 if x.shape[-1] == Cin else F.pad(w4, (0, 0, 0, 0, 0, x.shape[-1] - Cin))    # zero weights for the padded input channels
@@ -146,10 +155,11 @@ def conv(x, m, stride=1, ups=0):
 
 
 class _GroupNormAct(th.autograd.Function):
-    """y = silu?( GroupNorm32(x) [* (1 + scale) + shift] )   (nn.py:17-19,100; unet.py:198-219, use_scale_shift_norm)."""
+    """y = silu?( GroupNorm32(x) [* (1 + scale) + shift] )   (nn.py:17-19,100; unet.py:198-219, use_scale_shift_norm).  eps None: GroupNorm32's
+    1e-5 (hl_groupnorm_train_forward); otherwise that eps (hl_groupnorm_train_forward_eps: the SpatialTransformer's norm, 1e-6)."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, ss, silu):
+    def forward(ctx, x, gamma, beta, ss, silu, eps=None):
         L = _lib.lib()
         N, H, W, Cc = x.shape
         dev = x.device
@@ -159,9 +169,14 @@ class _GroupNormAct(th.autograd.Function):
         scr = th.empty(N * 8192, device=dev)
         ssc = ss.contiguous() if ss is not None else None
         with _lib.on(dev):
-            _lib.check(L.hl_groupnorm_train_forward(_lib.ptr(x), N, H, W, Cc, _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(ssc), 1 if silu else 0,
-                                                    _lib.ptr(A), _lib.ptr(B), _lib.ptr(gstat), _lib.ptr(y), _lib.ptr(scr), scr.numel() * 4,
-                                                    _lib.stream_ptr()), "hl_groupnorm_train_forward")
+            if eps is None:
+                _lib.check(L.hl_groupnorm_train_forward(_lib.ptr(x), N, H, W, Cc, _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(ssc), 1 if silu else 0,
+                                                        _lib.ptr(A), _lib.ptr(B), _lib.ptr(gstat), _lib.ptr(y), _lib.ptr(scr), scr.numel() * 4,
+                                                        _lib.stream_ptr()), "hl_groupnorm_train_forward")
+            else:
+                _lib.check(L.hl_groupnorm_train_forward_eps(_lib.ptr(x), N, H, W, Cc, _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(ssc), 1 if silu else 0,
+                                                            float(eps), _lib.ptr(A), _lib.ptr(B), _lib.ptr(gstat), _lib.ptr(y), _lib.ptr(scr),
+                                                            scr.numel() * 4, _lib.stream_ptr()), "hl_groupnorm_train_forward_eps")
         ctx.save_for_backward(x, A, B, gstat, gamma, beta, ssc if ssc is not None else th.empty(0, device=dev))
         ctx.silu = silu
         return y
@@ -183,11 +198,11 @@ class _GroupNormAct(th.autograd.Function):
                                                      _lib.ptr(gstat), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(ss) if has_ss else None, _lib.ptr(dx),
                                                      _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(dss), _lib.ptr(scr), scr.numel() * 4,
                                                      _lib.stream_ptr()), "hl_groupnorm_train_backward")
-        return dx, dgamma, dbeta, dss, None
+        return dx, dgamma, dbeta, dss, None, None
 
 
-def gn_act(x, m, ss=None, silu=True):
-    return _GroupNormAct.apply(x, m.weight, m.bias, ss, silu)
+def gn_act(x, m, ss=None, silu=True, eps=None):
+    return _GroupNormAct.apply(x, m.weight, m.bias, ss, silu, eps)
 
 
 class _Attention(th.autograd.Function):
@@ -221,6 +236,110 @@ class _Attention(th.autograd.Function):
         return dqkv, None
 
 
+class _TriplaneAgg(th.autograd.Function):
+    """use_3d_aware ResBlock (unet.py:208-214): g (N, H, 3W, C), the planes side by side -> silu(cat[g_p, two plane means]) (N, H, 3W, 3C)."""
+
+    @staticmethod
+    def forward(ctx, g):
+        g = g.contiguous()
+        N, H, W3, Cc = g.shape
+        W = W3 // 3
+        dev = g.device
+        rmean, cmean = th.empty((N, 3, H, Cc), device=dev), th.empty((N, 3, W, Cc), device=dev)
+        out = th.empty((N, H, W3, 3 * Cc), device=dev)
+        with _lib.on(dev):
+            _lib.check(_lib.lib().hl_triplane_agg_forward(_lib.ptr(g), N, H, W, Cc, _lib.ptr(rmean), _lib.ptr(cmean), _lib.ptr(out),
+                                                          _lib.stream_ptr()), "hl_triplane_agg_forward")
+        ctx.save_for_backward(g, rmean, cmean)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        g, rmean, cmean = ctx.saved_tensors
+        N, H, W3, Cc = g.shape
+        dout = dout.contiguous()
+        dg = th.empty_like(g)
+        scr = th.empty(N * 3 * (H + W3 // 3) * Cc, device=g.device)
+        with _lib.on(g.device):
+            _lib.check(_lib.lib().hl_triplane_agg_backward(_lib.ptr(dout), _lib.ptr(g), _lib.ptr(rmean), _lib.ptr(cmean), N, H, W3 // 3, Cc,
+                                                           _lib.ptr(dg), _lib.ptr(scr), scr.numel() * 4, _lib.stream_ptr()),
+                       "hl_triplane_agg_backward")
+        return dg
+
+
+class _LayerNorm(th.autograd.Function):
+    """nn.LayerNorm(C) over the channels of every pixel of x (..., C) (spatial_transformer.py:128-134)."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, eps):
+        x = x.contiguous()
+        Cc = x.shape[-1]
+        npix = x.numel() // Cc
+        y = th.empty_like(x)
+        stat = th.empty((npix, 2), device=x.device)
+        with _lib.on(x.device):
+            _lib.check(_lib.lib().hl_layernorm_train_forward(_lib.ptr(x), npix, Cc, _lib.ptr(gamma), _lib.ptr(beta), float(eps), _lib.ptr(y),
+                                                             _lib.ptr(stat), _lib.stream_ptr()), "hl_layernorm_train_forward")
+        ctx.save_for_backward(x, stat, gamma)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, stat, gamma = ctx.saved_tensors
+        L = _lib.lib()
+        Cc = x.shape[-1]
+        npix = x.numel() // Cc
+        dy = dy.contiguous()
+        dx = th.empty_like(x) if ctx.needs_input_grad[0] else None
+        dgamma, dbeta = th.empty(Cc, device=x.device), th.empty(Cc, device=x.device)
+        scr = th.empty(L.hl_layernorm_backward_scratch_bytes(npix, Cc) // 4 + 1, device=x.device)
+        with _lib.on(x.device):
+            _lib.check(L.hl_layernorm_train_backward(_lib.ptr(x), _lib.ptr(dy), _lib.ptr(stat), npix, Cc, _lib.ptr(gamma), _lib.ptr(dx),
+                                                     _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(scr), scr.numel() * 4, _lib.stream_ptr()),
+                       "hl_layernorm_train_backward")
+        return dx, dgamma, dbeta, None
+
+
+class _GEGLU(th.autograd.Function):
+    """GEGLU (spatial_transformer.py:37-44): p (..., 2F) = [u | gate] -> u * gelu(gate) (..., F), exact erf GELU."""
+
+    @staticmethod
+    def forward(ctx, p):
+        p = p.contiguous()
+        F2 = p.shape[-1]
+        npix = p.numel() // F2
+        out = th.empty((*p.shape[:-1], F2 // 2), device=p.device)
+        with _lib.on(p.device):
+            _lib.check(_lib.lib().hl_geglu_forward(_lib.ptr(p), npix, F2 // 2, _lib.ptr(out), _lib.stream_ptr()), "hl_geglu_forward")
+        ctx.save_for_backward(p)
+        return out
+
+    @staticmethod
+    def backward(ctx, d):
+        p, = ctx.saved_tensors
+        F2 = p.shape[-1]
+        dp = th.empty_like(p)
+        with _lib.on(p.device):
+            _lib.check(_lib.lib().hl_geglu_backward(_lib.ptr(p), _lib.ptr(d.contiguous()), p.numel() // F2, F2 // 2, _lib.ptr(dp), _lib.stream_ptr()),
+                       "hl_geglu_backward")
+        return dp
+
+
+class _ZeroGrad(th.autograd.Function):
+    """Identity on t; every further argument receives a gradient of exact zeros.  The cross-attention to ONE context token
+    (spatial_transformer.py:86-112) has softmax weights of exactly 1, so the reference's autograd gives attn2.to_q / to_k and norm2 zero
+    tensors (not None) - which AdamW's weight decay then acts on."""
+
+    @staticmethod
+    def forward(ctx, t, *params):
+        ctx.shapes = [(p.shape, p.device) for p in params]
+        return t.view_as(t)
+
+    @staticmethod
+    def backward(ctx, g):
+        return (g, *[th.zeros(s, device=d) for s, d in ctx.shapes])
+
+
 # ---- the network (unet.py:550-615) on those ops ---------------------------------------------------------------------------------------
 def _embedding(timesteps, dim):
     from .nn import timestep_embedding
@@ -234,7 +353,11 @@ def _silu(x):
 def _res_block(m, x, emb):
     h = conv(gn_act(x, m.in_layers[0]), m.in_layers[2])
     ss = m.emb_layers[1](_silu(emb))                                        # (N, 2*Cout): [scale | shift] (unet.py:203-206)
-    if getattr(m, "use_scale_shift_norm", True):
+    if getattr(m, "use_3d_aware", False):                                 # (N, H, 3W, C) -> (N, H, 3W, 3C) (unet.py:208-214)
+        if not getattr(m, "use_scale_shift_norm", True):
+            raise NotImplementedError("use_3d_aware needs use_scale_shift_norm=True (as in the reference)")
+        h = _TriplaneAgg.apply(gn_act(h, m.out_layers[0], ss, silu=False))
+    elif getattr(m, "use_scale_shift_norm", True):
         h = gn_act(h, m.out_layers[0], ss)
     else:                                                                   # (N, Cout) added before the GroupNorm (unet.py:216-218)
         h = gn_act(h + ss[:, None, None, :], m.out_layers[0], None)
@@ -252,10 +375,39 @@ def _attention(m, x):
     return x + conv(a.reshape(N, H, W, Cc), m.proj_out)
 
 
-def _run(seq, h, emb):
+def _fused_qkv(a):
+    """attn1's to_q / to_k / to_v (C, C) each, output channel head*d + c, stacked into the (3C, C) projection in QKVAttention's layout
+    head*3d + {q|k|v}*d + c that _Attention reads (differentiable: the gradient flows back to the three weights)."""
+    C_ = a.to_q.weight.shape[1]
+    ws = [w.reshape(a.heads, -1, C_) for w in (a.to_q.weight, a.to_k.weight, a.to_v.weight)]
+    return th.stack(ws, 1).reshape(-1, C_)
+
+
+def _spatial_transformer(m, x, context):
+    """SpatialTransformer.forward (spatial_transformer.py:165-178), depth 1, with its BasicTransformerBlock (:128-134); context (N, E).
+    Self-attention takes _Attention, whose kernel scales q and k by d^-1/4 each - d^-1/2 on the product like CrossAttention.scale, rounded
+    differently.  attn2 attends to ONE token: its softmax is exactly 1 and its output to_out(to_v(context)) at every pixel."""
+    N, H, W, Cc = x.shape
+    blk = m.transformer_blocks[0]
+    h = conv(gn_act(x, m.norm, None, silu=False, eps=m.norm.eps), m.proj_in)
+    n1 = _LayerNorm.apply(h, blk.norm1.weight, blk.norm1.bias, blk.norm1.eps)
+    qkv = _Conv.apply(n1, _fused_qkv(blk.attn1), None, 1, 0)
+    a = _Attention.apply(qkv.reshape(N, H * W, 3 * Cc), blk.attn1.heads)
+    h = h + conv(a.reshape(N, H, W, Cc), blk.attn1.to_out[0])
+    a2 = blk.attn2
+    v2 = _ZeroGrad.apply(a2.to_out[0](a2.to_v(context)), a2.to_q.weight, a2.to_k.weight, blk.norm2.weight, blk.norm2.bias)
+    h = h + v2[:, None, None, :]
+    p = conv(_LayerNorm.apply(h, blk.norm3.weight, blk.norm3.bias, blk.norm3.eps), blk.ff.net[0].proj)
+    h = h + conv(_GEGLU.apply(p), blk.ff.net[2])
+    return x + conv(h, m.proj_out)
+
+
+def _run(seq, h, emb, context=None):
     for m in seq:
         if isinstance(m, U.ResBlock):
             h = _res_block(m, h, emb)
+        elif isinstance(m, U.SpatialTransformer):
+            h = _spatial_transformer(m, h, context)
         elif isinstance(m, U.AttentionBlock):
             h = _attention(m, h)
         elif isinstance(m, U.Downsample):
@@ -267,14 +419,25 @@ def _run(seq, h, emb):
     return h
 
 
+def to_nhwc(t):
+    return _pad_c(t.float().permute(0, 2, 3, 1), 16).contiguous()          # (27 -> 32 channels, zeros)
+
+
+def _context(model, x_cond):
+    """cond_type='cross_attention' (unet.py:579-582): linear(conv_proj_2(conv_proj_1(x_cond))) (N, E), the one context token of every
+    image.  The two stride-2 convolutions run on _Conv: MIOpen's weight gradients of these layers differ from run to run, and the
+    training step is meant to give the same bits every time (the AdaGN branch keeps its torch modules)."""
+    h = conv(to_nhwc(x_cond), model.conv_proj_1, stride=2)                 # (N, H/2, W/2, 6)
+    h = conv(_pad_c(h, 16).contiguous(), model.conv_proj_2, stride=2)      # (N, H/4, W/4, 1): flattened, the same order as NCHW
+    return model.linear(h.reshape(h.shape[0], -1))
+
+
 def forward_train(model, x, timesteps, x_cond=None, y=None):
     """UNetModel.forward's contract (x (N,C,H,W), timesteps (N,), x_cond, y) -> (N,C_out,H,W), differentiable through HIP kernels."""
     if not x.is_cuda:
         raise RuntimeError("the HIP training path needs CUDA(HIP) tensors; there is no CPU path")
     if model.num_classes is not None:
         assert y is not None and y.shape == (x.shape[0],)
-    if model.cond_type == "concat" and x_cond is not None:   # unet.py:572-573 (UNetModel.forward has already joined them when it is the caller)
-        x, x_cond = th.cat([x, x_cond], dim=1), None
     if th.is_autocast_enabled():
         # The caller trains under autocast (train_util.py:214, --use_amp True).  The kernels in here take fp32 tensors, so torch's own
         # autocasting of the few tensor ops of this function is switched off; the convolutions take the autocast dtype as their operand
@@ -292,20 +455,32 @@ def forward_train(model, x, timesteps, x_cond=None, y=None):
                 return forward_train(model, x.float(), timesteps, None if x_cond is None else x_cond.float(), y)
         finally:
             _TLS.autocast = prev
+    aware = model.use_3d_aware
+    if aware:
+        # unet.py:566-570: (N, 3C, H, W) -> the planes side by side (N, C, H, 3W), x and x_cond each, BEFORE a 'concat' joins them (when
+        # UNetModel.forward is the caller it has joined them plane by plane already: rolling that gives the same tensor)
+        x = th.cat(x.chunk(3, dim=1), -1)
+        if x_cond is not None:
+            x_cond = th.cat(x_cond.chunk(3, dim=1), -1)
+    if model.cond_type == "concat" and x_cond is not None:   # unet.py:572-573 (UNetModel.forward has already joined them when it is the caller)
+        x, x_cond = th.cat([x, x_cond], dim=1), None
     emb = model.time_embed[2](_silu(model.time_embed[0](_embedding(timesteps, model.model_channels))))
-    if model.cond_type == "AdaGN":           # unet.py:574-578 (like the embedding MLP: three tiny torch modules, autograd's own backward)
-        assert x_cond is not None, "cond_type='AdaGN' needs x_cond"
-        xp = model.conv_proj_2(model.conv_proj_1(x_cond.float()))
-        emb = emb + model.linear(xp.reshape(xp.shape[0], -1))
+    context = None
+    if model.cond_type in ("AdaGN", "cross_attention"):   # unet.py:574-582 (like the embedding MLP: three tiny torch modules, autograd's own backward)
+        assert x_cond is not None, f"cond_type='{model.cond_type}' needs x_cond"
+        if model.cond_type == "AdaGN":
+            xp = model.conv_proj_2(model.conv_proj_1(x_cond.float()))
+            emb = emb + model.linear(xp.reshape(xp.shape[0], -1))
+        else:
+            context = _context(model, x_cond)             # (N, E): the one context token of every image
     if model.num_classes is not None:
         emb = emb + model.label_emb(y)
-    to_nhwc = lambda t: _pad_c(t.float().permute(0, 2, 3, 1), 16).contiguous()  # noqa: E731   (27 -> 32 channels, zeros)
     hs = []
     h = to_nhwc(x)
     for blk in model.input_blocks:
-        h = _run(blk, h, emb)
+        h = _run(blk, h, emb, context)
         hs.append(h)
-    h = _run(model.middle_block, h, emb)
+    h = _run(model.middle_block, h, emb, context)
     if model.cond_type == "controlnet":
         assert x_cond is not None, "cond_type='controlnet' needs x_cond (zeros for the first layer)"
         hs_cond = []
@@ -317,9 +492,12 @@ def forward_train(model, x, timesteps, x_cond=None, y=None):
         skip = hs.pop()
         if model.cond_type == "controlnet":
             skip = skip + hs_cond.pop()
-        h = _run(blk, th.cat([h, skip], dim=-1), emb)
+        h = _run(blk, th.cat([h, skip], dim=-1), emb, context)
     out = conv(gn_act(h, model.out[0]), model.out[2])                       # (N, H, W, C_out)
-    out = out.permute(0, 3, 1, 2).contiguous().to(x.dtype)
+    out = out.permute(0, 3, 1, 2)
+    if aware:                                                               # unet.py:613-614: (N, C, H, 3W) -> (N, 3C, H, W)
+        out = th.cat(out.chunk(3, dim=-1), 1)
+    out = out.contiguous().to(x.dtype)
     if out.requires_grad and model.training and model._any_param_requires_grad():
         # backward is what precedes an optimizer step: from here on the packed inference weights count as stale, also when a sampling
         # call between this forward and the step has re-packed them meanwhile (fused optimizers do not bump Tensor._version)

@@ -536,6 +536,41 @@ int hl_upsample2_backward_nhwc(const float *d_up, int N, int H, int W, int C, fl
 /* z (N,2Ho,2Wo,C): z[2y][2x] = dy[y][x], zero elsewhere - backward-data of a stride-2 3x3 conv = flipped 3x3 conv of z. */
 int hl_zero_stuff2_nhwc(const float *dy, int N, int Ho, int Wo, int C, float *z, void *stream);
 
+/* ---- training kernels of the 3-D-aware and cross-attention UNets (csrc/hl_unet_train_xf.hip; unet_train.py) ----------------------
+ * All fp32, enqueue-only (no host syncs, no allocations), fixed-order sums without float atomics: the same bits on every run.
+ *
+ * Tri-plane aggregation of the 3-D-aware ResBlock (unet.py:208-214).  g (N,H,3W,C) dense NHWC = the GroupNorm affine output (scale /
+ * shift applied, no SiLU) with the planes xy | xz | zy side by side, H == W, C % 4 == 0.
+ * forward   out (N,H,3W,3C) = silu(cat[g_p, m1_p, m2_p]) per plane p, with rowmean(q)[y] = mean over the W columns of plane q,
+ *           colmean(q)[x] = mean over its H rows:  xy: [g, rowmean(xz), colmean(zy)],  xz: [g, rowmean(xy), rowmean(zy)],
+ *           zy: [g, colmean(xy), colmean(xz)].  Also writes the means, rmean (N,3,H,C) and cmean (N,3,W,C), for the backward.
+ * backward  dg (N,H,3W,C) from dout (N,H,3W,3C): the own slot times silu'(g), plus, for every mean, the sum of its slot's gradient
+ *           along the broadcast axis times silu'(mean) / W (or / H), broadcast back onto the plane it came from.
+ *           scratch: N*3*(H+W)*C floats. */
+int hl_triplane_agg_forward(const float *g, int N, int H, int W, int C, float *rmean, float *cmean, float *out, void *stream);
+int hl_triplane_agg_backward(const float *dout, const float *g, const float *rmean, const float *cmean, int N, int H, int W, int C, float *dg,
+                             void *scratch, size_t scratch_bytes, void *stream);
+/* nn.LayerNorm(C) over the channels of each pixel, x / y / dy / dx dense (npix, C).
+ * forward   y = (x - mean) * rstd * gamma + beta, rstd = 1 / sqrt(var + eps) (biased variance); stat (npix, 2) = (mean, rstd).
+ * backward  dx (may be NULL) = rstd * (gd - mean_c(gd) - xh * mean_c(gd * xh)), gd = dy * gamma, xh = (x - mean) * rstd;
+ *           dgamma = sum_p dy * xh, dbeta = sum_p dy (C each, written, not accumulated).  C % 4 == 0, C <= 1024;
+ *           scratch: hl_layernorm_backward_scratch_bytes(npix, C). */
+int hl_layernorm_train_forward(const float *x, int64_t npix, int C, const float *gamma, const float *beta, float eps, float *y, float *stat,
+                               void *stream);
+size_t hl_layernorm_backward_scratch_bytes(int64_t npix, int C);
+int hl_layernorm_train_backward(const float *x, const float *dy, const float *stat, int64_t npix, int C, const float *gamma, float *dx,
+                                float *dgamma, float *dbeta, void *scratch, size_t scratch_bytes, void *stream);
+/* GEGLU (spatial_transformer.py:37-44): in (npix, 2F) = [u | gate], exact erf GELU.
+ * forward   out (npix, F) = u * gelu(gate).
+ * backward  din (npix, 2F) = [d * gelu(gate) | d * u * (Phi(gate) + gate * phi(gate))]. */
+int hl_geglu_forward(const float *in, int64_t npix, int F, float *out, void *stream);
+int hl_geglu_backward(const float *in, const float *dout, int64_t npix, int F, float *din, void *stream);
+/* hl_groupnorm_train_forward with the GroupNorm's eps as an argument (SpatialTransformer.norm: eps 1e-6, spatial_transformer.py:66-67);
+ * the same outputs, so hl_groupnorm_train_backward is its backward unchanged. */
+int hl_groupnorm_train_forward_eps(const float *x, int N, int H, int W, int C, const float *gamma, const float *beta, const float *scale_shift,
+                                   int silu, float eps, float *coefA, float *coefB, float *gstat, float *y, void *scratch, size_t scratch_bytes,
+                                   void *stream);
+
 /* hl_conv2d_nhwc_mode followed by the GroupNorm32 affine of its OUTPUT (nn.py:17-19,100: y = out*A[n,c] + B[n,c] for the layer
  * that normalises `out` next): the statistics come from the epilogue of the kernel that stored `out` (fixed-point group totals added
  * with integer atomics: order-free, bit-reproducible) - the tensor is not read again; *h_used_stats returns nonzero when the epilogue
