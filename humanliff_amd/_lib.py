@@ -157,6 +157,13 @@ SIGNATURES = {
     "hl_mc_emit": (_i, [_p, _i, _i, _i, C.c_double, _p, _p, _p, _sz, _p]),
     "hl_mc_max_triangles": (_i, []),
     "hl_mc_case_table": (_i, [_p, _p]),
+    "hl_adamw_chunks": (_i64, [C.POINTER(C.c_int64), _i]),
+    "hl_adamw_table_bytes": (_sz, [_i, _i64]),
+    "hl_adamw_table_pack": (_i, [_i, C.POINTER(C.c_int64), C.POINTER(C.c_void_p), _i, _p, _sz]),
+    "hl_adamw_scratch_bytes": (_sz, [_i64]),
+    "hl_adamw_step": (_i, [_p, _i, _i64, _i, C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                           C.c_float, C.c_float, _p, _sz, _p]),
+    "hl_adamw_sum_partials": (_i, [_p, _i64, _p, _p]),
 }
 
 

@@ -650,6 +650,26 @@ int hl_mc_emit(const double *vol, int nx, int ny, int nz, double iso, double *ve
 int hl_mc_max_triangles(void);
 int hl_mc_case_table(int8_t *h_tris, uint8_t *h_ntri);
 
+/* ---- fused optimizer tail (train_util.TrainLoop.optimize_normal: _log_grad_norm, clip_grad_value_, AdamW, update_ema) -------------
+ * Contract: DESIGN.md "Training loop".  fp32 tensors; the host packs a table once per parameter list and keeps it on the device.
+ *   hl_adamw_chunks: number of HL_ADAMW_CHUNK-element chunks of the list (-1 on a bad list); hl_adamw_table_bytes: its table size.
+ *   hl_adamw_table_pack: writes the table into HOST memory (the caller copies it to the device): ptrs holds 8 pointers per tensor,
+ *     p, g, m, v, e0..e3 (g NULL: no gradient, the tensor gets its EMA updates only; e_k unused for k >= n_ema, n_ema <= 4).
+ *   hl_adamw_step: one launch over the table.  Per element: the unclipped g*g into the chunk's fp64 partial (scratch, nchunks
+ *     doubles, fixed order), g clamped to [-clip, clip] when clip > 0 (NaN stays NaN; .grad is not written), AdamW in torch's
+ *     multi-tensor op order with the host's scalars (wd_scale = 1 - lr*wd, bc2_sqrt = sqrt(1 - beta2^step),
+ *     neg_step_size = -lr / (1 - beta1^step)), then e_k = e_k * r_k + (1 - r_k) * p; ema_rates = {r_0, 1 - r_0, r_1, 1 - r_1, ...}.
+ *   hl_adamw_sum_partials: one workgroup sums the n partials in a fixed order into out[0] (fp64, device).  Both enqueue-only. */
+#define HL_ADAMW_CHUNK 16384
+int64_t hl_adamw_chunks(const int64_t *numel, int ntensors);
+size_t hl_adamw_table_bytes(int ntensors, int64_t nchunks);
+int hl_adamw_table_pack(int ntensors, const int64_t *numel, void *const *ptrs, int n_ema, void *host_table, size_t table_bytes);
+size_t hl_adamw_scratch_bytes(int64_t nchunks);
+int hl_adamw_step(const void *table, int ntensors, int64_t nchunks, int n_ema, const float *ema_rates, float clip, float wd_scale,
+                  float one_minus_beta1, float beta2, float one_minus_beta2, float bc2_sqrt, float eps, float neg_step_size,
+                  void *scratch, size_t scratch_bytes, void *stream);
+int hl_adamw_sum_partials(const void *scratch, int64_t n, double *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
