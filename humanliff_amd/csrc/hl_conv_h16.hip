@@ -372,18 +372,18 @@ __global__ __launch_bounds__(256, 1) void k_conv_h16(const ConvK p) {
 // workgroups share a CU: the 16x16 kernel owns a CU alone (474 registers, 93 KB of LDS) and nothing overlaps its prologue, staging VALU and epilogue
 // (no-MFMA ablation 106 of 461 us at 192 -> 192, 256 px, B = 4; the matrix pipe alone 336 - 350 us).  Same arithmetic, same weight image, same
 // two-plane activation image; weight ring two k-steps deep; the epilogue exchange in two channel halves of 128 slots x 96 channels (50 KB).
+// Round 7: the 4 waves split N only (1 x 4), each owns all 128 pixels x 48 channels as 8 x 3 tiles of v_mfma_f32_16x16x32_f16 - a weight fragment
+// feeds 8 tiles instead of 2, which halves the weight bytes per FLOP (2048-workgroup launch at B = 4: 525 -> 479 us, profiles/r07_h2s_16x16x32_ab.md).
 // ---------------------------------------------------------------------------------------------------------------------------------------------
 constexpr int H2S_PH = 10, H2S_NPIX = H2S_PH * H16_PW;               // patch of an 8x16 tile: 10 rows x 18 columns
 constexpr int H2S_PLANE = H2S_PH * H16_LP * 64, H2S_STG = 2 * H2S_PLANE;   // bytes per plane / per stage (both planes)
 constexpr int H2S_EP = 100;                                            // epilogue row pitch in floats (96 + 4)
 constexpr int H2S_LDS = 2 * H2S_STG + 1024 > 128 * H2S_EP * 4 ? 2 * H2S_STG + 1024 : 128 * H2S_EP * 4;
 
-template <class PixFn>
-__device__ __forceinline__ void h2s_epilogue(const ConvK &p, char *lds, const f32x16 (&acc)[2][3], int tid, int lane, int wm, int wn, int n0, long tile, float rsx, PixFn pix) {
-    float *ep = reinterpret_cast<float *>(lds);
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {                      // channel half h = the tiles of the waves with wn == h
-        if (h) __syncthreads();
+// The accumulator scatters of h2s_epilogue: scatter(ep, h) writes the workgroup's channel half h (96 channels) as [pixel slot][H2S_EP floats].
+// 2 x 2 waves of 32x32 tiles (k_conv1_h2s, k_conv_h2d): wave (wm, wn) holds slots 64 wm .. 64 wm + 63 x channels 96 wn .. 96 wn + 95.
+__device__ __forceinline__ auto h2s_scatter_2x2(const f32x16 (&acc)[2][3], int lane, int wm, int wn) {
+    return [&acc, lane, wm, wn](float *ep, int h) {
         if (wn == h) {
 #pragma unroll
             for (int m2 = 0; m2 < 2; ++m2)
@@ -395,6 +395,39 @@ __device__ __forceinline__ void h2s_epilogue(const ConvK &p, char *lds, const f3
                         ep[(wm * 64 + m2 * 32 + r) * H2S_EP + nf * 32 + (lane & 31)] = acc[m2][nf][i];
                     }
         }
+    };
+}
+// 1 x 4 waves of 16x16 tiles (k_conv_h2s): wave w holds all 128 slots x channels 48 w .. 48 w + 47 (half w >> 1).  Register i of lane L in tile
+// (mf, f) is slot 16 mf + h2s_px(4 (L >> 4) + i), channel 48 w + 16 f + (L & 15).
+__device__ __forceinline__ int h2s_px(int r) { return r ^ (r & 8 ? 0 : 4); }   // A / C row r of a 16x16x32 tile -> pixel x of its tile row
+__device__ __forceinline__ int h2s_kgrp(int kg) { return ((kg & 1) << 1) | (kg >> 1); }   // k-group kg of a 16x16x32 operand -> 8-channel group of the chunk
+// byte offset of lane L's B fragment f of wave w inside one (chunk, tap) block of k_pack_conv_h2's image (plane 0; plane 1 is 6144 bytes further)
+__device__ __forceinline__ unsigned h2s_wfrag_off(int wave, int f, int lane) {
+    const int o = 48 * wave + 16 * f + (lane & 15), g = h2s_kgrp(lane >> 4);
+    const int k2 = g >> 1, wn = o / 96, nf = (o % 96) / 32, l = (o & 31) + 32 * (g & 1);
+    return (unsigned)(k2 * 12288 + wn * 3072 + nf * 1024 + l * 16);
+}
+__device__ __forceinline__ auto h2s_scatter_1x4(const f32x4 (&acc)[8][3], int lane, int wave) {
+    return [&acc, lane, wave](float *ep, int h) {
+        if ((wave >> 1) == h) {
+#pragma unroll
+            for (int mf = 0; mf < 8; ++mf)
+#pragma unroll
+                for (int f = 0; f < 3; ++f)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        ep[(16 * mf + h2s_px(4 * (lane >> 4) + i)) * H2S_EP + 48 * (wave & 1) + 16 * f + (lane & 15)] = acc[mf][f][i];
+        }
+    };
+}
+
+template <class ScatterFn, class PixFn>
+__device__ __forceinline__ void h2s_epilogue(const ConvK &p, char *lds, ScatterFn scatter, int tid, int n0, long tile, float rsx, PixFn pix) {
+    float *ep = reinterpret_cast<float *>(lds);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {                      // channel half h
+        if (h) __syncthreads();
+        scatter(ep, h);
         __syncthreads();
         // thread (pr0 = tid / 24 < 10, channel quad tid % 24 of this half) finishes pixel slots pr0, pr0 + 10, ... (<= 13 of the 128) in three batches:
         // the residual loads of a batch are in flight before its first store
@@ -482,20 +515,16 @@ __global__ __launch_bounds__(256, 2) void k_conv_h2s(const ConvK p) {
 #if __HIP_DEVICE_COMPILE__
     constexpr unsigned OOB = 0x80000000u;
     constexpr int NU = H2S_NPIX * 4, NUT = (NU + 255) / 256;      // staging units (pixel, 8-channel group): 720 -> 3 per thread
-#ifndef H2S_RING
-#define H2S_RING 2
-#endif
 #ifndef H2S_ABL   // timing ablations (wrong results): 1 no weight loads in the loop, 2 no patch loads / staging, 4 no A-fragment reads, 8 no MFMAs
 #define H2S_ABL 0
 #endif
 #ifndef H2S_ST0
-#define H2S_ST0 12
+#define H2S_ST0 6
 #endif
-    constexpr int RING = H2S_RING;                                 // k-steps of weights in flight (divides 18)
     constexpr int ST0 = H2S_ST0;                                   // k-step behind which the next chunk's patch goes to LDS (3 units, one per step)
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), wm = wave >> 1, wn = wave & 1;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int total = p.n_mtiles * p.n_nblocks;
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
     const int q8 = total >> 3, r8 = total & 7;
@@ -558,39 +587,43 @@ __global__ __launch_bounds__(256, 2) void k_conv_h2s(const ConvK p) {
         *reinterpret_cast<u32x4 *>(dst) = h0;
         if (sl[j] < 2u * H2S_STG) *reinterpret_cast<u32x4 *>(dst + H2S_PLANE) = h1;
     };
-    unsigned aoff[2][3];
+    // ---- 16x16x32 operands.  Lane L of an A / B fragment holds k-group kg = L >> 4: the chunk's 8-channel group h2s_kgrp(kg) (groups 0, 2, 1, 3).
+    // A fragment (mf, tap) = tile row mf, pixel x = h2s_px(L & 15) of row L & 15: one ds_read_b128 per plane from the swizzled patch.  With the
+    // permuted rows and groups every 16-lane group a ds_read_b128 is served in covers 16 distinct 16-byte slots for every tap column (the identity
+    // maps would put two lanes on one slot); tap row and fragment row are an immediate offset.
+    unsigned aoff[3];
     {
-        const int r = lane & 31, g = lane >> 5;
+        const int px0 = h2s_px(lane & 15), g = h2s_kgrp(lane >> 4);
 #pragma unroll
-        for (int mf = 0; mf < 2; ++mf)
-#pragma unroll
-            for (int kx = 0; kx < 3; ++kx) {
-                const int py = 4 * wm + 2 * mf + (r >> 4), px = (r & 15) + kx;
-                aoff[mf][kx] = (unsigned)((py * H16_LP + px) * 64 + ((g ^ ((px >> 2) & 3)) << 4));
-            }
+        for (int kx = 0; kx < 3; ++kx) {
+            const int px = px0 + kx;
+            aoff[kx] = (unsigned)(px * 64 + ((g ^ ((px >> 2) & 3)) << 4));
+        }
     }
-    const unsigned wv = (unsigned)lane * 16u;
-    const int wbase = nb * nch * 18 * 6144 * 2 + wn * 3072;
-    u32x4 ring[RING][2][3];
+    // B fragment f of wave w = output channels 48 w + 16 f + (L & 15) of the workgroup's 192, inputs 8 h2s_kgrp(kg) .. + 7 of the chunk, read from the
+    // packed image of k_pack_conv_h2 ([nb][chunk][tap][k2][plane][wn][nf][lane][8]) at a per-lane offset: one 16-byte load per lane, fragment and plane.
+    unsigned wof[3];
+#pragma unroll
+    for (int f = 0; f < 3; ++f) wof[f] = h2s_wfrag_off(wave, f, lane);
+    const int wbase = nb * nch * 18 * 6144 * 2;
+    u32x4 ring[2][2][3];                                           // [k-step slot S & 1][plane][fragment]: two k-steps of weights in flight
     const int c0 = (int)blockIdx.z * p.kt_per, c1 = min(nch, c0 + p.kt_per);
-    auto w_load = [&](int slot_, int chunk, int s18) {
-        const int so = wbase + (chunk * 18 + s18) * 6144 * 2;
+    auto w_load = [&](int slot_, int chunk, int tap) {
+        const int so = wbase + (chunk * 9 + tap) * 24576;
 #pragma unroll
         for (int pl = 0; pl < 2; ++pl)
 #pragma unroll
-            for (int nf = 0; nf < 3; ++nf) ring[slot_][pl][nf] = __builtin_amdgcn_raw_buffer_load_b128(rsW, wv, so + pl * 6144 + nf * 1024, 0);
+            for (int f = 0; f < 3; ++f) ring[slot_][pl][f] = __builtin_amdgcn_raw_buffer_load_b128(rsW, wof[f], so + pl * 6144, 0);
     };
-    f32x16 acc[2][3];
+    f32x4 acc[8][3];
 #pragma unroll
-    for (int mf = 0; mf < 2; ++mf)
+    for (int mf = 0; mf < 8; ++mf)
 #pragma unroll
-        for (int nf = 0; nf < 3; ++nf)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[mf][nf][i] = 0.f;
+        for (int f = 0; f < 3; ++f) acc[mf][f] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     a_load(c0);
-#pragma unroll
-    for (int s = 0; s < RING; ++s) w_load(s, c0, s);
+    w_load(0, c0, 0);
+    w_load(1, c0, 1);
     if (aff) {   // (the first patch and weights are on their way)
         if (p.cA) {
             for (int c = tid; c < p.Cin; c += 256) { sA[c] = p.cA[(long)img * p.Cin + c]; sB[c] = p.cB[(long)img * p.Cin + c]; }
@@ -604,40 +637,52 @@ __global__ __launch_bounds__(256, 2) void k_conv_h2s(const ConvK p) {
     for (int j = 0; j < NUT; ++j) a_store(0, j, c0);
     __syncthreads();
 
-    u32x4 af[2][2];                                                // [plane][fragment mf] of the current k-step (read at its start: the partner wave of the SIMD covers the LDS latency)
-    auto a_read = [&](const char *st, int tap, int k2, u32x4 (&dst)[2][2]) {
+    u32x4 af[2][2];                                                // [buffer][plane]: fragment row mf + 1 is read while the MFMAs of row mf run
+    auto a_read = [&](const char *st, int tap, int mf, u32x4 (&dst)[2]) {
 #pragma unroll
-        for (int pl = 0; pl < 2; ++pl)
-#pragma unroll
-            for (int mf = 0; mf < 2; ++mf) dst[pl][mf] = *reinterpret_cast<const u32x4 *>(st + pl * H2S_PLANE + (tap / 3) * (H16_LP * 64) + (aoff[mf][tap % 3] ^ (k2 ? 32u : 0u)));
+        for (int pl = 0; pl < 2; ++pl) dst[pl] = *reinterpret_cast<const u32x4 *>(st + pl * H2S_PLANE + (mf + tap / 3) * (H16_LP * 64) + aoff[tap % 3]);
     };
+    // one chunk = 9 k-steps (one tap x 32 channels) of 8 x 3 tiles x 3 products
     for (int c = c0; c < c1; ++c) {
         const char *st = lds + ((c - c0) & 1) * H2S_STG;
         const int cc = c, ccn = cc + 1 < nch ? cc + 1 : 0;
         if (!(H2S_ABL & 2)) a_load(ccn);
-        [&]<int... S>(std::integer_sequence<int, S...>) {
-            ([&] {
-                constexpr int rs = S % RING;
-                if constexpr (!(H2S_ABL & 4) || S == 0) a_read(st, S >> 1, S & 1, af);
-                __builtin_amdgcn_sched_barrier(0);
+        if (!(H2S_ABL & 4) || c == c0) a_read(st, 0, 0, af[0]);
+        auto row = [&](auto s_, auto m_) {                           // fragment row M of k-step S
+            constexpr int S = decltype(s_)::value, M = decltype(m_)::value, rs = S & 1, cur = (H2S_ABL & 4) ? 0 : M & 1;
+            if constexpr (!(H2S_ABL & 4)) {
+                if constexpr (M + 1 < 8) a_read(st, S, M + 1, af[cur ^ 1]);
+                else if constexpr (S + 1 < 9) a_read(st, S + 1, 0, af[cur ^ 1]);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (!(H2S_ABL & 8)) {
 #pragma unroll
-                for (int nf = 0; nf < 3; ++nf)
+                for (int pr = 0; pr < 3; ++pr)                          // smallest partial product first: h1 w0, h0 w1, h0 w0 into every tile
 #pragma unroll
-                    for (int mf = 0; mf < 2; ++mf) if constexpr (!(H2S_ABL & 8)) {                // smallest partial product first
-                        acc[mf][nf] = mma<true>(af[1][mf], ring[rs][0][nf], acc[mf][nf]);
-                        acc[mf][nf] = mma<true>(af[0][mf], ring[rs][1][nf], acc[mf][nf]);
-                        acc[mf][nf] = mma<true>(af[0][mf], ring[rs][0][nf], acc[mf][nf]);
-                    }
-                if constexpr (!(H2S_ABL & 1)) w_load(rs, S + RING < 18 ? cc : ccn, (S + RING) % 18);
-                if constexpr (S >= ST0 && S < ST0 + NUT && !(H2S_ABL & 2)) a_store((c - c0 + 1) & 1, S - ST0, ccn);
-                __builtin_amdgcn_sched_barrier(0);
-            }(), ...);
-        }(std::make_integer_sequence<int, 18>{});
+                    for (int f = 0; f < 3; ++f)
+                        acc[M][f] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, af[cur][pr == 0 ? 1 : 0]),
+                                                                            __builtin_bit_cast(f16x8, ring[rs][pr == 1 ? 1 : 0][f]), acc[M][f], 0, 0, 0);
+            } else {                                                   // (the operands still arrive: an empty asm consumes them)
+                __asm__ volatile("" ::"v"(af[cur][0]), "v"(af[cur][1]));
+                if constexpr (M == 7)
+#pragma unroll
+                    for (int f = 0; f < 3; ++f) __asm__ volatile("" ::"v"(ring[rs][0][f]), "v"(ring[rs][1][f]));
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        auto kstep = [&](auto s_) {
+            constexpr int S = decltype(s_)::value, rs = S & 1;
+            [&]<int... M>(std::integer_sequence<int, M...>) { (row(s_, std::integral_constant<int, M>{}), ...); }(std::make_integer_sequence<int, 8>{});
+            // two steps ahead; 9 steps per chunk, so steps 7 and 8 fetch the next chunk's steps 1 and 0 (each keeps its slot parity)
+            if constexpr (!(H2S_ABL & 1)) w_load(rs, S + 2 < 9 ? cc : ccn, S + 2 < 9 ? S + 2 : 8 - S);
+            if constexpr (S >= ST0 && S < ST0 + NUT && !(H2S_ABL & 2)) a_store((c - c0 + 1) & 1, S - ST0, ccn);
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        [&]<int... S>(std::integer_sequence<int, S...>) { (kstep(std::integral_constant<int, S>{}), ...); }(std::make_integer_sequence<int, 9>{});
         __syncthreads();
     }
-    h2s_epilogue(p, lds, acc, tid, lane, wm, wn, nb * 192, (long)tb, rsx, [&](int pc) {
-        const int wmm = pc >> 6, m2 = (pc >> 5) & 1, r = pc & 31;
-        return ((long)img * p.Hout + y0 + 4 * wmm + 2 * m2 + (r >> 4)) * p.Wout + x0 + (r & 15);
+    h2s_epilogue(p, lds, h2s_scatter_1x4(acc, lane, wave), tid, nb * 192, (long)tb, rsx, [&](int pc) {
+        return ((long)img * p.Hout + y0 + (pc >> 4)) * p.Wout + x0 + (pc & 15);
     });
 #endif
 }
@@ -985,7 +1030,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_h2d(const ConvK p) {
         }(std::make_integer_sequence<int, 9>{});
     }
     __syncthreads();
-    h2s_epilogue(p, lds, acc, tid, lane, wm, wn, nb * 192, (long)tb, rsx, [&](int pc) {
+    h2s_epilogue(p, lds, h2s_scatter_2x2(acc, lane, wm, wn), tid, nb * 192, (long)tb, rsx, [&](int pc) {
         const int wmm = pc >> 6, m2 = (pc >> 5) & 1, r = pc & 31;
         return ((long)img * p.Hout + y0 + 4 * wmm + 2 * m2 + (r >> 4)) * p.Wout + x0 + (r & 15);
     });
@@ -1118,7 +1163,7 @@ __global__ __launch_bounds__(256, 2) void k_conv1_h2s(const ConvK p) {
         }(std::make_integer_sequence<int, 3>{});
         __syncthreads();
     }
-    h2s_epilogue(p, lds, acc, tid, lane, wm, wn, nb * 192, (long)tb, rsx, [&](int pc) { return m0 + pc; });
+    h2s_epilogue(p, lds, h2s_scatter_2x2(acc, lane, wm, wn), tid, nb * 192, (long)tb, rsx, [&](int pc) { return m0 + pc; });
 #endif
 }
 
