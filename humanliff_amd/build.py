@@ -10,10 +10,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libhumanliff_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unused-result"] + os.environ.get("HL_FLAGS", "").split()   # HL_FLAGS: developer variants (-D...) for every file
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unused-result"] + os.environ.get("HL_FLAGS", "").split()   # HL_FLAGS: extra compiler flags for every file
 # per-file overrides (the last -std wins): k_conv_wino4w's compile-time slot schedule uses templated lambdas
-FILE_FLAGS = {"hl_conv_wino4w.hip": ["-std=c++20"] + os.environ.get("HL_W4W_FLAGS", "").split(), "hl_conv_h16.hip": ["-std=c++20"] + os.environ.get("HL_H16_FLAGS", "").split(),
-              "hl_render.hip": os.environ.get("HL_RENDER_FLAGS", "").split()}   # HL_*_FLAGS: developer variants (-D...)
+FILE_FLAGS = {"hl_conv_wino4w.hip": ["-std=c++20"], "hl_conv_h16.hip": ["-std=c++20"]}
 
 
 def _sources():
@@ -30,8 +29,8 @@ STAMP = LIB + ".flags"   # (next to the library: it travels with it)
 
 
 def _flag_key():
-    """Every flag the objects are compiled with (the HL_*_FLAGS developer variants included): a flags-only change must rebuild too -
-    an A / B of two -D variants that silently compares a library with itself measures nothing."""
+    """Every flag the objects are compiled with (HL_FLAGS included): a flags-only change must rebuild too -
+    an A / B of two flag sets that silently compares a library with itself measures nothing."""
     return repr((HIPCC, FLAGS, sorted(FILE_FLAGS.items())))
 
 

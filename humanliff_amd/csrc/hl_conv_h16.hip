@@ -53,15 +53,8 @@ __device__ __forceinline__ f32x16 mma(const u32x4 a, const u32x4 b, const f32x16
 constexpr int H16_PW = 18, H16_NPIX = H16_PW * H16_PW;       // patch of a 16x16 tile
 constexpr int H16_LP = 20;                                    // LDS row pitch of the patch in pixels (multiple of 4: the slot of a pixel depends on its x only)
 constexpr int H16_STAGE = H16_PW * H16_LP * 64;              // bytes per patch stage
-#ifndef H16_RING
-#define H16_RING 6                                         // k-steps of weights in flight (divides 18)
-#endif
-#ifndef H16_ABL   // timing ablations (wrong results): 1 no weight loads in the loop, 2 no patch loads / staging in the loop, 4 no A-fragment reads, 8 no MFMA
-#define H16_ABL 0
-#endif
-#ifndef H16_ST0
-#define H16_ST0 12                                        // k-step behind which the next chunk's patch goes to LDS (6 units, one per step)
-#endif
+constexpr int H16_RING = 6;                                   // k-steps of weights in flight (divides 18)
+constexpr int H16_ST0 = 12;                                   // k-step behind which the next chunk's patch goes to LDS (6 units, one per step)
 constexpr int H16_EP = 196;                                  // epilogue row pitch in floats (192 + 4: rows 4 apart are 16 banks apart)
 
 // Epilogue shared by the 3x3 and the 1x1 kernel: the wave tiles (128 pixel slots x 96 channels per wave) go through LDS in two rounds of
@@ -163,41 +156,21 @@ __device__ __forceinline__ void h16_epilogue(const ConvK &p, char *lds, const f3
     }
 }
 
-#ifndef HL_ACT_SCALE
-#define HL_ACT_SCALE 1      // developer A / B: 0 = no power-of-two activation scale (sx = 1 everywhere)
-#endif
 struct H2Pair { unsigned p0, p1; };
-// a pair of values -> the two packed planes.  Default (round 6, H2_SPLIT_RNE = 2): h0 = the NEAREST fp16 (v_cvt_pk_f16_f32), h1 = the nearest fp16 of the residual
+// a pair of values -> the two packed planes (round 6): h0 = the NEAREST fp16 (v_cvt_pk_f16_f32), h1 = the nearest fp16 of the residual
 // against h0 (v_fma_mix_f32 reads the packed halves: exact in fp32): |x - h0 - h1| <= 2^-24 |x| while both planes are normal, FOUR instructions per pair
 // (hl_split2_rne, hl_common.h) where round 5's truncating split took six, and a value beyond fp16's range becomes inf / NaN (loud) where v_cvt_pkrtz_f16_f32
 // saturated at 65504 without a trace.  The staging scales its input so that neither a plane overflows nor the low plane goes subnormal wherever the tensor's
-// totals are known (hl_stats.h).  rel-L2 against float64 3.50e-7 / 3.43e-7 / 3.28e-7 (stride-2, K = 864) for H2_SPLIT_RNE = 0 / 1 / 2.  Time: the forward is
+// totals are known (hl_stats.h).  rel-L2 against float64 3.28e-7 (stride-2, K = 864; round 5's truncating split 3.50e-7, the same h0 with h1 to nearest 3.43e-7).  Time: the forward is
 // 1 % (B = 1) to 3 % (B = 4) slower than round 5's on the same box, and none of it is instructions - planes that keep all their mantissa bits make the matrix
 // pipe issue fewer MFMAs per clock (same reported shader clock; profiles/r06_unet_regression.md, scripts/microbench/mfma_data_power.hip).
-// 0: h0 = the value with its low 13 mantissa bits cleared, both conversions truncating (round 5); 1: the same h0, h1 to nearest.
-#ifndef H2_SPLIT_RNE
-#define H2_SPLIT_RNE 2
-#endif
 __device__ __forceinline__ H2Pair split_h2(float x, float y) {
-    const float hx = __builtin_bit_cast(float, __float_as_uint(x) & 0xffffe000u), hy = __builtin_bit_cast(float, __float_as_uint(y) & 0xffffe000u);
-#if H2_SPLIT_RNE == 2
     H2Pair r;
     hl_split2_rne(x, y, r.p0, r.p1);
     return r;
-#elif H2_SPLIT_RNE
-    return H2Pair{pack2<true>(hx, hy), pack2<true>(x - hx, y - hy)};
-#else
-    return H2Pair{__builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(hx, hy)), __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(x - hx, y - hy))};
-#endif
 }
 
-
-// NPL = operand planes: 1 = 16-bit operands (the opt-in modes), 2 = fp16x2 (round 5: the DEFAULT mode's 3x3 layers where this kernel beats the fp32 Winograd
-// kernels): two fp16 planes per operand - activations h0 = the value with its low 13 mantissa bits cleared, h1 = the truncated residual (2^-20), weights
-// nearest-even planes (2^-22) - and the three partial products h1 w0 + h0 w1 + h0 w0 per k-step, fp32 accumulation: a DIRECT convolution, no transform
-// in front of the products, so its error is the fp32 direct kernel's class (and below F(4x4,3x3)'s).  Planes: LDS stage = [plane][patch], weights
-// [..][k-half][plane][wn][fragment][lane][8], a two-plane activation image (k_gn_apply_*: ConvK::in16 = 2) is [plane][pixel][C].
-template <bool F16, int NPL>
+template <bool F16>
 __global__ __launch_bounds__(256, 1) void k_conv_h16(const ConvK p) {
 #if __HIP_DEVICE_COMPILE__
     constexpr unsigned OOB = 0x80000000u;
@@ -214,15 +187,12 @@ __global__ __launch_bounds__(256, 1) void k_conv_h16(const ConvK p) {
     const int img = tb / (bw * bh), brem = tb - img * (bw * bh);
     const int y0 = (brem / bw) * 16, x0 = (brem - (brem / bw) * bw) * 16;
     const int nch = p.Cin >> 5;
-    constexpr int RING = NPL == 2 ? 3 : H16_RING;                            // k-steps of weights in flight (two planes: half as deep, the same registers)
-    constexpr int STG = NPL * H16_STAGE;                                      // bytes per stage (all planes)
     const unsigned pitch4 = (unsigned)p.in_pitch * (p.in16 ? 2u : 4u);      // bytes per pixel (16-bit image from the GroupNorm pass, or fp32)
-    const unsigned plane_b = (unsigned)((long)p.N * p.Hin * p.Win * p.in_pitch * 2);   // (in16 == 2: the second plane of the image)
 
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(
         (void *)p.in, (short)0, (int)((long)p.N * p.Hin * p.Win * pitch4 * (p.in16 == 2 ? 2 : 1)), 0x00020000);
     const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)p.w_bf3, (short)0, (int)((long)p.n_nblocks * nch * 18 * 6144 * NPL), 0x00020000);
+        (void *)p.w_bf3, (short)0, (int)((long)p.n_nblocks * nch * 18 * 6144), 0x00020000);
 
     // ---- patch staging: unit u = (pixel of the 18x18 patch, group of 8 channels) -> two 16-byte fp32 loads, one 16-byte LDS write ----
     unsigned sv[NUT], sl[NUT];
@@ -234,34 +204,23 @@ __global__ __launch_bounds__(256, 1) void k_conv_h16(const ConvK p) {
         const bool ok = u < NU && y >= 0 && y < p.Hout && x >= 0 && x < p.Wout;
         const int ys = p.ups ? y >> 1 : y, xs = p.ups ? x >> 1 : x;
         sv[j] = ok ? (unsigned)((img * p.Hin + ys) * p.Win + xs) * pitch4 + grp * (p.in16 ? 16 : 32) : OOB;
-        sl[j] = u < NU ? (unsigned)((py * H16_LP + px) * 64 + ((grp ^ ((px >> 2) & 3)) << 4)) : (unsigned)(2 * STG + (tid & 63) * 16);   // (no unit: a dump slot behind the stages)
+        sl[j] = u < NU ? (unsigned)((py * H16_LP + px) * 64 + ((grp ^ ((px >> 2) & 3)) << 4)) : (unsigned)(2 * H16_STAGE + (tid & 63) * 16);   // (no unit: a dump slot behind the stages)
     }
     u32x4 ar[NUT][2];
     auto a_load = [&](int chunk) {
 #pragma unroll
         for (int j = 0; j < NUT; ++j) {
-            const int so = (H16_ABL & 16) ? 0 : chunk * (p.in16 ? 64 : 128);      // (16: the patch from L2-hot addresses)
+            const int so = chunk * (p.in16 ? 64 : 128);
             ar[j][0] = __builtin_amdgcn_raw_buffer_load_b128(rsA, sv[j], so, 0);
             if (!p.in16) ar[j][1] = __builtin_amdgcn_raw_buffer_load_b128(rsA, sv[j] == OOB ? OOB : sv[j] + 16, so, 0);
-            else if (NPL == 2) ar[j][1] = __builtin_amdgcn_raw_buffer_load_b128(rsA, sv[j] == OOB ? OOB : sv[j] + plane_b, so, 0);
         }
     };
     auto a_store = [&](int stage, int j) {
         const f32x4 v0 = __builtin_bit_cast(f32x4, ar[j][0]), v1 = __builtin_bit_cast(f32x4, ar[j][1]);
-        char *dst = lds + (sl[j] >= 2u * STG ? 0 : stage * STG) + sl[j];
-        if constexpr (NPL == 2) {
-            u32x4 h0 = ar[j][0], h1 = ar[j][1];
-            if (!p.in16) {
-                const H2Pair q0 = split_h2(v0[0], v0[1]), q1 = split_h2(v0[2], v0[3]), q2 = split_h2(v1[0], v1[1]), q3 = split_h2(v1[2], v1[3]);
-                h0 = u32x4{q0.p0, q1.p0, q2.p0, q3.p0}; h1 = u32x4{q0.p1, q1.p1, q2.p1, q3.p1};
-            }
-            *reinterpret_cast<u32x4 *>(dst) = h0;
-            if (sl[j] < 2u * STG) *reinterpret_cast<u32x4 *>(dst + H16_STAGE) = h1;
-        } else {
-            const u32x4 h = p.in16 ? ar[j][0]
-                                   : u32x4{pack2<F16>(v0[0], v0[1]), pack2<F16>(v0[2], v0[3]), pack2<F16>(v1[0], v1[1]), pack2<F16>(v1[2], v1[3])};
-            *reinterpret_cast<u32x4 *>(dst) = h;
-        }
+        char *dst = lds + (sl[j] >= 2u * H16_STAGE ? 0 : stage * H16_STAGE) + sl[j];
+        const u32x4 h = p.in16 ? ar[j][0]
+                               : u32x4{pack2<F16>(v0[0], v0[1]), pack2<F16>(v0[2], v0[3]), pack2<F16>(v1[0], v1[1]), pack2<F16>(v1[2], v1[3])};
+        *reinterpret_cast<u32x4 *>(dst) = h;
     };
 
     // ---- A fragments: row r of fragment mf = pixel (8wm + 2mf + (r >> 4), r & 15) of the tile; lane half g holds channels 8g..8g+7 of the k-step
@@ -278,18 +237,16 @@ __global__ __launch_bounds__(256, 1) void k_conv_h16(const ConvK p) {
     }
     // ---- weights: packed [channel block][chunk][tap][k-half][wn][fragment][lane][8] -> one 16-byte load per lane and fragment
     const unsigned wv = (unsigned)lane * 16u;
-    const int wbase = nb * nch * 18 * 6144 * NPL + wn * 3072;
-    u32x4 ring[RING][NPL][3];
+    const int wbase = nb * nch * 18 * 6144 + wn * 3072;
+    u32x4 ring[H16_RING][3];
     // split-K (layers with few tiles): blockIdx.z owns the chunks [c0, c1) and stores raw accumulators to p.partial (k_splitk_finish sums
     // the slabs in a fixed order and applies bias / residual / statistics).  (A per-workgroup rotation of the chunk order,
     // tried against L2-channel hot spots - changed nothing and is gone.)
     const int c0 = (int)blockIdx.z * p.kt_per, c1 = min(nch, c0 + p.kt_per);
     auto w_load = [&](int slot_, int chunk, int s18) {
-        const int so = wbase + (chunk * 18 + s18) * 6144 * NPL;
+        const int so = wbase + (chunk * 18 + s18) * 6144;
 #pragma unroll
-        for (int pl = 0; pl < NPL; ++pl)
-#pragma unroll
-            for (int nf = 0; nf < 3; ++nf) ring[slot_][pl][nf] = __builtin_amdgcn_raw_buffer_load_b128(rsW, wv, so + pl * 6144 + nf * 1024, 0);
+        for (int nf = 0; nf < 3; ++nf) ring[slot_][nf] = __builtin_amdgcn_raw_buffer_load_b128(rsW, wv, so + nf * 1024, 0);
     };
 
     f32x16 acc[4][3];
@@ -303,56 +260,34 @@ __global__ __launch_bounds__(256, 1) void k_conv_h16(const ConvK p) {
     // ---- prologue: the first chunk staged, the first H16_RING k-steps of weights in flight
     a_load(c0);
 #pragma unroll
-    for (int s = 0; s < RING; ++s) w_load(s, c0 + s / 18 < nch ? c0 + s / 18 : c0, s % 18);
+    for (int s = 0; s < H16_RING; ++s) w_load(s, c0 + s / 18 < nch ? c0 + s / 18 : c0, s % 18);
 #pragma unroll
     for (int j = 0; j < NUT; ++j) a_store(0, j);
     __syncthreads();
 
-    u32x4 af[2][NPL][4];                                           // A fragments of the current / next k-step (per plane)
-    auto a_read = [&](const char *st, int tap, int k2, u32x4 (&dst)[NPL][4]) {
+    u32x4 af[2][4];                                                // A fragments of the current / next k-step
+    auto a_read = [&](const char *st, int tap, int k2, u32x4 (&dst)[4]) {
 #pragma unroll
-        for (int pl = 0; pl < NPL; ++pl)
-#pragma unroll
-            for (int mf = 0; mf < 4; ++mf) dst[pl][mf] = *reinterpret_cast<const u32x4 *>(st + pl * H16_STAGE + (tap / 3) * (H16_LP * 64) + (aoff[mf][tap % 3] ^ (k2 ? 32u : 0u)));
+        for (int mf = 0; mf < 4; ++mf) dst[mf] = *reinterpret_cast<const u32x4 *>(st + (tap / 3) * (H16_LP * 64) + (aoff[mf][tap % 3] ^ (k2 ? 32u : 0u)));
     };
     for (int c = c0; c < c1; ++c) {
-        const char *st = lds + ((c - c0) & 1) * STG;
+        const char *st = lds + ((c - c0) & 1) * H16_STAGE;
         const int cc = c;                                                // this chunk / the next one (past the end: a valid chunk, never used)
         const int ccn = cc + 1 < nch ? cc + 1 : 0;
-        if (!(H16_ABL & 2) && !(H16_ABL & 64)) a_load(ccn);              // (last chunk: a valid chunk again, staged and never read)
+        a_load(ccn);                                                     // (last chunk: a valid chunk again, staged and never read)
         a_read(st, 0, 0, af[0]);
         __builtin_amdgcn_sched_barrier(0);
         [&]<int... S>(std::integer_sequence<int, S...>) {
             ([&] {
-                constexpr int rs = S % RING, cur = S & 1;
-                if constexpr (S + 1 < 18 && !(H16_ABL & 4)) a_read(st, (S + 1) >> 1, (S + 1) & 1, af[cur ^ 1]);
+                constexpr int rs = S % H16_RING, cur = S & 1;
+                if constexpr (S + 1 < 18) a_read(st, (S + 1) >> 1, (S + 1) & 1, af[cur ^ 1]);
                 __builtin_amdgcn_sched_barrier(0);                 // the next step's fragments are on their way before this step's MFMAs
-#ifdef H2_ORDER_PRODUCT_OUTER
-                if constexpr (NPL == 2 && !(H16_ABL & 8)) {
-#pragma unroll
-                    for (int pr = 0; pr < 3; ++pr)
-#pragma unroll
-                        for (int nf = 0; nf < 3; ++nf)
-#pragma unroll
-                            for (int mf = 0; mf < 4; ++mf)
-                                acc[mf][nf] = mma<true>(af[cur][pr == 0 ? 1 : 0][mf], ring[rs][pr == 1 ? 1 : 0][nf], acc[mf][nf]);
-                } else
-#endif
 #pragma unroll
                 for (int nf = 0; nf < 3; ++nf)
 #pragma unroll
-                    for (int mf = 0; mf < 4; ++mf)
-                        if constexpr (!(H16_ABL & 8)) {
-                            if constexpr (NPL == 2) {               // smallest partial product first
-                                acc[mf][nf] = mma<true>(af[cur][1][mf], ring[rs][0][nf], acc[mf][nf]);
-                                acc[mf][nf] = mma<true>(af[cur][0][mf], ring[rs][1][nf], acc[mf][nf]);
-                                acc[mf][nf] = mma<true>(af[cur][0][mf], ring[rs][0][nf], acc[mf][nf]);
-                            } else acc[mf][nf] = mma<F16>(af[(H16_ABL & 4) ? 0 : cur][0][mf], ring[rs][0][nf], acc[mf][nf]);
-                        }
-                if constexpr (!(H16_ABL & 1)) w_load(rs, S + RING < 18 ? cc : ccn, (S + RING) % 18);
-                if constexpr (S >= H16_ST0 && S < H16_ST0 + NUT) {
-                    if (!(H16_ABL & 2) && !(H16_ABL & 32)) a_store((c - c0 + 1) & 1, S - H16_ST0);
-                }
+                    for (int mf = 0; mf < 4; ++mf) acc[mf][nf] = mma<F16>(af[cur][mf], ring[rs][nf], acc[mf][nf]);
+                w_load(rs, S + H16_RING < 18 ? cc : ccn, (S + H16_RING) % 18);
+                if constexpr (S >= H16_ST0 && S < H16_ST0 + NUT) a_store((c - c0 + 1) & 1, S - H16_ST0);
                 __builtin_amdgcn_sched_barrier(0);
             }(), ...);
         }(std::make_integer_sequence<int, 18>{});
@@ -515,13 +450,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_h2s(const ConvK p) {
 #if __HIP_DEVICE_COMPILE__
     constexpr unsigned OOB = 0x80000000u;
     constexpr int NU = H2S_NPIX * 4, NUT = (NU + 255) / 256;      // staging units (pixel, 8-channel group): 720 -> 3 per thread
-#ifndef H2S_ABL   // timing ablations (wrong results): 1 no weight loads in the loop, 2 no patch loads / staging, 4 no A-fragment reads, 8 no MFMAs
-#define H2S_ABL 0
-#endif
-#ifndef H2S_ST0
-#define H2S_ST0 6
-#endif
-    constexpr int ST0 = H2S_ST0;                                   // k-step behind which the next chunk's patch goes to LDS (3 units, one per step)
+    constexpr int ST0 = 6;                                         // k-step behind which the next chunk's patch goes to LDS (3 units, one per step)
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -628,9 +557,9 @@ __global__ __launch_bounds__(256, 2) void k_conv_h2s(const ConvK p) {
         if (p.cA) {
             for (int c = tid; c < p.Cin; c += 256) { sA[c] = p.cA[(long)img * p.Cin + c]; sB[c] = p.cB[(long)img * p.Cin + c]; }
             __syncthreads();
-        } else sx = wave_uniform(coef_to_lds<HL_ACT_SCALE != 0>(nullptr, nullptr, p.gn, p.N, img, sA, sB, sB + p.Cin, tid, 256));      // (ends with a barrier)
-    } else if (HL_ACT_SCALE && p.xs_max && !p.in16) sx = wave_uniform(pow2_scale_for_bound(p.xs_max[img]));
-    else if (HL_ACT_SCALE && p.xs_gt && !p.in16) sx = wave_uniform(act_scale_totals(p.xs_gt, p.N, img, p.xs_hw));
+        } else sx = wave_uniform(coef_to_lds<true>(nullptr, nullptr, p.gn, p.N, img, sA, sB, sB + p.Cin, tid, 256));      // (ends with a barrier)
+    } else if (p.xs_max && !p.in16) sx = wave_uniform(pow2_scale_for_bound(p.xs_max[img]));
+    else if (p.xs_gt && !p.in16) sx = wave_uniform(act_scale_totals(p.xs_gt, p.N, img, p.xs_hw));
     const float rsx = 1.f / sx;
     kq *= rsx;
 #pragma unroll
@@ -646,36 +575,27 @@ __global__ __launch_bounds__(256, 2) void k_conv_h2s(const ConvK p) {
     for (int c = c0; c < c1; ++c) {
         const char *st = lds + ((c - c0) & 1) * H2S_STG;
         const int cc = c, ccn = cc + 1 < nch ? cc + 1 : 0;
-        if (!(H2S_ABL & 2)) a_load(ccn);
-        if (!(H2S_ABL & 4) || c == c0) a_read(st, 0, 0, af[0]);
+        a_load(ccn);
+        a_read(st, 0, 0, af[0]);
         auto row = [&](auto s_, auto m_) {                           // fragment row M of k-step S
-            constexpr int S = decltype(s_)::value, M = decltype(m_)::value, rs = S & 1, cur = (H2S_ABL & 4) ? 0 : M & 1;
-            if constexpr (!(H2S_ABL & 4)) {
-                if constexpr (M + 1 < 8) a_read(st, S, M + 1, af[cur ^ 1]);
-                else if constexpr (S + 1 < 9) a_read(st, S + 1, 0, af[cur ^ 1]);
-            }
+            constexpr int S = decltype(s_)::value, M = decltype(m_)::value, rs = S & 1, cur = M & 1;
+            if constexpr (M + 1 < 8) a_read(st, S, M + 1, af[cur ^ 1]);
+            else if constexpr (S + 1 < 9) a_read(st, S + 1, 0, af[cur ^ 1]);
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (!(H2S_ABL & 8)) {
 #pragma unroll
-                for (int pr = 0; pr < 3; ++pr)                          // smallest partial product first: h1 w0, h0 w1, h0 w0 into every tile
+            for (int pr = 0; pr < 3; ++pr)                              // smallest partial product first: h1 w0, h0 w1, h0 w0 into every tile
 #pragma unroll
-                    for (int f = 0; f < 3; ++f)
-                        acc[M][f] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, af[cur][pr == 0 ? 1 : 0]),
-                                                                            __builtin_bit_cast(f16x8, ring[rs][pr == 1 ? 1 : 0][f]), acc[M][f], 0, 0, 0);
-            } else {                                                   // (the operands still arrive: an empty asm consumes them)
-                __asm__ volatile("" ::"v"(af[cur][0]), "v"(af[cur][1]));
-                if constexpr (M == 7)
-#pragma unroll
-                    for (int f = 0; f < 3; ++f) __asm__ volatile("" ::"v"(ring[rs][0][f]), "v"(ring[rs][1][f]));
-            }
+                for (int f = 0; f < 3; ++f)
+                    acc[M][f] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, af[cur][pr == 0 ? 1 : 0]),
+                                                                        __builtin_bit_cast(f16x8, ring[rs][pr == 1 ? 1 : 0][f]), acc[M][f], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
         };
         auto kstep = [&](auto s_) {
             constexpr int S = decltype(s_)::value, rs = S & 1;
             [&]<int... M>(std::integer_sequence<int, M...>) { (row(s_, std::integral_constant<int, M>{}), ...); }(std::make_integer_sequence<int, 8>{});
             // two steps ahead; 9 steps per chunk, so steps 7 and 8 fetch the next chunk's steps 1 and 0 (each keeps its slot parity)
-            if constexpr (!(H2S_ABL & 1)) w_load(rs, S + 2 < 9 ? cc : ccn, S + 2 < 9 ? S + 2 : 8 - S);
-            if constexpr (S >= ST0 && S < ST0 + NUT && !(H2S_ABL & 2)) a_store((c - c0 + 1) & 1, S - ST0, ccn);
+            w_load(rs, S + 2 < 9 ? cc : ccn, S + 2 < 9 ? S + 2 : 8 - S);
+            if constexpr (S >= ST0 && S < ST0 + NUT) a_store((c - c0 + 1) & 1, S - ST0, ccn);
             __builtin_amdgcn_sched_barrier(0);
         };
         [&]<int... S>(std::integer_sequence<int, S...>) { (kstep(std::integral_constant<int, S>{}), ...); }(std::make_integer_sequence<int, 9>{});
@@ -788,125 +708,6 @@ __global__ __launch_bounds__(256, 1) void k_conv1_h16(const ConvK p) {
         }(std::make_integer_sequence<int, 6>{});
         __syncthreads();
     }
-    if constexpr (H16_ABL & 128) { if (acc[0][0][0] == 12345.f) p.out[0] = acc[1][1][1] + acc[3][2][5]; return; }
-    h16_epilogue(p, lds, acc, tid, lane, wm, wn, nb * 192, (long)tb, [&](int q, int pc) {
-        return m0 + 128 * (pc >> 6) + 32 * (2 * q + ((pc >> 5) & 1)) + (pc & 31);
-    });
-#endif
-}
-
-// k_conv1_h2 (round 5): the 1x1 convolutions of the DEFAULT fp32 mode with fp16x2 products - every operand as two fp16 planes (activations
-// h0 = the value with its low 13 mantissa bits cleared, h1 = the truncated residual: 2^-20; weights nearest-even planes at pack time: 2^-22),
-// x w ~ h1 w0 + h0 w1 + h0 w0 accumulated in fp32 on v_mfma_f32_32x32x16_f16.  These layers (ResBlock skips, attention qkv / proj_out, the
-// control tower's zero convolutions) are bound by HBM once they leave the fp32 matrix pipe (a 384->192 layer at 256x256 moves 600 MB for 39
-// GFLOP): the three products cost nothing next to the memory time, and the fp32 kernel (k_conv_dma, 0.83 of the fp32 matrix peak) takes twice as
-// long.  Error: a CPU emulation of exactly this arithmetic in ALL 1x1 layers of the production network moves its output by 3.1e-6 against the fp32
-// oracle (scripts/unet_fp16x2_emulation.py; the fp32 kernels sit at 4.5e-6, the parity bound is 5e-5).  Same workgroup shape, wave split and
-// epilogue as k_conv1_h16; K in chunks of 48 input channels = three k-steps (two planes of a chunk: 2 x 28 KB per stage), pixel pitch 112 bytes
-// (7 quarters: odd), weights [channel block of 192][chunk of 48][k-step 3][plane 2][wn][fragment nf][lane][8], three k-steps in flight.
-constexpr int H2_PITCH = 112, H2_PLANE = 256 * H2_PITCH, H2_STAGE = 2 * H2_PLANE;
-
-__global__ __launch_bounds__(256, 1) void k_conv1_h2(const ConvK p) {
-#if __HIP_DEVICE_COMPILE__
-    constexpr int NUT = 6;                                         // staging units per thread: 256 px x 6 groups of 8 channels / 256 threads
-    extern __shared__ __attribute__((aligned(16))) char lds[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), wm = wave >> 1, wn = wave & 1;
-    const int total = p.n_mtiles * p.n_nblocks;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int q8 = total >> 3, r8 = total & 7;
-    const int wi = xcd * q8 + (xcd < r8 ? xcd : r8) + slot;
-    const int tb = __builtin_amdgcn_readfirstlane(wi / p.n_nblocks), nb = wi - tb * p.n_nblocks;
-    const long m0 = (long)tb * 256;
-    const int nch = p.Cin / 48;
-    const unsigned pitch4 = (unsigned)p.in_pitch * 4u;
-    const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)p.in, (short)0, (int)((long)p.N * p.Hin * p.Win * pitch4), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)p.w_bf3, (short)0, (int)((long)p.n_nblocks * nch * 3 * 12288), 0x00020000);
-
-    unsigned sv[NUT], sl[NUT];
-#pragma unroll
-    for (int j = 0; j < NUT; ++j) {
-        const int u = tid + 256 * j, pix = u / 6, grp = u - pix * 6;
-        sv[j] = (unsigned)(m0 + pix) * pitch4 + grp * 32;
-        sl[j] = (unsigned)(pix * H2_PITCH + grp * 16);
-    }
-    u32x4 ar[NUT][2];
-    auto a_load = [&](int chunk) {
-#pragma unroll
-        for (int j = 0; j < NUT; ++j) {
-            ar[j][0] = __builtin_amdgcn_raw_buffer_load_b128(rsA, sv[j], chunk * 192, 0);
-            ar[j][1] = __builtin_amdgcn_raw_buffer_load_b128(rsA, sv[j] + 16, chunk * 192, 0);
-        }
-    };
-    auto a_store = [&](int stage, int j) {
-        const f32x4 v0 = __builtin_bit_cast(f32x4, ar[j][0]), v1 = __builtin_bit_cast(f32x4, ar[j][1]);
-        const H2Pair q0 = split_h2(v0[0], v0[1]), q1 = split_h2(v0[2], v0[3]), q2 = split_h2(v1[0], v1[1]), q3 = split_h2(v1[2], v1[3]);
-        const u32x4 h0 = {q0.p0, q1.p0, q2.p0, q3.p0}, h1 = {q0.p1, q1.p1, q2.p1, q3.p1};
-        *reinterpret_cast<u32x4 *>(lds + stage * H2_STAGE + sl[j]) = h0;
-        *reinterpret_cast<u32x4 *>(lds + stage * H2_STAGE + H2_PLANE + sl[j]) = h1;
-    };
-    unsigned aoff[4];
-#pragma unroll
-    for (int mf = 0; mf < 4; ++mf) aoff[mf] = (unsigned)((128 * wm + 32 * mf + (lane & 31)) * H2_PITCH + (lane >> 5) * 16);
-    const unsigned wv = (unsigned)lane * 16u;
-    const int wbase = nb * nch * 3 * 12288 + wn * 3072;
-    u32x4 ring[3][2][3];                                            // [k-step of the chunk][plane][fragment nf]
-    auto w_load = [&](int slot_, int step) {
-        const int so = wbase + min(step, nch * 3 - 1) * 12288;       // (past the end: the last step again, never used)
-#pragma unroll
-        for (int pl = 0; pl < 2; ++pl)
-#pragma unroll
-            for (int nf = 0; nf < 3; ++nf) ring[slot_][pl][nf] = __builtin_amdgcn_raw_buffer_load_b128(rsW, wv, so + pl * 6144 + nf * 1024, 0);
-    };
-    f32x16 acc[4][3];
-#pragma unroll
-    for (int mf = 0; mf < 4; ++mf)
-#pragma unroll
-        for (int nf = 0; nf < 3; ++nf)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[mf][nf][i] = 0.f;
-
-    a_load(0);
-#pragma unroll
-    for (int s = 0; s < 3; ++s) w_load(s, s);
-#pragma unroll
-    for (int j = 0; j < NUT; ++j) a_store(0, j);
-    __syncthreads();
-
-    u32x4 af[2][2][4];                                              // [buffer][plane][fragment mf]
-    auto a_read = [&](const char *st, int k2, u32x4 (&dst)[2][4]) {
-#pragma unroll
-        for (int pl = 0; pl < 2; ++pl)
-#pragma unroll
-            for (int mf = 0; mf < 4; ++mf) dst[pl][mf] = *reinterpret_cast<const u32x4 *>(st + pl * H2_PLANE + aoff[mf] + k2 * 32);
-    };
-    for (int c = 0; c < nch; ++c) {
-        const char *st = lds + (c & 1) * H2_STAGE;
-        if (!(H16_ABL & 2)) a_load(c + 1 < nch ? c + 1 : c);          // (last chunk: staged again, never read)
-        a_read(st, 0, af[0]);
-        __builtin_amdgcn_sched_barrier(0);
-        [&]<int... S>(std::integer_sequence<int, S...>) {
-            ([&] {
-                constexpr int cur = S & 1;
-                if constexpr (S + 1 < 3 && !(H16_ABL & 4)) a_read(st, S + 1, af[cur ^ 1]);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int nf = 0; nf < 3; ++nf)
-#pragma unroll
-                    for (int mf = 0; mf < 4; ++mf) if constexpr (!(H16_ABL & 8)) {                 // smallest partial product first
-                        acc[mf][nf] = mma<true>(af[cur][1][mf], ring[S][0][nf], acc[mf][nf]);
-                        acc[mf][nf] = mma<true>(af[cur][0][mf], ring[S][1][nf], acc[mf][nf]);
-                        acc[mf][nf] = mma<true>(af[cur][0][mf], ring[S][0][nf], acc[mf][nf]);
-                    }
-                if constexpr (!(H16_ABL & 1)) w_load(S, c * 3 + S + 3);
-                if constexpr (!(H16_ABL & 2)) { a_store((c + 1) & 1, 2 * S); a_store((c + 1) & 1, 2 * S + 1); }
-                __builtin_amdgcn_sched_barrier(0);
-            }(), ...);
-        }(std::make_integer_sequence<int, 3>{});
-        __syncthreads();
-    }
     h16_epilogue(p, lds, acc, tid, lane, wm, wn, nb * 192, (long)tb, [&](int q, int pc) {
         return m0 + 128 * (pc >> 6) + 32 * (2 * q + ((pc >> 5) & 1)) + (pc & 31);
     });
@@ -960,7 +761,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_h2d(const ConvK p) {
         }
     };
     // power-of-two scale of the raw input from its producers' totals (hl_stats.h)
-    const float axs = !HL_ACT_SCALE ? 1.f : p.xs_max ? wave_uniform(pow2_scale_for_bound(p.xs_max[img])) : (p.xs_gt ? wave_uniform(act_scale_totals(p.xs_gt, p.N, img, p.xs_hw)) : 1.f), rsx = 1.f / axs;
+    const float axs = p.xs_max ? wave_uniform(pow2_scale_for_bound(p.xs_max[img])) : (p.xs_gt ? wave_uniform(act_scale_totals(p.xs_gt, p.N, img, p.xs_hw)) : 1.f), rsx = 1.f / axs;
     auto a_store = [&](int j) {
         const f32x4 v0 = __builtin_bit_cast(f32x4, ar[j][0]) * axs, v1 = __builtin_bit_cast(f32x4, ar[j][1]) * axs;
         const H2Pair q0 = split_h2(v0[0], v0[1]), q1 = split_h2(v0[2], v0[3]), q2 = split_h2(v1[0], v1[1]), q3 = split_h2(v1[2], v1[3]);
@@ -1037,9 +838,18 @@ __global__ __launch_bounds__(256, 2) void k_conv_h2d(const ConvK p) {
 #endif
 }
 
-// k_conv1_h2s: k_conv1_h2 on 128 pixels x 192 channels per workgroup (96 accumulator registers per wave, 56 KB of LDS): TWO workgroups share a CU, so the
-// prologue (the first slab's HBM round trip) and the epilogue of one overlap the main loop of the other - with one 256-pixel workgroup per CU they were ~14 of
-// ~46 us per workgroup (timing ablations, profiles/r05_unet_fill_experiments.md section 7).  Same arithmetic, same weight image, h2s_epilogue.
+// k_conv1_h2s: the 1x1 convolutions of the DEFAULT fp32 mode with fp16x2 products - every operand as two fp16 planes (activations
+// h0 = the value with its low 13 mantissa bits cleared, h1 = the truncated residual: 2^-20; weights nearest-even planes at pack time: 2^-22),
+// x w ~ h1 w0 + h0 w1 + h0 w0 accumulated in fp32.  These layers (ResBlock skips, attention qkv / proj_out, the control tower's zero convolutions)
+// are bound by HBM once they leave the fp32 matrix pipe (a 384->192 layer at 256x256 moves 600 MB for 39 GFLOP): the three products cost nothing
+// next to the memory time, and the fp32 kernel (k_conv_dma, 0.83 of the fp32 matrix peak) takes twice as long.  Error: a CPU emulation of exactly
+// this arithmetic in ALL 1x1 layers of the production network moves its output by 3.1e-6 against the fp32 oracle (scripts/unet_fp16x2_emulation.py;
+// the fp32 kernels sit at 4.5e-6, the parity bound is 5e-5).  K in chunks of 48 input channels, pixel pitch 112 bytes (7 quarters: odd), weights
+// [channel block of 192][chunk of 48][k-step 3][plane 2][wn][fragment nf][lane][8].
+// 128 pixels x 192 channels per workgroup (96 accumulator registers per wave, 56 KB of LDS): TWO workgroups share a CU, so the prologue (the first
+// slab's HBM round trip) and the epilogue of one overlap the main loop of the other - with one 256-pixel workgroup per CU (round 5's k_conv1_h2)
+// they were ~14 of ~46 us per workgroup (timing ablations, profiles/r05_unet_fill_experiments.md section 7).
+constexpr int H2_PITCH = 112;
 constexpr int H2S1_PLANE = 128 * H2_PITCH, H2S1_STAGE = 2 * H2S1_PLANE;          // 14 KB per plane, 28 KB per stage
 constexpr int H2S1_LDS = 2 * H2S1_STAGE > 128 * H2S_EP * 4 ? 2 * H2S1_STAGE : 128 * H2S_EP * 4;
 
@@ -1128,9 +938,9 @@ __global__ __launch_bounds__(256, 2) void k_conv1_h2s(const ConvK p) {
         if (p.cA) {
             for (int c = tid; c < p.Cin; c += 256) { sA[c] = p.cA[(long)img * p.Cin + c]; sB[c] = p.cB[(long)img * p.Cin + c]; }
             __syncthreads();
-        } else sx = wave_uniform(coef_to_lds<HL_ACT_SCALE != 0>(nullptr, nullptr, p.gn, p.N, img, sA, sB, sB + p.Cin, tid, 256));      // (ends with a barrier)
-    } else if (HL_ACT_SCALE && p.xs_max && !p.in16) sx = wave_uniform(pow2_scale_for_bound(p.xs_max[img]));
-    else if (HL_ACT_SCALE && p.xs_gt && !p.in16) sx = wave_uniform(act_scale_totals(p.xs_gt, p.N, img, p.xs_hw));
+        } else sx = wave_uniform(coef_to_lds<true>(nullptr, nullptr, p.gn, p.N, img, sA, sB, sB + p.Cin, tid, 256));      // (ends with a barrier)
+    } else if (p.xs_max && !p.in16) sx = wave_uniform(pow2_scale_for_bound(p.xs_max[img]));
+    else if (p.xs_gt && !p.in16) sx = wave_uniform(act_scale_totals(p.xs_gt, p.N, img, p.xs_hw));
     const float rsx = 1.f / sx;
     kq *= rsx;
 #pragma unroll
@@ -1346,19 +1156,7 @@ int conv_pack_weights_h2(const float *w, int Cout, int Cin, int Cin_pad, int ks,
     else hipLaunchKernelGGL(k_pack_conv1_h2, dim3(512), dim3(256), 0, st, w, Cout, Cin, Cin_pad, static_cast<unsigned short *>(packed), tf, inv);
     return check_launch("k_pack_conv_h2");
 }
-// the 3x3 / stride-1 layers with fp16x2 products (k_conv_h16<true, 2>)
-static size_t conv3_h2_lds_bytes() { return (size_t)2 * H1_STAGE; }   // (two stages of two planes + the dump slot = 93 KB; the epilogue exchange 98 KB)
-static_assert(4 * H16_STAGE + 1024 <= 2 * H1_STAGE, "k_conv_h2 stages");
-int conv3_h2_launch(const ConvK &p, hipStream_t st, int splits) {
-    HL_REQUIRE(p.w_bf3 && p.ks == 3 && conv_h16_applies(p.Hout, p.Wout, p.Cin, p.Cout, p.ks, p.stride, p.ups) && (splits == 1 || p.partial), "k_conv_h2: bad layer");
-    const size_t sh = conv3_h2_lds_bytes();
-    static const bool attr_ok = hipFuncSetAttribute((const void *)k_conv_h16<true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)conv3_h2_lds_bytes()) == hipSuccess;
-    HL_REQUIRE(attr_ok, "k_conv_h2: cannot raise the dynamic LDS limit to %zu bytes", sh);
-    hipLaunchKernelGGL((k_conv_h16<true, 2>), dim3((unsigned)(p.n_mtiles * p.n_nblocks), 1, (unsigned)splits), dim3(256), sh, st, p);
-    return check_launch("k_conv_h2");
-}
-
-// the same layers on the 8x16-pixel tile (two workgroups per CU): p.n_mtiles = pixels / 128
+// the 3x3 / stride-1 layers with fp16x2 products on the 8x16-pixel tile (two workgroups per CU): p.n_mtiles = pixels / 128
 int conv3_h2s_launch(const ConvK &p, hipStream_t st, int splits) {
     HL_REQUIRE(p.w_bf3 && p.ks == 3 && conv_h16_applies(p.Hout, p.Wout, p.Cin, p.Cout, p.ks, p.stride, p.ups) && (splits == 1 || p.partial), "k_conv_h2s: bad layer");
     constexpr int LDS_MAX = H2S_LDS + (2 * 4096 + COEF_SCR_FLOATS) * 4;         // + the coefficient table of a fused GroupNorm (<= 4096 input channels)
@@ -1395,14 +1193,6 @@ int conv1_h2s_launch(const ConvK &p, hipStream_t st, int splits) {
     return check_launch("k_conv1_h2s");
 }
 
-int conv1_h2_launch(const ConvK &p, hipStream_t st) {
-    HL_REQUIRE(p.w_bf3 && conv1_h2_applies(p.Hout, p.Wout, p.Cin, p.Cout, p.ks, p.stride, p.ups) && !p.in16 && !p.partial, "k_conv1_h2: bad layer");
-    static const bool attr_ok = hipFuncSetAttribute((const void *)k_conv1_h2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * H2_STAGE)) == hipSuccess;
-    HL_REQUIRE(attr_ok, "k_conv1_h2: cannot raise the dynamic LDS limit");
-    hipLaunchKernelGGL(k_conv1_h2, dim3((unsigned)(p.n_mtiles * p.n_nblocks)), dim3(256), (size_t)2 * H2_STAGE, st, p);   // 112 KB (the epilogue exchange needs 98 KB)
-    return check_launch("k_conv1_h2");
-}
-
 size_t conv_h16_lds_bytes() { return (size_t)2 * H1_STAGE; }   // 104 KB: the two 1x1 stages (the epilogue exchange needs 98 KB, the 3x3 patch stages 45 KB)
 
 int conv_h16_launch(const ConvK &p, int f16, hipStream_t st, int splits) {
@@ -1412,8 +1202,8 @@ int conv_h16_launch(const ConvK &p, int f16, hipStream_t st, int splits) {
     const size_t sh = conv_h16_lds_bytes();
     static const bool attr_ok = [] {
         const int b = (int)conv_h16_lds_bytes();
-        return hipFuncSetAttribute((const void *)k_conv_h16<true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, b) == hipSuccess &&
-               hipFuncSetAttribute((const void *)k_conv_h16<false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, b) == hipSuccess &&
+        return hipFuncSetAttribute((const void *)k_conv_h16<true>, hipFuncAttributeMaxDynamicSharedMemorySize, b) == hipSuccess &&
+               hipFuncSetAttribute((const void *)k_conv_h16<false>, hipFuncAttributeMaxDynamicSharedMemorySize, b) == hipSuccess &&
                hipFuncSetAttribute((const void *)k_conv1_h16<true>, hipFuncAttributeMaxDynamicSharedMemorySize, b) == hipSuccess &&
                hipFuncSetAttribute((const void *)k_conv1_h16<false>, hipFuncAttributeMaxDynamicSharedMemorySize, b) == hipSuccess;
     }();
@@ -1423,8 +1213,8 @@ int conv_h16_launch(const ConvK &p, int f16, hipStream_t st, int splits) {
         else hipLaunchKernelGGL((k_conv1_h16<false>), grid, dim3(256), sh, st, p);
         return check_launch("k_conv1_h16");
     }
-    if (f16) hipLaunchKernelGGL((k_conv_h16<true, 1>), grid, dim3(256), sh, st, p);
-    else hipLaunchKernelGGL((k_conv_h16<false, 1>), grid, dim3(256), sh, st, p);
+    if (f16) hipLaunchKernelGGL((k_conv_h16<true>), grid, dim3(256), sh, st, p);
+    else hipLaunchKernelGGL((k_conv_h16<false>), grid, dim3(256), sh, st, p);
     return check_launch("k_conv_h16");
 }
 

@@ -31,28 +31,8 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 constexpr float W4_A = 0.75f, W4_B = 1.5f;
 constexpr float W4_C0 = W4_A * W4_A * W4_B * W4_B, W4_C2 = -(W4_A * W4_A + W4_B * W4_B);
 
-#ifndef HL_W4W_SCALAR_FMA
-#define HL_W4W_SCALAR_FMA 0
-#endif
-#ifndef HL_W4W_ABL   // timing ablations (wrong results; 256 no epilogue global traffic, 512 no epilogue LDS exchange): 1 no per-tile barrier, 2 no transform, 4 no weight loads, 8 no patch DMA, 16 no MFMA
-#define HL_W4W_ABL 0
-#endif
-// d = c * x + y on four channels.  Packed (v_pk_fma_f32 x2) or four plain v_fma_f32 (HL_W4W_SCALAR_FMA: the instruction selector would
-// re-pack scalar fmas, so those are written as asm)
-__device__ __forceinline__ f32x4 fma4(float c, f32x4 x, f32x4 y) {
-#if HL_W4W_SCALAR_FMA
-    f32x4 d;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        float r;
-        asm("v_fma_f32 %0, %1, %2, %3" : "=v"(r) : "v"(x[i]), "s"(c), "v"(y[i]));
-        d[i] = r;
-    }
-    return d;
-#else
-    return __builtin_elementwise_fma((f32x4)(c), x, y);
-#endif
-}
+// d = c * x + y on four channels (v_pk_fma_f32 x2)
+__device__ __forceinline__ f32x4 fma4(float c, f32x4 x, f32x4 y) { return __builtin_elementwise_fma((f32x4)(c), x, y); }
 __device__ __forceinline__ f32x2 fma2(float c, f32x2 x, f32x2 y) { return __builtin_elementwise_fma((f32x2)(c), x, y); }
 // one side of the output transform: four outputs from the six frequencies (0, +a, -a, +b, -b, inf), two channels at once
 __device__ __forceinline__ void w4_out(f32x2 m0, f32x2 m1, f32x2 m2, f32x2 m3, f32x2 m4, f32x2 m5, f32x2 (&y)[4]) {
@@ -235,15 +215,6 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino4w(const ConvK p) {
     const __amdgpu_buffer_rsrc_t rsU = __builtin_amdgcn_make_buffer_rsrc(
         (void *)p.w_wino, (short)0, (int)((long)(p.Cout >> 5) * nkt * 36 * 1024), 0x00020000);
 
-#ifndef HL_W4W_STAGGER
-#define HL_W4W_STAGGER 0
-#endif
-    // HL_W4W_STAGGER = n (experiment): the first workgroup of every CU starts (its index / 8 mod 4) * n * 0.9 us late, so that the CUs of an XCD
-    // are not all in their epilogues (256 KB of HBM traffic per workgroup) at the same moment.
-    if (HL_W4W_STAGGER > 0 && blockIdx.x < 256 && gridDim.x >= 512) {
-        const int ph = (blockIdx.x >> 3) & 3;
-        for (int i = 0; i < ph * HL_W4W_STAGGER; ++i) __builtin_amdgcn_s_sleep(32);
-    }
     // accumulators [frequency f of the wave's 3x3 block][32-channel half cb]: tile f*2+cb; tiles 0..15 = the accumulator file, 16 / 17 here
     f32x16 accv[2];
 #pragma unroll
@@ -329,12 +300,8 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino4w(const ConvK p) {
         const unsigned uvp = (unsigned)lane * 16u;
         const int cbstep = nkt * 36 * 1024;                           // second 32-channel half of the workgroup's 64: the next packed block
         const int ubase = ((2 * nb * nkt + kt0) * 36 + W * 9) * 1024; // (k-tile kt0, frequency 0, half 0) of this wave
-#ifndef HL_W4W_RING
-#define HL_W4W_RING 3   // frequency pairs in the weight ring (3 or 6): prefetch distance 24 or 48 MFMAs (measured equal: 120.8 vs 120.2 denoise-steps/s)
-#endif
-        constexpr int RING = HL_W4W_RING;
-        static_assert(RING == 3 || RING == 6, "weight ring");
-        f32x4 U[2 * RING];                                            // global pair g = 9 t + f lives in U[(g % RING) * 2 + cb] (RING 6: the phase alternates with t & 1)
+        constexpr int RING = 3;   // frequency pairs in the weight ring: prefetch distance 24 MFMAs (a ring of 6, 48 MFMAs, measured equal: 120.8 vs 120.2 denoise-steps/s)
+        f32x4 U[2 * RING];                                            // pair f of every k-tile lives in U[(f % RING) * 2 + cb]
         auto load_u = [&](int soffU, auto fc, auto slotc) {           // frequency pair f of the k-tile at soffU -> ring slot
             constexpr int f = decltype(fc)::value, sl = decltype(slotc)::value;
 #pragma unroll
@@ -342,15 +309,10 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino4w(const ConvK p) {
                 U[sl * 2 + cb] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsU, uvp, soffU + f * 1024 + cb * cbstep, 0));
         };
 
-#ifndef HL_W4W_ROTATE
-#define HL_W4W_ROTATE 0
-#endif
-        // HL_W4W_ROTATE = 1 (tried, measured, off): every workgroup walks K from its own starting k-tile and wraps, so that the 32 CUs of
-        // an XCD - which run in step - do not ask the L2 for the SAME weight fragments at the same time (the SQ counters show 10 % of the
-        // wave cycles parked at s_waitcnt although the loads are issued 24 MFMAs ahead).  Result: 15 % SLOWER (1 712 -> 1 970 us at 768
-        // input channels, 519 -> 564 us at 192): the lock-step is what makes one CU's miss everybody else's hit.
-        const int rot = HL_W4W_ROTATE ? (int)(((unsigned)tb * 7u + (unsigned)nb * 3u) % (unsigned)max(ntiles, 1)) : 0;
-        auto tmap = [&](int t) { const int x = min(t, ntiles - 1) + rot; return x >= ntiles ? x - ntiles : x; };   // t-th k-tile this workgroup takes
+        // Every workgroup walks K in the same order.  (Tried, measured, dropped: each workgroup starting from its own k-tile and wrapping, so
+        // that the 32 CUs of an XCD - which run in step - do not ask the L2 for the SAME weight fragments at the same time: 15 % SLOWER, 1 712 ->
+        // 1 970 us at 768 input channels, 519 -> 564 us at 192.  The lock-step is what makes one CU's miss everybody else's hit.)
+        auto tmap = [&](int t) { return min(t, ntiles - 1); };   // t-th k-tile this workgroup takes (past the end: the last one again)
         f32x4 V0[9], V1[9];
         if (ntiles > 0) {
             // prologue: patches 0 and 1 into the two stages, the first six weight pairs, the transform of patch 0 (nothing to overlap it with)
@@ -374,30 +336,27 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino4w(const ConvK p) {
             asm volatile("" ::: "memory");
         }
         // One k-tile = 72 gaps.  MFMA order inside a frequency pair f: (cb0,s0) (cb1,s0) (cb0,s1) ... - consecutive MFMAs never share an
-        // accumulator.  TP = t & 1 fixes the ring phase (9 pairs per k-tile on a ring of 6).  Nothing in the body depends on t otherwise:
-        // past the end the loads re-read the last k-tile and the transform chews on a stale stage.
+        // accumulator.  Nothing in the body depends on t but the addresses: past the end the loads re-read the last k-tile and the transform
+        // chews on a stale stage.
         auto body = [&](auto sc, f32x4 (&Vc)[9], f32x4 (&Vn)[9], int t) {
             constexpr int S = decltype(sc)::value;                    // = t & 1: stage of patch t
             const int tl0 = tmap(t), tl1 = tmap(t + 1), tl2 = tmap(t + 2);
-            const int soffU0 = (HL_W4W_ABL & 64) ? ubase : ubase + tl0 * (36 * 1024), soffU1 = (HL_W4W_ABL & 64) ? ubase : ubase + tl1 * (36 * 1024);   // (64: hot weights)
-            const int soffA2 = (HL_W4W_ABL & 128) ? kt0 * kstep : (kt0 + tl2) * kstep;                                                                   // (128: hot patch)
+            const int soffU0 = ubase + tl0 * (36 * 1024), soffU1 = ubase + tl1 * (36 * 1024);
+            const int soffA2 = (kt0 + tl2) * kstep;
             [&]<int... J>(std::integer_sequence<int, J...>) {
                 ([&] {
                     constexpr int Jc = J, f = J >> 3, idx = J & 7, s = idx >> 1, cb = idx & 1;
-                    constexpr int g = 9 * S + f, us = (g % RING) * 2;     // global pair index (mod 18), its ring slot
-                    if constexpr (!(HL_W4W_ABL & 16)) mfma_tile<f * 2 + cb>(accv[(f * 2 + cb) & 1], Vc[f][s], U[us + cb][s]);
-                    if constexpr ((HL_W4W_ABL & 32) != 0) asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
+                    constexpr int us = (f % RING) * 2;                    // ring slot of pair f
+                    mfma_tile<f * 2 + cb>(accv[(f * 2 + cb) & 1], Vc[f][s], U[us + cb][s]);
                     __builtin_amdgcn_sched_barrier(0);
-                    if constexpr (!(HL_W4W_ABL & 2)) {
-                        // window reads of column step k: one per gap, after the burst that consumed the column buffer
-                        [&]<int... K>(std::integer_sequence<int, K...>) {
-                            ([&] {
-                                if constexpr (Jc >= read_gap(K, 0) && Jc < read_gap(K, 0) + 5)
-                                    tr_read(S ^ 1, std::integral_constant<int, K>{}, std::integral_constant<int, Jc - read_gap(K, 0)>{});
-                                if constexpr (Jc == GAP_BURST0 + K * GAP_BURST_STEP) tr_burst(Vn, std::integral_constant<int, K>{});
-                            }(), ...);
-                        }(std::make_integer_sequence<int, 5>{});
-                    }
+                    // window reads of column step k: one per gap, after the burst that consumed the column buffer
+                    [&]<int... K>(std::integer_sequence<int, K...>) {
+                        ([&] {
+                            if constexpr (Jc >= read_gap(K, 0) && Jc < read_gap(K, 0) + 5)
+                                tr_read(S ^ 1, std::integral_constant<int, K>{}, std::integral_constant<int, Jc - read_gap(K, 0)>{});
+                            if constexpr (Jc == GAP_BURST0 + K * GAP_BURST_STEP) tr_burst(Vn, std::integral_constant<int, K>{});
+                        }(), ...);
+                    }(std::make_integer_sequence<int, 5>{});
                     // The MFMA reads its A / B operands while it runs, and the compiler - to which the asm statement is opaque - hands operand
                     // registers that die at an MFMA to the instructions right behind it (a burst overwrote the weight fragment of the MFMA in
                     // front of it: wrong sums).  The operands of this gap's MFMA and of the one before stay alive to the end of the gap.
@@ -406,24 +365,20 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino4w(const ConvK p) {
                     } else if constexpr (J >= 1) asm volatile("" ::"v"(Vc[f - 1]));
                     asm volatile("" ::"v"(Vc[f]), "v"(U[us + cb]));
                     __builtin_amdgcn_sched_barrier(0);
-                    if constexpr (idx == 7 && !(HL_W4W_ABL & 4)) {   // pair f is consumed: its ring slot takes pair f+3 (of this k-tile or the next)
-                        // (its slot takes pair g + RING: RING pairs = 8 RING MFMAs ahead; patch loads that sit in front of it in the in-order
-                        //  return queue then have that long to land before they can stall a weight wait)
-                        if constexpr (f + RING < 9) load_u(soffU0, std::integral_constant<int, f + RING>{}, std::integral_constant<int, g % RING>{});
-                        else load_u(soffU1, std::integral_constant<int, f + RING - 9>{}, std::integral_constant<int, g % RING>{});
+                    if constexpr (idx == 7) {   // pair f is consumed: its ring slot takes pair f+3 (of this k-tile or the next)
+                        // (RING pairs = 8 RING MFMAs ahead; patch loads that sit in front of it in the in-order return queue then have that
+                        //  long to land before they can stall a weight wait)
+                        if constexpr (f + RING < 9) load_u(soffU0, std::integral_constant<int, f + RING>{}, std::integral_constant<int, f % RING>{});
+                        else load_u(soffU1, std::integral_constant<int, f + RING - 9>{}, std::integral_constant<int, f % RING>{});
                     }
-                    if constexpr (!(HL_W4W_ABL & 8)) {
-                        if constexpr (Jc == GAP_PATCH_LOAD) load_pieces(soffA2);
-                        if constexpr (Jc >= GAP_PATCH_STORE && Jc < GAP_PATCH_STORE + 6) store_piece(S, std::integral_constant<int, Jc - GAP_PATCH_STORE>{});
-                    }
+                    if constexpr (Jc == GAP_PATCH_LOAD) load_pieces(soffA2);
+                    if constexpr (Jc >= GAP_PATCH_STORE && Jc < GAP_PATCH_STORE + 6) store_piece(S, std::integral_constant<int, Jc - GAP_PATCH_STORE>{});
                     __builtin_amdgcn_sched_barrier(0);
                 }(), ...);
             }(std::make_integer_sequence<int, 72>{});
             // patch t+2 is in LDS (this wave's share); all waves are done with stage S^1
-            if constexpr (!(HL_W4W_ABL & 1)) {
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
         };
         using S0 = std::integral_constant<int, 0>;
@@ -460,7 +415,6 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino4w(const ConvK p) {
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
         __syncthreads();
-        if (!((HL_W4W_ABL & 512) && p.Hin != 12345))
         [&]<int... I>(std::integer_sequence<int, I...>) {   // I = (f, cb, rr): accumulator register 8q + rr of tile f*2+cb holds tile 16q + (rr&3) + 8(rr>>2) + 4 half
             ([&] {
                 constexpr int f = I / 16, cb = (I >> 3) & 1, rr = I & 7;
@@ -497,7 +451,6 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino4w(const ConvK p) {
             for (int k = 0; k < 16; ++k) *reinterpret_cast<f32x4 *>(dst + (long)((k >> 2) * Wv + (k & 3)) * p.Cout) = v[k];
             continue;
         }
-        if ((HL_W4W_ABL & 256) && p.Hin != 12345) continue;
         if (p.res) {
             const float *rp = p.res + m0 * p.res_pitch + n;
             f32x4 rr[16];

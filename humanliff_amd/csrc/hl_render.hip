@@ -857,7 +857,7 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_march16(const MarchArgs a
 }
 
 // ---------------------------------------------------------------------------------------------
-// k_march_b3 (round 4): the evaluate pass (FULL + STORE) with the fp32 products formed on the 16-bit matrix pipe WITHOUT leaving fp32
+// bf16x3 (round 4): the evaluate pass (FULL + STORE) with the fp32 products formed on the 16-bit matrix pipe WITHOUT leaving fp32
 // tolerance - both operands of every product are split EXACTLY into three bf16 planes (x = x0 + x1 + x2: 3 x 8 significand bits hold all
 // 24 of an fp32 value; the weights once at pack time, an activation fragment in registers right where k_march16 rounds it to fp16) and
 // the six partial products of weight >= 2^-16 are accumulated in fp32 on v_mfma_f32_32x32x16_bf16; the three dropped terms are below
@@ -868,8 +868,8 @@ __global__ __launch_bounds__(NWV * 64, NWV / 4) void k_march16(const MarchArgs a
 //                 SIMD's fp32 lanes: profiles/r03_microbench_mfma_fill.txt)                                  -> 84k cycles, 0.78 of the peak
 //   this kernel :   792 MFMAs of 32 cycles, and ~5 VALU issues hide behind each (profiles/r04_microbench_mfma16_mix.txt)
 // The three planes are 396 KB: they stream from L2 through an LDS ring, the chunk pair after next staged in registers - the scheme of
-// k_march.  Chunk = 4 fragment positions x 3 planes = the weights of one 8-wide k-group for four output tiles (12 KB).  4 waves per
-// workgroup = one per SIMD (the 512-entry register budget).
+// k_march.  Chunk = 4 fragment positions x 3 planes = the weights of one 8-wide k-group for four output tiles (12 KB).  The kernel is
+// k_march_plw<3> (k_march_b3w, below).
 constexpr int B3_POS = 4, B3_NCH = P16_FRAGS / B3_POS, B3_CH_U4 = B3_POS * 3 * 64;   // positions per chunk, chunks, u32x4 per chunk (12 KB)
 static_assert(P16_FRAGS % B3_POS == 0, "chunking");
 constexpr size_t B3_BYTES = (size_t)P16_FRAGS * 3 * 1024;
@@ -921,402 +921,32 @@ __global__ void k_pack_mlp_h2(PackArgs a, unsigned short *out) {
         if (sidx < per && k < 27) in = k;
     }
     float v = in >= 0 ? a.w[d.w][outu * d.ld + d.col0 + in] : 0.f;
-#ifndef HL_H2_NO_LOG2
     // log2-domain softplus (k_march_plw<2>, see softplus_l2): a layer in front of a softplus produces log2(e) x its pre-activation, a layer behind one
     // consumes log2-unit activations (x ln 2) - for hidden -> hidden layers the two cancel and the planes are those of the unscaled weights
     constexpr float PSC[7] = {1.44269504088896341f, 1.f, 1.44269504088896341f, 1.f, 0.693147180559945309f, 1.44269504088896341f, 1.44269504088896341f};
     v *= PSC[pi];
     v *= a.out[NCH_FULL * CHUNK_FLOATS + SM_SC + d.w];          // the layer's power of two (k_mlp_scales_h2): exact
-#endif
     _Float16 h = (_Float16)v;                                   // nearest even
     if (plane == 1) h = (_Float16)(v - (float)h);               // (the residual is exact in fp32)
     out[idx] = __builtin_bit_cast(unsigned short, h);
 }
 
-// registers 8hi..8hi+7 of an accumulator tile -> three planes of 8 bf16 (v = p0 + p1 + p2 exactly)
-__device__ __forceinline__ unsigned cvt_pk_bf16(float lo, float hi) {
-    unsigned r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-    return r;
-}
-__device__ __forceinline__ void split_b3(const f32x16 &v, int hi, u32x4 (&pl)[3]) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        float x = v[8 * hi + 2 * q], y = v[8 * hi + 2 * q + 1];
-        const unsigned p0 = cvt_pk_bf16(x, y);
-        x -= __builtin_bit_cast(float, p0 << 16); y -= __builtin_bit_cast(float, p0 & 0xffff0000u);
-        const unsigned p1 = cvt_pk_bf16(x, y);
-        x -= __builtin_bit_cast(float, p1 << 16); y -= __builtin_bit_cast(float, p1 & 0xffff0000u);
-        pl[0][q] = p0; pl[1][q] = p1; pl[2][q] = cvt_pk_bf16(x, y);
-    }
-}
-// ---------------------------------------------------------------------------------------------
-// The instruction stream of k_march_b3 is laid out by hand.  Left to itself the compiler keeps the VALU work of a layer (softplus, the three-way
-// split) outside the MFMA groups, where nothing overlaps it (ablations in profiles/r04_render_b3_ablations.md: everything adds up).  Measured
-// with one wave per SIMD (profiles/r04_microbench_mfma16_mix.txt): behind a v_mfma_f32_32x32x16_bf16 five plain VALU issues are free, a gap
-// then costs ~8 + 4.8 cycles per plain instruction, and v_exp / v_log / v_cvt_pk_bf16_f32 / v_accvgpr_read count double.  Hence:
-//   * every MFMA of a chunk is followed by a fixed slice (~5 plain-instruction equivalents) of the work that prepares the NEXT chunk's B
-//     operand: softplus + split of a pair of values = six slices, a raw split = three;
-//   * the split truncates instead of rounding (v_and + v_perm, plain rate; still exact: 3 x 8 bits) and max(x, 0) is a v_max_i32;
-//   * the next chunk's weight fragments are read from LDS one chunk ahead (one ds_read_b128 behind each of the first twelve MFMAs);
-//   * where a chunk's operand depends on the layer that is just finishing, that layer's last chunk runs tile 0 first and prepares the
-//     operand behind the MFMAs of tiles 1..3;
-//   * the ring holds three slots of two chunks (24 KB): one barrier per 48 MFMAs.
-struct B3Op { u32x4 p[3]; };
-struct B3Tmp { float x, y, ex, ey; unsigned hx, hy; };
-template <int N, class F, int... I>
-__device__ __forceinline__ void b3_seq_impl(F &&f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, class F>
-__device__ __forceinline__ void b3_seq(F &&f) { b3_seq_impl<N>(f, std::make_integer_sequence<int, N>{}); }
 __device__ __forceinline__ float b3_max0(float x) { return __builtin_bit_cast(float, max(__builtin_bit_cast(int, x), 0)); }   // v_max_i32: max(x, +0) for every non-NaN x
 __device__ __forceinline__ unsigned b3_hi(float x) { return __builtin_bit_cast(unsigned, x) & 0xffff0000u; }
 __device__ __forceinline__ unsigned b3_pack(float x, float y) { return __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, y), __builtin_bit_cast(unsigned, x), 0x07060302u); }
-// Preparation of pair Q (registers 8H + 2Q, +1 of `src`) of operand `o`, slice T.  KIND 0: raw split, T = 0..2; KIND 1: softplus, then
-// split, T = 0..5; KIND 2: as 1, and the softplus values also feed the density head (asum += value * aw[register]).
-template <int KIND, int H, int Q, int T>
-__device__ __forceinline__ void b3_prep(const f32x16 &src, B3Op &o, B3Tmp &t, float &asum, const float *__restrict__ aw) {
-    constexpr int r = 8 * H + 2 * Q;
-    if constexpr (KIND == 0) {
-        if constexpr (T == 0) { t.x = src[r]; t.y = src[r + 1]; t.hx = b3_hi(t.x); }
-        else if constexpr (T == 1) {
-            t.hy = b3_hi(t.y); o.p[0][Q] = b3_pack(t.x, t.y);
-            t.x -= __builtin_bit_cast(float, t.hx); t.y -= __builtin_bit_cast(float, t.hy); t.hx = b3_hi(t.x);
-        } else {
-            t.hy = b3_hi(t.y); o.p[1][Q] = b3_pack(t.x, t.y);
-            t.x -= __builtin_bit_cast(float, t.hx); t.y -= __builtin_bit_cast(float, t.hy); o.p[2][Q] = b3_pack(t.x, t.y);
-        }
-    } else {
-        if constexpr (T == 0) {
-            t.x = src[r]; t.y = src[r + 1];
-            t.ex = -1.44269504088896341f * fabsf(t.x); t.ey = -1.44269504088896341f * fabsf(t.y);
-        } else if constexpr (T == 1) {
-            t.ex = __builtin_amdgcn_exp2f(t.ex); t.ey = __builtin_amdgcn_exp2f(t.ey); t.ex = 1.f + t.ex;
-        } else if constexpr (T == 2) {
-            t.ey = 1.f + t.ey; t.ex = __builtin_amdgcn_logf(t.ex); t.ey = __builtin_amdgcn_logf(t.ey);
-        } else if constexpr (T == 3) {
-            t.x = fmaf(0.693147180559945309f, t.ex, b3_max0(t.x));
-            t.y = fmaf(0.693147180559945309f, t.ey, b3_max0(t.y));
-            if constexpr (KIND == 2) { const float2 w2 = *reinterpret_cast<const float2 *>(aw + r); asum = fmaf(t.x, w2.x, asum); asum = fmaf(t.y, w2.y, asum); }
-            t.hx = b3_hi(t.x);
-        } else if constexpr (T == 4) {
-            t.hy = b3_hi(t.y); o.p[0][Q] = b3_pack(t.x, t.y);
-            t.x -= __builtin_bit_cast(float, t.hx); t.y -= __builtin_bit_cast(float, t.hy); t.hx = b3_hi(t.x);
-        } else {
-            t.hy = b3_hi(t.y); o.p[1][Q] = b3_pack(t.x, t.y);
-            t.x -= __builtin_bit_cast(float, t.hx); t.y -= __builtin_bit_cast(float, t.hy); o.p[2][Q] = b3_pack(t.x, t.y);
-        }
-    }
-}
-// slice ST of one operand: 4 pairs x (3 | 6) slices
-template <int KIND, int H, int ST>
-__device__ __forceinline__ void b3_prep_step(const f32x16 &src, B3Op &o, B3Tmp &t, float &asum, const float *__restrict__ aw) {
-    constexpr int NS = KIND == 0 ? 3 : 6;
-    if constexpr (ST < 4 * NS) b3_prep<KIND, H, ST / NS, ST % NS>(src, o, t, asum, aw);
-}
-// The 24 MFMAs of a chunk.  NT2 == 4: one k-group (operand oa) x four output tiles (positions 0..3); NT2 == 2: two k-groups (oa, ob) x two
-// tiles (positions 0,1 | 2,3).  TM (tile-major, NT2 == 4): tile 0 completes before tile 1 starts, ...  after(idx) runs behind MFMA idx.
-template <int NT2, bool TM, class ACC, class F>
-__device__ __forceinline__ void b3_chunk(ACC &acc, const B3Op &oa, const B3Op &ob, const u32x4 (&w)[12], F &&after) {
-    constexpr int PW[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0};
-    b3_seq<24>([&](auto ic) {
-        constexpr int idx = decltype(ic)::value;
-        constexpr int i = NT2 == 4 ? (TM ? idx % 6 : idx / 4) : (idx % 12) / 2;
-        constexpr int t = NT2 == 4 ? (TM ? idx / 6 : idx % 4) : (idx & 1);
-        constexpr int q = NT2 == 4 ? t : 2 * (idx / 12) + t;
-        const B3Op &b = (NT2 == 2 && idx >= 12) ? ob : oa;
-        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, w[q * 3 + PW[i]]), __builtin_bit_cast(bf16x8, b.p[PB[i]]), acc[t], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        after(ic);
-        __builtin_amdgcn_sched_barrier(0);
-    });
-}
-constexpr int B3R_NPAIR = (B3_NCH + 1) / 2, B3R_SLOT_U4 = 2 * B3_CH_U4;                     // 17 chunk pairs per sample; 1536 u32x4 = 24 KB per ring slot
-constexpr size_t B3R_LDS = (size_t)3 * B3R_SLOT_U4 * 16 + SMALL_FLOATS * sizeof(float);
-
-template <int ABL>
-__global__ __launch_bounds__(256, 1) void k_march_b3(const MarchArgs a, const unsigned short *__restrict__ packed_b3) {
-    extern __shared__ __attribute__((aligned(16))) float ldsb[];
-    constexpr int NT = 256, NST = B3R_SLOT_U4 / NT;   // threads; u32x4 per thread and chunk pair (6)
-    const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5;
-    const int nwg = gridDim.x, xcd = blockIdx.x & 7, q8 = nwg >> 3, r8 = nwg & 7;
-    const long long wg = (long long)xcd * q8 + (xcd < r8 ? xcd : r8) + (blockIdx.x >> 3);
-    const long long tile = wg * 4 + (tid >> 6);
-    const long long ray = tile * 32 + (lane & 31);
-    const bool valid = ray < a.R;
-    const long long rc = valid ? ray : a.R - 1;
-    const long long tiles_n = (a.R + 31) / 32;
-    const long long zt_base = (tile < tiles_n ? tile : tiles_n - 1) * 32 * (long long)a.S + (lane & 31);
-
-    u32x4 *ring = reinterpret_cast<u32x4 *>(ldsb);
-    float *small = ldsb + 3 * B3R_SLOT_U4 * 4;
-    for (int i = tid; i < SMALL_FLOATS; i += NT) small[i] = a.packed[NCH_FULL * CHUNK_FLOATS + i];
-    // the image is 33 chunks; the 34th (second half of the last pair) lies beyond the buffer's range and loads as zeros - it is never multiplied
-    const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void *)packed_b3, (short)0, (int)B3_BYTES, 0x00020000);
-    const int wv = tid * 16;
-    auto ldw = [&](int u4_index) -> u32x4 { return __builtin_amdgcn_raw_buffer_load_b128(rsw, wv, u4_index * 16, 0); };
-#pragma unroll
-    for (int q = 0; q < 2 * NST; ++q) ring[q * NT + tid] = ldw(q * NT);                       // pairs 0, 1 -> slots 0, 1
-    constexpr bool DMA = (ABL & 2048) != 0;   // developer A/B: the ring filled by LDS-DMA (buffer_load ... lds) instead of loads + ds_write_b128
-    u32x4 st[NST];
-    if constexpr (DMA) {
-#pragma unroll
-        for (int q = 0; q < NST; ++q) ring[2 * B3R_SLOT_U4 + q * NT + tid] = ldw(2 * B3R_SLOT_U4 + q * NT);   // pair 2 -> slot 2
-    } else {
-#pragma unroll
-        for (int q = 0; q < NST; ++q) st[q] = ldw(2 * B3R_SLOT_U4 + q * NT);                  // pair 2 staged
-    }
-    int pslot = 0;                                                                            // ring slot (0..2) of the pair being multiplied
-
-    const float ox = a.rays_o[rc * 3 + 0], oy = a.rays_o[rc * 3 + 1], oz = a.rays_o[rc * 3 + 2];
-    const float dx = a.rays_d[rc * 3 + 0], dy = a.rays_d[rc * 3 + 1], dz = a.rays_d[rc * 3 + 2];
-    const float nr = a.near[rc], fr_ = a.far[rc];
-    const int S = a.S;
-    const float offH = (float)(1.0 / (double)a.H);
-    const float bmin0 = a.bounds[0], bmin1 = a.bounds[1], bmin2 = a.bounds[2];
-    const float bext0 = a.bounds[3] - bmin0, bext1 = a.bounds[4] - bmin1, bext2 = a.bounds[5] - bmin2;
-
-    B3Op bev0, bev1;
-    {
-        f32x16 ev;
-        const float nrm = sqrtf(dx * dx + dy * dy + dz * dz);
-        const float vd[3] = {dx / nrm, dy / nrm, dz / nrm};
-#pragma unroll
-        for (int s = 0; s < 16; ++s) {
-            float val = 0.f;
-            if (s < 14) {
-                const int kl = s, kh = s + 14;
-                const int jl = (kl - 3) / 3, cl = (kl - 3) % 3, jh = (kh - 3) / 3, ch = (kh - 3) % 3;
-                const float argl = kl < 3 ? 0.f : ((jl & 1) ? 1.57079632679489661923f : 0.f) + vd[kl < 3 ? 0 : cl] * (float)(1 << (jl >> 1));
-                const float argh = ((jh & 1) ? 1.57079632679489661923f : 0.f) + vd[ch] * (float)(1 << (jh >> 1));
-                if (kl < 3) {
-                    const float sh = sinf(argh);
-                    val = half ? sh : vd[kl];
-                } else if (kh >= 27) {
-                    const float sl = sinf(argl);
-                    val = half ? 0.f : sl;
-                } else {
-                    val = sinf(half ? argh : argl);
-                }
-            }
-            ev[s] = val;
-        }
-        split_b3(ev, 0, bev0.p);
-        split_b3(ev, 1, bev1.p);
-    }
-
-    float zc;
-    if (a.z) zc = a.z_tiled ? a.z[zt_base] : a.z[rc * S];
-    else zc = nr * (1.f - linspace01(0, S)) + fr_ * linspace01(0, S);
-    __syncthreads();
-    u32x4 w[12];                                                                              // fragments of the current chunk
-#pragma unroll
-    for (int i = 0; i < 12; ++i) w[i] = ring[i * 64 + lane];
-
-    // Ring while pair P (chunks 2P, 2P+1) is multiplied: its slot and the next pair's are complete and visible; the slot of pair P-1 takes
-    // the staged pair P+2 right after the barrier that opens P, the staging registers then receive pair P+3.  A chunk's fragments are read
-    // into registers behind the MFMAs of the chunk before it.
-    // run(g, ...): [g even: barrier, ring write, loads] the 24 MFMAs of chunk g with their slices and the fragment reads of chunk g+1.
-    const float *aw = small + SM_AW;
-    auto run = [&](auto gc, auto nt2c, auto tmc, auto &acc, const B3Op &oa, const B3Op &ob, auto &&slice) {
-        constexpr int g = decltype(gc)::value, NT2 = decltype(nt2c)::value;
-        constexpr bool TM = decltype(tmc)::value;
-        constexpr bool last_of_pair = (g & 1) || g == B3_NCH - 1;
-        const int s_cur = pslot * B3R_SLOT_U4, s_nxt = (pslot == 2 ? 0 : pslot + 1) * B3R_SLOT_U4, s_old = (pslot == 0 ? 2 : pslot - 1) * B3R_SLOT_U4;
-        constexpr bool ring_here = !(ABL & 4) && (g & 1) == 0;       // the first chunk of a pair carries the ring traffic
-        if constexpr (ring_here && DMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of the pair requested one pair ago have landed
-        if constexpr (ring_here && !(ABL & 64)) __syncthreads();      // (64: timing only - no barrier; 128: no ring traffic; 512: no LDS writes; 1024: no loads)
-        const u32x4 *nxt = ring + ((ABL & 4) ? 0 : (last_of_pair ? s_nxt : s_cur + B3_CH_U4));
-        u32x4 wn[12];
-        b3_chunk<NT2, TM>(acc, oa, ob, w, [&](auto ic) {
-            constexpr int idx = decltype(ic)::value;
-            if constexpr (idx < 12) wn[idx] = nxt[idx * 64 + lane];
-            // ring traffic one instruction per gap (in a burst behind the barrier each ds_write_b128 cost ~100 cycles: profiles/r04_render_b3_ablations.md)
-            if constexpr (DMA) {
-                if constexpr (ring_here && !(ABL & 128) && idx >= 12 && idx < 12 + NST)
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (__attribute__((address_space(3))) void *)(ring + s_old + (idx - 12) * NT + (tid & ~63)), 16, lane * 16,
-                                                             (((g / 2 + 2) % B3R_NPAIR) * B3R_SLOT_U4 + (idx - 12) * NT) * 16 + (tid & ~63) * 16, 0, 0);
-            } else {
-                if constexpr (ring_here && !(ABL & 128) && idx >= 12 && idx < 12 + NST) {
-                    if constexpr (!(ABL & 512)) ring[s_old + (idx - 12) * NT + tid] = st[idx - 12];
-                    else asm volatile("" ::"v"(st[idx - 12]));
-                }
-                if constexpr (ring_here && !(ABL & 128) && !(ABL & 1024) && idx >= 12 + NST && idx < 12 + 2 * NST)
-                    st[idx - 12 - NST] = ldw(((g / 2 + 3) % B3R_NPAIR) * B3R_SLOT_U4 + (idx - 12 - NST) * NT);
-            }
-            if constexpr (!(ABL & 256)) slice(ic);                   // (256: timing only - no operand preparation behind the MFMAs)
-        });
-#pragma unroll
-        for (int i = 0; i < 12; ++i) w[i] = wn[i];
-        if constexpr (last_of_pair) pslot = pslot == 2 ? 0 : pslot + 1;
-    };
-    using I0 = std::integral_constant<int, 0>;
-    auto none = [](auto) {};
-    using C4 = std::integral_constant<int, 4>;
-    using C2 = std::integral_constant<int, 2>;
-    using TMy = std::true_type;
-    using TMn = std::false_type;
-
-    for (int s = 0; s < S; ++s) {
-        float zn = 0.f;
-        if (s + 1 < S) {
-            if (a.z) zn = a.z_tiled ? a.z[zt_base + 32LL * (s + 1)] : a.z[rc * S + s + 1];
-            else { const float t = linspace01(s + 1, S); zn = nr * (1.f - t) + fr_ * t; }
-        }
-        // ---- tri-plane features of this half (fp32, exactly as k_march)  [renderer.py:502-531] ----
-        const float px = ox + dx * zc, py = oy + dy * zc, pz = oz + dz * zc;
-        const float nx = 2.f * (px - bmin0) / bext0 - 1.f;
-        const float ny = 2.f * (py - bmin1) / bext1 - 1.f;
-        const float nz = 2.f * (pz - bmin2) / bext2 - 1.f;
-        f32x16 f;
-        f[15] = 0.f;
-        if constexpr (ABL & 1) {
-#pragma unroll
-            for (int i = 0; i < 15; ++i) f[i] = nx * (float)i + ny;
-        } else
-#pragma unroll
-        for (int i = 0; i < 5; ++i) {
-            const int qlo = i, qhi = (i + 5 > 8) ? 8 : i + 5;
-            const int q = half ? qhi : qlo;
-            const int p = half ? qhi / 3 : qlo / 3, g = half ? qhi % 3 : qlo % 3;
-            float gu = (p == 2) ? nz : nx;
-            float gv = (p == 1) ? nz : ny;
-            gu = (g == 1) ? gu + offH : gu;
-            gv = (g == 2) ? gv + offH : gv;
-            const float ix = ((gu + 1.f) * (float)a.W - 1.f) / 2.f;
-            const float iy = ((gv + 1.f) * (float)a.H - 1.f) / 2.f;
-            const float x0f = floorf(ix), y0f = floorf(iy);
-            const float x1f = x0f + 1.f, y1f = y0f + 1.f;
-            float w_nw = (x1f - ix) * (y1f - iy), w_ne = (ix - x0f) * (y1f - iy);
-            float w_sw = (x1f - ix) * (iy - y0f), w_se = (ix - x0f) * (iy - y0f);
-            const int x0 = (int)x0f, y0 = (int)y0f, x1 = x0 + 1, y1 = y0 + 1;
-            const bool vx0 = (x0 >= 0) & (x0 < a.W), vx1 = (x1 >= 0) & (x1 < a.W);
-            const bool vy0 = (y0 >= 0) & (y0 < a.H), vy1 = (y1 >= 0) & (y1 < a.H);
-            w_nw = (vx0 & vy0) ? w_nw : 0.f;
-            w_ne = (vx1 & vy0) ? w_ne : 0.f;
-            w_sw = (vx0 & vy1) ? w_sw : 0.f;
-            w_se = (vx1 & vy1) ? w_se : 0.f;
-            const int cx0 = min(max(x0, 0), a.W - 1), cx1 = min(max(x1, 0), a.W - 1);
-            const int cy0 = min(max(y0, 0), a.H - 1), cy1 = min(max(y1, 0), a.H - 1);
-            const float4 *pl = a.planes + (long long)q * a.H * a.W;
-            const float4 t_nw = pl[cy0 * a.W + cx0], t_ne = pl[cy0 * a.W + cx1];
-            const float4 t_sw = pl[cy1 * a.W + cx0], t_se = pl[cy1 * a.W + cx1];
-            const bool live = half ? (i + 5 <= 8) : true;
-            const float r0 = t_nw.x * w_nw + t_ne.x * w_ne + t_sw.x * w_sw + t_se.x * w_se;
-            const float r1 = t_nw.y * w_nw + t_ne.y * w_ne + t_sw.y * w_sw + t_se.y * w_se;
-            const float r2 = t_nw.z * w_nw + t_ne.z * w_ne + t_sw.z * w_sw + t_se.z * w_se;
-            f[3 * i + 0] = live ? r0 : 0.f;
-            f[3 * i + 1] = live ? r1 : 0.f;
-            f[3 * i + 2] = live ? r2 : 0.f;
-        }
-        B3Op bf0, bf1, oa, ob;                                     // feature operands; the operands in flight
-        if constexpr (ABL & 256) { oa = bev0; ob = bev1; bf1 = bev0; }
-        B3Tmp tm;
-        float asum = 0.f, dummy = 0.f;
-        b3_seq<12>([&](auto ic) { b3_prep_step<0, 0, decltype(ic)::value>(f, bf0, tm, dummy, aw); });
-        // ---- MLP  [renderer.py:134-156]: chunk g = fragment positions 4g .. 4g+3 ----
-        f32x16 X[4], Y[4];
-        load_bias<4>(X, small + SM_B0, half);
-        // L0 (chunks 0, 1).  Behind chunk 0: the split of the features' second half; chunk 1 tile-major, behind tiles 1..3: X[0] half 0
-        run(I0{}, C4{}, TMn{}, X, bf0, bf0, [&](auto ic) { b3_prep_step<0, 1, decltype(ic)::value>(f, bf1, tm, dummy, aw); });
-        run(std::integral_constant<int, 1>{}, C4{}, TMy{}, X, bf1, bf1, [&](auto ic) {
-            constexpr int i = decltype(ic)::value;
-            if constexpr (i >= 6) {   // 24 slices behind 18 MFMAs: 4 slices per 3 gaps
-                constexpr int lo = (4 * (i - 6)) / 3, hi = (4 * (i - 5)) / 3;
-                b3_seq<hi - lo>([&](auto uc) { b3_prep_step<1, 0, lo + decltype(uc)::value>(X[0], oa, tm, dummy, aw); });
-            }
-        });
-        load_bias<4>(Y, small + SM_B1, half);
-        // L1 (chunks 2..9): chunk 2 + 2k + h takes softplus(X[k]) half h; the operand of the next chunk is prepared behind this one's MFMAs
-        b3_seq<8>([&](auto jc) {
-            constexpr int j = decltype(jc)::value, k = j >> 1, h = j & 1;      // this chunk: (k, h); next: (k + h, h ^ 1)
-            constexpr int kn = k + h, hn = h ^ 1;
-            if constexpr (h == 0) run(std::integral_constant<int, 2 + j>{}, C4{}, TMn{}, Y, oa, oa, [&](auto ic) { b3_prep_step<1, hn, decltype(ic)::value>(X[kn < 4 ? kn : 3], ob, tm, dummy, aw); });
-            else if constexpr (kn < 4) run(std::integral_constant<int, 2 + j>{}, C4{}, TMn{}, Y, ob, ob, [&](auto ic) { b3_prep_step<1, hn, decltype(ic)::value>(X[kn < 4 ? kn : 3], oa, tm, dummy, aw); });
-            else run(std::integral_constant<int, 2 + j>{}, C4{}, TMn{}, Y, ob, ob, none);
-        });
-        // L2, feature part (chunks 10, 11); behind chunk 11: softplus(Y[0]) half 0
-        load_bias<4>(X, small + SM_B2, half);
-        run(std::integral_constant<int, 10>{}, C4{}, TMn{}, X, bf0, bf0, none);
-        run(std::integral_constant<int, 11>{}, C4{}, TMn{}, X, bf1, bf1, [&](auto ic) { b3_prep_step<1, 0, decltype(ic)::value>(Y[0], oa, tm, dummy, aw); });
-        // L2, hidden part (chunks 12..19); the last chunk tile-major with softplus(X[0]) half 0 (-> density head + feature_linear) behind tiles 1..3
-        b3_seq<8>([&](auto jc) {
-            constexpr int j = decltype(jc)::value, k = j >> 1, h = j & 1;
-            constexpr int kn = k + h, hn = h ^ 1;
-            if constexpr (h == 0) run(std::integral_constant<int, 12 + j>{}, C4{}, TMn{}, X, oa, oa, [&](auto ic) { b3_prep_step<1, hn, decltype(ic)::value>(Y[kn < 4 ? kn : 3], ob, tm, dummy, aw); });
-            else if constexpr (kn < 4) run(std::integral_constant<int, 12 + j>{}, C4{}, TMn{}, X, ob, ob, [&](auto ic) { b3_prep_step<1, hn, decltype(ic)::value>(Y[kn < 4 ? kn : 3], oa, tm, dummy, aw); });
-            else run(std::integral_constant<int, 12 + j>{}, C4{}, TMy{}, X, ob, ob, [&](auto ic) {
-                constexpr int i = decltype(ic)::value;
-                if constexpr (i >= 6) {
-                    constexpr int lo = (4 * (i - 6)) / 3, hi = (4 * (i - 5)) / 3;
-                    b3_seq<hi - lo>([&](auto uc) { b3_prep_step<2, 0, lo + decltype(uc)::value>(X[0], oa, tm, asum, aw + (0 * 2 + half) * 16); });
-                }
-            });
-        });
-        // feature_linear (chunks 20..27): softplus(X[k]) half h (the density head rides along); the last chunk tile-major with the raw split of
-        // Y[0] (both halves: the two k-groups of chunk 28) behind tiles 1..3
-        load_bias<4>(Y, small + SM_BF, half);
-        B3Op oc, od;
-        if constexpr (ABL & 256) { oc = bev0; od = bev1; }
-        b3_seq<8>([&](auto jc) {
-            constexpr int j = decltype(jc)::value, k = j >> 1, h = j & 1;
-            constexpr int kn = k + h, hn = h ^ 1;
-            if constexpr (h == 0) run(std::integral_constant<int, 20 + j>{}, C4{}, TMn{}, Y, oa, oa, [&](auto ic) { b3_prep_step<2, hn, decltype(ic)::value>(X[kn < 4 ? kn : 3], ob, tm, asum, aw + ((kn < 4 ? kn : 3) * 2 + half) * 16); });
-            else if constexpr (kn < 4) run(std::integral_constant<int, 20 + j>{}, C4{}, TMn{}, Y, ob, ob, [&](auto ic) { b3_prep_step<2, hn, decltype(ic)::value>(X[kn < 4 ? kn : 3], oa, tm, asum, aw + ((kn < 4 ? kn : 3) * 2 + half) * 16); });
-            else run(std::integral_constant<int, 20 + j>{}, C4{}, TMy{}, Y, ob, ob, [&](auto ic) {
-                constexpr int i = decltype(ic)::value;
-                if constexpr (i >= 6) {   // 2 x 12 slices behind 18 MFMAs
-                    constexpr int lo = (4 * (i - 6)) / 3, hi = (4 * (i - 5)) / 3;
-                    b3_seq<hi - lo>([&](auto uc) {
-                        constexpr int st_ = lo + decltype(uc)::value;
-                        if constexpr (st_ < 12) b3_prep_step<0, 0, st_>(Y[0], oc, tm, dummy, aw);
-                        else b3_prep_step<0, 1, st_ - 12>(Y[0], od, tm, dummy, aw);
-                    });
-                }
-            });
-        });
-        const float sigma_raw = (asum + __shfl_xor(asum, 32)) + small[SM_AB];
-        // views_linear, feature part (chunks 28..31: two k-groups x two tiles each), then the direction encoding (chunk 32)
-        f32x16 V[2];
-        load_bias<2>(V, small + SM_BV, half);
-        b3_seq<4>([&](auto kc) {
-            constexpr int k = decltype(kc)::value;
-            auto prep2 = [&](auto ic) {   // the two operands of chunk 28 + k + 1: 2 x 12 slices behind 24 MFMAs
-                constexpr int i = decltype(ic)::value;
-                if constexpr (k < 3) {
-                    B3Op &na = (k & 1) ? oc : oa, &nb = (k & 1) ? od : ob;
-                    if constexpr (i < 12) b3_prep_step<0, 0, i>(Y[k + 1 < 4 ? k + 1 : 3], na, tm, dummy, aw);
-                    else b3_prep_step<0, 1, i - 12>(Y[k + 1 < 4 ? k + 1 : 3], nb, tm, dummy, aw);
-                }
-            };
-            if constexpr ((k & 1) == 0) run(std::integral_constant<int, 28 + k>{}, C2{}, TMn{}, V, oc, od, prep2);
-            else run(std::integral_constant<int, 28 + k>{}, C2{}, TMn{}, V, oa, ob, prep2);
-        });
-        run(std::integral_constant<int, 32>{}, C2{}, TMn{}, V, bev0, bev1, none);
-        V[0] = softplus16(V[0]);
-        V[1] = softplus16(V[1]);
-        const float cr = dot_lane<2>(V, small + SM_RW, half) + small[SM_RB + 0];
-        const float cg = dot_lane<2>(V, small + SM_RW + 64, half) + small[SM_RB + 1];
-        const float cb = dot_lane<2>(V, small + SM_RW + 128, half) + small[SM_RB + 2];
-        if (tile * 32 < a.R) {   // lanes 0-31 store (sigma, r), lanes 32-63 (g, b); hidden store: see k_march
-            const float2 rec = half ? make_float2(cg, cb) : make_float2(sigma_raw, cr);
-            float *dst = reinterpret_cast<float *>(a.vals_out + (zt_base + 32LL * s)) + 2 * half;
-            asm volatile("global_store_dwordx2 %0, %1, off" : : "v"(dst), "v"(rec) : "memory");
-        }
-        zc = zn;
-    }
-}
 
 // ---------------------------------------------------------------------------------------------
-// k_march_b3w: the same arithmetic with EIGHT waves per workgroup (two per SIMD, 256 registers each), compiler-scheduled.  The partner wave
-// covers what one wave per SIMD has to schedule by hand (LDS and L2 latencies, the VALU phases between MFMA groups), and 256 rays share every
-// weight chunk that goes through LDS - half the ring traffic per ray, which is what bounds k_march_b3 (profiles/r04_render_b3_ablations.md).
+// k_march_b3w: the bf16x3 arithmetic with EIGHT waves per workgroup (two per SIMD, 256 registers each), compiler-scheduled.  The partner wave
+// covers what one wave per SIMD had to schedule by hand in round 4's k_march_b3 (LDS and L2 latencies, the VALU phases between MFMA groups), and
+// 256 rays share every weight chunk that goes through LDS - half the ring traffic per ray, which is what bounded k_march_b3
+// (profiles/r04_render_b3_ablations.md).
 constexpr int B3W_NPAIR = (B3_NCH - 1) / 2;                                               // 16 chunk pairs per sample: chunk 32 (direction encoding) runs once per ray
 // NPL = operand planes: 3 = bf16x3 (six partial products), 2 = fp16x2 (three partial products, below)
 template <int NPL> constexpr int PLW_CH_U4 = B3_POS * NPL * 64;            // u32x4 per chunk (4 fragment positions x NPL planes x 64 lanes)
 template <int NPL> constexpr int PLW_SLOT_U4 = 2 * PLW_CH_U4<NPL>;         // a ring slot = a PAIR of chunks (24 KB / 16 KB)
 template <int NPL> constexpr size_t PLW_BYTES = (size_t)P16_FRAGS * NPL * 1024;
 template <int NPL> constexpr size_t PLW_LDS = (size_t)2 * PLW_SLOT_U4<NPL> * 16 + SMALL_FLOATS * sizeof(float) + (size_t)8 * 512 * 16;
-template <int NPL> constexpr size_t PLW_LDS_FUSE = PLW_LDS<NPL> + (size_t)8 * 4 * 64 * 16;      // (HL_FUSE_LQ: + the gathered coarse records, [wave 8][4][64 lanes] x 16 bytes)
+template <int NPL> constexpr size_t PLW_LDS_FUSE = PLW_LDS<NPL> + (size_t)8 * 4 * 64 * 16;      // (the one-pass launch: + 32 KB, [wave 8][4][64 lanes] x 16 bytes, sized for a gathered-record variant measured in round 6 and not taken; one workgroup per CU either way)
 constexpr size_t B3W_LDS = PLW_LDS<3>;
 template <int NT>
 __device__ __forceinline__ void load_bias_global(f32x16 (&acc)[NT], const float *__restrict__ tbl, int half) {   // load_bias from the packed image in global memory
@@ -1345,15 +975,12 @@ __device__ __forceinline__ void split_b3t(const f32x16 &v, int hi, u32x4 (&pl)[3
 // Round 6: rs = the inverse of the power of two the layer's weight planes carry (k_mlp_scales_h2): the accumulators hold x' / rs.  And the large-x branch of
 // F.softplus (threshold 20: returns x): 2^x' overflows at x' = 128 (a pre-activation of 88.7) and round 5 returned inf there; now y' = med3(L, x', 128) with
 // L = log2(1 + 2^x'): for x' < 128, x' <= L <= 128 and the median is L; beyond, L = inf and the median is x' - one v_med3_f32, no compare / select.
-#ifndef HL_SP_NOCLAMP
-#define HL_SP_NOCLAMP 0
-#endif
 template <int I0, int I1>
 __device__ __forceinline__ void softplus_l2_r(f32x16 &v, float rs) {
 #pragma unroll
     for (int i = I0; i < I1; ++i) {
         const float x = v[i] * rs, l = __builtin_amdgcn_logf(1.f + __builtin_amdgcn_exp2f(x));
-        v[i] = HL_SP_NOCLAMP ? l : __builtin_amdgcn_fmed3f(l, x, 128.f);
+        v[i] = __builtin_amdgcn_fmed3f(l, x, 128.f);
     }
 }
 template <int I0, int I1>
@@ -1402,39 +1029,24 @@ __device__ __forceinline__ void mma_b3(f32x16 (&acc)[NT], const u32x4 (&b)[3], c
 // plain fp32 (profiles/r05_render_fp16x2.md).  h0 = the value with its low 13 mantissa bits cleared (v_and: what a round-toward-zero conversion
 // to fp16 keeps), so the residual x - h0 is exact in fp32; both planes packed by v_cvt_pkrtz_f16_f32.  Range: |x| < 65504 (fp16); values below
 // 2^-14 keep an ABSOLUTE error of 2^-24.
-#ifndef HL_RENDER_SPLIT_RNE
-// 1 (round 6, measured three times and NOT taken): nearest-even planes - h0 = the nearest fp16, h1 = the nearest fp16 of the residual (2^-24; a value beyond fp16
+// Round 6, measured three times and NOT taken: nearest-even planes - h0 = the nearest fp16, h1 = the nearest fp16 of the residual (2^-24; a value beyond fp16
 // becomes inf / NaN).  With hl_split2_rne's four-instruction form (hl_common.h) the kernels issue 7 % fewer vector instructions than with the truncating split below
 // (7802 against 8385 in k_march_plw<2>) and every instruction involved issues at full rate (scripts/microbench/valu_rate.hip), yet a view takes 26.67 ms against
 // 25.90 on the same box - also in the build where no kernel spills (the coarse kernel takes the compiler's five-instruction form, split_h2t<1>: with the asm form
 // its sample loop needs 84 bytes of scratch).  The staging of these kernels is placed between the MFMAs by instruction class (sched_group_barrier), and an asm
-// statement belongs to no class.
-// 0: round 5's truncating split (h0 = the low 13 mantissa bits cleared, v_cvt_pkrtz: 2^-20, saturates silently - the clamped softplus and the sigma / rgb heads
-// keep the renderer's activations far inside fp16's range).
-#define HL_RENDER_SPLIT_RNE 0
-#endif
-template <int MODE = 0>   // 0: truncating; 1: nearest, left to the compiler (five instructions per pair); 2: nearest, hl_split2_rne's four - the same planes as 1, bit for bit
+// statement belongs to no class.  So round 5's truncating split stays (h0 = the low 13 mantissa bits cleared, v_cvt_pkrtz: 2^-20, saturates silently - the
+// clamped softplus and the sigma / rgb heads keep the renderer's activations far inside fp16's range).
 __device__ __forceinline__ void split_h2t(const f32x16 &v, int hi, u32x4 (&pl)[2]) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const float x = v[8 * hi + 2 * q], y = v[8 * hi + 2 * q + 1];
-        if constexpr (MODE == 2) {
-            unsigned w0, w1;
-            hl_split2_rne(x, y, w0, w1);
-            pl[0][q] = w0; pl[1][q] = w1;
-        } else if constexpr (MODE == 1) {
-            unsigned w0, w1;
-            hl_split2_rne_c(x, y, w0, w1);
-            pl[0][q] = w0; pl[1][q] = w1;
-        } else {
-            const float hx = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, x) & 0xffffe000u), hy = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, y) & 0xffffe000u);
-            pl[0][q] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(hx, hy));
-            pl[1][q] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(x - hx, y - hy));
-        }
+        const float hx = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, x) & 0xffffe000u), hy = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, y) & 0xffffe000u);
+        pl[0][q] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(hx, hy));
+        pl[1][q] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(x - hx, y - hy));
     }
 }
-template <int MODE = 0> __device__ __forceinline__ void split_plt(const f32x16 &v, int hi, u32x4 (&pl)[3]) { split_b3t(v, hi, pl); }
-template <int MODE = 0> __device__ __forceinline__ void split_plt(const f32x16 &v, int hi, u32x4 (&pl)[2]) { split_h2t<MODE>(v, hi, pl); }
+__device__ __forceinline__ void split_plt(const f32x16 &v, int hi, u32x4 (&pl)[3]) { split_b3t(v, hi, pl); }
+__device__ __forceinline__ void split_plt(const f32x16 &v, int hi, u32x4 (&pl)[2]) { split_h2t(v, hi, pl); }
 // NT output tiles x one 8-wide k-group for NPL planes: the partial products, smallest first, two tiles at a time
 template <int NT, int NPL>   // (both deduced from the arguments: the call sites sit inside macro arguments, where a template comma would split them)
 __device__ __forceinline__ void mma_pl(f32x16 (&acc)[NT], const u32x4 (&b)[NPL], const u32x4 *__restrict__ ch, int q0, int lane) {
@@ -1612,10 +1224,8 @@ __device__ __forceinline__ void importance_tile(const float4 *__restrict__ vc_ti
     }
 }
 
-#ifndef HL_H2_K
-#define HL_H2_K 4   // VALU instructions asked for behind every MFMA of a hidden-layer chunk in the fp16x2 kernel (12 MFMAs, ~48 VALU of preparation with the
-                    // log2-domain softplus; same box, ms per 512x512 view: 3: 25.56, 4: 25.74, 5: 25.81 - 26.00, 6: 26.35; natural-log softplus at 5: 26.71)
-#endif
+constexpr int HL_H2_K = 4;   // VALU instructions asked for behind every MFMA of a hidden-layer chunk in the fp16x2 kernel (12 MFMAs, ~48 VALU of preparation with the
+                             // log2-domain softplus; same box, ms per 512x512 view: 3: 25.56, 4: 25.74, 5: 25.81 - 26.00, 6: 26.35; natural-log softplus at 5: 26.71)
 // ACTS (training; round 5): the evaluate pass of the fitting step on this kernel - every activation of the MLP is also written to the
 // activation matrix (row = unit, column = sample point; the rows k_mlp_bwd and k_wgrad read), a workgroup takes the sample range blockIdx.y * s_per ... of its 256 rays
 // (a fitting batch has few rays), one workgroup per CU (the stores need registers).  Softplus outputs are stored in natural units (x ln 2 in the log2 domain).
@@ -1628,15 +1238,10 @@ __device__ __forceinline__ void importance_tile(const float4 *__restrict__ vc_ti
 template <int NPL, bool ACTS = false, bool FUSE = false>
 __global__ __launch_bounds__(512, ACTS ? 1 : 2) void k_march_plw(const MarchArgs a, const unsigned short *__restrict__ packed_b3) {
     static_assert(!(ACTS && FUSE), "the training pass stores records");
-    constexpr int SPL = !HL_RENDER_SPLIT_RNE ? 0 : ((ACTS || FUSE) ? 2 : 1);   // (the coarse kernel's register allocation spills with the asm form; the planes are the same)
-    constexpr int B3R_SLOT_U4 = PLW_SLOT_U4<NPL>, B3_CH_U4 = PLW_CH_U4<NPL>;      // (shadow the bf16x3 constants of k_march_b3)
+    constexpr int B3R_SLOT_U4 = PLW_SLOT_U4<NPL>, B3_CH_U4 = PLW_CH_U4<NPL>;      // (the ring geometry of NPL planes, named as the B3_* macros below use it)
     constexpr size_t B3_BYTES = PLW_BYTES<NPL>;
     constexpr int NMF = NPL == 3 ? 24 : 12;                                        // MFMAs of a chunk (4 tiles x 6 | 3 products)
-#ifndef HL_H2_NO_LOG2
     constexpr bool LOG2D = NPL == 2;                                               // softplus in the log2 domain (softplus_l2_r; scaled planes and tables)
-#else
-    constexpr bool LOG2D = false;
-#endif
     constexpr float L2E = 1.44269504088896341f, LN2 = 0.693147180559945309f;
     extern __shared__ __attribute__((aligned(16))) float ldsb[];   // [ring: 2 x 24 KB][small 4 KB][per wave: the 2 x 16 x 64 accumulator image of views_linear's bias + direction part, 8 KB]
     constexpr int NT = 512, NST = B3R_SLOT_U4 / NT;   // threads; u32x4 per thread and chunk pair (3 | 2)
@@ -1667,7 +1272,7 @@ __global__ __launch_bounds__(512, ACTS ? 1 : 2) void k_march_plw(const MarchArgs
     }
     const u32x4 *gb3 = reinterpret_cast<const u32x4 *>(packed_b3);
     if constexpr (FUSE) {   // phase B: this wave's importance depths
-        if (tile < tiles_n && !(a.flags & 0x10000u)) {             // (0x10000: developer timing switch - the depths of an earlier call are still in the scratch)
+        if (tile < tiles_n) {
             // (LDS: the weights / cdf and the depths of the ray in the wave's share of the weight ring, not yet loaded; the half-tile stage of the sorted depths -
             //  8 KB - in the wave's vinit block, not yet written)
             float *s_w = reinterpret_cast<float *>(ring) + (tid >> 6) * 384, *s_z = s_w + 128;
@@ -1722,8 +1327,8 @@ __global__ __launch_bounds__(512, ACTS ? 1 : 2) void k_march_plw(const MarchArgs
             }
             ev[s] = val;
         }
-        split_plt<SPL>(ev, 0, bev0);
-        split_plt<SPL>(ev, 1, bev1);
+        split_plt(ev, 0, bev0);
+        split_plt(ev, 1, bev1);
         if constexpr (ACTS) {   // the encoding is a row block of the activation matrix, the same for every sample of the ray: written here for the whole sample range
             const int s_lo_ = (int)blockIdx.y * a.s_per, s_hi_ = min(a.S, s_lo_ + a.s_per);
             const unsigned as4 = (unsigned)a.act_stride * 4u;
@@ -1839,38 +1444,6 @@ __global__ __launch_bounds__(512, ACTS ? 1 : 2) void k_march_plw(const MarchArgs
     // Every coarse sample at or in front of zlim.  The record at the cursor was requested while views_linear ran; inside a run every further record costs a round trip
     // to L2 (measured alternatives: two / four records requested together need 4 / 8 more registers from the views stage on and the allocator starts to spill -
     // 6 ... 25 registers of scratch - which costs more than the round trips: every reload is a vmcnt(0) in front of the weight ring's counted waits).
-#ifndef HL_FUSE_LQ
-#define HL_FUSE_LQ 0
-#endif
-#if HL_FUSE_LQ
-    // A / B variant: the LQ records at the cursor ... cursor + LQ - 1 of every lane gathered into a per-wave LDS block [LQ][64 lanes] x 16 bytes by LDS-DMA while
-    // views_linear runs (no registers); waited for in front of the ring advance (where the only other loads in flight are the ring's staged ones, needed there anyway)
-    constexpr int LQ = 4;
-    auto lqp = [&]() __attribute__((always_inline)) -> f32x4 * { const int t_ = opaque_tid(); return reinterpret_cast<f32x4 *>(small + SMALL_FLOATS) + 8 * 512 + (t_ >> 6) * (LQ * 64); };
-    auto lq_request = [&]() __attribute__((always_inline)) {
-        const int t_ = opaque_tid();
-        const long long tl = wg * 8 + (t_ >> 6);
-        const float4 *base_ = a.fz_vc + (tl < tiles_n ? tl : tiles_n - 1) * 32 * (long long)Nc;
-        const __amdgpu_buffer_rsrc_t rsv = __builtin_amdgcn_make_buffer_rsrc((void *)base_, (short)0, Nc * 512, 0x00020000);
-        f32x4 *q_ = lqp();
-#pragma unroll
-        for (int k = 0; k < LQ; ++k) {
-            const int row = ci + k < Nc ? ci + k : Nc - 1;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsv, (__attribute__((address_space(3))) void *)(q_ + k * 64), 16, (row * 32 + (t_ & 31)) * 16, 0, 0, 0);
-        }
-    };
-    auto emit_coarse_until = [&](float zlim) __attribute__((always_inline)) {
-        const f32x4 *q_ = lqp() + (opaque_tid() & 63);
-        int k = 0;
-        while (zco(ci) <= zlim) {
-            f32x4 rec;
-            if (k < LQ) rec = q_[k * 64];
-            else { const float4 r_ = a.fz_vc[((wg * 8 + (opaque_tid() >> 6)) < tiles_n ? (wg * 8 + (opaque_tid() >> 6)) : tiles_n - 1) * 32 * (long long)Nc + 32LL * ci + (opaque_tid() & 31)]; rec = f32x4{r_.x, r_.y, r_.z, r_.w}; }
-            emit(zco(ci), rec[0], half ? rec[2] : rec[1], rec[3]);
-            ++ci; ++k;
-        }
-    };
-#else
     auto emit_coarse_until = [&](float zlim) __attribute__((always_inline)) {
         while (zco(ci) <= zlim) {
             emit(zco(ci), lower_half(crec.x), half ? crec.x : crec.y, crec.y);      // (the density sits in half 0)
@@ -1879,7 +1452,6 @@ __global__ __launch_bounds__(512, ACTS ? 1 : 2) void k_march_plw(const MarchArgs
             if (ci + 1 < Nc) crec1 = vcp()[64LL * (ci + 1)];
         }
     };
-#endif
     auto body = [&](auto rotc) {
     constexpr bool ROT = decltype(rotc)::value;
     for (int s = s_lo; s < s_hi; ++s) {
@@ -1960,8 +1532,8 @@ __global__ __launch_bounds__(512, ACTS ? 1 : 2) void k_march_plw(const MarchArgs
         }
         constexpr float SPU = LOG2D ? LN2 : 1.f;                    // softplus outputs of this kernel -> natural units
         u32x4 bf0[NPL], bf1[NPL], ba[NPL], bb[NPL];
-        split_plt<SPL>(f, 0, bf0);
-        split_plt<SPL>(f, 1, bf1);
+        split_plt(f, 0, bf0);
+        split_plt(f, 1, bf1);
         // ---- MLP  [renderer.py:134-156]: chunk g = fragment positions 4g .. 4g+3.  Software-pipelined: the operand of chunk g+1 is prepared
         // (softplus of a tile at its first use, three-way split of one half) in the same scheduling region as the MFMAs of chunk g, and the
         // (__builtin_amdgcn_sched_group_barrier patterns over regions of this size do not finish compiling) ----
@@ -1971,36 +1543,36 @@ __global__ __launch_bounds__(512, ACTS ? 1 : 2) void k_march_plw(const MarchArgs
         B3_ADV(1) mma_pl(X, bf1, B3_AT(1), 0, lane);
         load_bias<4>(Y, small + SM_B1, half);
         SP_R(0, 8, X[0], rs0);                                             // (the second half: behind the first chunk of the layer)
-        split_plt<SPL>(X[0], 0, ba);
+        split_plt(X[0], 0, ba);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {                                               // L1: chunks 2..9 = (tile k of X, half 0 | 1)
             B3_ADV(2 + 2 * k)
-            B3_MV24(5, mma_pl(Y, ba, B3_AT(2 + 2 * k), 0, lane), { SP_R(8, 16, X[k], rs0); split_plt<SPL>(X[k], 1, bb); })
+            B3_MV24(5, mma_pl(Y, ba, B3_AT(2 + 2 * k), 0, lane), { SP_R(8, 16, X[k], rs0); split_plt(X[k], 1, bb); })
             B3_ADV(3 + 2 * k)
-            B3_MV24(5, mma_pl(Y, bb, B3_AT(3 + 2 * k), 0, lane), if (k < 3) { SP_R(0, 8, X[k + 1 < 4 ? k + 1 : 3], rs0); split_plt<SPL>(X[k + 1 < 4 ? k + 1 : 3], 0, ba); })
+            B3_MV24(5, mma_pl(Y, bb, B3_AT(3 + 2 * k), 0, lane), if (k < 3) { SP_R(0, 8, X[k + 1 < 4 ? k + 1 : 3], rs0); split_plt(X[k + 1 < 4 ? k + 1 : 3], 0, ba); })
         }
         act_rows(ROW_X0, X, SPU);
         load_bias<4>(X, small + SM_B2, half);
         B3_ADV(10) mma_pl(X, bf0, B3_AT(10), 0, lane);                          // L2 (features): chunks 10, 11; the first hidden operand rides along
         B3_ADV(11)
-        B3_VM({ SP_R(0, 8, Y[0], rs1); split_plt<SPL>(Y[0], 0, ba); }, mma_pl(X, bf1, B3_AT(11), 0, lane))
+        B3_VM({ SP_R(0, 8, Y[0], rs1); split_plt(Y[0], 0, ba); }, mma_pl(X, bf1, B3_AT(11), 0, lane))
 #pragma unroll
         for (int k = 0; k < 4; ++k) {                                               // L2 (hidden): chunks 12..19
             B3_ADV(12 + 2 * k)
-            B3_MV24(5, mma_pl(X, ba, B3_AT(12 + 2 * k), 0, lane), { SP_R(8, 16, Y[k], rs1); split_plt<SPL>(Y[k], 1, bb); })
+            B3_MV24(5, mma_pl(X, ba, B3_AT(12 + 2 * k), 0, lane), { SP_R(8, 16, Y[k], rs1); split_plt(Y[k], 1, bb); })
             B3_ADV(13 + 2 * k)
-            B3_MV24(5, mma_pl(X, bb, B3_AT(13 + 2 * k), 0, lane), if (k < 3) { SP_R(0, 8, Y[k + 1 < 4 ? k + 1 : 3], rs1); split_plt<SPL>(Y[k + 1 < 4 ? k + 1 : 3], 0, ba); })
+            B3_MV24(5, mma_pl(X, bb, B3_AT(13 + 2 * k), 0, lane), if (k < 3) { SP_R(0, 8, Y[k + 1 < 4 ? k + 1 : 3], rs1); split_plt(Y[k + 1 < 4 ? k + 1 : 3], 0, ba); })
         }
         act_rows(ROW_X1, Y, SPU);
         load_bias<4>(Y, small + SM_BF, half);
         SP_R(0, 8, X[0], rs2);                                             // (the second half: behind the first chunk of the layer)
-        split_plt<SPL>(X[0], 0, ba);
+        split_plt(X[0], 0, ba);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {                                               // feature_linear: chunks 20..27
             B3_ADV(20 + 2 * k)
-            B3_MV24(5, mma_pl(Y, ba, B3_AT(20 + 2 * k), 0, lane), { SP_R(8, 16, X[k], rs2); split_plt<SPL>(X[k], 1, bb); })
+            B3_MV24(5, mma_pl(Y, ba, B3_AT(20 + 2 * k), 0, lane), { SP_R(8, 16, X[k], rs2); split_plt(X[k], 1, bb); })
             B3_ADV(21 + 2 * k)
-            B3_MV24(5, mma_pl(Y, bb, B3_AT(21 + 2 * k), 0, lane), if (k < 3) { SP_R(0, 8, X[k + 1 < 4 ? k + 1 : 3], rs2); split_plt<SPL>(X[k + 1 < 4 ? k + 1 : 3], 0, ba); })
+            B3_MV24(5, mma_pl(Y, bb, B3_AT(21 + 2 * k), 0, lane), if (k < 3) { SP_R(0, 8, X[k + 1 < 4 ? k + 1 : 3], rs2); split_plt(X[k + 1 < 4 ? k + 1 : 3], 0, ba); })
         }
         act_rows(ROW_X2, X, SPU);
         if constexpr (LOG2D) {   // feature_linear has no activation: its accumulators leave the plane scale here, on their way into views_linear's operand
@@ -2010,15 +1582,11 @@ __global__ __launch_bounds__(512, ACTS ? 1 : 2) void k_march_plw(const MarchArgs
                 for (int r = 0; r < 16; ++r) Y[t][r] *= rsF;
         }
         act_rows(ROW_Y, Y, 1.f);
-#if HL_FUSE_LQ
-        if constexpr (FUSE) lq_request();
-#else
         if constexpr (FUSE) {   // the coarse records at the cursor and behind it: requested here, used at the end of the sample
             const float2 *p_ = vcp();
             crec = p_[64LL * (ci < Nc ? ci : Nc - 1)];
             crec1 = p_[64LL * (ci + 1 < Nc ? ci + 1 : Nc - 1)];
         }
-#endif
         const float sigma_raw = dot_lane<4>(X, small + SM_AW, half) + small[SM_AB];   // X holds softplus(pts_linears.2) by now
         f32x16 V[2];
 #pragma unroll
@@ -2028,12 +1596,12 @@ __global__ __launch_bounds__(512, ACTS ? 1 : 2) void k_march_plw(const MarchArgs
                 const f32x4 v4 = vinit[(t * 4 + q) * 64 + lane];
                 V[t][4 * q] = v4[0]; V[t][4 * q + 1] = v4[1]; V[t][4 * q + 2] = v4[2]; V[t][4 * q + 3] = v4[3];
             }
-        split_plt<SPL>(Y[0], 0, ba);
+        split_plt(Y[0], 0, ba);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {                                               // views_linear (feature part): chunks 28..31, two k-groups each
             B3_ADV(28 + k)
-            B3_VM(split_plt<SPL>(Y[k], 1, bb), mma_pl(V, ba, B3_AT(28 + k), 0, lane))
-            B3_VM(if (k < 3) split_plt<SPL>(Y[k + 1 < 4 ? k + 1 : 3], 0, ba), mma_pl(V, bb, B3_AT(28 + k), 2, lane))
+            B3_VM(split_plt(Y[k], 1, bb), mma_pl(V, ba, B3_AT(28 + k), 0, lane))
+            B3_VM(if (k < 3) split_plt(Y[k + 1 < 4 ? k + 1 : 3], 0, ba), mma_pl(V, bb, B3_AT(28 + k), 2, lane))
         }
         if constexpr (LOG2D) { softplus_l2_r<0, 16>(V[0], rsV); softplus_l2_r<0, 16>(V[1], rsV); }
         else { V[0] = softplus16_b3(V[0]); V[1] = softplus16_b3(V[1]); }
@@ -2041,9 +1609,6 @@ __global__ __launch_bounds__(512, ACTS ? 1 : 2) void k_march_plw(const MarchArgs
         const float cr = dot_lane<2>(V, small + SM_RW, half) + small[SM_RB + 0];
         const float cg = dot_lane<2>(V, small + SM_RW + 64, half) + small[SM_RB + 1];
         const float cb = dot_lane<2>(V, small + SM_RW + 128, half) + small[SM_RB + 2];
-#if HL_FUSE_LQ
-        if constexpr (FUSE) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // the gathered records (and the ring's staged pair, which B3_ADV writes first thing anyway)
-#endif
         B3_ADV(B3_NCH - 1)                                                          // pair 0 of the next sample (the stream of a sample is chunks 0..31)
         if constexpr (FUSE) {   // the coarse samples in front of (or at: k_composite takes the coarse one first) this depth, then the sample itself
             emit_coarse_until(zc);
@@ -2059,16 +1624,11 @@ __global__ __launch_bounds__(512, ACTS ? 1 : 2) void k_march_plw(const MarchArgs
     if ((tid >> 6) < 4) body(std::false_type{});
     else body(std::true_type{});
     if constexpr (FUSE) {   // the coarse samples behind the last new depth, the last sample (distance 1e10: renderer.py:213), the image
-#if HL_FUSE_LQ
-        lq_request();
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#else
         {
             const float2 *p_ = vcp();
             crec = p_[64LL * (ci < Nc ? ci : Nc - 1)];
             crec1 = p_[64LL * (ci + 1 < Nc ? ci + 1 : Nc - 1)];
         }
-#endif
         emit_coarse_until(3.0e38f);                                 // (zco is +inf behind the last coarse sample)
         finish_pending(1e10f);
         const float cW = __shfl(cB, lane & 31);                 // the sum of the weights (half 0 keeps it)
@@ -3886,7 +3446,7 @@ __global__ __launch_bounds__(256) void k_wgrad_finish(const WgradArgs a, int n_r
 
 extern "C" {
 
-// fp32 image + the fp16 fragments of k_march16 + the three bf16 planes of k_march_b3
+// fp32 image + the fp16 fragments of k_march16 + the three bf16 planes of k_march_plw<3>
 // (+ the two fp16 planes of the fp16x2 products)
 size_t hl_render_mlp_packed_bytes(void) { return (size_t)PACKED_FLOATS * sizeof(float) + (size_t)P16_FRAGS * 1024 + B3_BYTES + (size_t)P16_FRAGS * 2 * 1024; }
 
@@ -4021,44 +3581,18 @@ static int render_eval_impl(const void *mlp_packed, const void *planes_packed, i
     }
     if (mlp_mode == 2) {   // HL_RENDER_MLP_BF16X3: exact three-way bf16 split of both operands, six partial products, fp32 accumulation
         const unsigned short *pb3 = reinterpret_cast<const unsigned short *>(static_cast<const char *>(mlp_packed) + (size_t)PACKED_FLOATS * sizeof(float) + (size_t)P16_FRAGS * 1024);
-        static const int b3_waves = getenv("HL_B3_WAVES") ? atoi(getenv("HL_B3_WAVES")) : 8;   // developer switch: 4 = k_march_b3 (one wave per SIMD, hand-scheduled)
-        if (b3_waves == 8) {
-            static const bool okw = hipFuncSetAttribute((const void *)k_march_plw<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)B3W_LDS) == hipSuccess;
-            HL_REQUIRE(okw, "k_march_b3w: cannot raise the dynamic LDS limit to %zu bytes", B3W_LDS);
-            hipLaunchKernelGGL(k_march_plw<3>, dim3((unsigned)((n_rays + 255) / 256)), dim3(512), B3W_LDS, (hipStream_t)stream, a, pb3);
-            return hl::check_launch("k_march_b3w");
-        }
-        const dim3 grid((unsigned)((n_rays + 127) / 128));
-#define HL_B3_LAUNCH(A)                                                                                                                    \
-    case A: {                                                                                                                              \
-        static const bool ok_ = hipFuncSetAttribute((const void *)k_march_b3<A>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)B3R_LDS) == hipSuccess; \
-        HL_REQUIRE(ok_, "k_march_b3: cannot raise the dynamic LDS limit to %zu bytes", B3R_LDS);                                           \
-        hipLaunchKernelGGL(k_march_b3<A>, grid, dim3(256), B3R_LDS, (hipStream_t)stream, a, pb3);                                          \
-        break;                                                                                                                             \
-    }
-#ifdef HL_B3_ABLATIONS   // developer builds (HL_RENDER_FLAGS=-DHL_B3_ABLATIONS): timing ablations selected by the environment, wrong images
-        static const int abl = getenv("HL_B3_ABL") ? atoi(getenv("HL_B3_ABL")) : 0;
-        switch (abl) {
-            HL_B3_LAUNCH(4) HL_B3_LAUNCH(64) HL_B3_LAUNCH(128) HL_B3_LAUNCH(256) HL_B3_LAUNCH(512) HL_B3_LAUNCH(1024) HL_B3_LAUNCH(2048)
-            default: HL_B3_LAUNCH(0)
-        }
-#else
-        switch (0) { default: HL_B3_LAUNCH(0) }
-#endif
-#undef HL_B3_LAUNCH
-        return hl::check_launch("k_march_b3");
+        static const bool okw = hipFuncSetAttribute((const void *)k_march_plw<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)B3W_LDS) == hipSuccess;
+        HL_REQUIRE(okw, "k_march_b3w: cannot raise the dynamic LDS limit to %zu bytes", B3W_LDS);
+        hipLaunchKernelGGL(k_march_plw<3>, dim3((unsigned)((n_rays + 255) / 256)), dim3(512), B3W_LDS, (hipStream_t)stream, a, pb3);
+        return hl::check_launch("k_march_b3w");
     }
     if (mlp_mode == 1) {   // HL_RENDER_MLP_FP16 (opt-in): fp16 operands, all weights LDS-resident
         const size_t sh = (size_t)P16_FRAGS * 1024 + SMALL_FLOATS * sizeof(float);
-        static const bool attr_ok = hipFuncSetAttribute((const void *)k_march16<8>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                        (int)((size_t)P16_FRAGS * 1024 + SMALL_FLOATS * sizeof(float))) == hipSuccess &&
-                                    hipFuncSetAttribute((const void *)k_march16<4>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                        (int)((size_t)P16_FRAGS * 1024 + SMALL_FLOATS * sizeof(float))) == hipSuccess;
+        static const bool attr_ok = hipFuncSetAttribute((const void *)k_march16<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh) == hipSuccess;
         HL_REQUIRE(attr_ok, "k_march16: cannot raise the dynamic LDS limit to %zu bytes", sh);
         const unsigned short *p16 = reinterpret_cast<const unsigned short *>(static_cast<const float *>(mlp_packed) + PACKED_FLOATS);
-        static const int nwv = getenv("HL_MARCH16_WAVES") ? atoi(getenv("HL_MARCH16_WAVES")) : 4;      // 4 = one wave per SIMD (512 registers, no spills: 20.1 against 21.9 ms per view); 8: developer switch
-        if (nwv == 4) hipLaunchKernelGGL(k_march16<4>, dim3((unsigned)((n_rays + 127) / 128)), dim3(256), sh, (hipStream_t)stream, a, p16);
-        else hipLaunchKernelGGL(k_march16<8>, dim3((unsigned)((n_rays + 255) / 256)), dim3(512), sh, (hipStream_t)stream, a, p16);
+        // 4 waves = one per SIMD (512 registers, no spills: 20.1 against 21.9 ms per view with 8)
+        hipLaunchKernelGGL(k_march16<4>, dim3((unsigned)((n_rays + 127) / 128)), dim3(256), sh, (hipStream_t)stream, a, p16);
         return hl::check_launch("k_march16");
     }
     // (4-wave workgroups, two per CU with independent barriers, measured equal - 74.5 vs 74.7 ms per view - at twice the weight
@@ -4076,7 +3610,6 @@ static int render_onepass_fine(const void *mlp_packed, const void *planes_packed
     int rcode = fill_march(a, mlp_packed, planes_packed, H, W, bounds, rays_o, rays_d, near, far);
     if (rcode) return rcode;
     a.z = zn_scratch; a.z_tiled = 1; a.R = n_rays; a.S = n_samples; a.flags = flags;
-    if (const char *e_ = getenv("HL_ONEPASS_DEV")) a.flags |= (unsigned)strtoul(e_, nullptr, 0);
     a.fz_vc = (const float4 *)vc; a.fz_u = u; a.fz_zn = zn_scratch; a.fz_N = n_samples;
     a.rgb = rgb; a.acc = acc; a.depth = depth;
     const dim3 grid((unsigned)((n_rays + 255) / 256));
@@ -4193,18 +3726,13 @@ int hl_render_eval_acts(const void *mlp_packed, const void *planes_packed, int H
     const unsigned splits = sample_splits(groups, n_samples);
     a.s_per = (n_samples + (int)splits - 1) / (int)splits;
     // round 5: the evaluate pass of the fitting step on the fp16x2 kernel (k_march_plw<2, ACTS>: the inference default's arithmetic; the backward reads the
-    // activations it writes).  HL_FIT_FP32=1 (developer knob, read once): the fp32-MFMA kernel of rounds 1-4.
-    static const int fit_fp32 = [] { const char *e_ = getenv("HL_FIT_FP32"); return e_ ? atoi(e_) : 0; }();
+    // activations it writes)
     const dim3 grid(groups, (unsigned)((n_samples + a.s_per - 1) / a.s_per));
-    if (!fit_fp32) {
-        const unsigned short *ph2 = reinterpret_cast<const unsigned short *>(static_cast<const char *>(mlp_packed) + (size_t)PACKED_FLOATS * sizeof(float) + (size_t)P16_FRAGS * 1024 + B3_BYTES);
-        static const bool okh = hipFuncSetAttribute((const void *)k_march_plw<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PLW_LDS<2>) == hipSuccess;
-        HL_REQUIRE(okh, "k_march_plw<2, acts>: cannot raise the dynamic LDS limit to %zu bytes", PLW_LDS<2>);
-        hipLaunchKernelGGL((k_march_plw<2, true>), grid, dim3(512), PLW_LDS<2>, (hipStream_t)stream, a, ph2);
-        return hl::check_launch("k_march_plw<2, acts>");
-    }
-    hipLaunchKernelGGL((k_march<true, true, 8, false, true>), grid, dim3(512), 0, (hipStream_t)stream, a);
-    return hl::check_launch("k_march<eval, acts>");
+    const unsigned short *ph2 = reinterpret_cast<const unsigned short *>(static_cast<const char *>(mlp_packed) + (size_t)PACKED_FLOATS * sizeof(float) + (size_t)P16_FRAGS * 1024 + B3_BYTES);
+    static const bool okh = hipFuncSetAttribute((const void *)k_march_plw<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PLW_LDS<2>) == hipSuccess;
+    HL_REQUIRE(okh, "k_march_plw<2, acts>: cannot raise the dynamic LDS limit to %zu bytes", PLW_LDS<2>);
+    hipLaunchKernelGGL((k_march_plw<2, true>), grid, dim3(512), PLW_LDS<2>, (hipStream_t)stream, a, ph2);
+    return hl::check_launch("k_march_plw<2, acts>");
 }
 
 size_t hl_render_composite_backward_scratch_bytes(int64_t n_rays, int n_samples, int n_importance) {
@@ -4258,9 +3786,7 @@ int hl_render_mlp_backward(const void *mlp_packed, const void *mlp_bwd_packed, i
     const unsigned groups = (unsigned)((n_rays + 255) / 256);
     const unsigned splits = sample_splits(groups, n_samples);
     a.s_per = (n_samples + (int)splits - 1) / (int)splits;
-    static const int fit_fp32 = [] { const char *e_ = getenv("HL_FIT_FP32"); return e_ ? atoi(e_) : 0; }();   // developer knob (read once): the fp32-MFMA kernel of rounds 1-4
-    if (!fit_fp32) hipLaunchKernelGGL((k_mlp_bwd<8, true>), dim3(groups, (unsigned)((n_samples + a.s_per - 1) / a.s_per)), dim3(512), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((k_mlp_bwd<8, false>), dim3(groups, (unsigned)((n_samples + a.s_per - 1) / a.s_per)), dim3(512), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL((k_mlp_bwd<8, true>), dim3(groups, (unsigned)((n_samples + a.s_per - 1) / a.s_per)), dim3(512), 0, (hipStream_t)stream, a);
     return hl::check_launch("k_mlp_bwd");
 }
 
@@ -4326,8 +3852,8 @@ int hl_render_plane_grads_points(int H, int W, const float *bounds, const float 
     return hl::check_launch("k_plane_scatter_pts");
 }
 
-static int64_t wgrad_points_per_range(int64_t n_cols) {   // 256 point ranges (HL_WGRAD_RANGES: developer knob, read once) of at least 1024 points
-    static const int64_t nr = [] { const char *e_ = getenv("HL_WGRAD_RANGES"); return e_ ? (int64_t)atol(e_) : (int64_t)256; }();
+static int64_t wgrad_points_per_range(int64_t n_cols) {   // 256 point ranges of at least 1024 points
+    constexpr int64_t nr = 256;
     int64_t per = ((n_cols + nr - 1) / nr + 31) / 32 * 32;
     return per < 1024 ? 1024 : per;
 }

@@ -32,9 +32,6 @@ __device__ __forceinline__ unsigned long long *stat_word(float *st, int N, long 
 // with many workgroups per image the totals are kept in stat_shards(HW) copies (the workgroup picks one by its index: atomics on one word
 // serialise); consumers add the copies up - exact integers.
 __device__ __forceinline__ void stat_add(float *st, int N, long img, int g, long HW, float s, float q) {
-#ifdef HL_STAT_ABL   // timing ablation: no atomics (wrong results)
-    if (N != 12345) return;
-#endif
     unsigned long long *t = stat_word(st, N, img, g, HW);
     if (!(q < 1.0e11f)) { atomicOr(t + 1, STAT_POISON); return; }
     atomicAdd(t, (unsigned long long)__double2ll_rn((double)s * STAT_SC_SUM));
@@ -90,9 +87,6 @@ __device__ __forceinline__ void wg_group_flush(const float *red, unsigned long l
     }
     __syncthreads();
     const int nlast = (n0 + NC < Cout ? n0 + NC : Cout) - 1, ng = (c0 + nlast) / cg - g0 + 1;
-#ifdef HL_STAT_ABL
-    if (N != 12345) { __syncthreads(); return; }
-#endif
     if (tid < ng) {
         unsigned long long *t = stat_word(st, N, img, g0 + tid, HW);
         const unsigned long long Sv = lg[tid * 2], Qv = lg[tid * 2 + 1];

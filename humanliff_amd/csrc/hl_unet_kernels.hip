@@ -2874,13 +2874,11 @@ int conv_pack_weights_wino4(const float *w, int Cout, int Cin, int Cin_pad, floa
 
 static inline long hw_o_early(const ConvArgs &a) { return (long)a.out.H * a.out.W; }
 
-// k_conv_h16 is taken from this many workgroups on.  The default (48; HL_H16_MIN_BLOCKS, read ONCE) is what the network dispatch uses; the
-// unit tests that run the kernel on single tiles set it through hl_debug_set_h16_min_blocks (no getenv per convolution launch).
+// k_conv_h16 is taken from this many workgroups on.  The default (48) is what the network dispatch uses; the unit tests that run the
+// kernel on single tiles set it through hl_debug_set_h16_min_blocks.
+constexpr long kH16MinBlocks = 48;
 static long g_h16_min_blocks = -1;
-static long h16_min_blocks() {
-    static const long dflt = [] { const char *e = getenv("HL_H16_MIN_BLOCKS"); return e ? atol(e) : 48L; }();
-    return g_h16_min_blocks >= 0 ? g_h16_min_blocks : dflt;
-}
+static long h16_min_blocks() { return g_h16_min_blocks >= 0 ? g_h16_min_blocks : kH16MinBlocks; }
 void set_h16_min_blocks(long v) { g_h16_min_blocks = v; }
 
 int conv2d(const ConvArgs &a, hipStream_t st) {
@@ -2913,7 +2911,7 @@ int conv2d(const ConvArgs &a, hipStream_t st) {
     // 1 = 128x32 (Cout <= 32), 2 = 64x64.  Small-M layers keep the efficient main tile and split K instead
     // (deterministic slabs + k_splitk_finish) until the grid covers the chip.
     const long main_blocks = ((M + 127) / 128) * (cpad / 96);
-    static const int split_cap = [] { const char *e_ = getenv("HL_MAX_SPLITS"); return e_ ? atoi(e_) : 16; }();   // developer knob (read once)
+    constexpr int split_cap = 16;
     const int max_splits = a.splitk_ws ? (nk / 8 < split_cap ? nk / 8 : split_cap) : 1;
     int cfg;
     long blocks;
@@ -2950,8 +2948,6 @@ int conv2d(const ConvArgs &a, hipStream_t st) {
     auto finish = [&](const char *what) -> int {   // split-K: the slab sum (+ statistics when wanted)
         int rc = check_launch(what);
         if (rc) return rc;
-        static const int abl_ = [] { const char *e_ = getenv("HL_ABL_SKIP"); return e_ ? atoi(e_) : 0; }();   // TIMING ablation (wrong results)
-        if (abl_ & 1) { if (st_rows32 && M % 32 == 0) a.stat_slots = (int)(hw_o_early(a) / 32); return HL_OK; }
         if (st_rows32 && M % 32 == 0) {
             p.st1 = a.stats; p.st2 = a.out2 ? a.stats2 : nullptr;
             a.stat_slots = (int)(hw_o_early(a) / 32);
@@ -3017,13 +3013,12 @@ int conv2d(const ConvArgs &a, hipStream_t st) {
     //     768 smaller workgroups of the F(2x2) kernel take 188 us),
     //   * below that with the input channels split into slabs until W x slabs reaches one round (k_splitk_finish sums them).
     // In between (1.5 rounds: 128x128 at batch 4, 384 workgroups, 151 us against 131 us) the two-workgroups-per-CU kernels keep the layer.
-    static const int w4w_mode = [] { const char *e_ = getenv("HL_WINO4W"); return e_ ? atoi(e_) : 1; }();   // developer switch, read once: 0 = off, 2 = wherever it can run
     const long w4w_blocks = wino4_blocks / 2;
     bool wino4w = false;
     int w4w_splits = 1;
-    if (wino4_ok && w4w_mode != 0 && a.Cout % 64 == 0 && w4w_blocks > 0) {
+    if (wino4_ok && a.Cout % 64 == 0 && w4w_blocks > 0) {
         const int nkt8 = a.in.C / 8;
-        if (w4w_blocks >= 768 || (w4w_blocks >= 160 && w4w_blocks <= 256) || (w4w_mode == 2 && w4w_blocks >= 160)) wino4w = true;
+        if (w4w_blocks >= 768 || (w4w_blocks >= 160 && w4w_blocks <= 256)) wino4w = true;
         else if (w4w_blocks < 160 && a.splitk_ws) {
             w4w_splits = (int)(256 / w4w_blocks);
             if (w4w_splits > nkt8 / 8) w4w_splits = nkt8 / 8;            // at least 8 k-tiles (64 channels) per slab
@@ -3056,38 +3051,37 @@ int conv2d(const ConvArgs &a, hipStream_t st) {
         }
         if (h16_splits < 2 || h16_blocks * h16_splits < h16_min_blocks()) { h16 = false; h16_splits = 1; }
     }
-    // 1x1 / stride-1 layers of the DEFAULT mode on the 16-bit matrix pipe with fp16x2 products (k_conv1_h2): once off the fp32 pipe they are bound by HBM, the
+    // 1x1 / stride-1 layers of the DEFAULT mode on the 16-bit matrix pipe with fp16x2 products (k_conv1_h2s): once off the fp32 pipe they are bound by HBM, the
     // fp32 kernel takes twice as long.  From h2_min_blocks workgroups of 256 pixels x 192 channels on (fewer: the split-K fp32 path keeps the layer).
-    static const long h2_min_blocks = [] { const char *e_ = getenv("HL_H2_MIN_BLOCKS"); return e_ ? atol(e_) : 12L; }();   // developer knob (read once); < 0 disables (12: with the 128-pixel tiles; 48 with the 256-pixel ones)
+    constexpr long h2_min_blocks = 12;   // (12: with the 128-pixel tiles; 48 with the 256-pixel ones)
     const long h2_blocks = (M / 256) * (a.Cout / 192);
-    const bool h2 = !h16 && a.w_h2 && h2_min_blocks >= 0 && (!gn_on || a.act_ws) && !a.out_nchw && !a.w_bf3 &&
+    const bool h2 = !h16 && a.w_h2 && (!gn_on || a.act_ws) && !a.out_nchw && !a.w_bf3 &&
                     conv1_h2_applies(a.out.H, a.out.W, a.in.C, a.Cout, a.ks, a.stride, a.ups) &&
                     (long)a.in.N * a.in.H * a.in.W * a.in.pitch * 4 < (1L << 31) && a.in.pitch % 4 == 0 && h2_blocks >= h2_min_blocks;
     // 3x3 / stride-1 layers of the default mode in the same arithmetic, from 100 workgroups of 256 pixels x 192 channels on: k_conv_h2s, a direct convolution on
     // 8x16-pixel tiles with TWO workgroups per CU (late round 5).  Same box, forward wall time: B = 1 12.8 -> 12.2 ms, B = 4 32.5 -> 30.4, B = 8 58.9 -> 54.9 (both
-    // small-tile kernels).  The first version of the kernel (16x16 tiles, one workgroup per CU: k_conv_h16<., 2>, HL_H2_SMALL=0) won only where a layer was about one
+    // small-tile kernels).  The first version of the kernel (16x16 tiles, one workgroup per CU: k_conv_h16's workgroups with two planes, since removed) won only where a layer was about one
     // round of workgroups: alone it beat k_conv_wino4w by 12 % on the 256-pixel level and the forward's wall time did not move - a kernel that owns whole CUs cannot fill
     // the other encoder tower's bubbles, and nothing overlapped its own prologue / staging / epilogue (profiles/r05_unet_fill_experiments.md, sections 6 - 8).
-    static const long h3_min_blocks = [] { const char *e_ = getenv("HL_H2_CONV3_MIN_BLOCKS"); return e_ ? atol(e_) : 100L; }();   // developer knobs (read once); min < 0 disables
-    static const long h3_max_blocks = [] { const char *e_ = getenv("HL_H2_CONV3_MAX_BLOCKS"); return e_ ? atol(e_) : (1L << 40); }();
-    const bool h3_base = !h16 && !h2 && a.w_h2 && a.ks == 3 && h3_min_blocks >= 0 && (!gn_on || (a.act_ws && !a.ups)) && !a.out_nchw && !a.w_bf3 &&
+    constexpr long h3_min_blocks = 100;
+    const bool h3_base = !h16 && !h2 && a.w_h2 && a.ks == 3 && (!gn_on || (a.act_ws && !a.ups)) && !a.out_nchw && !a.w_bf3 &&
                          conv_h16_applies(a.out.H, a.out.W, a.in.C, a.Cout, a.ks, a.stride, a.ups) &&
                          (long)a.in.N * a.in.H * a.in.W * a.in.pitch * 4 < (1L << 31) && a.in.pitch % 4 == 0;
-    bool h3 = h3_base && h16_blocks >= h3_min_blocks && h16_blocks <= h3_max_blocks;
+    bool h3 = h3_base && h16_blocks >= h3_min_blocks;
     // below that: the input channels split into slabs of >= 2 chunks until about one round of 128-pixel workgroups runs (k_splitk_finish[_st] sums the slabs)
-    static const long h3_split_min = [] { const char *e_ = getenv("HL_H2_CONV3_SPLIT_MIN"); return e_ ? atol(e_) : 8L; }();   // developer knob (read once); < 0: no split-K on this kernel
+    constexpr long h3_split_min = 8;
     int h3_splits = 1;
-    if (h3_base && !h3 && h3_split_min >= 0 && h16_blocks >= h3_split_min && h16_blocks < h3_min_blocks && a.splitk_ws && !a.out2) {
-        static const long h3_min_chunks = [] { const char *e_ = getenv("HL_H2_SPLIT_MIN_CHUNKS"); return e_ ? std::max(1L, atol(e_)) : 2L; }();   // developer knob (read once): chunks of 32 input channels per slab, at least
-        static const long h3_max_splits = [] { const char *e_ = getenv("HL_H2_SPLIT_MAX"); return e_ ? std::max(1L, atol(e_)) : 16L; }();
-        static const long h3_target = [] { const char *e_ = getenv("HL_H2_SPLIT_TARGET"); return e_ ? std::max(1L, atol(e_)) : 256L; }();                // workgroups (of 256 pixels x 192 channels) aimed at
+    if (h3_base && !h3 && h16_blocks >= h3_split_min && a.splitk_ws && !a.out2) {
+        constexpr long h3_min_chunks = 2;     // chunks of 32 input channels per slab, at least
+        constexpr long h3_max_splits = 16;
+        constexpr long h3_target = 256;       // workgroups (of 256 pixels x 192 channels) aimed at
         h3_splits = (int)std::min<long>(std::min<long>(h3_target / h16_blocks, (a.in.C / 32) / h3_min_chunks), h3_max_splits);
         while (h3_splits > 1 && (size_t)h3_splits * M * a.Cout * sizeof(float) > a.splitk_ws_bytes) --h3_splits;
         if (h3_splits >= 2) h3 = true; else h3_splits = 1;
     }
     // 3x3 / stride-2 layers (Downsample) of the default mode in the same arithmetic (k_conv_h2d), from h3d_min_blocks workgroups' worth of output (256 pixels x 192 channels) on
-    static const long h3d_min_blocks = [] { const char *e_ = getenv("HL_H2_CONV3S2_MIN_BLOCKS"); return e_ ? atol(e_) : 32L; }();   // developer knob (read once); < 0 disables
-    const bool h3d = !h16 && !h2 && !h3 && a.w_h2 && a.ks == 3 && a.stride == 2 && !a.ups && mode == 0 && h3d_min_blocks >= 0 && !a.out_nchw && !a.w_bf3 &&
+    constexpr long h3d_min_blocks = 32;
+    const bool h3d = !h16 && !h2 && !h3 && a.w_h2 && a.ks == 3 && a.stride == 2 && !a.ups && mode == 0 && !a.out_nchw && !a.w_bf3 &&
                      conv3_h2d_applies(a.out.H, a.out.W, a.in.C, a.Cout) && (long)a.in.N * a.in.H * a.in.W * a.in.pitch * 4 < (1L << 31) && a.in.pitch % 4 == 0 &&
                      h16_blocks >= h3d_min_blocks;
     if (a.plan_only) {   // which weight layout will this launch read?  (single-op entry points pack only that one)
@@ -3149,9 +3143,7 @@ int conv2d(const ConvArgs &a, hipStream_t st) {
         a.path = 6;
         p.in16 = 0;
         // GroupNorm(+SiLU) of the input: applied by k_conv_h2s while it stages the patch (its two workgroups per CU hide the VALU) - no pass over the tensor
-        static const int h3_fuse = [] { const char *e_ = getenv("HL_H2_FUSE_GN"); return e_ ? atoi(e_) : 1; }();   // developer knob (read once)
-        static const int h3_small_ = [] { const char *e_ = getenv("HL_H2_SMALL"); return e_ ? atoi(e_) : 1; }();      // 0: the 16x16-pixel kernel, one workgroup per CU
-        const bool fuse = mode != 0 && h3_fuse && h3_small_ && !a.ups && a.in.C <= 4096;
+        const bool fuse = mode != 0 && !a.ups && a.in.C <= 4096;
         if (mode != 0 && !fuse) {   // GroupNorm(+SiLU) materialised once, as the two-plane image the kernel stages without conversion (the same bytes as fp32)
             HL_REQUIRE((size_t)a.in.pixels() * a.in.C * sizeof(float) <= a.act_ws_bytes, "conv2d: act scratch too small");
             const long npix = a.in.pixels();
@@ -3182,25 +3174,19 @@ int conv2d(const ConvArgs &a, hipStream_t st) {
             p.st1 = a.stats; p.st2 = a.out2 ? a.stats2 : nullptr;
             a.stat_slots = a.out.H * a.out.W / 128;
         }
+        p.n_mtiles *= 2;   // 8x16-pixel tiles, two workgroups per CU
         if (splits > 1) {   // the finish kernel adds bias / residual and emits the statistics
             p.st1 = p.st2 = nullptr;
             a.stat_slots = 0;
-            p.n_mtiles *= 2;
             int rc = conv3_h2s_launch(p, st, splits);
             if (rc) return rc;
             return finish("k_conv_h2s");
         }
-        if (h3_small_) {   // 8x16-pixel tiles, two workgroups per CU
-            p.n_mtiles *= 2;
-            return conv3_h2s_launch(p, st);
-        }
-        return conv3_h2_launch(p, st);
+        return conv3_h2s_launch(p, st);
     }
     if (h2) {
         a.path = 6;
-        static const int h2_fuse = [] { const char *e_ = getenv("HL_H2_FUSE_GN"); return e_ ? atoi(e_) : 1; }();     // developer knobs (read once)
-        static const int h2_small_ = [] { const char *e_ = getenv("HL_H2_SMALL1"); return e_ ? atoi(e_) : 1; }();
-        const bool fuse1 = mode != 0 && h2_fuse && h2_small_ && a.in.C <= 4096;      // GroupNorm(+SiLU) applied by k_conv1_h2s while staging
+        const bool fuse1 = mode != 0 && a.in.C <= 4096;      // GroupNorm(+SiLU) applied by k_conv1_h2s while staging
         if (mode != 0 && !fuse1) {   // GroupNorm(+SiLU) materialised once as dense fp32 (the kernel splits into its two fp16 planes while staging)
             HL_REQUIRE((size_t)a.in.pixels() * a.in.C * sizeof(float) <= a.act_ws_bytes, "conv2d: act scratch too small");
             const long npix = a.in.pixels();
@@ -3225,28 +3211,25 @@ int conv2d(const ConvArgs &a, hipStream_t st) {
             p.st1 = a.stats; p.st2 = a.out2 ? a.stats2 : nullptr;
             a.stat_slots = 1;
         }
-        if (h2_small_) {   // 128-pixel tiles, two workgroups per CU
-            p.n_mtiles *= 2;
-            p.kt_per = a.in.C / 48;
-            // few workgroups (the 16- and 32-pixel levels, batch 1): the input channels split into slabs of >= 4 chunks until ~256 workgroups run (k_splitk_finish[_st] sums them)
-            static const long h2_split_max = [] { const char *e_ = getenv("HL_H2_SPLIT_MAX_BLOCKS"); return e_ ? atol(e_) : 64L; }();   // developer knob (read once); 0: no split-K
-            if (h2_blocks < h2_split_max && a.splitk_ws && !a.out2) {
-                int sp = (int)std::min<long>(std::min<long>(128 / std::max<long>(h2_blocks, 1), (a.in.C / 48) / 4), 8);
-                while (sp > 1 && (size_t)sp * M * a.Cout * sizeof(float) > a.splitk_ws_bytes) --sp;
-                if (sp >= 2) {
-                    p.kt_per = (a.in.C / 48 + sp - 1) / sp;
-                    splits = (a.in.C / 48 + p.kt_per - 1) / p.kt_per;
-                    p.partial = a.splitk_ws;
-                    p.st1 = p.st2 = nullptr;
-                    a.stat_slots = 0;
-                    int rc = conv1_h2s_launch(p, st, splits);
-                    if (rc) return rc;
-                    return finish("k_conv1_h2s");
-                }
+        p.n_mtiles *= 2;   // 128-pixel tiles, two workgroups per CU
+        p.kt_per = a.in.C / 48;
+        // few workgroups (the 16- and 32-pixel levels, batch 1): the input channels split into slabs of >= 4 chunks until ~256 workgroups run (k_splitk_finish[_st] sums them)
+        constexpr long h2_split_max = 64;
+        if (h2_blocks < h2_split_max && a.splitk_ws && !a.out2) {
+            int sp = (int)std::min<long>(std::min<long>(128 / std::max<long>(h2_blocks, 1), (a.in.C / 48) / 4), 8);
+            while (sp > 1 && (size_t)sp * M * a.Cout * sizeof(float) > a.splitk_ws_bytes) --sp;
+            if (sp >= 2) {
+                p.kt_per = (a.in.C / 48 + sp - 1) / sp;
+                splits = (a.in.C / 48 + p.kt_per - 1) / p.kt_per;
+                p.partial = a.splitk_ws;
+                p.st1 = p.st2 = nullptr;
+                a.stat_slots = 0;
+                int rc = conv1_h2s_launch(p, st, splits);
+                if (rc) return rc;
+                return finish("k_conv1_h2s");
             }
-            return conv1_h2s_launch(p, st);
         }
-        return conv1_h2_launch(p, st);
+        return conv1_h2s_launch(p, st);
     }
     bool blk4 = false;
     if (dma || wino4) {
@@ -3441,8 +3424,6 @@ int groupnorm_coef_stats(const View &x, const float *gt, const float *gamma, con
                          long emb_pitch, float *cA, float *cB, hipStream_t st, float eps) {
     HL_REQUIRE(gt && gamma && beta && cA && cB, "groupnorm_coef_stats: bad argument");
     HL_REQUIRE(x.C % 32 == 0, "GroupNorm32 needs C %% 32 == 0 (C=%d)", x.C);
-    static const int abl_ = [] { const char *e_ = getenv("HL_ABL_SKIP"); return e_ ? atoi(e_) : 0; }();   // TIMING ablation (wrong results)
-    if (abl_ & 2) return HL_OK;
     hipLaunchKernelGGL(k_gn_coef_tot, dim3(32, x.N), dim3(64), 0, st, gt, x.H * x.W, x.C, gamma, beta, emb, emb_pitch, cA, cB, eps);
     return check_launch("k_gn_coef_tot");
 }
@@ -3470,8 +3451,6 @@ int timestep_embedding(const int64_t *t, const float *tf, int B, int dim, float 
 int attention(const float *qkv, int N, int T, int C, int heads, float *out, hipStream_t st, int h2, float *out_totals, int *totals_emitted) {
     HL_REQUIRE(qkv && out && heads > 0 && C % heads == 0, "attention: bad argument");
     if (totals_emitted) *totals_emitted = 0;
-    static const int att_h2 = [] { const char *e_ = getenv("HL_ATT_H2"); return e_ ? atoi(e_) : 1; }();   // developer knob (read once): 0 = the fp32-MFMA kernels in every mode
-    if (!att_h2) h2 = 0;
     const int ch = C / heads;
     // 32 queries per wave; pick waves per workgroup so the grid has at least ~256 workgroups (K/V tiles are
     // shared through LDS inside a workgroup, and are L2-resident across workgroups)
@@ -3487,8 +3466,8 @@ int attention(const float *qkv, int N, int T, int C, int heads, float *out, hipS
     } while (0)
     // short sequences: split the keys over the 4 waves of a workgroup instead (one query tile per workgroup)
     // (with fp16x2 products the key-split kernel also takes the 1 024-token level of batches 8 ... 16: B = 8 49.4 -> 49.0 ms per forward)
-    static const long ks_max = [] { const char *e_ = getenv("HL_ATT_KS_MAX"); return e_ ? atol(e_) : 4097L; }();   // developer knob (read once)
-    if ((long)qtiles * N * heads < (h2 ? std::max(ks_max, 1024L) : 1024L) && (ch == 96 || ch == 192) && (3L * C) % 4 == 0) {
+    constexpr long ks_max = 1024, ks_max_h2 = 4097;
+    if ((long)qtiles * N * heads < (h2 ? ks_max_h2 : ks_max) && (ch == 96 || ch == 192) && (3L * C) % 4 == 0) {
         dim3 gks(qtiles, N * heads);
         if (ch == 96 && h2)
             hipLaunchKernelGGL((k_attention_ks<96, 4, true, true>), gks, dim3(256), (size_t)4 * (96 * 33 + 64) * sizeof(float), st, qkv, T, C, heads, out, out_totals, N);

@@ -75,7 +75,7 @@ int hl_planes_pack(const float *planes, int H, int W, void *packed, void *stream
                                         (k_march16, all weights LDS-resident); features, encodings, softplus, compositing stay fp32 */
 #define HL_RENDER_MLP_BF16X3 32u     /* hl_render_rays, evaluate-once pipeline: every fp32 product of the MLP (renderer.py:134-156) formed from an
                                         EXACT three-way bf16 split of both operands - six partial products on v_mfma_f32_32x32x16_bf16, fp32
-                                        accumulation, dropped terms < 2^-24 |a b| (k_march_b3); an fp32-tolerance mode, not a reduced-precision one */
+                                        accumulation, dropped terms < 2^-24 |a b| (k_march_plw<3>); an fp32-tolerance mode, not a reduced-precision one */
 
 #define HL_RENDER_MLP_FP16X2 64u     /* the same pipeline with TWO fp16 planes per operand (activations x = h0 + h1 to 2^-20 |x| while 2^-3 <= |x| < 65504, absolute 2^-24
                                         below; weights: every layer's planes are those of 2^k W with max |2^k W| in [2^12, 2^13) - nearest-even, 2^-22 of the layer's
@@ -600,8 +600,8 @@ int hl_attention_nhwc_backward(const float *qkv, const float *out, const float *
 /* timestep_embedding (nn.py:103-121): t int64 (B) or t_float fp32 (B) -> out (B, dim), dim even */
 int hl_timestep_embedding(const int64_t *t, const float *t_float, int B, int dim, float *out, void *stream);
 
-/* Developer / test switch: the number of workgroups from which the convolution dispatch takes k_conv_h16 in the 16-bit modes (default 48,
- * or HL_H16_MIN_BLOCKS read once at the first launch); v < 0 restores the default.  The unit tests run the kernel on single tiles with it. */
+/* Test switch: the number of workgroups from which the convolution dispatch takes k_conv_h16 in the 16-bit modes (default 48);
+ * v < 0 restores the default.  The unit tests run the kernel on single tiles with it. */
 int hl_debug_set_h16_min_blocks(long v);
 /* test switch of the single-convolution entry points (hl_conv2d_nhwc*): where the power-of-two scale of a raw input of the fp16x2 kernels comes from.
    0 (default): an exact abs-max pass over the input (tensor_absmax); 1: the fixed-point group totals (sum x^2) - what the producers' epilogues leave inside
