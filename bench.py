@@ -5,6 +5,11 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
     python bench.py --gpus 1 --steps 8 --warmup 2 --dump-outputs DIR
+    python bench.py --gpus 1 --steps 8 --warmup 2 --full
+
+A plain run does what the headline needs and no more: it sets up, warms up, times the K steps, writes the outputs of
+--dump-outputs and prints the line.  Everything else below (the secondary metrics, the roofline, the sustained and batch-sweep
+legs, the other product modes, parity, CPU baselines, the e2e slice, the RCCL probe) runs after the timed region with --full only.
 
 Primary metric (BASELINE.json configs[1]): denoise-steps/sec of the production 256x256x27 tri-plane UNet
 (497M params) inside the 1000-step DDPM p_sample loop at batch 4 per GPU.  A "step" is one p_sample call:
@@ -22,8 +27,8 @@ gather) when N > 1 - as DIR/<name>.npy in float32, rank 0 only.  The inputs are 
 the per-step noise), so two runs with the same arguments, e.g. of two builds, can be compared array for array.  Above 64 MB in all,
 every array is cut to the same fixed, seeded sample of its flattened elements.
 
-Prints ONE JSON line on rank 0.  `roofline` is measured live with HIP events (per-kernel-category events
-inside hl_unet_forward for the conv kernels; torch events around the stage launches for the ray-march
+Prints ONE JSON line on rank 0; with --full everything measured also goes to bench_detail.json.  `roofline` is measured
+live with HIP events (per-kernel-category events inside hl_unet_forward for the conv kernels; torch events around the stage launches for the ray-march
 kernel) on one extra pass after the timed region; `cpu_baseline` times the oracle (a PyTorch-CPU
 restatement of the reference's algorithm, kind "port") on this box's host cores on a bounded sample.
 """
@@ -68,6 +73,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step returned (sample, pred_xstart) as DIR/<name>.npy, float32, at most 64 MB in all")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, run every other leg (roofline, sustained, batch sweep, product modes, parity, CPU baselines, e2e, "
+                         "train, render, fit, RCCL probe; the --no-<leg> options below skip single ones) and write bench_detail.json; "
+                         "without it the run does only what `value` and `ms_per_step` need")
     ap.add_argument("--batch", type=int, default=4, help="subjects per GPU in the denoise loop (configs[1]: 4)")
     ap.add_argument("--views", type=int, default=36, help="512x512 views per GPU in the render leg (configs[2]: the whole 36-view orbit)")
     ap.add_argument("--sustained-steps", type=int, default=200,
@@ -117,9 +126,9 @@ def main():
         dump_outputs(last, args.dump_outputs)
     del last
     value = world * args.batch * args.steps / secs
-    rccl = collective_probe(args, rank, world, dev) if world > 1 else None
+    rccl = collective_probe(args, rank, world, dev) if args.full and world > 1 else None
     parity = None
-    if rank == 0 and world == 1 and not args.no_parity:
+    if args.full and rank == 0 and world == 1 and not args.no_parity:
         chain = e2e_chain(model, dev)
         parity = {"psnr_db": min(l["image_psnr_db"] for l in chain["layers"]), "max_abs": max(l["image_max_abs"] for l in chain["layers"]),
                   "triplane_psnr_db": min(l["triplane_psnr_db"] for l in chain["layers"]),
@@ -127,24 +136,24 @@ def main():
                   "ddim50_vs_reference": ddim50_parity(model, dev)}
     cpu = step_parity = None
     threads = min(len(os.sched_getaffinity(0)), 32)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # PyTorch-CPU stops scaling (and then collapses) beyond ~32 threads on this path: measured on the
         # MI355X host (256 logical CPUs) 3x3 conv 192->192@256^2: 49/47/40/90/208 ms at 8/16/32/64/128 threads
         cpu, step_parity = cpu_baseline_unet(sd, threads, None if args.no_parity else model, dev)
         if parity is not None:
             parity["denoise_steps_vs_oracle"] = step_parity
     e2e = None
-    if not args.no_e2e:
+    if args.full and not args.no_e2e:
         e2e = e2e_slice(model, dev, rank, world, n_layers=args.e2e_layers, ddim=args.e2e_ddim, n_views=args.e2e_views,
                         oracle=(world == 1 and not args.no_parity), subjects_per_gpu=args.e2e_subjects, batch=min(args.e2e_batch, args.e2e_subjects))
     train = None
-    if not args.no_train:
+    if args.full and not args.no_train:
         from humanliff_amd.improved_diffusion.script_util import create_gaussian_diffusion
         train = bench_train(model, create_gaussian_diffusion(steps=1000), dev, rank, world)
     del model
     torch.cuda.empty_cache()
     render = None
-    if not args.no_render:
+    if args.full and not args.no_render:
         rsecs, rroof, rays_per_rank = bench_render(args, rank, world, dev)
         render = {"metric": "Mrays/sec@256spp", "value": round(world * rays_per_rank / rsecs / 1e6, 4), "unit": "Mrays/s",
                   "dtype": "f32 results; MLP products = fp16x2 (two fp16 planes per operand, three partial products, fp32 accumulation - fp32 tolerance, same test "
@@ -153,7 +162,7 @@ def main():
                   "config": {"workload": "configs[2]: tri-plane NeRF render 512x512, n_samples=128 + n_importance=128, "
                                          "views of a 36-view orbit, random 256x256x27 tri-plane", "rays_per_view": 512 * 512}}
     fit = None
-    if not args.no_fit:
+    if args.full and not args.no_fit:
         torch.cuda.empty_cache()
         fit = bench_fit(args, rank, world, dev)
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
@@ -191,15 +200,14 @@ def main():
             if isinstance(roof, dict) and v is not None and k not in ("n_gpus",):
                 roof["hl_" + k] = v
         line["summary"] = summary
-        # Everything measured goes to bench_detail.json; stdout gets ONE compact line (bench_line.py: < 6 KB, no long strings) - round 5's
+        # Everything measured goes to bench_detail.json (--full); stdout gets ONE compact line (bench_line.py: < 6 KB, no long strings) - round 5's
         # 20 KB line was more than the driver's log reader kept.
         import bench_line
-        detail = json.dumps(line, indent=1)
-        for d in (os.path.join(ROOT, "gpurun_out"), ROOT):
+        line["detail_file"] = "bench_detail.json" if args.full else None
+        if args.full:
             try:
-                os.makedirs(d, exist_ok=True)
-                with open(os.path.join(d, "bench_detail.json"), "w") as f:
-                    f.write(detail + "\n")
+                with open(os.path.join(ROOT, "bench_detail.json"), "w") as f:
+                    f.write(json.dumps(line, indent=1) + "\n")
             except OSError:
                 pass
         sys.stdout.flush()

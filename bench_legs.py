@@ -1,7 +1,7 @@
 """bench_legs.py - the measurement legs behind bench.py (not a script).
 
 bench.py holds the driver contract: argument parsing, the N > 1 self-launch, the order of the legs and the ONE compact JSON line (bench_line.py).  Everything that
-measures lives here: the headline denoise loop (`bench_unet`: configs[1], with the live roofline of the dominant convolution kernel), the batch sweep, the parity legs
+measures lives here: the headline denoise loop (`bench_unet`: configs[1]; under --full also the live roofline of the dominant convolution kernel), the batch sweep, the parity legs
 against the reference's vectors and the oracle, the configs[3]/[4] per-GPU slice (`e2e_slice`), the render leg (configs[2]: both schedules, three product modes), the
 SURVEY 8(f) legs (fit, train) and the `cpu_baseline` legs (the ONLY place besides tests/ and smoke() that imports oracle/).
 """
@@ -164,6 +164,8 @@ def bench_unet(args, rank, world, dev):
         last = {k: v.detach().cpu() for k, v in out.items()}
         if world > 1:
             last["sample_all_ranks"] = gathered.cpu()
+    if not args.full:     # a plain run ends with the timed steps; the legs below run under bench.py --full only
+        return secs, None, sd, model, last
     # ---- roofline leg: one more step with per-launch HIP events inside hl_unet_forward ----
     L = _lib.lib()
     handle = model._hip[0]

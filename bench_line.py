@@ -1,7 +1,7 @@
 """The ONE JSON line `bench.py` prints, kept small enough for any log-tail reader.
 
-`bench.py` measures many legs (batch sweep, product modes, per-step parity tables, stage times ...).  All of that goes to
-`bench_detail.json` (written beside the repo's `gpurun_out/`, and copied to `profiles/rNN_bench_detail.json` by hand); the line on stdout
+`bench.py --full` measures many legs (batch sweep, product modes, per-step parity tables, stage times ...).  All of that goes to
+`bench_detail.json` in the repository root (copied to `profiles/rNN_bench_detail.json` by hand); the line on stdout
 carries only what SURVEY.md 8(d) names: metric / value / unit / n_gpus / steps / warmup / ms_per_step / dtype / config, the `roofline` of
 the dominant kernel, the `cpu_baseline`, `parity`, one five-number object per secondary leg and a flat `summary`.
 
@@ -108,7 +108,7 @@ def compact_line(full):
     line["config"] = {"workload": _clip(cfg.get("workload", "")), **_pick(cfg, ("global_batch", "parallelism", "gflop_per_sample_step"))}
     line["dtype_note"] = _clip(full.get("dtype_note", ""))
     line["step_tflops"] = _num(full.get("step_tflops"))
-    line["roofline"] = _roofline(roof, full.get("roofline_kernel_short"))
+    line["roofline"] = _roofline(full.get("roofline"), full.get("roofline_kernel_short"))     # None in a plain run (no --full)
     for k in ("fp32_mfma_mode", "fp16_mode", "bf16x3_mode"):
         v = _get(roof, k, "value")
         if v is not None:

@@ -147,9 +147,9 @@ def test_four_ranks_thirty_two_subjects_rehearsal(tmp_path):
 
 
 def test_bench_self_launches_for_more_than_one_gpu():
-    """`python bench.py --gpus 2` as the driver issues it - a plain process, no launcher, no WORLD_SIZE - must start its own ranks
-    (torch.distributed.run) and print ONE JSON line with n_gpus = 2 and the `rccl` block (ranks seen, backend, gather rates).  Rehearsed
-    with HL_BENCH_BACKEND=gloo: both ranks share the one GPU of this box; on an 8-GPU node the same path runs on RCCL."""
+    """`python bench.py --gpus 2 --full` as the driver issues it - a plain process, no launcher, no WORLD_SIZE - must start its own ranks
+    (torch.distributed.run) and print ONE JSON line with n_gpus = 2 and the `rccl` block (ranks seen, backend, gather rates; a --full leg).
+    Rehearsed with HL_BENCH_BACKEND=gloo: both ranks share the one GPU of this box; on an 8-GPU node the same path runs on RCCL."""
     import json
     import subprocess
     import sys
@@ -157,7 +157,7 @@ def test_bench_self_launches_for_more_than_one_gpu():
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
     env["HL_BENCH_BACKEND"] = "gloo"
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--batch", "1", "--sustained-steps", "0",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--batch", "1", "--full", "--sustained-steps", "0",
            "--no-cpu-baseline", "--no-parity", "--no-batch-sweep", "--no-render", "--no-e2e", "--no-train", "--no-fit", "--no-bf16x3-leg", "--e2e-views", "4"]
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, cwd=root)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
