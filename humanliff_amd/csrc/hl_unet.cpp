@@ -22,6 +22,27 @@ using hl::View;
 
 static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
+bool conv_mode_known(int mode) {
+    return mode == HL_CONV_FP32 || mode == HL_CONV_FP32_MFMA || mode == HL_CONV_BF16X3 || mode == HL_CONV_FP32_DIRECT || mode == HL_CONV_FP32_F23 ||
+           mode == HL_CONV_BF16 || mode == HL_CONV_FP16;
+}
+// The packed weight forms (besides the fp32 one) a convolution may use under the HL_CONV_* `mode`.  bf16_h16: the caller can pack the 16-bit
+// form in bf16 - the network packs it in fp16 only, so its HL_CONV_BF16 never reaches k_conv_h16.  bwd_data: a backward-data call (tf = 1),
+// which never takes the fp16x2 forms (measured in round 6 with the scale-invariant planes - the training step at microbatch 2 went from 102.6
+// to 110.1 ms as a HIP graph: per call the gradient's abs-max pass, the weights' scale + pack, and kernels that at two rounds of workgroups are
+// no faster than F(4x4,3x3) on the fp32 pipe).
+struct ConvForms { bool bf3, wino, wino4, h2, h16; };
+ConvForms conv_forms(int mode, bool bf16_h16, bool bwd_data) {
+    const bool f32 = mode == HL_CONV_FP32 || mode == HL_CONV_FP32_MFMA || mode == HL_CONV_FP16;   // (HL_CONV_FP16: the other layers as HL_CONV_FP32)
+    ConvForms f;
+    f.bf3 = mode == HL_CONV_BF16X3 || mode == HL_CONV_BF16;
+    f.wino = f32 || mode == HL_CONV_FP32_F23;
+    f.wino4 = f32;
+    f.h2 = mode == HL_CONV_FP32 && !bwd_data;
+    f.h16 = mode == HL_CONV_FP16 || (bf16_h16 && mode == HL_CONV_BF16);
+    return f;
+}
+
 struct Conv {
     const float *w = nullptr;  // packed
     const void *w_bf3 = nullptr;  // packed split-bf16 copy (layers that take the DMA tile), used when Net::conv_mode == 1
@@ -110,8 +131,8 @@ struct Net {
     std::vector<Span> spans;
     size_t ev_used = 0;
     // which kernel family each convolution of the LAST forward took, per resolution level (hl_unet_dispatch_census):
-    // [path 0 direct / 1 Winograd F(2x2) / 2 bf16x3 / 3 Winograd F(4x4)][log2(H / H_out)]
-    int64_t census[5][8] = {};   // (row 4: k_conv1_h2, the 1x1 layers with fp16x2 products)
+    // [hl::conv_census_row(path)][log2(H / H_out)]
+    int64_t census[5][8] = {};
     ~Net() {
         for (auto e : ev_pool) if (e) hipEventDestroy(e);
         for (auto e : ev_block) if (e) hipEventDestroy(e);
@@ -150,60 +171,30 @@ Conv make_conv(Net &n, const std::string &p, int Cin, int Cout, int ks, bool has
 Conv make_conv_w(Net &n, const float *w, const float *bias, int Cin, int Cout, int ks) {
     Conv c;
     c.Cin = Cin; c.Cin_pad = round_up(Cin, 16); c.Cout = Cout; c.ks = ks;
-    const size_t fl = hl::conv_packed_floats(Cout, c.Cin_pad, ks);
     c.bias = n.dry ? nullptr : bias;
-    if (!n.dry && w) {
-        float *dst = n.packed + n.packed_off;
-        if (hl::conv_pack_weights(w, Cout, Cin, c.Cin_pad, ks, dst, n.st) != 0 && n.err.empty()) n.err = hl_last_error();
-        c.w = dst;
-    }
-    n.packed_off += (fl + 63) / 64 * 64;
-    const size_t bf3 = hl::conv_packed_bf3_bytes(Cout, c.Cin_pad, ks);
-    if (bf3) {
-        if (!n.dry && w) {
-            void *dst = n.packed + n.packed_off;
-            if (hl::conv_pack_weights_bf3(w, Cout, Cin, c.Cin_pad, ks, dst, n.st) != 0 && n.err.empty()) n.err = hl_last_error();
-            c.w_bf3 = dst;
-        }
-        n.packed_off += (bf3 / 4 + 63) / 64 * 64;
-    }
-    const size_t wino = hl::conv_packed_wino_bytes(Cout, c.Cin_pad, ks);
-    if (wino) {
-        if (!n.dry && w) {
-            float *dst = n.packed + n.packed_off;
-            if (hl::conv_pack_weights_wino(w, Cout, Cin, c.Cin_pad, dst, n.st) != 0 && n.err.empty()) n.err = hl_last_error();
-            c.w_wino = dst;
-        }
-        n.packed_off += (wino / 4 + 63) / 64 * 64;
-    }
+    const int cp = c.Cin_pad;
     // F(4x4,3x3) weights are 4x the direct ones: kept for the layers that can reach a level wide enough for that kernel (up to 64 MB a layer)
-    size_t wino4 = hl::conv_packed_wino4_bytes(Cout, c.Cin_pad, ks);
+    size_t wino4 = hl::conv_packed_wino4_bytes(Cout, cp, ks);
     if (wino4 > ((size_t)64 << 20)) wino4 = 0;
-    if (wino4) {
-        if (!n.dry && w) {
-            float *dst = n.packed + n.packed_off;
-            if (hl::conv_pack_weights_wino4(w, Cout, Cin, c.Cin_pad, dst, n.st) != 0 && n.err.empty()) n.err = hl_last_error();
-            c.w_wino4 = dst;
+    // every form the layer has, in buffer order (fp32, bf16x3, F(2x2), F(4x4), fp16x2, fp16), each starting on 256 bytes; 0 bytes: no such form
+    const size_t bytes[6] = {hl::conv_packed_floats(Cout, cp, ks) * sizeof(float), hl::conv_packed_bf3_bytes(Cout, cp, ks),
+                             hl::conv_packed_wino_bytes(Cout, cp, ks), wino4, hl::conv_packed_h2_bytes(Cout, cp, ks),
+                             hl::conv_packed_h16_bytes(Cout, cp, ks)};
+    for (int f = 0; f < 6; ++f) {
+        if (!bytes[f]) continue;
+        float *dst = n.dry ? nullptr : n.packed + n.packed_off;
+        n.packed_off += (bytes[f] / 4 + 63) / 64 * 64;
+        if (n.dry || !w) continue;
+        int rc = 0;
+        switch (f) {
+        case 0: rc = hl::conv_pack_weights(w, Cout, Cin, cp, ks, dst, n.st); c.w = dst; break;
+        case 1: rc = hl::conv_pack_weights_bf3(w, Cout, Cin, cp, ks, dst, n.st); c.w_bf3 = dst; break;
+        case 2: rc = hl::conv_pack_weights_wino(w, Cout, Cin, cp, dst, n.st); c.w_wino = dst; break;
+        case 3: rc = hl::conv_pack_weights_wino4(w, Cout, Cin, cp, dst, n.st); c.w_wino4 = dst; break;
+        case 4: rc = hl::conv_pack_weights_h2(w, Cout, Cin, cp, ks, dst, n.st); c.w_h2 = dst; break;
+        default: rc = hl::conv_pack_weights_h16(w, Cout, Cin, cp, ks, dst, 1, n.st); c.w_h16 = dst; break;   // (fp16 only: conv_forms)
         }
-        n.packed_off += (wino4 / 4 + 63) / 64 * 64;
-    }
-    const size_t h2 = hl::conv_packed_h2_bytes(Cout, c.Cin_pad, ks);
-    if (h2) {
-        if (!n.dry && w) {
-            void *dst = n.packed + n.packed_off;
-            if (hl::conv_pack_weights_h2(w, Cout, Cin, c.Cin_pad, ks, dst, n.st) != 0 && n.err.empty()) n.err = hl_last_error();
-            c.w_h2 = dst;
-        }
-        n.packed_off += (h2 / 4 + 63) / 64 * 64;
-    }
-    const size_t h16 = hl::conv_packed_h16_bytes(Cout, c.Cin_pad, ks);
-    if (h16) {
-        if (!n.dry && w) {
-            void *dst = n.packed + n.packed_off;
-            if (hl::conv_pack_weights_h16(w, Cout, Cin, c.Cin_pad, ks, dst, 1, n.st) != 0 && n.err.empty()) n.err = hl_last_error();
-            c.w_h16 = dst;
-        }
-        n.packed_off += (h16 / 4 + 63) / 64 * 64;
+        if (rc != 0 && n.err.empty()) n.err = hl_last_error();
     }
     return c;
 }
@@ -508,11 +499,12 @@ struct Exec {
         if (!run) return;
         ConvArgs a{};
         a.in = in; a.in.C = c.Cin_pad;
-        a.w = c.w; a.w_bf3 = (n.conv_mode == HL_CONV_BF16X3 || n.conv_mode == HL_CONV_BF16) ? c.w_bf3 : nullptr; a.bf16_single = n.conv_mode == HL_CONV_BF16;
-        a.w_wino = (n.conv_mode == HL_CONV_FP32 || n.conv_mode == HL_CONV_FP32_MFMA || n.conv_mode == HL_CONV_FP32_F23 || n.conv_mode == HL_CONV_FP16) ? c.w_wino : nullptr;
-        a.w_h16 = n.conv_mode == HL_CONV_FP16 ? c.w_h16 : nullptr; a.h16_fp16 = 1;
-        a.w_h2 = n.conv_mode == HL_CONV_FP32 ? c.w_h2 : nullptr;
-        a.w_wino4 = (n.conv_mode == HL_CONV_FP32 || n.conv_mode == HL_CONV_FP32_MFMA || n.conv_mode == HL_CONV_FP16) ? c.w_wino4 : nullptr; a.bias = c.bias; a.Cout = c.Cout; a.ks = c.ks; a.stride = stride; a.ups = ups;
+        const ConvForms f = conv_forms(n.conv_mode, false, false);
+        a.w = c.w; a.w_bf3 = f.bf3 ? c.w_bf3 : nullptr; a.bf16_single = n.conv_mode == HL_CONV_BF16;
+        a.w_wino = f.wino ? c.w_wino : nullptr; a.w_wino4 = f.wino4 ? c.w_wino4 : nullptr;
+        a.w_h16 = f.h16 ? c.w_h16 : nullptr; a.h16_fp16 = 1;
+        a.w_h2 = f.h2 ? c.w_h2 : nullptr;
+        a.bias = c.bias; a.Cout = c.Cout; a.ks = c.ks; a.stride = stride; a.ups = ups;
         a.coefA = cA; a.coefB = cB; a.act = act; a.gn = af.gn;
         a.out = out; a.res = res; a.res_pitch = res_pitch;
         a.out2 = out2; a.out2_pitch = out2_pitch; a.res2 = res2; a.res2_pitch = res2_pitch; a.out_nchw = nchw;
@@ -524,25 +516,25 @@ struct Exec {
         const size_t e0 = span_begin();
         size_t emid = 0;
         if (n.prof) { emid = n.next_event(); a.ev_mid = n.ev_pool[emid]; }
-        ok(hl::conv2d(a, st));
+        const hl::ConvPlan pl = hl::plan_conv(a);
+        ok(hl::conv2d(a, pl, st));
         {   // developer audit (HL_AUDIT_SCALE=1, read once): fp16x2 launches whose raw input came without totals - their activation planes are unscaled (sx = 1)
             static const int audit_ = [] { const char *e_ = getenv("HL_AUDIT_SCALE"); return e_ ? atoi(e_) : 0; }();
-            if (audit_ && a.path == 6 && af.cA == nullptr && af.gn.gt == nullptr && a.in_stats == nullptr)
+            if (audit_ && pl.path == hl::ConvPath::Fp16x2 && af.cA == nullptr && af.gn.gt == nullptr && a.in_stats == nullptr)
                 fprintf(stderr, "[hl audit] fp16x2 convolution with an unscaled raw input: %dx%d px, %d -> %d channels, ks %d, stride %d\n", in.H, in.W, in.C, c.Cout, c.ks, stride);
         }
-        if (n.prof && a.ev_mid_used) span_mid = (long)emid;
+        if (n.prof && a.ev_mid && pl.pre != hl::ConvPrePass::None) span_mid = (long)emid;
         {
             int lvl = 0;
             while (lvl < 7 && (out.H << lvl) < H) ++lvl;
-            n.census[a.path == 6 ? 4 : (a.path == 5 ? 2 : (a.path & 3))][lvl] += 1;   // (k_conv_h16 counts with the other kernels of the 16-bit matrix pipe)
+            n.census[hl::conv_census_row(pl.path)][lvl] += 1;
             // (keyed like a rocprofv3 per-kernel, per-grid row: kernel family, level, Cout, kernel size - the input channel counts of a level share a row)
-            span_key[0] = a.path; span_key[1] = lvl; span_key[2] = ups ? 1 : 0; span_key[3] = c.Cout; span_key[4] = c.ks;
+            span_key[0] = (int)pl.path; span_key[1] = lvl; span_key[2] = ups ? 1 : 0; span_key[3] = c.Cout; span_key[4] = c.ks;
         }
         const double fl = 2.0 * (double)out.pixels() * c.Cout * c.Cin * c.ks * c.ks;
-        // Winograd F(2x2,3x3): 16 multiplies per 2x2 outputs instead of 36; bf16x3: six bf16 MFMA products per fp32 product
-        span_end(CAT_CONV, e0, fl, a.path == 1 ? fl * (16.0 / 36.0) : (a.path == 3 ? fl * 0.25 : (a.path == 2 ? fl * 6.0 : fl)));
+        span_end(CAT_CONV, e0, fl, fl * hl::conv_issued_factor(pl.path));
         // whoever stored the tensor last owns its statistics
-        if (a.stat_slots > 0) {
+        if (pl.stat_slots > 0) {
             stat_reg[out.p] = {st1, pi1.viewC, pi1.c0, c.Cout};
             if (out2) stat_reg[out2] = {st2, pi2.viewC, pi2.c0, c.Cout};
         } else {
@@ -930,7 +922,7 @@ int hl_unet_set_overlap(void *handle, int enable) {
 
 int hl_unet_set_conv_mode(void *handle, int mode) {
     HL_REQUIRE(handle, "hl_unet_set_conv_mode: null handle");
-    HL_REQUIRE(mode == HL_CONV_FP32 || mode == HL_CONV_FP32_MFMA || mode == HL_CONV_BF16X3 || mode == HL_CONV_FP32_DIRECT || mode == HL_CONV_FP32_F23 || mode == HL_CONV_BF16 || mode == HL_CONV_FP16, "hl_unet_set_conv_mode: unknown mode %d", mode);
+    HL_REQUIRE(conv_mode_known(mode), "hl_unet_set_conv_mode: unknown mode %d", mode);
     static_cast<Net *>(handle)->conv_mode = mode;
     return HL_OK;
 }
@@ -1043,7 +1035,7 @@ int hl_unet_profile_dominant(void *handle, double *h_vals, int *h_key) {
 // One convolution through the kernels of the network.  Cin = channels of `in` (multiple of 16); the weight tensor covers
 // Cin_w <= Cin of them (the rest are zero-padded channels with zero weights).  tf = 1: `w` is laid out (Cin_w, Cout, ks, ks) and is
 // read flipped and channel-transposed - the backward-data convolution of the training path.  Only the weight layout the chosen
-// kernel reads is packed (conv2d in plan mode decides first).
+// kernel reads is packed (plan_conv decides first).
 static int g_single_op_scale_from_totals = 0;   // hl_debug_set_single_op_scale_source (test switch)
 static int conv2d_single(int mode, const float *in, int N, int H, int W, int Cin, const float *w_oihw, const float *bias, int Cout,
                          int ks, int stride, int upsample, const float *coefA, const float *coefB, int silu,
@@ -1052,28 +1044,26 @@ static int conv2d_single(int mode, const float *in, int N, int H, int W, int Cin
     HL_REQUIRE(Cin % 16 == 0, "hl_conv2d_nhwc: Cin must be a multiple of 16");
     if (Cin_w < 0) Cin_w = Cin;
     HL_REQUIRE(Cin_w <= Cin, "hl_conv2d_nhwc: the weight has more input channels than the tensor");
+    hipStream_t st = (hipStream_t)stream;
     const size_t need32 = (hl::conv_packed_floats(Cout, Cin, ks) * sizeof(float) + 255) / 256 * 256;
-    const bool bf = mode == HL_CONV_BF16X3 || mode == HL_CONV_BF16;
-    const bool h16m = mode == HL_CONV_BF16 || mode == HL_CONV_FP16;      // 16-bit operands where k_conv_h16 applies
-    const bool f32m = mode == HL_CONV_FP32 || mode == HL_CONV_FP32_MFMA || mode == HL_CONV_FP16;      // (HL_CONV_FP16: the other layers as HL_CONV_FP32)
-    size_t extra = bf ? hl::conv_packed_bf3_bytes(Cout, Cin, ks)
-                      : (mode == HL_CONV_FP32_F23 ? hl::conv_packed_wino_bytes(Cout, Cin, ks)
-                         : (f32m ? std::max(hl::conv_packed_wino_bytes(Cout, Cin, ks), hl::conv_packed_wino4_bytes(Cout, Cin, ks)) : 0));
-    if (h16m) extra = std::max(extra, hl::conv_packed_h16_bytes(Cout, Cin, ks));
-    // (not the backward-data calls, tf = 1: measured in round 6 with the scale-invariant planes - the training step at microbatch 2 went from 102.6 to 110.1 ms as a HIP
-    //  graph: per call the gradient's abs-max pass, the weights' scale + pack, and kernels that at two rounds of workgroups are no faster than F(4x4,3x3) on the fp32 pipe)
-    if (mode == HL_CONV_FP32 && !tf) extra = std::max(extra, hl::conv_packed_h2_bytes(Cout, Cin, ks));
+    // the second weight layout: room for the largest form the mode allows (only the one the plan reads is packed)
+    const ConvForms f = conv_forms(mode, true, tf != 0);
+    const size_t b_bf3 = f.bf3 ? hl::conv_packed_bf3_bytes(Cout, Cin, ks) : 0, b_wino = f.wino ? hl::conv_packed_wino_bytes(Cout, Cin, ks) : 0,
+                 b_wino4 = f.wino4 ? hl::conv_packed_wino4_bytes(Cout, Cin, ks) : 0, b_h2 = f.h2 ? hl::conv_packed_h2_bytes(Cout, Cin, ks) : 0,
+                 b_h16 = f.h16 ? hl::conv_packed_h16_bytes(Cout, Cin, ks) : 0;
+    const size_t extra = std::max({b_bf3, b_wino, b_wino4, b_h2, b_h16});
     const size_t need = need32 + (extra + 255) / 256 * 256;
     HL_REQUIRE(scratch && scratch_bytes >= need, "hl_conv2d_nhwc: scratch too small (%zu < %zu)", scratch_bytes, need);
     ConvArgs a{};
     void *extra_dst = static_cast<char *>(scratch) + need32;
     a.in.p = const_cast<float *>(in); a.in.N = N; a.in.H = H; a.in.W = W; a.in.C = Cin; a.in.pitch = Cin;
     a.w = static_cast<float *>(scratch); a.bias = bias; a.Cout = Cout; a.ks = ks; a.stride = stride; a.ups = upsample;
-    if (bf && need > need32) { a.w_bf3 = extra_dst; a.bf16_single = mode == HL_CONV_BF16; }
-    if ((f32m || mode == HL_CONV_FP32_F23) && hl::conv_packed_wino_bytes(Cout, Cin, ks)) a.w_wino = static_cast<float *>(extra_dst);
-    if (f32m && hl::conv_packed_wino4_bytes(Cout, Cin, ks)) a.w_wino4 = static_cast<float *>(extra_dst);
-    if (h16m && hl::conv_packed_h16_bytes(Cout, Cin, ks)) { a.w_h16 = extra_dst; a.h16_fp16 = mode == HL_CONV_FP16; }
-    if (mode == HL_CONV_FP32 && !tf && hl::conv_packed_h2_bytes(Cout, Cin, ks)) a.w_h2 = extra_dst;
+    // every form the layer has under the mode points at that room, for plan_conv to choose from
+    if (b_bf3) { a.w_bf3 = extra_dst; a.bf16_single = mode == HL_CONV_BF16; }
+    if (b_wino) a.w_wino = static_cast<float *>(extra_dst);
+    if (b_wino4) a.w_wino4 = static_cast<float *>(extra_dst);
+    if (b_h16) { a.w_h16 = extra_dst; a.h16_fp16 = mode == HL_CONV_FP16; }
+    if (b_h2) a.w_h2 = extra_dst;
     a.coefA = coefA; a.coefB = coefB; a.act = silu;
     const int pad = ks / 2, Hv = upsample ? 2 * H : H, Wv = upsample ? 2 * W : W;
     a.out.p = out; a.out.N = N; a.out.H = (Hv + 2 * pad - ks) / stride + 1; a.out.W = (Wv + 2 * pad - ks) / stride + 1;
@@ -1097,47 +1087,38 @@ static int conv2d_single(int mode, const float *in, int N, int H, int W, int Cin
         a.splitk_ws_bytes = scratch_bytes - used;
     }
     a.stats = stats;
-    if (stats) HL_HIP(hipMemsetAsync(stats, 0, hl::conv_stats_floats(N, (long)a.out.H * a.out.W) * sizeof(float), (hipStream_t)stream));   // the epilogues ADD to the totals
-    a.plan_only = 1;
-    int rc = hl::conv2d(a, (hipStream_t)stream);
-    if (rc) return rc;
-    a.plan_only = 0;
-    if (a.path == 5) {
-        rc = hl::conv_pack_weights_h16(w_oihw, Cout, Cin_w, Cin, ks, extra_dst, a.h16_fp16, (hipStream_t)stream, tf);
-        a.w_wino = nullptr; a.w_wino4 = nullptr; a.w_bf3 = nullptr;
-    } else if (a.path == 6) {
-        rc = hl::conv_pack_weights_h2(w_oihw, Cout, Cin_w, Cin, ks, extra_dst, (hipStream_t)stream, tf);
-        a.w_wino = nullptr; a.w_wino4 = nullptr; a.w_bf3 = nullptr;
-    } else if (a.path == 3) {
-        rc = hl::conv_pack_weights_wino4(w_oihw, Cout, Cin_w, Cin, static_cast<float *>(extra_dst), (hipStream_t)stream, tf);
-        a.w_wino = nullptr;
-    } else if (a.path == 1) {
-        rc = hl::conv_pack_weights_wino(w_oihw, Cout, Cin_w, Cin, static_cast<float *>(extra_dst), (hipStream_t)stream, tf);
-        a.w_wino4 = nullptr;
-    } else {
-        if (a.path == 2) rc = hl::conv_pack_weights_bf3(w_oihw, Cout, Cin_w, Cin, ks, extra_dst, (hipStream_t)stream, tf);   // (k_conv_bf3 reads only these planes)
-        else rc = hl::conv_pack_weights(w_oihw, Cout, Cin_w, Cin, ks, static_cast<float *>(scratch), (hipStream_t)stream, tf);
-        a.w_wino = nullptr;
-        a.w_wino4 = nullptr;
+    if (stats) HL_HIP(hipMemsetAsync(stats, 0, hl::conv_stats_floats(N, (long)a.out.H * a.out.W) * sizeof(float), st));   // the epilogues ADD to the totals
+    const hl::ConvPlan pl = hl::plan_conv(a);
+    int rc;
+    switch (pl.path) {
+    case hl::ConvPath::H16: rc = hl::conv_pack_weights_h16(w_oihw, Cout, Cin_w, Cin, ks, extra_dst, a.h16_fp16, st, tf); break;
+    case hl::ConvPath::Fp16x2: rc = hl::conv_pack_weights_h2(w_oihw, Cout, Cin_w, Cin, ks, extra_dst, st, tf); break;
+    case hl::ConvPath::Wino4: rc = hl::conv_pack_weights_wino4(w_oihw, Cout, Cin_w, Cin, static_cast<float *>(extra_dst), st, tf); break;
+    case hl::ConvPath::Wino2: rc = hl::conv_pack_weights_wino(w_oihw, Cout, Cin_w, Cin, static_cast<float *>(extra_dst), st, tf); break;
+    case hl::ConvPath::Bf16x3: rc = hl::conv_pack_weights_bf3(w_oihw, Cout, Cin_w, Cin, ks, extra_dst, st, tf); break;   // (k_conv_bf3 reads only these planes)
+    default: rc = hl::conv_pack_weights(w_oihw, Cout, Cin_w, Cin, ks, static_cast<float *>(scratch), st, tf); break;
     }
     if (rc) return rc;
-    if (a.path != 5) a.w_h16 = nullptr;
-    if (a.path != 6) a.w_h2 = nullptr;
-    if (a.path == 6 && !coefA && tot_room) {   // fp16x2 products on a raw input: the largest |x| of every image fixes the power-of-two scale of the activation planes
+    // the room holds that form only: no kernel argument points at the others
+    if (pl.path != hl::ConvPath::Bf16x3) a.w_bf3 = nullptr;
+    if (pl.path != hl::ConvPath::Wino2) a.w_wino = nullptr;
+    if (pl.path != hl::ConvPath::Wino4) a.w_wino4 = nullptr;
+    if (pl.path != hl::ConvPath::H16) a.w_h16 = nullptr;
+    if (pl.path != hl::ConvPath::Fp16x2) a.w_h2 = nullptr;
+    if (pl.path == hl::ConvPath::Fp16x2 && !coefA && tot_room) {   // fp16x2 products on a raw input: the largest |x| of every image fixes the power-of-two scale of the activation planes
         // (in the network the producers' sum x^2 bounds it; here one pass over the tensor - exact at any magnitude, which the backward-data calls need: gradients are 1e-4 ... 1e-9)
         if (g_single_op_scale_from_totals) {      // (test switch: the network's scale source - the group totals - on a single layer)
-            rc = hl::tensor_totals(a.in, tot_room, (hipStream_t)stream);
+            rc = hl::tensor_totals(a.in, tot_room, st);
             if (rc) return rc;
             a.in_stats = tot_room;
         } else {
-            rc = hl::tensor_absmax(a.in, tot_room, (hipStream_t)stream);
+            rc = hl::tensor_absmax(a.in, tot_room, st);
             if (rc) return rc;
             a.in_absmax = tot_room;
         }
     }
-    rc = hl::conv2d(a, (hipStream_t)stream);
-    if (stat_slots) *stat_slots = a.stat_slots;
-    return rc;
+    if (stat_slots) *stat_slots = pl.stat_slots;
+    return hl::conv2d(a, pl, st);
 }
 
 int hl_conv2d_nhwc_bwd_data(int conv_mode, const float *dy, int N, int Ho, int Wo, int Cy, const float *w_oihw, int Cout, int Cin, int ks,
@@ -1178,7 +1159,7 @@ int hl_conv2d_nhwc_gn(int conv_mode, const float *in, int N, int H, int W, int C
                       int ks, int stride, int upsample, const float *coefA, const float *coefB, int silu, const float *residual,
                       float *out, const float *gamma, const float *beta, float *next_coefA, float *next_coefB, int *h_used_stats,
                       void *scratch, size_t scratch_bytes, void *stream) {
-    HL_REQUIRE(conv_mode == HL_CONV_FP32 || conv_mode == HL_CONV_FP32_MFMA || conv_mode == HL_CONV_BF16X3 || conv_mode == HL_CONV_FP32_DIRECT || conv_mode == HL_CONV_FP32_F23 || conv_mode == HL_CONV_BF16 || conv_mode == HL_CONV_FP16, "hl_conv2d_nhwc_gn: unknown mode %d", conv_mode);
+    HL_REQUIRE(conv_mode_known(conv_mode), "hl_conv2d_nhwc_gn: unknown mode %d", conv_mode);
     HL_REQUIRE(gamma && beta && next_coefA && next_coefB && scratch, "hl_conv2d_nhwc_gn: null argument");
     const int pad = ks / 2, Hv = upsample ? 2 * H : H, Wv = upsample ? 2 * W : W;
     const int Ho = (Hv + 2 * pad - ks) / stride + 1, Wo = (Wv + 2 * pad - ks) / stride + 1;
@@ -1211,7 +1192,7 @@ int hl_conv2d_nhwc(const float *in, int N, int H, int W, int Cin, const float *w
 int hl_conv2d_nhwc_mode(int conv_mode, const float *in, int N, int H, int W, int Cin, const float *w_oihw, const float *bias,
                         int Cout, int ks, int stride, int upsample, const float *coefA, const float *coefB, int silu,
                         const float *residual, float *out, void *scratch, size_t scratch_bytes, void *stream) {
-    HL_REQUIRE(conv_mode == HL_CONV_FP32 || conv_mode == HL_CONV_FP32_MFMA || conv_mode == HL_CONV_BF16X3 || conv_mode == HL_CONV_FP32_DIRECT || conv_mode == HL_CONV_FP32_F23 || conv_mode == HL_CONV_BF16 || conv_mode == HL_CONV_FP16, "hl_conv2d_nhwc_mode: unknown mode %d", conv_mode);
+    HL_REQUIRE(conv_mode_known(conv_mode), "hl_conv2d_nhwc_mode: unknown mode %d", conv_mode);
     return conv2d_single(conv_mode, in, N, H, W, Cin, w_oihw, bias, Cout, ks, stride, upsample, coefA, coefB, silu, residual, out,
                          scratch, scratch_bytes, stream);
 }

@@ -57,7 +57,6 @@ struct ConvArgs {
     int out_nchw;        // write (N, Cout, H, W) instead of NHWC
     float *act_ws;       // optional scratch (pixels*Cin floats) for the materialised GroupNorm(+SiLU) input of k_conv_dma
     size_t act_ws_bytes;
-    mutable int path;    // set by conv2d: 0 direct implicit GEMM, 1 Winograd F(2x2,3x3), 2 bf16x3 emulation, 3 Winograd F(4x4,3x3), 5 k_conv_h16, 6 fp16x2 (k_conv1_h2s / k_conv_h2s / k_conv_h2d)
     float *splitk_ws;    // optional scratch for split-K partial sums (small-M layers); null disables split-K
     size_t splitk_ws_bytes;
     // GroupNorm statistics of the OUTPUT for the layer that will normalise it, emitted by the epilogue of whichever kernel stores
@@ -65,15 +64,12 @@ struct ConvArgs {
     // that the workgroups add to with integer atomics (hl_stats.h) - integer addition is associative, so the totals are bit-identical
     // from run to run.  `stats` (and `stats2` for out2) need conv_stats_floats(N, pixels per image) floats each, ZEROED before the first
     // producer of the view runs; null = not wanted.  st_cg = channels per group of the view (0: Cout / 32), st_c0 = channel of the view
-    // that output channel 0 is (a decoder "concat" has two producers adding into one block).  On return stat_slots is 1 when the launch
-    // added its totals, 0 when this path emits none (register-staged / bf16x3 / NCHW / odd sizes): the consumer then computes the
+    // that output channel 0 is (a decoder "concat" has two producers adding into one block).  ConvPlan::stat_slots says whether the
+    // launch adds its totals (> 0) or this path emits none (register-staged / bf16x3 / NCHW / odd sizes): the consumer then computes the
     // statistics from the tensor (groupnorm_coef).
     float *stats, *stats2;
     int st_cg, st_c0, st2_cg, st2_c0;
-    mutable int stat_slots;
     hipEvent_t ev_mid;   // optional (profiling): recorded between the GroupNorm pre-pass and the convolution kernel, when there is a pre-pass
-    mutable int ev_mid_used;
-    int plan_only;       // 1: no launch, only set `path` (w / w_wino / w_bf3 are then just non-null markers of what could be packed)
 };
 // kernel-side argument block of the convolution kernels (filled by conv2d)
 struct ConvK {
@@ -140,7 +136,48 @@ size_t conv_splitk_ws_bytes();
 int tensor_totals(const View &x, float *totals, hipStream_t st);
 // [N] floats: the largest |x| of every image (zeroed here; non-negative floats order like their bit patterns: one integer atomicMax per workgroup)
 int tensor_absmax(const View &x, float *amax, hipStream_t st);
-int conv2d(const ConvArgs &a, hipStream_t st);
+
+// The kernel family a convolution runs on.  The values reach Python (hl_unet_dispatch_census, hl_unet_profile_dominant) and keep their numbers.
+enum class ConvPath : int {
+    Direct = 0,   // implicit GEMM on the fp32 matrix pipe: k_conv, k_conv_dma
+    Wino2 = 1,    // Winograd F(2x2,3x3): k_conv_wino
+    Bf16x3 = 2,   // fp32 emulated on the bf16 matrix pipe (or HL_CONV_BF16): k_conv_bf3
+    Wino4 = 3,    // Winograd F(4x4,3x3): k_conv_wino4, k_conv_wino4w
+    H16 = 5,      // 16-bit operands: k_conv_h16
+    Fp16x2 = 6,   // fp16x2 products: k_conv1_h2s, k_conv_h2s, k_conv_h2d
+};
+// row of hl_unet_dispatch_census: 0 direct, 1 F(2x2), 2 the 16-bit matrix pipe (bf16x3 and k_conv_h16), 3 F(4x4), 4 fp16x2
+constexpr int conv_census_row(ConvPath p) {
+    return p == ConvPath::Fp16x2 ? 4 : (p == ConvPath::H16 ? 2 : (int)p);
+}
+// FLOPs a family issues per algorithmic FLOP: Winograd F(2x2,3x3) 16 multiplies per 2x2 outputs instead of 36, F(4x4,3x3) a quarter,
+// bf16x3 six bf16 MFMA products per fp32 product
+constexpr double conv_issued_factor(ConvPath p) {
+    return p == ConvPath::Wino2 ? 16.0 / 36.0 : (p == ConvPath::Wino4 ? 0.25 : (p == ConvPath::Bf16x3 ? 6.0 : 1.0));
+}
+// the kernel within the family
+enum class ConvKernel { Conv, Dma, Bf3, Wino, Wino4, Wino4w, H16, H2s, H2s1, H2d };
+// GroupNorm(+SiLU) materialised into ConvArgs::act_ws before the convolution, and its format: dense fp32, fp32 channel-blocked [C/8][pixel][8]
+// (k_conv_wino4 / k_conv_wino4w read it), the 16-bit image (k_conv_h16) or the two-plane fp16 image (k_conv_h2s)
+enum class ConvPrePass { None, Dense, Blocked, Half, TwoPlane };
+// which kernel adds the output statistics (ConvArgs::stats): the convolution's epilogue, or the split-K finish
+enum class ConvStatsBy { None, Epilogue, Finish };
+
+// Everything a convolution launch decides, made by plan_conv without any HIP call.
+struct ConvPlan {
+    ConvPath path = ConvPath::Direct;
+    ConvKernel kernel = ConvKernel::Conv;
+    int cfg = 0;             // k_conv tile config: 0 = 128x96, 1 = 128x32 (Cout <= 32), 2 = 64x64
+    bool tile8 = false;      // k_conv_dma / k_conv_bf3: the 8-wave 256x96 tile (else 4 waves x 128x96)
+    int gn_mode = 0;         // GroupNorm in front of the convolution: 0 none, 1 the affine, 2 the affine + SiLU
+    ConvPrePass pre = ConvPrePass::None;
+    int splits = 1, kt_per = 0;   // split-K slabs (k_splitk_finish[_st] sums them when > 1) and k-tiles per slab
+    ConvStatsBy stats_by = ConvStatsBy::None;
+    int stat_slots = 0;      // > 0: the launch adds the output statistics (ConvArgs::stats); 0: the consumer computes them from the tensor
+};
+ConvPlan plan_conv(const ConvArgs &a);
+// runs `pl` = plan_conv(a); a caller may change a weight pointer in between only to point it at the form the plan reads (conv2d_single)
+int conv2d(const ConvArgs &a, const ConvPlan &pl, hipStream_t st);
 size_t conv_packed_floats(int Cout, int Cin_pad, int ks);
 // tf = 1: the source is laid out (Cin, Cout, ks, ks) and is read flipped and channel-transposed (backward-data weights)
 int conv_pack_weights(const float *w_oihw, int Cout, int Cin, int Cin_pad, int ks, float *packed, hipStream_t st, int tf = 0);

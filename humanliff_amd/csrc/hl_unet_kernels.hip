@@ -2872,8 +2872,6 @@ int conv_pack_weights_wino4(const float *w, int Cout, int Cin, int Cin_pad, floa
     return check_launch("k_pack_conv_wino4");
 }
 
-static inline long hw_o_early(const ConvArgs &a) { return (long)a.out.H * a.out.W; }
-
 // k_conv_h16 is taken from this many workgroups on.  The default (48) is what the network dispatch uses; the unit tests that run the
 // kernel on single tiles set it through hl_debug_set_h16_min_blocks.
 constexpr long kH16MinBlocks = 48;
@@ -2881,478 +2879,376 @@ static long g_h16_min_blocks = -1;
 static long h16_min_blocks() { return g_h16_min_blocks >= 0 ? g_h16_min_blocks : kH16MinBlocks; }
 void set_h16_min_blocks(long v) { g_h16_min_blocks = v; }
 
-int conv2d(const ConvArgs &a, hipStream_t st) {
-    a.path = 0;
-    HL_REQUIRE(a.in.p && a.w && a.out.p, "conv2d: null tensor");
-    HL_REQUIRE(a.in.C % 16 == 0, "conv2d: Cin (%d) must be padded to a multiple of 16", a.in.C);
-    HL_REQUIRE(a.ks == 1 || a.ks == 3, "conv2d: kernel size %d", a.ks);
-    HL_REQUIRE(a.stride == 1 || (a.stride == 2 && !a.ups), "conv2d: stride/upsample combination");
-    HL_REQUIRE((a.in.pitch % 4) == 0 && ((uintptr_t)a.in.p % 16) == 0, "conv2d: input must be 16-byte aligned per pixel");
-    ConvK p{};
-    p.in = a.in.p; p.in_pitch = a.in.pitch; p.N = a.in.N; p.Hin = a.in.H; p.Win = a.in.W; p.Cin = a.in.C;
-    p.Hout = a.out.H; p.Wout = a.out.W; p.ks = a.ks; p.stride = a.stride; p.ups = a.ups; p.taps = a.ks * a.ks;
-    const int pad = a.ks / 2;
-    const int Hv = a.ups ? 2 * a.in.H : a.in.H, Wv = a.ups ? 2 * a.in.W : a.in.W;
-    HL_REQUIRE(a.out.H == (Hv + 2 * pad - a.ks) / a.stride + 1 && a.out.W == (Wv + 2 * pad - a.ks) / a.stride + 1 &&
-                   a.out.N == a.in.N, "conv2d: output shape mismatch");
-    p.w = a.w; p.w_bf3 = a.w_bf3; p.w_wino = a.w_wino; p.Ktot = (long)a.in.C * p.taps; p.bias = a.bias; p.Cout = a.Cout; p.wrows = round_up(a.Cout, 64);
-    p.cA = a.coefA; p.cB = a.coefB; p.act = a.act; p.gn = a.gn;
-    p.st1_cg = a.st_cg > 0 ? a.st_cg : std::max(1, a.Cout / 32); p.st1_c0 = a.st_c0; p.st2_cg = a.st2_cg > 0 ? a.st2_cg : std::max(1, a.Cout / 32); p.st2_c0 = a.st2_c0;
+// Split-K over nk k-tiles: `want` slabs (each family applies its own target, caps and floor first) are cut until their partial sums
+// (M x Cout floats a slab) fit the workspace, then re-rounded so that every slab holds kt_per k-tiles (the last one fewer).  Fewer than two
+// slabs left, or fewer than min_blocks workgroups (blocks x slabs): one slab of the whole K.  (Every family caps `want` at nk / 2 or less,
+// so a split that is taken stays a split after the re-rounding.)
+struct SplitK { int splits, kt_per; };
+static SplitK split_k(const ConvArgs &a, int nk, int want, long blocks = 0, long min_blocks = 0) {
+    const long M = (long)a.out.N * a.out.H * a.out.W;
+    if (!a.splitk_ws) want = 1;
+    while (want > 1 && (size_t)want * M * a.Cout * sizeof(float) > a.splitk_ws_bytes) --want;
+    if (want < 2 || blocks * want < min_blocks) return {1, nk};
+    const int kt = (nk + want - 1) / want;
+    return {(nk + kt - 1) / kt, kt};
+}
+
+ConvPlan plan_conv(const ConvArgs &a) {
+    ConvPlan pl;
     const bool gn_on = a.coefA != nullptr || a.gn.gt != nullptr;      // a GroupNorm affine in front of the convolution (arrays, or formed in the kernels)
-    HL_REQUIRE(!gn_on || a.coefA || a.gn.C == a.in.C, "conv2d: GnSrc covers %d of %d channels", a.gn.C, a.in.C);
-    p.out = a.out.p; p.out_pitch = a.out.pitch; p.res = a.res; p.res_pitch = a.res_pitch;
-    p.out2 = a.out2; p.out2_pitch = a.out2_pitch; p.res2 = a.res2; p.res2_pitch = a.res2_pitch;
-    p.out_nchw = a.out_nchw;
-    p.M = (long)a.out.N * a.out.H * a.out.W;
-    const long M = p.M;
-    const int cpad = p.wrows;
-    const int nk = (a.in.C / 16) * p.taps;
+    pl.gn_mode = gn_on ? (a.act ? 2 : 1) : 0;
+    const long M = (long)a.out.N * a.out.H * a.out.W, hw_o = (long)a.out.H * a.out.W;
+    const int cpad = round_up(a.Cout, 64);
+    const long Ktot = (long)a.in.C * a.ks * a.ks;
+    const int nk = (a.in.C / 16) * a.ks * a.ks;
+    const bool in_31 = (long)a.in.N * a.in.H * a.in.W * a.in.pitch * 4 < (1L << 31);   // byte offsets into the input fit 31 bits
+    // GroupNorm statistics of the output (ConvK::st1 / st2): slots of 32 consecutive pixels must not straddle images
+    const bool st_rows32 = a.stats && !a.out_nchw && hw_o % 32 == 0;
+    // the statistics of an unsplit launch come from the kernel's epilogue (`epi`: it has them here, `slots` of them), those of a split one from the finish
+    auto done = [&](bool epi, int slots) {
+        if (pl.splits > 1) {
+            if (st_rows32 && M % 32 == 0) { pl.stats_by = ConvStatsBy::Finish; pl.stat_slots = (int)(hw_o / 32); }
+        } else if (epi) {
+            pl.stats_by = ConvStatsBy::Epilogue; pl.stat_slots = slots;
+        }
+        return pl;
+    };
+    auto take = [&](ConvPath path, ConvKernel kernel, SplitK sk) { pl.path = path; pl.kernel = kernel; pl.splits = sk.splits; pl.kt_per = sk.kt_per; };
+
     // tile configs: 0 = 128x96 (4 waves of 32x96: 48 accumulators -> 4 waves/SIMD, 4 workgroups/CU = 1024 slots),
     // 1 = 128x32 (Cout <= 32), 2 = 64x64.  Small-M layers keep the efficient main tile and split K instead
     // (deterministic slabs + k_splitk_finish) until the grid covers the chip.
     const long main_blocks = ((M + 127) / 128) * (cpad / 96);
     constexpr int split_cap = 16;
     const int max_splits = a.splitk_ws ? (nk / 8 < split_cap ? nk / 8 : split_cap) : 1;
-    int cfg;
     long blocks;
-    if (cpad % 96 == 0 && main_blocks * (max_splits > 0 ? max_splits : 1) >= 192) { cfg = 0; blocks = main_blocks; }
-    else if (a.Cout <= 32) { cfg = 1; blocks = (M + 127) / 128; }
-    else { cfg = 2; blocks = ((M + 63) / 64) * (cpad / 64); }
+    if (cpad % 96 == 0 && main_blocks * (max_splits > 0 ? max_splits : 1) >= 192) { pl.cfg = 0; blocks = main_blocks; }
+    else if (a.Cout <= 32) { pl.cfg = 1; blocks = (M + 127) / 128; }
+    else { pl.cfg = 2; blocks = ((M + 63) / 64) * (cpad / 64); }
     // main-tile layers that need no upsampling go through k_conv_dma (GroupNorm materialised by k_gn_apply first);
     // the 8-wave 256x96 tile when that covers at least half the chip (2 workgroups/CU = 512 slots), else 4 waves x 128x96
     constexpr int dma_thr = 256;      // 256x96 tiles when they give at least this many workgroups
-    constexpr long wino_thr = 512;    // Winograd: workgroups wanted per launch (smaller layers split the input channels)
-    constexpr long wino_min = 384;    // fewer even after splitting: direct kernel
-    const bool dma = cfg == 0 && (!gn_on || a.act_ws) &&
-                     (long)a.in.N * a.in.H * a.in.W * a.in.pitch * 4 < (1L << 31) && (long)cpad * p.Ktot * 4 < (1L << 31);
+    const bool dma = pl.cfg == 0 && (!gn_on || a.act_ws) && in_31 && (long)cpad * Ktot * 4 < (1L << 31);
     const long blocks8 = ((M + 255) / 256) * (cpad / 96);
-    const bool tile8 = dma && blocks8 >= dma_thr;
-    if (tile8) blocks = blocks8;
-    int splits = 1;
-    const long target = cfg == 2 ? 1280 : (tile8 ? 512 : (dma ? 768 : 1024));
-    if (a.splitk_ws && blocks <= target / 2 && nk >= 16) {
-        splits = (int)(target / blocks);
-        if (splits > nk / 8) splits = nk / 8;
-        if (splits > split_cap) splits = split_cap;
-        while (splits > 1 && (size_t)splits * M * a.Cout * sizeof(float) > a.splitk_ws_bytes) --splits;
-        if (splits < 1) splits = 1;
-    }
-    p.kt_per = (nk + splits - 1) / splits;
-    splits = (nk + p.kt_per - 1) / p.kt_per;
-    p.partial = splits > 1 ? a.splitk_ws : nullptr;
-    const int mode = gn_on ? (a.act ? 2 : 1) : 0;
-    HL_REQUIRE(gn_on || !a.act, "conv2d: SiLU without the GroupNorm affine is not used by the UNet");
-    // GroupNorm statistics of the output (ConvK::st1 / st2): slots of 32 consecutive pixels must not straddle images
-    a.stat_slots = 0;
-    const bool st_rows32 = a.stats && !a.out_nchw && hw_o_early(a) % 32 == 0;
-    auto finish = [&](const char *what) -> int {   // split-K: the slab sum (+ statistics when wanted)
-        int rc = check_launch(what);
-        if (rc) return rc;
-        if (st_rows32 && M % 32 == 0) {
-            p.st1 = a.stats; p.st2 = a.out2 ? a.stats2 : nullptr;
-            a.stat_slots = (int)(hw_o_early(a) / 32);
-            hipLaunchKernelGGL(k_splitk_finish_st, dim3((unsigned)(M / 32), (unsigned)((a.Cout + 63) / 64)), dim3(256), 0, st, p, splits);
-        } else {
-            long gf = (M * a.Cout + 255) / 256;
-            if (gf > 2048) gf = 2048;
-            hipLaunchKernelGGL(k_splitk_finish, dim3((unsigned)gf), dim3(256), 0, st, p, splits);
-        }
-        return check_launch("k_splitk_finish");
-    };
-    const long hw_o = (long)a.out.H * a.out.W;
-#define HL_CONV_GO(WM_, WN_, MT_, NT_, GRID)                                                         \
-    do {                                                                                             \
-        constexpr int BM_ = WM_ * MT_ * 32, BN_ = WN_ * NT_ * 32;                                    \
-        const int nimg = (int)((BM_ + hw_o - 1) / hw_o) + 1;                                         \
-        const size_t shm = ((size_t)2 * (BM_ + BN_) * 20 + (mode ? (size_t)nimg * 2 * a.in.C + COEF_SCR_FLOATS : 0)) * sizeof(float); \
-        HL_REQUIRE(shm <= 160 * 1024, "conv2d: LDS request %zu too large", shm);                     \
-        if (a.ups) {   /* nearest x2 + conv: only ever follows a raw tensor (unet.py:77-79) */                \
-            HL_REQUIRE(mode == 0, "conv2d: upsample with a GroupNorm prologue is not used by the UNet");    \
-            hipLaunchKernelGGL((k_conv<WM_, WN_, MT_, NT_, 0, true>), GRID, dim3(256), shm, st, p);          \
-        } else if (mode == 0) hipLaunchKernelGGL((k_conv<WM_, WN_, MT_, NT_, 0, false>), GRID, dim3(256), shm, st, p); \
-        else if (mode == 1) hipLaunchKernelGGL((k_conv<WM_, WN_, MT_, NT_, 1, false>), GRID, dim3(256), shm, st, p);   \
-        else hipLaunchKernelGGL((k_conv<WM_, WN_, MT_, NT_, 2, false>), GRID, dim3(256), shm, st, p);                  \
-    } while (0)
-    // 3x3 / stride-1 layers: Winograd F(2x2,3x3) with 16x8-pixel x 64-channel workgroups; layers that do not fill the chip
-    // that way split the input channels into slabs (the output transform is linear: k_splitk_finish sums outputs)
-    const long wino_blocks = (long)a.out.N * (a.out.H / 8) * (a.out.W / 16) * (a.Cout / 64);
-    bool wino = dma && a.w_wino && !a.w_bf3 && a.ks == 3 && a.stride == 1 && a.out.H % 8 == 0 && a.out.W % 16 == 0 &&
-                a.Cout % 64 == 0 && (long)a.Cout * a.in.C * 64 < (1L << 31);   // (stride 1: out = in, or 2x in when upsampling)
-    int wsplits = 1;
-    if (wino && wino_blocks < wino_thr) {
-        const int nkt8 = a.in.C / 8;
-        // the most slabs that still fit ONE round of workgroups (2 per CU): rounding up instead put 576 workgroups on 512 slots - a second,
-        // nearly empty round (measured: 66 -> 63 us at 32x32, 67 -> 57 us at 16x16, 122 -> 102 us with 1536 input channels)
-        wsplits = (int)(wino_thr / wino_blocks);
-        if (wsplits < 2) wsplits = 2;
-        if (wsplits > nkt8 / 6) wsplits = nkt8 / 6;              // at least 6 k-tiles (48 channels) per slab
-        if (wsplits > 16) wsplits = 16;
-        while (wsplits > 1 && (size_t)wsplits * M * a.Cout * sizeof(float) > a.splitk_ws_bytes) --wsplits;
-        if (!a.splitk_ws || wsplits < 2 || wino_blocks * wsplits < wino_min) wino = false;
-    }
-    if (wino) {
-        splits = wsplits;
-        p.kt_per = (a.in.C / 8 + splits - 1) / splits;
-        splits = (a.in.C / 8 + p.kt_per - 1) / p.kt_per;
-        p.partial = splits > 1 ? a.splitk_ws : nullptr;
-    }
-    // the same layers by Winograd F(4x4,3x3) (32x16-pixel x 32-channel workgroups, a quarter of the direct multiplies) where that
-    // alone fills the chip
-    constexpr long wino4_thr = 512;
-    // (the 27-channel NCHW output convolution takes the F(4x4) kernel too: its weights are padded to 32 rows, the epilogue stores 27)
-    const bool small_nchw = a.out_nchw && a.Cout < 32 && !a.res && !a.out2 && !a.stats && (!gn_on || a.act_ws) &&
-                            (long)a.in.N * a.in.H * a.in.W * a.in.pitch * 4 < (1L << 31);
-    const long wino4_blocks = (long)a.out.N * (a.out.H / 16) * (a.out.W / 32) * ((a.Cout + 31) / 32);
-    const bool wino4_ok = (dma || small_nchw) && a.w_wino4 && !a.w_bf3 && a.ks == 3 && a.stride == 1 && a.out.H % 16 == 0 && a.out.W % 32 == 0 &&
-                          (a.Cout % 32 == 0 || small_nchw) && (long)round_up(a.Cout, 32) * a.in.C * 144 < (1L << 31);
-    bool wino4 = wino4_ok && wino4_blocks >= wino4_thr;
-    // k_conv_wino4w: the same arithmetic with 64 output channels per workgroup at ONE workgroup per CU (hl_conv_wino4w.hip).  With W
-    // = 32x16-pixel x 64-channel workgroups it is taken
-    //   * from three rounds of the 256 CUs on (W >= 768: the 256-pixel level at batch >= 2),
-    //   * where one round nearly fills the chip (160 <= W <= 256: the 64-pixel level at batch 4 - 192 workgroups run 140 us where the
-    //     768 smaller workgroups of the F(2x2) kernel take 188 us),
-    //   * below that with the input channels split into slabs until W x slabs reaches one round (k_splitk_finish sums them).
-    // In between (1.5 rounds: 128x128 at batch 4, 384 workgroups, 151 us against 131 us) the two-workgroups-per-CU kernels keep the layer.
-    const long w4w_blocks = wino4_blocks / 2;
-    bool wino4w = false;
-    int w4w_splits = 1;
-    if (wino4_ok && a.Cout % 64 == 0 && w4w_blocks > 0) {
-        const int nkt8 = a.in.C / 8;
-        if (w4w_blocks >= 768 || (w4w_blocks >= 160 && w4w_blocks <= 256)) wino4w = true;
-        else if (w4w_blocks < 160 && a.splitk_ws) {
-            w4w_splits = (int)(256 / w4w_blocks);
-            if (w4w_splits > nkt8 / 8) w4w_splits = nkt8 / 8;            // at least 8 k-tiles (64 channels) per slab
-            while (w4w_splits > 1 && (size_t)w4w_splits * M * a.Cout * sizeof(float) > a.splitk_ws_bytes) --w4w_splits;
-            wino4w = w4w_splits >= 2 && w4w_blocks * w4w_splits >= 128;
-            if (!wino4w) w4w_splits = 1;
-        }
-    }
-    if (wino4w) wino4 = true;
-    if (wino4) {
-        wino = false;
-        splits = wino4w ? w4w_splits : 1;
-        p.kt_per = (a.in.C / 8 + splits - 1) / splits;
-        splits = (a.in.C / 8 + p.kt_per - 1) / p.kt_per;
-        p.partial = splits > 1 ? a.splitk_ws : nullptr;
-    }
-    // 16-bit operands (opt-in modes): the 3x3 / stride-1 layers k_conv_h16 covers; the rest of the mode stays on k_conv_bf3 / fp32
+    pl.tile8 = dma && blocks8 >= dma_thr;
+    if (pl.tile8) blocks = blocks8;
+    const long target = pl.cfg == 2 ? 1280 : (pl.tile8 ? 512 : (dma ? 768 : 1024));
+    const SplitK direct_sk = split_k(a, nk, a.splitk_ws && blocks <= target / 2 && nk >= 16 ? (int)std::min<long>(std::min<long>(target / blocks, nk / 8), split_cap) : 1);
+
     // 16-bit operands (opt-in modes): the 3x3 / 1x1 stride-1 layers k_conv_h16 / k_conv1_h16 cover, from h16_min_blocks() workgroups on; a 3x3
     // layer with fewer tiles splits its input channels into slabs of >= 2 chunks (k_splitk_finish sums them) until ~128 workgroups run
     const long h16_blocks = ((long)a.out.N * a.out.H * a.out.W / 256) * (a.Cout / 192);
-    bool h16 = a.w_h16 && (!gn_on || (a.act_ws && !a.ups)) && !a.out_nchw &&
-               conv_h16_applies(a.out.H, a.out.W, a.in.C, a.Cout, a.ks, a.stride, a.ups) &&
-               (long)a.in.N * a.in.H * a.in.W * a.in.pitch * 4 < (1L << 31) && a.in.pitch % 4 == 0 && h16_blocks > 0;
-    int h16_splits = 1;
-    if (h16 && h16_blocks < h16_min_blocks()) {
-        const int nch32 = a.in.C / 32;
-        if (a.ks == 3 && a.splitk_ws && !a.out2 && h16_blocks >= 4) {
-            h16_splits = (int)std::min<long>(std::min<long>(128 / h16_blocks, nch32 / 2), 16);
-            while (h16_splits > 1 && (size_t)h16_splits * M * a.Cout * sizeof(float) > a.splitk_ws_bytes) --h16_splits;
+    const int nk32 = a.in.C / 32;      // chunks of 32 input channels: the k-tiles of k_conv_h16 / k_conv_h2s
+    if (a.w_h16 && (!gn_on || (a.act_ws && !a.ups)) && !a.out_nchw && conv_h16_applies(a.out.H, a.out.W, a.in.C, a.Cout, a.ks, a.stride, a.ups) &&
+        in_31 && a.in.pitch % 4 == 0 && h16_blocks > 0) {
+        const bool fills = h16_blocks >= h16_min_blocks();
+        const int want = a.ks == 3 && !a.out2 && h16_blocks >= 4 ? (int)std::min<long>(std::min<long>(128 / h16_blocks, nk32 / 2), 16) : 0;
+        const SplitK sk = split_k(a, nk32, fills ? 1 : want, h16_blocks, h16_min_blocks());
+        if (fills || sk.splits > 1) {
+            take(ConvPath::H16, ConvKernel::H16, sk);
+            if (gn_on) pl.pre = ConvPrePass::Half;      // GroupNorm(+SiLU) materialised once, as the 16-bit image the kernel stages without conversion
+            return done(a.stats, (int)(hw_o / 128));    // slot = (tile, round) = 128 pixels
         }
-        if (h16_splits < 2 || h16_blocks * h16_splits < h16_min_blocks()) { h16 = false; h16_splits = 1; }
     }
     // 1x1 / stride-1 layers of the DEFAULT mode on the 16-bit matrix pipe with fp16x2 products (k_conv1_h2s): once off the fp32 pipe they are bound by HBM, the
     // fp32 kernel takes twice as long.  From h2_min_blocks workgroups of 256 pixels x 192 channels on (fewer: the split-K fp32 path keeps the layer).
     constexpr long h2_min_blocks = 12;   // (12: with the 128-pixel tiles; 48 with the 256-pixel ones)
     const long h2_blocks = (M / 256) * (a.Cout / 192);
-    const bool h2 = !h16 && a.w_h2 && (!gn_on || a.act_ws) && !a.out_nchw && !a.w_bf3 &&
-                    conv1_h2_applies(a.out.H, a.out.W, a.in.C, a.Cout, a.ks, a.stride, a.ups) &&
-                    (long)a.in.N * a.in.H * a.in.W * a.in.pitch * 4 < (1L << 31) && a.in.pitch % 4 == 0 && h2_blocks >= h2_min_blocks;
+    if (a.w_h2 && (!gn_on || a.act_ws) && !a.out_nchw && !a.w_bf3 && conv1_h2_applies(a.out.H, a.out.W, a.in.C, a.Cout, a.ks, a.stride, a.ups) &&
+        in_31 && a.in.pitch % 4 == 0 && h2_blocks >= h2_min_blocks) {
+        // few workgroups (the 16- and 32-pixel levels, batch 1): the input channels split into slabs of >= 4 chunks until ~256 workgroups run (k_splitk_finish[_st] sums them)
+        constexpr long h2_split_max = 64;
+        const int nk48 = a.in.C / 48;
+        take(ConvPath::Fp16x2, ConvKernel::H2s1,
+             split_k(a, nk48, h2_blocks < h2_split_max && !a.out2 ? (int)std::min<long>(std::min<long>(128 / std::max<long>(h2_blocks, 1), nk48 / 4), 8) : 1));
+        const bool fuse1 = a.in.C <= 4096;      // GroupNorm(+SiLU) applied by k_conv1_h2s while staging
+        if (gn_on && !fuse1) pl.pre = ConvPrePass::Dense;   // else materialised once as dense fp32 (the kernel splits into its two fp16 planes while staging)
+        return done(a.stats, 1);                // statistics from the epilogue (128 pixels of one image per round)
+    }
     // 3x3 / stride-1 layers of the default mode in the same arithmetic, from 100 workgroups of 256 pixels x 192 channels on: k_conv_h2s, a direct convolution on
     // 8x16-pixel tiles with TWO workgroups per CU (late round 5).  Same box, forward wall time: B = 1 12.8 -> 12.2 ms, B = 4 32.5 -> 30.4, B = 8 58.9 -> 54.9 (both
     // small-tile kernels).  The first version of the kernel (16x16 tiles, one workgroup per CU: k_conv_h16's workgroups with two planes, since removed) won only where a layer was about one
     // round of workgroups: alone it beat k_conv_wino4w by 12 % on the 256-pixel level and the forward's wall time did not move - a kernel that owns whole CUs cannot fill
     // the other encoder tower's bubbles, and nothing overlapped its own prologue / staging / epilogue (profiles/r05_unet_fill_experiments.md, sections 6 - 8).
     constexpr long h3_min_blocks = 100;
-    const bool h3_base = !h16 && !h2 && a.w_h2 && a.ks == 3 && (!gn_on || (a.act_ws && !a.ups)) && !a.out_nchw && !a.w_bf3 &&
-                         conv_h16_applies(a.out.H, a.out.W, a.in.C, a.Cout, a.ks, a.stride, a.ups) &&
-                         (long)a.in.N * a.in.H * a.in.W * a.in.pitch * 4 < (1L << 31) && a.in.pitch % 4 == 0;
-    bool h3 = h3_base && h16_blocks >= h3_min_blocks;
-    // below that: the input channels split into slabs of >= 2 chunks until about one round of 128-pixel workgroups runs (k_splitk_finish[_st] sums the slabs)
-    constexpr long h3_split_min = 8;
-    int h3_splits = 1;
-    if (h3_base && !h3 && h16_blocks >= h3_split_min && a.splitk_ws && !a.out2) {
+    if (a.w_h2 && a.ks == 3 && (!gn_on || (a.act_ws && !a.ups)) && !a.out_nchw && !a.w_bf3 &&
+        conv_h16_applies(a.out.H, a.out.W, a.in.C, a.Cout, a.ks, a.stride, a.ups) && in_31 && a.in.pitch % 4 == 0) {
+        // below that: the input channels split into slabs of >= 2 chunks until about one round of 128-pixel workgroups runs (k_splitk_finish[_st] sums the slabs)
+        constexpr long h3_split_min = 8;
         constexpr long h3_min_chunks = 2;     // chunks of 32 input channels per slab, at least
         constexpr long h3_max_splits = 16;
         constexpr long h3_target = 256;       // workgroups (of 256 pixels x 192 channels) aimed at
-        h3_splits = (int)std::min<long>(std::min<long>(h3_target / h16_blocks, (a.in.C / 32) / h3_min_chunks), h3_max_splits);
-        while (h3_splits > 1 && (size_t)h3_splits * M * a.Cout * sizeof(float) > a.splitk_ws_bytes) --h3_splits;
-        if (h3_splits >= 2) h3 = true; else h3_splits = 1;
+        const bool fills = h16_blocks >= h3_min_blocks;
+        const int want = h16_blocks >= h3_split_min && !a.out2 ? (int)std::min<long>(std::min<long>(h3_target / h16_blocks, nk32 / h3_min_chunks), h3_max_splits) : 0;
+        const SplitK sk = split_k(a, nk32, fills ? 1 : want);
+        if (fills || sk.splits > 1) {
+            take(ConvPath::Fp16x2, ConvKernel::H2s, sk);
+            // GroupNorm(+SiLU) of the input: applied by k_conv_h2s while it stages the patch (its two workgroups per CU hide the VALU) - no pass over the tensor;
+            // beyond 4096 channels materialised once, as the two-plane image the kernel stages without conversion (the same bytes as fp32)
+            const bool fuse = !a.ups && a.in.C <= 4096;
+            if (gn_on && !fuse) pl.pre = ConvPrePass::TwoPlane;
+            return done(a.stats, (int)(hw_o / 128));
+        }
     }
     // 3x3 / stride-2 layers (Downsample) of the default mode in the same arithmetic (k_conv_h2d), from h3d_min_blocks workgroups' worth of output (256 pixels x 192 channels) on
     constexpr long h3d_min_blocks = 32;
-    const bool h3d = !h16 && !h2 && !h3 && a.w_h2 && a.ks == 3 && a.stride == 2 && !a.ups && mode == 0 && !a.out_nchw && !a.w_bf3 &&
-                     conv3_h2d_applies(a.out.H, a.out.W, a.in.C, a.Cout) && (long)a.in.N * a.in.H * a.in.W * a.in.pitch * 4 < (1L << 31) && a.in.pitch % 4 == 0 &&
-                     h16_blocks >= h3d_min_blocks;
-    if (a.plan_only) {   // which weight layout will this launch read?  (single-op entry points pack only that one)
-        a.path = h16 ? 5 : (h2 || h3 || h3d) ? 6 : (wino4 ? 3 : ((dma && wino) ? 1 : ((dma && a.w_bf3 && (long)cpad * p.Ktot * 6 < (1L << 31)) ? 2 : 0)));
-        return HL_OK;
+    if (a.w_h2 && a.ks == 3 && a.stride == 2 && !a.ups && !gn_on && !a.out_nchw && !a.w_bf3 && conv3_h2d_applies(a.out.H, a.out.W, a.in.C, a.Cout) &&
+        in_31 && a.in.pitch % 4 == 0 && h16_blocks >= h3d_min_blocks) {
+        take(ConvPath::Fp16x2, ConvKernel::H2d, {1, direct_sk.kt_per});   // one launch over the whole K (k_conv_h2d does not read kt_per)
+        return done(a.stats, (int)(hw_o / 128));
     }
-    if (h16) {
-        a.path = 5;
-        if (mode != 0) {   // GroupNorm(+SiLU) materialised once, as the 16-bit image the kernel stages without conversion
-            HL_REQUIRE((size_t)a.in.pixels() * a.in.C * sizeof(float) <= a.act_ws_bytes, "conv2d: act scratch too small");
-            const long npix = a.in.pixels();
-            long g = (npix * (a.in.C / 4) + 255) / 256;
-            if (g > 4096) g = 4096;
-            if (a.coefA == nullptr) {
-                const int ppw = gn_gs_ppw(a.in.H * a.in.W, a.in.N, a.in.C);
-                hipLaunchKernelGGL(k_gn_apply_gs<1>, dim3((unsigned)((a.in.H * a.in.W + ppw - 1) / ppw), (unsigned)a.in.N), dim3(256), (size_t)(2 * a.in.C + COEF_SCR_FLOATS) * sizeof(float), st,
-                                   a.in.p, a.in.pitch, a.in.H * a.in.W, a.in.C, a.gn, a.in.N, a.act, (void *)a.act_ws, a.h16_fp16, ppw);
-            } else
-            hipLaunchKernelGGL(k_gn_apply_h16, dim3((unsigned)g), dim3(256), 0, st, a.in.p, a.in.pitch, (long)a.in.H * a.in.W, npix, a.in.C, a.coefA,
-                               a.coefB, a.act, reinterpret_cast<unsigned short *>(a.act_ws), a.h16_fp16);
-            p.in = a.act_ws; p.in_pitch = a.in.C; p.cA = nullptr; p.cB = nullptr; p.act = 0; p.gn = GnSrc{};
-            p.in16 = 1;                                  // in_pitch counts 16-bit elements now
-            if (a.ev_mid) { hipEventRecord(a.ev_mid, st); a.ev_mid_used = 1; }
+
+    // the Winograd kernels and k_conv_dma read a materialised GroupNorm(+SiLU)
+    const ConvPrePass dense = gn_on ? ConvPrePass::Dense : ConvPrePass::None;
+    const int nk8 = a.in.C / 8;      // the k-tiles of the Winograd kernels: 8 input channels
+    // 3x3 / stride-1 layers by Winograd F(4x4,3x3) (32x16-pixel x 32-channel workgroups, a quarter of the direct multiplies) where that
+    // alone fills the chip
+    constexpr long wino4_thr = 512;
+    // (the 27-channel NCHW output convolution takes the F(4x4) kernel too: its weights are padded to 32 rows, the epilogue stores 27)
+    const bool small_nchw = a.out_nchw && a.Cout < 32 && !a.res && !a.out2 && !a.stats && (!gn_on || a.act_ws) && in_31;
+    const long wino4_blocks = (long)a.out.N * (a.out.H / 16) * (a.out.W / 32) * ((a.Cout + 31) / 32);
+    if ((dma || small_nchw) && a.w_wino4 && !a.w_bf3 && a.ks == 3 && a.stride == 1 && a.out.H % 16 == 0 && a.out.W % 32 == 0 &&
+        (a.Cout % 32 == 0 || small_nchw) && (long)round_up(a.Cout, 32) * a.in.C * 144 < (1L << 31)) {
+        // k_conv_wino4w: the same arithmetic with 64 output channels per workgroup at ONE workgroup per CU (hl_conv_wino4w.hip).  With W
+        // = 32x16-pixel x 64-channel workgroups it is taken
+        //   * from three rounds of the 256 CUs on (W >= 768: the 256-pixel level at batch >= 2),
+        //   * where one round nearly fills the chip (160 <= W <= 256: the 64-pixel level at batch 4 - 192 workgroups run 140 us where the
+        //     768 smaller workgroups of the F(2x2) kernel take 188 us),
+        //   * below that with the input channels split into slabs until W x slabs reaches one round (k_splitk_finish sums them).
+        // In between (1.5 rounds: 128x128 at batch 4, 384 workgroups, 151 us against 131 us) the two-workgroups-per-CU kernels keep the layer.
+        const long w4w_blocks = wino4_blocks / 2;
+        const bool w4w_fills = a.Cout % 64 == 0 && (w4w_blocks >= 768 || (w4w_blocks >= 160 && w4w_blocks <= 256));
+        const SplitK w4w_sk = a.Cout % 64 == 0 && w4w_blocks > 0 && w4w_blocks < 160
+                                  ? split_k(a, nk8, (int)std::min<long>(256 / w4w_blocks, nk8 / 8), w4w_blocks, 128)   // at least 8 k-tiles (64 channels) per slab
+                                  : SplitK{1, nk8};
+        if (w4w_fills || w4w_sk.splits > 1) take(ConvPath::Wino4, ConvKernel::Wino4w, w4w_sk);
+        else if (wino4_blocks >= wino4_thr) take(ConvPath::Wino4, ConvKernel::Wino4, w4w_sk);
+        if (pl.path == ConvPath::Wino4) {
+            // for the F(4x4) kernels the normalised copy is channel-blocked, [C/8][pixel][8]: its patch DMA then reads 128 contiguous
+            // bytes per four pixels instead of 32 per pixel (the gather rate of the LDS-DMA path is set by the number of distinct
+            // segments: 33 B/ns/CU at 32 bytes, 148 at 128 - scripts/microbench/dma_bw.hip)
+            const bool blk = a.in.pixels() % 64 == 0 && (a.coefA || ((long)a.in.H * a.in.W) % 8 == 0);
+            pl.pre = gn_on ? (blk ? ConvPrePass::Blocked : ConvPrePass::Dense) : ConvPrePass::None;
+            return done(a.stats && !a.out_nchw, (a.out.H / 16) * (a.out.W / 32) * 8);   // slot = (32x16 block, round, wave) = 64 pixels
         }
-        p.w_bf3 = a.w_h16;
-        splits = h16_splits;
-        p.kt_per = (a.in.C / 32 + splits - 1) / splits;                  // chunks of 32 input channels per slab
-        splits = (a.in.C / 32 + p.kt_per - 1) / p.kt_per;
-        p.partial = splits > 1 ? a.splitk_ws : nullptr;
-        p.n_nblocks = a.Cout / 192;
-        p.n_mtiles = (int)((long)a.out.N * a.out.H * a.out.W / 256);   // 16x16-pixel tiles (3x3) / runs of 256 pixels (1x1)
-        if (a.stats) {   // statistics from the epilogue: slot = (tile, round) = 128 pixels
-            p.st1 = a.stats; p.st2 = a.out2 ? a.stats2 : nullptr;
-            a.stat_slots = a.out.H * a.out.W / 128;
-        }
-        if (splits > 1) {   // the finish kernel emits the statistics
-            p.st1 = p.st2 = nullptr;
-            a.stat_slots = 0;
-            int rc = conv_h16_launch(p, a.h16_fp16, st, splits);
-            if (rc) return rc;
-            return finish("k_conv_h16");
-        }
-        return conv_h16_launch(p, a.h16_fp16, st);
     }
-    if (h3d) {
-        a.path = 6;
-        p.in16 = 0; p.w_bf3 = a.w_h2; p.partial = nullptr;
-        p.wsc = conv_h2_wscale(a.w_h2, a.Cout, a.in.C, a.ks);
-        p.xs_gt = a.in_stats; p.xs_hw = a.in.H * a.in.W; p.xs_max = a.in_absmax;
-        p.n_nblocks = a.Cout / 192;
-        p.n_mtiles = (int)((long)a.out.N * a.out.H * a.out.W / 128);
-        if (a.stats) {
-            p.st1 = a.stats; p.st2 = a.out2 ? a.stats2 : nullptr;
-            a.stat_slots = a.out.H * a.out.W / 128;
+    // 3x3 / stride-1 layers: Winograd F(2x2,3x3) with 16x8-pixel x 64-channel workgroups; layers that do not fill the chip
+    // that way split the input channels into slabs (the output transform is linear: k_splitk_finish sums outputs)
+    constexpr long wino_thr = 512;    // Winograd: workgroups wanted per launch (smaller layers split the input channels)
+    constexpr long wino_min = 384;    // fewer even after splitting: direct kernel
+    const long wino_blocks = (long)a.out.N * (a.out.H / 8) * (a.out.W / 16) * (a.Cout / 64);
+    if (dma && a.w_wino && !a.w_bf3 && a.ks == 3 && a.stride == 1 && a.out.H % 8 == 0 && a.out.W % 16 == 0 &&
+        a.Cout % 64 == 0 && (long)a.Cout * a.in.C * 64 < (1L << 31)) {   // (stride 1: out = in, or 2x in when upsampling)
+        const bool fills = wino_blocks >= wino_thr;
+        // the most slabs that still fit ONE round of workgroups (2 per CU): rounding up instead put 576 workgroups on 512 slots - a second,
+        // nearly empty round (measured: 66 -> 63 us at 32x32, 67 -> 57 us at 16x16, 122 -> 102 us with 1536 input channels)
+        const int want = fills ? 1 : (int)std::min<long>(std::min<long>(std::max<long>(wino_thr / wino_blocks, 2), nk8 / 6), 16);   // at least 6 k-tiles (48 channels) per slab
+        const SplitK sk = split_k(a, nk8, want, wino_blocks, wino_min);
+        if (fills || sk.splits > 1) {
+            take(ConvPath::Wino2, ConvKernel::Wino, sk);
+            pl.pre = dense;
+            return done(a.stats && !a.out_nchw, (a.out.H / 8) * (a.out.W / 16) * 2);   // slot = (16x8 block, column parity)
         }
-        return conv3_h2d_launch(p, st);
     }
-    if (h3) {
-        a.path = 6;
-        p.in16 = 0;
-        // GroupNorm(+SiLU) of the input: applied by k_conv_h2s while it stages the patch (its two workgroups per CU hide the VALU) - no pass over the tensor
-        const bool fuse = mode != 0 && !a.ups && a.in.C <= 4096;
-        if (mode != 0 && !fuse) {   // GroupNorm(+SiLU) materialised once, as the two-plane image the kernel stages without conversion (the same bytes as fp32)
-            HL_REQUIRE((size_t)a.in.pixels() * a.in.C * sizeof(float) <= a.act_ws_bytes, "conv2d: act scratch too small");
-            const long npix = a.in.pixels();
-            if (a.coefA == nullptr) {
-                const int ppw = gn_gs_ppw(a.in.H * a.in.W, a.in.N, a.in.C);
-                hipLaunchKernelGGL(k_gn_apply_gs<1>, dim3((unsigned)((a.in.H * a.in.W + ppw - 1) / ppw), (unsigned)a.in.N), dim3(256), (size_t)(2 * a.in.C + COEF_SCR_FLOATS) * sizeof(float), st,
-                                   a.in.p, a.in.pitch, a.in.H * a.in.W, a.in.C, a.gn, a.in.N, a.act, (void *)a.act_ws, 2, ppw);
-            } else {
-                long g = (npix * (a.in.C / 4) + 255) / 256;
-                if (g > 4096) g = 4096;
-                hipLaunchKernelGGL(k_gn_apply_h16, dim3((unsigned)g), dim3(256), 0, st, a.in.p, a.in.pitch, (long)a.in.H * a.in.W, npix, a.in.C, a.coefA,
-                                   a.coefB, a.act, reinterpret_cast<unsigned short *>(a.act_ws), 2);
-            }
-            p.in = a.act_ws; p.in_pitch = a.in.C; p.cA = nullptr; p.cB = nullptr; p.act = 0; p.gn = GnSrc{};
-            p.in16 = 2;
-            if (a.ev_mid) { hipEventRecord(a.ev_mid, st); a.ev_mid_used = 1; }
-        }
-        p.w_bf3 = a.w_h2;
-        p.wsc = conv_h2_wscale(a.w_h2, a.Cout, a.in.C, a.ks);
-        if (mode == 0) { p.xs_gt = a.in_stats; p.xs_hw = a.in.H * a.in.W; p.xs_max = a.in_absmax; }      // (raw input; a fused GroupNorm bounds its own output)
-        splits = h3_splits;
-        p.kt_per = (a.in.C / 32 + splits - 1) / splits;                  // chunks of 32 input channels per slab
-        splits = (a.in.C / 32 + p.kt_per - 1) / p.kt_per;
-        p.partial = splits > 1 ? a.splitk_ws : nullptr;
-        p.n_nblocks = a.Cout / 192;
-        p.n_mtiles = (int)((long)a.out.N * a.out.H * a.out.W / 256);
-        if (a.stats) {
-            p.st1 = a.stats; p.st2 = a.out2 ? a.stats2 : nullptr;
-            a.stat_slots = a.out.H * a.out.W / 128;
-        }
-        p.n_mtiles *= 2;   // 8x16-pixel tiles, two workgroups per CU
-        if (splits > 1) {   // the finish kernel adds bias / residual and emits the statistics
-            p.st1 = p.st2 = nullptr;
-            a.stat_slots = 0;
-            int rc = conv3_h2s_launch(p, st, splits);
-            if (rc) return rc;
-            return finish("k_conv_h2s");
-        }
-        return conv3_h2s_launch(p, st);
+    if (dma) {
+        const bool bf3 = a.w_bf3 && (long)cpad * Ktot * 6 < (1L << 31);   // fp32 emulated on the bf16 matrix pipe (opt-in)
+        take(bf3 ? ConvPath::Bf16x3 : ConvPath::Direct, bf3 ? ConvKernel::Bf3 : ConvKernel::Dma, direct_sk);
+        pl.pre = dense;
+        return done(st_rows32 && !bf3, (int)(hw_o / 32));   // slot = a wave's 32 rows
     }
-    if (h2) {
-        a.path = 6;
-        const bool fuse1 = mode != 0 && a.in.C <= 4096;      // GroupNorm(+SiLU) applied by k_conv1_h2s while staging
-        if (mode != 0 && !fuse1) {   // GroupNorm(+SiLU) materialised once as dense fp32 (the kernel splits into its two fp16 planes while staging)
-            HL_REQUIRE((size_t)a.in.pixels() * a.in.C * sizeof(float) <= a.act_ws_bytes, "conv2d: act scratch too small");
-            const long npix = a.in.pixels();
-            if (a.coefA == nullptr) {
-                const int ppw = gn_gs_ppw(a.in.H * a.in.W, a.in.N, a.in.C);
-                hipLaunchKernelGGL(k_gn_apply_gs<0>, dim3((unsigned)((a.in.H * a.in.W + ppw - 1) / ppw), (unsigned)a.in.N), dim3(256), (size_t)(2 * a.in.C + COEF_SCR_FLOATS) * sizeof(float), st,
-                                   a.in.p, a.in.pitch, a.in.H * a.in.W, a.in.C, a.gn, a.in.N, a.act, (void *)a.act_ws, 0, ppw);
-            } else {
-                long g = (npix * (a.in.C / 4) + 255) / 256;
-                if (g > 4096) g = 4096;
-                hipLaunchKernelGGL(k_gn_apply, dim3((unsigned)g), dim3(256), 0, st, a.in.p, a.in.pitch, (long)a.in.H * a.in.W, npix, a.in.C, a.coefA, a.coefB, a.act, a.act_ws);
-            }
-            p.in = a.act_ws; p.in_pitch = a.in.C; p.cA = nullptr; p.cB = nullptr; p.act = 0; p.gn = GnSrc{};
-            if (a.ev_mid) { hipEventRecord(a.ev_mid, st); a.ev_mid_used = 1; }
+    take(ConvPath::Direct, ConvKernel::Conv, direct_sk);   // k_conv applies the GroupNorm(+SiLU) itself
+    return done(false, 0);
+}
+
+// GroupNorm(+SiLU) of the input materialised once into a.act_ws, in the format the convolution kernel stages without conversion
+static int gn_prepass(const ConvArgs &a, ConvPrePass fmt, hipStream_t st) {
+    HL_REQUIRE((size_t)a.in.pixels() * a.in.C * sizeof(float) <= a.act_ws_bytes, "conv2d: act scratch too small");
+    const long npix = a.in.pixels();
+    const int out16 = fmt == ConvPrePass::TwoPlane ? 2 : a.h16_fp16;   // k_gn_apply_h16 / k_gn_apply_gs<1>: 2 = two fp16 planes, 1 fp16, 0 bf16
+    if (fmt == ConvPrePass::Blocked) {
+        const int tp = 8;   // (8 pixels = 256 contiguous bytes per plane; larger tiles cost occupancy: 64 pixels 93 us, 8 pixels 70 us = the plain pass)
+        const int pad = ((4 - (a.in.C / 4) % 16 + 16) % 16) * 4;   // row length / 4 = 4 (mod 16): the read-back groups (8 pixels x 2 halves of two planes) hit 16 different slots
+        const size_t shb = (size_t)(tp * (a.in.C + pad) + (a.coefA ? 0 : 2 * a.in.C + COEF_SCR_FLOATS)) * sizeof(float);
+        // coefficients formed in the kernel: a workgroup amortises them over `reps` tiles of its image (at most 16, at least ~2048 workgroups)
+        int reps = 1;
+        if (!a.coefA) {
+            const long tiles_img = (long)a.in.H * a.in.W / tp;
+            while (reps < 16 && tiles_img % (reps * 2) == 0 && npix / tp / (reps * 2) >= 2048) reps *= 2;
         }
-        p.w_bf3 = a.w_h2; p.in16 = 0; p.partial = nullptr;
-        p.wsc = conv_h2_wscale(a.w_h2, a.Cout, a.in.C, a.ks);
-        if (mode == 0) { p.xs_gt = a.in_stats; p.xs_hw = a.in.H * a.in.W; p.xs_max = a.in_absmax; }
-        p.n_nblocks = a.Cout / 192;
-        p.n_mtiles = (int)(M / 256);
-        if (a.stats) {   // statistics from the epilogue (128 pixels of one image per round)
-            p.st1 = a.stats; p.st2 = a.out2 ? a.stats2 : nullptr;
-            a.stat_slots = 1;
-        }
-        p.n_mtiles *= 2;   // 128-pixel tiles, two workgroups per CU
-        p.kt_per = a.in.C / 48;
-        // few workgroups (the 16- and 32-pixel levels, batch 1): the input channels split into slabs of >= 4 chunks until ~256 workgroups run (k_splitk_finish[_st] sums them)
-        constexpr long h2_split_max = 64;
-        if (h2_blocks < h2_split_max && a.splitk_ws && !a.out2) {
-            int sp = (int)std::min<long>(std::min<long>(128 / std::max<long>(h2_blocks, 1), (a.in.C / 48) / 4), 8);
-            while (sp > 1 && (size_t)sp * M * a.Cout * sizeof(float) > a.splitk_ws_bytes) --sp;
-            if (sp >= 2) {
-                p.kt_per = (a.in.C / 48 + sp - 1) / sp;
-                splits = (a.in.C / 48 + p.kt_per - 1) / p.kt_per;
-                p.partial = a.splitk_ws;
-                p.st1 = p.st2 = nullptr;
-                a.stat_slots = 0;
-                int rc = conv1_h2s_launch(p, st, splits);
-                if (rc) return rc;
-                return finish("k_conv1_h2s");
-            }
-        }
-        return conv1_h2s_launch(p, st);
+        hipLaunchKernelGGL(k_gn_apply_blk, dim3((unsigned)(npix / tp / reps)), dim3(256), shb, st, a.in.p, a.in.pitch, (long)a.in.H * a.in.W, npix,
+                           a.in.C, a.coefA, a.coefB, a.act, a.act_ws, tp, a.in.C + pad, a.gn, a.in.N, reps);
+    } else if (a.coefA == nullptr) {   // the coefficients formed from the producers' totals
+        const int ppw = gn_gs_ppw(a.in.H * a.in.W, a.in.N, a.in.C);
+        const dim3 grid((unsigned)((a.in.H * a.in.W + ppw - 1) / ppw), (unsigned)a.in.N);
+        const size_t sh = (size_t)(2 * a.in.C + COEF_SCR_FLOATS) * sizeof(float);
+        if (fmt == ConvPrePass::Dense)
+            hipLaunchKernelGGL(k_gn_apply_gs<0>, grid, dim3(256), sh, st, a.in.p, a.in.pitch, a.in.H * a.in.W, a.in.C, a.gn, a.in.N, a.act, (void *)a.act_ws, 0, ppw);
+        else
+            hipLaunchKernelGGL(k_gn_apply_gs<1>, grid, dim3(256), sh, st, a.in.p, a.in.pitch, a.in.H * a.in.W, a.in.C, a.gn, a.in.N, a.act, (void *)a.act_ws, out16, ppw);
+    } else {
+        const unsigned g = (unsigned)std::min<long>((npix * (a.in.C / 4) + 255) / 256, 4096);
+        if (fmt == ConvPrePass::Dense)
+            hipLaunchKernelGGL(k_gn_apply, dim3(g), dim3(256), 0, st, a.in.p, a.in.pitch, (long)a.in.H * a.in.W, npix, a.in.C, a.coefA, a.coefB, a.act, a.act_ws);
+        else
+            hipLaunchKernelGGL(k_gn_apply_h16, dim3(g), dim3(256), 0, st, a.in.p, a.in.pitch, (long)a.in.H * a.in.W, npix, a.in.C, a.coefA,
+                               a.coefB, a.act, reinterpret_cast<unsigned short *>(a.act_ws), out16);
     }
-    bool blk4 = false;
-    if (dma || wino4) {
-        HL_REQUIRE(mode == 0 || !a.ups, "conv2d: upsample with a GroupNorm prologue is not used by the UNet");
-        if (mode != 0) {   // materialise GroupNorm(+SiLU) once, then the DMA kernels read it raw
-            HL_REQUIRE((size_t)a.in.pixels() * a.in.C * sizeof(float) <= a.act_ws_bytes, "conv2d: act scratch too small");
-            const long npix = a.in.pixels();
-            long g = (npix * (a.in.C / 4) + 255) / 256;
-            if (g > 4096) g = 4096;
-            if (wino4 && npix % 64 == 0 && (a.coefA || ((long)a.in.H * a.in.W) % 8 == 0)) {
-                // for the F(4x4) kernel the normalised copy is channel-blocked, [C/8][pixel][8]: its patch DMA then reads 128 contiguous
-                // bytes per four pixels instead of 32 per pixel (the gather rate of the LDS-DMA path is set by the number of distinct
-                // segments: 33 B/ns/CU at 32 bytes, 148 at 128 - scripts/microbench/dma_bw.hip)
-                blk4 = true;
-                const int tp = 8;   // (8 pixels = 256 contiguous bytes per plane; larger tiles cost occupancy: 64 pixels 93 us, 8 pixels 70 us = the plain pass)
-                const int pad = ((4 - (a.in.C / 4) % 16 + 16) % 16) * 4;   // row length / 4 = 4 (mod 16): the read-back groups (8 pixels x 2 halves of two planes) hit 16 different slots
-                const size_t shb = (size_t)(tp * (a.in.C + pad) + (a.coefA ? 0 : 2 * a.in.C + COEF_SCR_FLOATS)) * sizeof(float);
-                // coefficients formed in the kernel: a workgroup amortises them over `reps` tiles of its image (at most 16, at least ~2048 workgroups)
-                int reps = 1;
-                if (!a.coefA) {
-                    const long tiles_img = (long)a.in.H * a.in.W / tp;
-                    while (reps < 16 && tiles_img % (reps * 2) == 0 && npix / tp / (reps * 2) >= 2048) reps *= 2;
-                }
-                hipLaunchKernelGGL(k_gn_apply_blk, dim3((unsigned)(npix / tp / reps)), dim3(256), shb, st, a.in.p, a.in.pitch, (long)a.in.H * a.in.W, npix,
-                                   a.in.C, a.coefA, a.coefB, a.act, a.act_ws, tp, a.in.C + pad, a.gn, a.in.N, reps);
-            } else if (a.coefA == nullptr) {
-                const int ppw = gn_gs_ppw(a.in.H * a.in.W, a.in.N, a.in.C);
-                hipLaunchKernelGGL(k_gn_apply_gs<0>, dim3((unsigned)((a.in.H * a.in.W + ppw - 1) / ppw), (unsigned)a.in.N), dim3(256), (size_t)(2 * a.in.C + COEF_SCR_FLOATS) * sizeof(float), st,
-                                   a.in.p, a.in.pitch, a.in.H * a.in.W, a.in.C, a.gn, a.in.N, a.act, (void *)a.act_ws, 0, ppw);
-            } else
-            hipLaunchKernelGGL(k_gn_apply, dim3((unsigned)g), dim3(256), 0, st, a.in.p, a.in.pitch, (long)a.in.H * a.in.W, npix,
-                               a.in.C, a.coefA, a.coefB, a.act, a.act_ws);
-            p.in = a.act_ws; p.in_pitch = a.in.C; p.cA = nullptr; p.cB = nullptr; p.act = 0; p.gn = GnSrc{};
-            if (a.ev_mid) { hipEventRecord(a.ev_mid, st); a.ev_mid_used = 1; }
+    return HL_OK;
+}
+
+// k_conv on tile config WM x WN waves of MT x NT 32x32 tiles; MODE = ConvPlan::gn_mode (the GroupNorm(+SiLU) applied while staging)
+template <int WM, int WN, int MT, int NT>
+static int launch_k_conv(const ConvK &p, const ConvArgs &a, int mode, int splits, hipStream_t st) {
+    constexpr int BM = WM * MT * 32, BN = WN * NT * 32;
+    const long hw_o = (long)a.out.H * a.out.W;
+    const int nimg = (int)((BM + hw_o - 1) / hw_o) + 1;
+    const size_t shm = ((size_t)2 * (BM + BN) * 20 + (mode ? (size_t)nimg * 2 * a.in.C + COEF_SCR_FLOATS : 0)) * sizeof(float);
+    HL_REQUIRE(shm <= 160 * 1024, "conv2d: LDS request %zu too large", shm);
+    const dim3 grid((unsigned)(p.n_mtiles * p.n_nblocks), 1, splits);
+    if (a.ups) hipLaunchKernelGGL((k_conv<WM, WN, MT, NT, 0, true>), grid, dim3(256), shm, st, p);   // nearest x2 + conv: only ever follows a raw tensor (unet.py:77-79)
+    else if (mode == 0) hipLaunchKernelGGL((k_conv<WM, WN, MT, NT, 0, false>), grid, dim3(256), shm, st, p);
+    else if (mode == 1) hipLaunchKernelGGL((k_conv<WM, WN, MT, NT, 1, false>), grid, dim3(256), shm, st, p);
+    else hipLaunchKernelGGL((k_conv<WM, WN, MT, NT, 2, false>), grid, dim3(256), shm, st, p);
+    return check_launch("k_conv");
+}
+
+// k_conv_bf3 (NPL = 3: bf16x3 emulation, 1: HL_CONV_BF16) on the 8-wave 256x96 or the 4-wave 128x96 tile
+template <int NPL>
+static int launch_k_conv_bf3(const ConvK &p, dim3 grid, bool tile8, bool ups, hipStream_t st) {
+    const size_t s8 = (size_t)3 * (256 * 16 + 6 * 96 * 4) * sizeof(float), s4 = (size_t)3 * (128 * 16 + 6 * 96 * 4) * sizeof(float);
+    if (tile8 && ups) hipLaunchKernelGGL((k_conv_bf3<8, true, NPL>), grid, dim3(512), s8, st, p);
+    else if (tile8) hipLaunchKernelGGL((k_conv_bf3<8, false, NPL>), grid, dim3(512), s8, st, p);
+    else if (ups) hipLaunchKernelGGL((k_conv_bf3<4, true, NPL>), grid, dim3(256), s4, st, p);
+    else hipLaunchKernelGGL((k_conv_bf3<4, false, NPL>), grid, dim3(256), s4, st, p);
+    return check_launch("k_conv");
+}
+
+// the convolution kernel of the plan, on p filled by conv2d (its grid fields set here)
+static int launch_conv(ConvK &p, const ConvArgs &a, const ConvPlan &pl, hipStream_t st) {
+    const long M = p.M;
+    const int cpad = p.wrows;
+    switch (pl.kernel) {
+    case ConvKernel::Conv:
+        if (pl.cfg == 0) {
+            p.n_mtiles = (int)((M + 127) / 128); p.n_nblocks = cpad / 96;
+            return launch_k_conv<4, 1, 1, 3>(p, a, pl.gn_mode, pl.splits, st);
         }
-        if (wino4 && wino4w) {
-            // 64 output channels per workgroup, one wave per SIMD, accumulators in the accumulator registers (hl_conv_wino4w.hip)
-            a.path = 3;
-            p.w_wino = a.w_wino4;
-            p.n_nblocks = a.Cout / 64;
-            p.n_mtiles = a.out.N * (a.out.H / 16) * (a.out.W / 32);
-            if (splits == 1 && a.stats && !a.out_nchw) {   // statistics from the epilogue: slot = (32x16 block, round, wave) = 64 pixels
-                p.st1 = a.stats; p.st2 = a.out2 ? a.stats2 : nullptr;
-                a.stat_slots = (a.out.H / 16) * (a.out.W / 32) * 8;
-            }
-            int rc = conv_wino4w_launch(p, a.ups, blk4 ? 1 : 0, splits, st);
-            if (rc) return rc;
-            if (splits > 1) return finish("k_conv_wino4w");
-            return HL_OK;
+        if (pl.cfg == 1) {
+            p.n_mtiles = (int)((M + 127) / 128); p.n_nblocks = 1;
+            return launch_k_conv<4, 1, 1, 1>(p, a, pl.gn_mode, pl.splits, st);
         }
-        if (wino4) {
-            a.path = 3;
-            p.w_wino = a.w_wino4;
-            p.n_nblocks = (a.Cout + 31) / 32;
-            p.n_mtiles = a.out.N * (a.out.H / 16) * (a.out.W / 32);
-            const dim3 nblk((unsigned)(p.n_mtiles * p.n_nblocks), 1, splits);
-            const size_t sh4 = (size_t)(36 * 256 + 2 * 1296 * 4) * sizeof(float);   // 76.5 KB: two workgroups per CU
-            if (splits == 1 && a.stats && !a.out_nchw) {   // statistics from the epilogue: slot = (32x16 block, round, wave) = 64 pixels
-                p.st1 = a.stats; p.st2 = a.out2 ? a.stats2 : nullptr;
-                a.stat_slots = (a.out.H / 16) * (a.out.W / 32) * 8;
-            }
-            if (a.ups) hipLaunchKernelGGL((k_conv_wino4<true, false>), nblk, dim3(256), sh4, st, p);
-            else if (blk4) hipLaunchKernelGGL((k_conv_wino4<false, true>), nblk, dim3(256), sh4, st, p);
-            else hipLaunchKernelGGL((k_conv_wino4<false, false>), nblk, dim3(256), sh4, st, p);
-            if (splits > 1) return finish("k_conv_wino4");
-            return check_launch("k_conv_wino4");
-        }
-        if (wino) {
-            a.path = 1;
-            p.n_nblocks = a.Cout / 64;
-            p.n_mtiles = a.out.N * (a.out.H / 8) * (a.out.W / 16);
-            const dim3 nblk((unsigned)(p.n_mtiles * p.n_nblocks), 1, splits);
-            const size_t sh1 = (size_t)2 * (8192 + 7 * 256) * sizeof(float);
-            if (splits == 1 && a.stats && !a.out_nchw) {   // statistics from the epilogue: slot = (16x8 block, column parity)
-                p.st1 = a.stats; p.st2 = a.out2 ? a.stats2 : nullptr;
-                a.stat_slots = (a.out.H / 8) * (a.out.W / 16) * 2;
-            }
-            if (a.ups) hipLaunchKernelGGL((k_conv_wino<true>), nblk, dim3(256), sh1, st, p);
-            else hipLaunchKernelGGL((k_conv_wino<false>), nblk, dim3(256), sh1, st, p);
-            if (splits > 1) return finish("k_conv_wino");
-            return check_launch("k_conv_wino");
-        }
+        p.n_mtiles = (int)((M + 63) / 64); p.n_nblocks = cpad / 64;
+        return launch_k_conv<2, 2, 1, 1>(p, a, pl.gn_mode, pl.splits, st);
+    case ConvKernel::Dma:
+    case ConvKernel::Bf3: {
         p.n_nblocks = cpad / 96;
-        p.n_mtiles = (int)((M + (tile8 ? 255 : 127)) / (tile8 ? 256 : 128));
-        dim3 grid((unsigned)(p.n_mtiles * p.n_nblocks), 1, splits);
+        p.n_mtiles = (int)((M + (pl.tile8 ? 255 : 127)) / (pl.tile8 ? 256 : 128));
+        const dim3 grid((unsigned)(p.n_mtiles * p.n_nblocks), 1, pl.splits);
+        if (pl.kernel == ConvKernel::Bf3) return a.bf16_single ? launch_k_conv_bf3<1>(p, grid, pl.tile8, a.ups, st) : launch_k_conv_bf3<3>(p, grid, pl.tile8, a.ups, st);
         const size_t shm8 = (size_t)3 * 352 * 16 * sizeof(float), shm4 = (size_t)3 * 224 * 16 * sizeof(float);
-        if (splits == 1 && st_rows32 && !(a.w_bf3 && (long)cpad * p.Ktot * 6 < (1L << 31))) {   // statistics from the epilogue: slot = a wave's 32 rows
-            p.st1 = a.stats; p.st2 = a.out2 ? a.stats2 : nullptr;
-            a.stat_slots = (int)(hw_o_early(a) / 32);
-        }
-        if (a.w_bf3 && (long)cpad * p.Ktot * 6 < (1L << 31)) {   // fp32 emulated on the bf16 matrix pipe (opt-in)
-            a.path = 2;
-            const size_t s8 = (size_t)3 * (256 * 16 + 6 * 96 * 4) * sizeof(float), s4 = (size_t)3 * (128 * 16 + 6 * 96 * 4) * sizeof(float);
-            if (a.bf16_single) {   // HL_CONV_BF16: bf16 activations x 16-bit weights
-                if (tile8 && a.ups) hipLaunchKernelGGL((k_conv_bf3<8, true, 1>), grid, dim3(512), s8, st, p);
-                else if (tile8) hipLaunchKernelGGL((k_conv_bf3<8, false, 1>), grid, dim3(512), s8, st, p);
-                else if (a.ups) hipLaunchKernelGGL((k_conv_bf3<4, true, 1>), grid, dim3(256), s4, st, p);
-                else hipLaunchKernelGGL((k_conv_bf3<4, false, 1>), grid, dim3(256), s4, st, p);
-            } else if (tile8 && a.ups) hipLaunchKernelGGL((k_conv_bf3<8, true>), grid, dim3(512), s8, st, p);
-            else if (tile8) hipLaunchKernelGGL((k_conv_bf3<8, false>), grid, dim3(512), s8, st, p);
-            else if (a.ups) hipLaunchKernelGGL((k_conv_bf3<4, true>), grid, dim3(256), s4, st, p);
-            else hipLaunchKernelGGL((k_conv_bf3<4, false>), grid, dim3(256), s4, st, p);
-        } else
-        if (tile8 && a.ups) hipLaunchKernelGGL((k_conv_dma<8, 3, true>), grid, dim3(512), shm8, st, p);
-        else if (tile8) hipLaunchKernelGGL((k_conv_dma<8, 3, false>), grid, dim3(512), shm8, st, p);
+        if (pl.tile8 && a.ups) hipLaunchKernelGGL((k_conv_dma<8, 3, true>), grid, dim3(512), shm8, st, p);
+        else if (pl.tile8) hipLaunchKernelGGL((k_conv_dma<8, 3, false>), grid, dim3(512), shm8, st, p);
         else if (a.ups) hipLaunchKernelGGL((k_conv_dma<4, 3, true>), grid, dim3(256), shm4, st, p);
         else hipLaunchKernelGGL((k_conv_dma<4, 3, false>), grid, dim3(256), shm4, st, p);
-    } else if (cfg == 0) {
-        p.n_mtiles = (int)((M + 127) / 128); p.n_nblocks = cpad / 96;
-        dim3 grid((unsigned)(p.n_mtiles * p.n_nblocks), 1, splits);
-        HL_CONV_GO(4, 1, 1, 3, grid);
-    } else if (cfg == 1) {
-        p.n_mtiles = (int)((M + 127) / 128); p.n_nblocks = 1;
-        dim3 grid((unsigned)p.n_mtiles, 1, splits);
-        HL_CONV_GO(4, 1, 1, 1, grid);
-    } else {
-        p.n_mtiles = (int)((M + 63) / 64); p.n_nblocks = cpad / 64;
-        dim3 grid((unsigned)(p.n_mtiles * p.n_nblocks), 1, splits);
-        HL_CONV_GO(2, 2, 1, 1, grid);
+        return check_launch("k_conv");
     }
-#undef HL_CONV_GO
-    if (splits > 1) return finish("k_conv");
-    return check_launch("k_conv");
+    case ConvKernel::Wino: {
+        p.n_nblocks = a.Cout / 64;
+        p.n_mtiles = a.out.N * (a.out.H / 8) * (a.out.W / 16);
+        const dim3 grid((unsigned)(p.n_mtiles * p.n_nblocks), 1, pl.splits);
+        const size_t sh1 = (size_t)2 * (8192 + 7 * 256) * sizeof(float);
+        if (a.ups) hipLaunchKernelGGL((k_conv_wino<true>), grid, dim3(256), sh1, st, p);
+        else hipLaunchKernelGGL((k_conv_wino<false>), grid, dim3(256), sh1, st, p);
+        return check_launch("k_conv_wino");
+    }
+    case ConvKernel::Wino4: {
+        p.w_wino = a.w_wino4;
+        p.n_nblocks = (a.Cout + 31) / 32;
+        p.n_mtiles = a.out.N * (a.out.H / 16) * (a.out.W / 32);
+        const dim3 grid((unsigned)(p.n_mtiles * p.n_nblocks), 1, pl.splits);
+        const size_t sh4 = (size_t)(36 * 256 + 2 * 1296 * 4) * sizeof(float);   // 76.5 KB: two workgroups per CU
+        if (a.ups) hipLaunchKernelGGL((k_conv_wino4<true, false>), grid, dim3(256), sh4, st, p);
+        else if (pl.pre == ConvPrePass::Blocked) hipLaunchKernelGGL((k_conv_wino4<false, true>), grid, dim3(256), sh4, st, p);
+        else hipLaunchKernelGGL((k_conv_wino4<false, false>), grid, dim3(256), sh4, st, p);
+        return check_launch("k_conv_wino4");
+    }
+    case ConvKernel::Wino4w:   // 64 output channels per workgroup, one wave per SIMD, accumulators in the accumulator registers (hl_conv_wino4w.hip)
+        p.w_wino = a.w_wino4;
+        p.n_nblocks = a.Cout / 64;
+        p.n_mtiles = a.out.N * (a.out.H / 16) * (a.out.W / 32);
+        return conv_wino4w_launch(p, a.ups, pl.pre == ConvPrePass::Blocked ? 1 : 0, pl.splits, st);
+    case ConvKernel::H16:
+        p.w_bf3 = a.w_h16;
+        p.n_nblocks = a.Cout / 192;
+        p.n_mtiles = (int)(M / 256);   // 16x16-pixel tiles (3x3) / runs of 256 pixels (1x1)
+        return conv_h16_launch(p, a.h16_fp16, st, pl.splits);
+    case ConvKernel::H2s:
+        p.n_nblocks = a.Cout / 192;
+        p.n_mtiles = (int)(M / 256) * 2;   // 8x16-pixel tiles, two workgroups per CU
+        return conv3_h2s_launch(p, st, pl.splits);
+    case ConvKernel::H2s1:
+        p.n_nblocks = a.Cout / 192;
+        p.n_mtiles = (int)(M / 256) * 2;   // 128-pixel tiles, two workgroups per CU
+        return conv1_h2s_launch(p, st, pl.splits);
+    case ConvKernel::H2d:
+        p.n_nblocks = a.Cout / 192;
+        p.n_mtiles = (int)(M / 128);
+        return conv3_h2d_launch(p, st);
+    }
+    return fail(HL_ERR_RUNTIME, "conv2d: no kernel");
+}
+
+static void wire_stats(ConvK &p, const ConvArgs &a) { p.st1 = a.stats; p.st2 = a.out2 ? a.stats2 : nullptr; }
+
+int conv2d(const ConvArgs &a, const ConvPlan &pl, hipStream_t st) {
+    HL_REQUIRE(a.in.p && a.w && a.out.p, "conv2d: null tensor");
+    HL_REQUIRE(a.in.C % 16 == 0, "conv2d: Cin (%d) must be padded to a multiple of 16", a.in.C);
+    HL_REQUIRE(a.ks == 1 || a.ks == 3, "conv2d: kernel size %d", a.ks);
+    HL_REQUIRE(a.stride == 1 || (a.stride == 2 && !a.ups), "conv2d: stride/upsample combination");
+    HL_REQUIRE((a.in.pitch % 4) == 0 && ((uintptr_t)a.in.p % 16) == 0, "conv2d: input must be 16-byte aligned per pixel");
+    const int pad = a.ks / 2;
+    const int Hv = a.ups ? 2 * a.in.H : a.in.H, Wv = a.ups ? 2 * a.in.W : a.in.W;
+    HL_REQUIRE(a.out.H == (Hv + 2 * pad - a.ks) / a.stride + 1 && a.out.W == (Wv + 2 * pad - a.ks) / a.stride + 1 &&
+                   a.out.N == a.in.N, "conv2d: output shape mismatch");
+    const bool gn_on = a.coefA != nullptr || a.gn.gt != nullptr;
+    HL_REQUIRE(!gn_on || a.coefA || a.gn.C == a.in.C, "conv2d: GnSrc covers %d of %d channels", a.gn.C, a.in.C);
+    HL_REQUIRE(gn_on || !a.act, "conv2d: SiLU without the GroupNorm affine is not used by the UNet");
+    HL_REQUIRE(!gn_on || !a.ups, "conv2d: upsample with a GroupNorm prologue is not used by the UNet");   // (nearest x2 + conv only ever follows a raw tensor)
+    ConvK p{};
+    p.in = a.in.p; p.in_pitch = a.in.pitch; p.N = a.in.N; p.Hin = a.in.H; p.Win = a.in.W; p.Cin = a.in.C;
+    p.Hout = a.out.H; p.Wout = a.out.W; p.ks = a.ks; p.stride = a.stride; p.ups = a.ups; p.taps = a.ks * a.ks;
+    p.w = a.w; p.w_bf3 = a.w_bf3; p.w_wino = a.w_wino; p.Ktot = (long)a.in.C * p.taps; p.bias = a.bias; p.Cout = a.Cout; p.wrows = round_up(a.Cout, 64);
+    p.cA = a.coefA; p.cB = a.coefB; p.act = a.act; p.gn = a.gn;
+    p.st1_cg = a.st_cg > 0 ? a.st_cg : std::max(1, a.Cout / 32); p.st1_c0 = a.st_c0; p.st2_cg = a.st2_cg > 0 ? a.st2_cg : std::max(1, a.Cout / 32); p.st2_c0 = a.st2_c0;
+    p.out = a.out.p; p.out_pitch = a.out.pitch; p.res = a.res; p.res_pitch = a.res_pitch;
+    p.out2 = a.out2; p.out2_pitch = a.out2_pitch; p.res2 = a.res2; p.res2_pitch = a.res2_pitch;
+    p.out_nchw = a.out_nchw;
+    p.M = (long)a.out.N * a.out.H * a.out.W;
+    p.kt_per = pl.kt_per;
+    p.partial = pl.splits > 1 ? a.splitk_ws : nullptr;
+    if (pl.stats_by == ConvStatsBy::Epilogue) wire_stats(p, a);
+    if (pl.pre != ConvPrePass::None) {
+        int rc = gn_prepass(a, pl.pre, st);
+        if (rc) return rc;
+        p.in = a.act_ws; p.in_pitch = a.in.C; p.cA = nullptr; p.cB = nullptr; p.act = 0; p.gn = GnSrc{};
+        p.in16 = pl.pre == ConvPrePass::Half ? 1 : (pl.pre == ConvPrePass::TwoPlane ? 2 : 0);   // (1: in_pitch counts 16-bit elements now)
+        if (a.ev_mid) hipEventRecord(a.ev_mid, st);
+    }
+    if (pl.path == ConvPath::Fp16x2) {
+        p.w_bf3 = a.w_h2;
+        p.wsc = conv_h2_wscale(a.w_h2, a.Cout, a.in.C, a.ks);
+        if (pl.gn_mode == 0) { p.xs_gt = a.in_stats; p.xs_hw = a.in.H * a.in.W; p.xs_max = a.in_absmax; }   // (raw input; a fused GroupNorm bounds its own output)
+    }
+    int rc = launch_conv(p, a, pl, st);
+    if (rc || pl.splits == 1) return rc;
+    // split-K: the slab sum (+ the statistics when wanted; it adds bias / residual too)
+    if (pl.stats_by == ConvStatsBy::Finish) {
+        wire_stats(p, a);
+        hipLaunchKernelGGL(k_splitk_finish_st, dim3((unsigned)(p.M / 32), (unsigned)((a.Cout + 63) / 64)), dim3(256), 0, st, p, pl.splits);
+    } else {
+        hipLaunchKernelGGL(k_splitk_finish, dim3((unsigned)std::min<long>((p.M * a.Cout + 255) / 256, 2048)), dim3(256), 0, st, p, pl.splits);
+    }
+    return check_launch("k_splitk_finish");
 }
 
 static int gn_chunks(int HW, int C) {
