@@ -32,6 +32,9 @@ def _row_pad():
     return 96
 
 
+LAUNCHES = {"hl_render_weight_grads": 0}    # calls enqueued by this process (tests of the frozen-decoder path read it)
+
+
 def train_rows():
     a, d = C.c_int(0), C.c_int(0)
     _lib.lib().hl_render_train_rows(C.byref(a), C.byref(d))
@@ -138,6 +141,10 @@ class RenderRaysFunction(torch.autograd.Function):
             sb = torch.empty(L.hl_render_plane_grads_scratch_bytes(R) // 4, dtype=torch.float32, device=dev)
             _lib.check(L.hl_render_plane_grads(H, W, p(bd), p(ro), p(rd), p(nr), p(fr), p(zb), p(zr), 1, R, N, Ni, p(delta), LD, p(d_planes),
                                                p(sb), st), "hl_render_plane_grads")
+        needs = ctx.needs_input_grad   # (renderer, geo, planes, *mlp)
+        out = [None, None, d_planes.view(3, 9, H, W) if needs[2] else None]
+        if not any(needs[3:]):         # frozen decoder (fitting with ft_triplane_only): no weight-gradient launch, no scratch for it
+            return tuple(out + [None] * len(mlp))
         # all 14 parameter gradients: rows of `delta` x rows of `act` over the sample points (include/humanliff_hip.h lists the rows)
         flat = torch.zeros(sum(t.numel() for t in mlp), dtype=torch.float32, device=dev)
         grads, o = [], 0
@@ -147,7 +154,6 @@ class RenderRaysFunction(torch.autograd.Function):
         gp = _lib.RenderMlpParams(*[C.c_void_p(g.data_ptr()) for g in grads])
         wsb = torch.empty(L.hl_render_weight_grads_scratch_bytes(P) // 4, dtype=torch.float32, device=dev)    # the point ranges' partial results
         _lib.check(L.hl_render_weight_grads(p(delta), LD, p(act), LD, P, C.byref(gp), p(wsb), st), "hl_render_weight_grads")
-        needs = ctx.needs_input_grad   # (renderer, geo, planes, *mlp)
-        out = [None, None, d_planes.view(3, 9, H, W) if needs[2] else None]
+        LAUNCHES["hl_render_weight_grads"] += 1
         out += [g if needs[3 + i] else None for i, g in enumerate(grads)]
         return tuple(out)

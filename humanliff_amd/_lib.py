@@ -164,6 +164,10 @@ SIGNATURES = {
     "hl_adamw_step": (_i, [_p, _i, _i64, _i, C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                            C.c_float, C.c_float, _p, _sz, _p]),
     "hl_adamw_sum_partials": (_i, [_p, _i64, _p, _p]),
+    "hl_fit_reg_scratch_bytes": (_sz, [_i64, _i, _i]),
+    "hl_fit_reg": (_i, [_p, _p, _i64, _i, _i, C.c_float, C.c_float, C.c_float, _p, _p, _sz, _p]),
+    "hl_fit_adam_planes": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                C.c_float, _i, _p]),
 }
 
 

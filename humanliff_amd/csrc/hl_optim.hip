@@ -18,15 +18,14 @@
 //   e_k = fma(1 - r_k, p, e_k * r_k)                            update_ema: targ.mul_(r).add_(src, alpha=1 - r)
 // The clipped gradient is NOT written back: .grad keeps the unclipped values (nothing in the training loop reads it after the step).
 // A tensor without a gradient (g == NULL) gets its EMA updates only, as torch's optimizers skip it and update_ema does not.
-#include "hl_common.h"
+#include "hl_adam.h"
 
-#include <cmath>
 #include <cstdint>
 
 namespace hl {
 namespace {
 
-constexpr int kThreads = 256;
+constexpr int kThreads = kOptThreads;
 constexpr int64_t kChunk = HL_ADAMW_CHUNK;                 // elements per workgroup
 static_assert(kChunk % (4 * kThreads) == 0, "a chunk is whole float4 rows of the workgroup");
 
@@ -46,19 +45,16 @@ struct OptChunk {             // 16 bytes, the table's second part (one per chun
 };
 
 struct Coef {
-    float clip, wd_scale, b1c, b1c_hi, b2, b2c, bc2_sqrt, eps, neg_step;
+    AdamCoef adam;
+    float clip, wd_scale;
     float r[4], rc[4];
-    int use_wd, lerp_lo;
+    int use_wd;
 };
 
 __device__ __forceinline__ void adam1(float g, float &p, float &m, float &v, const Coef &c) {
     if (c.clip > 0.f) g = g < -c.clip ? -c.clip : (g > c.clip ? c.clip : g);   // (comparisons with NaN are false: NaN passes through)
     if (c.use_wd) p = p * c.wd_scale;
-    // at::lerp: weight < 0.5 ? self + w (end - self) : end - (end - self)(1 - w)
-    m = c.lerp_lo ? fmaf(c.b1c, g - m, m) : fmaf(-(g - m), c.b1c_hi, g);
-    v = fmaf(c.b2c, g * g, v * c.b2);
-    const float den = sqrtf(v) / c.bc2_sqrt + c.eps;
-    p = fmaf(c.neg_step, m / den, p);
+    adam_moments(g, p, m, v, c.adam);
 }
 
 template <int NE>
@@ -66,9 +62,6 @@ __device__ __forceinline__ void ema1(float p, float *e, const Coef &c) {
 #pragma unroll
     for (int k = 0; k < NE; ++k) e[k] = fmaf(c.rc[k], p, e[k] * c.r[k]);
 }
-
-__device__ __forceinline__ f32x4 ld4(const float *p) { return *reinterpret_cast<const f32x4 *>(p); }
-__device__ __forceinline__ void st4(float *p, f32x4 v) { *reinterpret_cast<f32x4 *>(p) = v; }
 
 // one element at index i of tensor t (head / tail / unaligned tensors)
 template <int NE>
@@ -126,18 +119,6 @@ __device__ __forceinline__ double quad(const OptTensor &t, int64_t i, const Coef
         for (int k = 0; k < NE; ++k) st4(t.e[k] + i, e[k]);
     }
     return sq;
-}
-
-// fixed-shape tree over the workgroup's 256 fp64 values; thread 0 ends with the sum
-__device__ __forceinline__ double block_sum(double x, double *sh) {
-    sh[threadIdx.x] = x;
-    __syncthreads();
-#pragma unroll
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-        __syncthreads();
-    }
-    return sh[0];
 }
 
 // grid (nchunks): workgroup b owns chunk b
@@ -244,14 +225,7 @@ int hl_adamw_step(const void *table, int ntensors, int64_t nchunks, int n_ema, c
     c.clip = clip;
     c.wd_scale = wd_scale;
     c.use_wd = wd_scale != 1.f;
-    c.b1c = one_minus_beta1;
-    c.b1c_hi = 1.f - one_minus_beta1;          // (at::lerp's 1 - weight, in the weight's precision)
-    c.lerp_lo = fabsf(one_minus_beta1) < 0.5f;
-    c.b2 = beta2;
-    c.b2c = one_minus_beta2;
-    c.bc2_sqrt = bc2_sqrt;
-    c.eps = eps;
-    c.neg_step = neg_step_size;
+    c.adam = adam_coef(one_minus_beta1, beta2, one_minus_beta2, bc2_sqrt, eps, neg_step_size);
     for (int k = 0; k < n_ema; ++k) {
         c.r[k] = ema_rates[2 * k];
         c.rc[k] = ema_rates[2 * k + 1];

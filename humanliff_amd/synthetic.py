@@ -208,3 +208,27 @@ def smpl_like_pose(n_vertices, model, seed=31, n_points=1024):
     vd = vd / torch.linalg.norm(vd, dim=-1, keepdim=True)
     return {"params": {"poses": poses, "shapes": shapes, "R": Rw, "Th": Th}, "t_params": t_params, "vertices": vertices,
             "t_world_bounds": torch.tensor([[[-1.0, -1.2, -0.6], [1.0, 1.2, 0.6]]]), "pts": pts, "viewdirs": vd}
+
+
+# ---- batches for the tri-plane fitting loop (recon_NeRF/fit.py) ---------------------------------------------------------------
+def fit_batch(bs, n_rays, num_instances, seed=41, instance_idx=None, layer_idx=None, n_views=8, res=128):
+    """A tp_input batch with the keys and shapes run_nerf_batch.py:238-246 reads (one view per entry: `*_all` are (bs, 1, n_rays, .)):
+    rays of an orbit view that hit the bounds, a random target colour and mask, and the (instance, cloth layer) pair of every entry
+    (drawn from the seed unless given).  CPU tensors; the caller moves them to the device like the reference's to_cuda."""
+    g = _gen(seed)
+    ro, rd, nr, fr = [], [], [], []
+    for b in range(bs):
+        o, d, n, f = orbit_rays(int(torch.randint(0, n_views, (1,), generator=g)), n_views, res, res)
+        pick = torch.nonzero(f != 1).flatten()
+        pick = pick[torch.randperm(pick.numel(), generator=g)[:n_rays]]
+        assert pick.numel() == n_rays, "fit_batch: not enough rays hit the bounds at this resolution"
+        ro.append(o[pick]), rd.append(d[pick]), nr.append(n[pick]), fr.append(f[pick])
+    one = lambda ts: torch.stack(ts)[:, None]  # noqa: E731
+    if instance_idx is None:
+        instance_idx = torch.randint(0, num_instances, (bs,), generator=g)
+    if layer_idx is None:
+        layer_idx = torch.randint(0, 4, (bs,), generator=g)
+    return {"ray_o_all": one(ro), "ray_d_all": one(rd), "near_all": one(nr)[..., None], "far_all": one(fr)[..., None],
+            "rgb_all": torch.rand((bs, 1, n_rays, 3), generator=g), "bkgd_msk_all": (torch.rand((bs, 1, n_rays, 1), generator=g) > 0.3).float(),
+            "instance_idx": torch.as_tensor(instance_idx, dtype=torch.int64), "cloth_layer_index": torch.as_tensor(layer_idx, dtype=torch.int64),
+            "world_bounds": torch.tensor(WORLD_BOUNDS)[None].expand(bs, 2, 3).contiguous()}

@@ -670,6 +670,28 @@ int hl_adamw_step(const void *table, int ntensors, int64_t nchunks, int n_ema, c
                   void *scratch, size_t scratch_bytes, void *stream);
 int hl_adamw_sum_partials(const void *scratch, int64_t n, double *out, void *stream);
 
+/* ---- tail of a tri-plane fitting iteration (recon_NeRF/run_nerf_batch.py:256-272: TV / L1 regularisers, Adam on tri_planes, clamp_) ----
+ * Contract: DESIGN.md "Fitting loop"; csrc/hl_fit.hip.  fp32, contiguous, enqueue-only on `stream`, caller-owned scratch.
+ *   hl_fit_reg: planes and grad are nplanes (= batch x 27) images of H x W (H, W >= 2), the gathered plane sets and the gradient
+ *     the render backward left for them.  sums[0..2] (fp64, device) = sum |x[h] - x[h+1]|, sum |x[w] - x[w+1]|, sum |x| (fp32
+ *     differences, fp64 sums in a fixed order); grad += cx (sign(x - x_dn) - sign(x_up - x)) + cy (the same along W) + cl sign(x),
+ *     sign(0) = 0, sign(NaN) = NaN, a missing neighbour contributing nothing; cx, cy, cl are the host's coef / n as floats.
+ *     scratch: hl_fit_reg_scratch_bytes (the workgroups' partials).
+ *   hl_fit_adam_planes: torch's multi-tensor Adam (weight_decay 0; the scalars as for hl_adamw_step) over the whole parameter of
+ *     num_instances x num_layers slices of slice_numel elements.  The gradient of a slice is 0 + the entries b of grad (bs x
+ *     slice_numel) with (instance_idx[b], layer_idx[b]) == the slice, added in batch order; the two index arrays are int64 in DEVICE
+ *     memory and are read by the kernel only (negative indices wrap, a pair out of range selects nothing).  clamp != 0: then
+ *     p = clamp(p, -1, 1).  bs <= HL_FIT_MAX_BATCH. */
+#define HL_FIT_CHUNK 16384
+#define HL_FIT_REG_CHUNK 4096
+#define HL_FIT_MAX_BATCH 64
+size_t hl_fit_reg_scratch_bytes(int64_t nplanes, int H, int W);
+int hl_fit_reg(const float *planes, float *grad, int64_t nplanes, int H, int W, float cx, float cy, float cl, double *sums, void *scratch,
+               size_t scratch_bytes, void *stream);
+int hl_fit_adam_planes(float *param, float *exp_avg, float *exp_avg_sq, const float *grad, const int64_t *instance_idx,
+                       const int64_t *layer_idx, int bs, int num_instances, int num_layers, int64_t slice_numel, float one_minus_beta1,
+                       float beta2, float one_minus_beta2, float bc2_sqrt, float eps, float neg_step_size, int clamp, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
