@@ -168,6 +168,8 @@ SIGNATURES = {
     "hl_fit_reg": (_i, [_p, _p, _i64, _i, _i, C.c_float, C.c_float, C.c_float, _p, _p, _sz, _p]),
     "hl_fit_adam_planes": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                 C.c_float, _i, _p]),
+    "hl_image_metrics_workspace_bytes": (_sz, [_i, _i, _i]),
+    "hl_image_metrics": (_i, [_p, _p, _p, _i, _i, _i, C.c_double, _u, _p, _p, _p, _p, _sz, _p]),
 }
 
 

@@ -692,6 +692,24 @@ int hl_fit_adam_planes(float *param, float *exp_avg, float *exp_avg_sq, const fl
                        const int64_t *layer_idx, int bs, int num_instances, int num_layers, int64_t slice_numel, float one_minus_beta1,
                        float beta2, float one_minus_beta2, float bc2_sqrt, float eps, float neg_step_size, int clamp, void *stream);
 
+/* ---- held-out view scores (recon_NeRF/lib/all_test.py:19-42, 175-188: psnr_metric, ssim_metric, to8b) ----
+ * Contract: DESIGN.md "Evaluation"; csrc/hl_metrics.hip.  Contiguous, enqueue-only on `stream`, caller-owned workspace.
+ *   pred, gt: (V, H, W, 3) fp32, only read; mask: (V, H, W) uint8, nonzero = inside (mask_at_box).  Both images count as 0 outside
+ *   the mask.  Per view one record: mse = mean of (pred - gt)^2 over the 3 count masked values (fp32 difference, float64 from the
+ *   square on), psnr = -10 log10(mse), the mask's bounding rectangle (cv2.boundingRect; all 0 for an empty mask), and ssim =
+ *   skimage's structural_similarity on the crop (7 x 7 uniform window per channel, sample covariance, K1 0.01, K2 0.03, the mean
+ *   over the crop's interior, then over the channels; float64, fixed summation order).  ssim is NaN when w < 7 or h < 7.
+ *   data_range: skimage's R.  flags: reserved, 0.  pred_u8 / gt_u8 (V, H, W, 3) uint8, each optional: (255 clip(x, 0, 1)) truncated,
+ *   of the masked prediction and of the unmasked ground truth.  workspace: hl_image_metrics_workspace_bytes. */
+typedef struct hl_metrics_record {
+    double mse, psnr, ssim;
+    int32_t count, x, y, w, h, reserved;
+} hl_metrics_record;
+size_t hl_image_metrics_workspace_bytes(int V, int H, int W);
+int hl_image_metrics(const float *pred, const float *gt, const unsigned char *mask, int V, int H, int W, double data_range, unsigned flags,
+                     unsigned char *pred_u8, unsigned char *gt_u8, hl_metrics_record *results, void *workspace, size_t workspace_bytes,
+                     void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,108 @@
+"""Held-out view evaluation of fitted tri-planes: recon_NeRF/run_nerf_batch.py --test -> humanliff_amd evaluate_views.
+
+    python scripts/triplane_eval.py --ckpt logs/fit/001000.tar --humans 0 1 --view_ids 6 7 --image_size 128 --savedir logs/fit/test
+    python scripts/triplane_eval.py --ckpt logs/fit/001000.tar --views-npz views.npz
+
+--ckpt is a FitLoop checkpoint (scripts/triplane_fit.py).  No dataset ships with the project: without --views-npz the views are orbit
+cameras of humanliff_amd.synthetic (rays, near / far and mask_at_box by SynBodyView_datasets.camera_rays) with a seeded smooth target
+image - plumbing, not a quality number.  With --views_num 185 the view ids are the reference's held-out list (heldout_view_ids,
+optionally --test_layer_id); any other orbit needs --view_ids.  View id i is orbit position i % views_num of cloth layer i // views_num.
+
+--views-npz loads real views: arrays ray_o_all, ray_d_all (N, R, 3), near_all, far_all (N, R), rgb_all (N, R, 3), mask_at_box_all (N, R),
+instance_idx, cloth_layer_index, pose_index, view_id (N), world_bounds (N, 2, 3) and optionally H, W; the N views must be grouped by
+instance_idx.  LPIPS is not computed (its VGG weights are not available offline); evaluate_views takes a hook for it.
+"""
+import argparse
+import math
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from humanliff_amd import synthetic as syn                                           # noqa: E402
+from humanliff_amd.SynBodyView_datasets import camera_rays                           # noqa: E402
+from humanliff_amd.recon_NeRF import Renderer                                        # noqa: E402
+from humanliff_amd.recon_NeRF.lib.all_test import evaluate_views, heldout_view_ids   # noqa: E402
+
+
+def parse():
+    a = argparse.ArgumentParser()
+    a.add_argument("--ckpt", type=str, required=True)
+    a.add_argument("--savedir", type=str, default=None)
+    a.add_argument("--humans", type=int, nargs="*", default=None, help="instance indices (default: every instance of the checkpoint)")
+    a.add_argument("--views_num", type=int, default=185)
+    a.add_argument("--test_layer_id", type=int, default=-1)
+    a.add_argument("--view_ids", type=int, nargs="*", default=None)
+    a.add_argument("--image_size", type=int, default=256)
+    a.add_argument("--n_samples", type=int, default=128)
+    a.add_argument("--n_importance", type=int, default=128)
+    a.add_argument("--white_bkgd", action="store_true")
+    a.add_argument("--data_range", type=float, default=2.0)
+    a.add_argument("--views-npz", dest="views_npz", type=str, default=None)
+    a.add_argument("--seed", type=int, default=0)
+    return a.parse_args()
+
+
+def target_image(H, W, seed):
+    """A smooth seeded RGB image in [0, 1]."""
+    rng = np.random.default_rng(seed)
+    ph, fx, fy = rng.random(3) * 2 * math.pi, 2 + rng.random(3) * 4, 2 + rng.random(3) * 4
+    yy, xx = np.meshgrid(np.linspace(0, 1, H), np.linspace(0, 1, W), indexing="ij")
+    return torch.from_numpy(np.stack([0.5 + 0.5 * np.sin(fx[c] * xx + fy[c] * yy + ph[c]) for c in range(3)], -1)).float()
+
+
+def synthetic_views(args, humans, dev):
+    ids = heldout_view_ids(args.views_num, args.test_layer_id, view_ids=args.view_ids)
+    H = W = args.image_size
+    for human in humans:
+        for view_id in ids:
+            K, c2w, cam = syn.orbit_camera(view_id % args.views_num, args.views_num, H, W)
+            R = c2w.T                                                        # world -> camera
+            ro, rd, near, far, mask = camera_rays(H, W, K, R, -R @ cam, syn.WORLD_BOUNDS, dev, return_mask=True)
+            yield {"ray_o_all": ro[None, None], "ray_d_all": rd[None, None], "near_all": near[None, None, :, None],
+                   "far_all": far[None, None, :, None], "mask_at_box_all": mask[None, None],
+                   "rgb_all": target_image(H, W, args.seed * 1000003 + view_id).reshape(1, 1, H * W, 3),
+                   "instance_idx": torch.tensor([human]), "cloth_layer_index": torch.tensor([(view_id // args.views_num) % 4]),
+                   "pose_index": torch.tensor([0]), "world_bounds": torch.tensor(syn.WORLD_BOUNDS)[None], "view_id": view_id, "H": H, "W": W}
+
+
+def npz_views(path):
+    z = np.load(path)
+    n = z["ray_o_all"].shape[0]
+    for i in range(n):
+        t = lambda k: torch.from_numpy(np.ascontiguousarray(z[k][i]))        # noqa: E731
+        tp = {"ray_o_all": t("ray_o_all")[None, None].float(), "ray_d_all": t("ray_d_all")[None, None].float(),
+              "near_all": t("near_all").reshape(1, 1, -1, 1).float(), "far_all": t("far_all").reshape(1, 1, -1, 1).float(),
+              "rgb_all": t("rgb_all")[None, None].float(), "mask_at_box_all": t("mask_at_box_all")[None, None] != 0,
+              "instance_idx": torch.tensor([int(z["instance_idx"][i])]), "cloth_layer_index": torch.tensor([int(z["cloth_layer_index"][i])]),
+              "pose_index": torch.tensor([int(z["pose_index"][i])]), "world_bounds": t("world_bounds")[None].float(),
+              "view_id": int(z["view_id"][i])}
+        if "H" in z and "W" in z:
+            tp["H"], tp["W"] = int(np.asarray(z["H"]).reshape(-1)[0]), int(np.asarray(z["W"]).reshape(-1)[0])
+        yield tp
+
+
+def main():
+    args = parse()
+    if not torch.cuda.is_available():
+        raise SystemExit("triplane_eval.py needs a HIP device: humanliff_amd has no CPU path")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    sd = torch.load(args.ckpt, map_location="cpu")["network_fn_state_dict"]
+    ni, _, _, ch, dim, _ = sd["tri_planes"].shape
+    model = Renderer(use_canonical_space=False, num_instances=ni, triplane_dim=dim, triplane_ch=3 * ch, test=True)
+    model.load_state_dict(sd, strict=True)
+    model = model.to(dev)
+    torch.manual_seed(args.seed)
+    humans = list(range(ni)) if args.humans is None else args.humans
+    views = npz_views(args.views_npz) if args.views_npz else synthetic_views(args, humans, dev)
+    metric = evaluate_views(model, views, n_samples=args.n_samples, n_importance=args.n_importance, white_bkgd=args.white_bkgd,
+                            data_range=args.data_range, savedir=args.savedir)
+    mse, psnr, ssim = metric["novel_view_mean_human"]
+    print(f"mean over {metric['novel_view_mse'].size} views of {len(metric['all_human_names'])} subjects: mse {mse:.6f} psnr {psnr:.4f} ssim {ssim:.6f}")
+
+
+if __name__ == "__main__":
+    main()
