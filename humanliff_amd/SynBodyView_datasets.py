@@ -3,7 +3,9 @@
 
 The reference builds every view's rays with numpy on the host (get_rays :316-329, get_near_far :370-403, called from
 sample_ray_batch :405-436) and uploads 6.3 MB per 512x512 view; here one kernel writes the same float32 arrays directly
-in HBM.  Image / mask handling of sample_ray_batch (cv2.fillPoly bound mask, rgb) is dataset code and stays out.
+in HBM.  The image / mask half of sample_ray_batch (bound mask, body / background pixel classes, the rejection loop, rgb) runs on the
+device as well: recon_NeRF/lib/if_nerf_data_utils.py (ViewStore, sample_ray_batch), which shares this file's per-pixel ray function.
+Reading and resizing image files stays dataset code.
 """
 import ctypes as C
 
@@ -18,14 +20,21 @@ def _f64(a, shape):
     return a, a.ctypes.data_as(C.c_void_p)
 
 
-def camera_rays(H, W, K, R, T, bounds, device=None, return_mask=True):
+def camera_rays(H, W, K, R, T, bounds, device=None, return_mask=True, split='test'):
     """Rays of one pinhole view, as sample_ray_batch returns them (:422-433):
     rays_o, rays_d (H*W,3) float32, near, far (H*W) float32, mask_at_box (H*W) bool - device tensors.
 
     K (3,3) intrinsics, R (3,3) / T (3,1) world->camera extrinsics, bounds (2,3) world_bounds; any array-likes.
     Like the reference, exact zeros of rays_d come back as 1e-8 (get_near_far writes them in place, :373) and rays
     that do not cross the 0.01-padded box exactly twice get near=0, far=1.
+
+    split='train' (hl_camera_rays_train) is the arithmetic of the training split of recon_NeRF/lib/if_nerf_data_utils.py (:146-149,
+    163-167): get_near_far on the float64 rays, rounded to float32 afterwards - what sample_ray_batch there returns per sampled
+    pixel.  The default rounds the rays first, as this file's reference and that module's test split do; near / far of the two
+    differ by a few float32 ulp, rays_o / rays_d are the same bits.
     """
+    if split not in ('test', 'train'):
+        raise ValueError(f"camera_rays: split must be 'test' or 'train', got {split!r}")
     assert int(H) > 0 and int(W) > 0
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     Ki, pKi = _f64(np.linalg.inv(np.asarray(K, dtype=np.float64)), (3, 3))   # :324
@@ -39,8 +48,9 @@ def camera_rays(H, W, K, R, T, bounds, device=None, return_mask=True):
     far = torch.empty((n,), device=device, dtype=torch.float32)
     mask = torch.empty((n,), device=device, dtype=torch.uint8) if return_mask else None
     with torch.cuda.device(device):
-        _lib.check(_lib.lib().hl_camera_rays(pKi, pR, pT, pB, int(H), int(W), _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(near),
-                                             _lib.ptr(far), _lib.ptr(mask, torch.uint8) if return_mask else None, _lib.stream_ptr()))
+        fn = _lib.lib().hl_camera_rays_train if split == 'train' else _lib.lib().hl_camera_rays
+        _lib.check(fn(pKi, pR, pT, pB, int(H), int(W), _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(near),
+                      _lib.ptr(far), _lib.ptr(mask, torch.uint8) if return_mask else None, _lib.stream_ptr()))
     return rays_o, rays_d, near, far, (mask.bool() if return_mask else None)
 
 

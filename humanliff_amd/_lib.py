@@ -73,6 +73,7 @@ SIGNATURES = {
     "hl_render_canonical_workspace_bytes": (_sz, [_i64, _i, _i]),
     "hl_render_rays_canonical": (_i, [_p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i64, _i, _i, _u, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p]),
     "hl_camera_rays": (_i, [_p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p]),
+    "hl_camera_rays_train": (_i, [_p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p]),
     "hl_render_eval": (_i, [_p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _i, _i64, _i, _p, _p]),
     "hl_render_eval_products": (_i, [_p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _i, _i64, _i, _u, _p, _p]),
     "hl_render_importance_new": (_i, [_p, _p, _p, _p, _p, _p, _i64, _i, _i, _p, _p]),
@@ -170,6 +171,10 @@ SIGNATURES = {
                                 C.c_float, _i, _p]),
     "hl_image_metrics_workspace_bytes": (_sz, [_i, _i, _i]),
     "hl_image_metrics": (_i, [_p, _p, _p, _i, _i, _i, C.c_double, _u, _p, _p, _p, _p, _sz, _p]),
+    "hl_camera_table_row": (_i, [_p, _p, _p, _p, _p]),
+    "hl_ray_views_prepare": (_i, [_p, _p, _i64, _i, _i, _p, _p, _p]),
+    "hl_ray_batch": (_i, [_p, _i, _p, _i, _p, _p, _p, _i64, _i, _i, _i, C.c_double, _p, C.c_uint64, C.c_uint64, _i, _p, _p, _p, _p, _p, _p,
+                          _p, _p, _p, _p]),
 }
 
 

@@ -248,6 +248,12 @@ size_t hl_render_plane_grads_scratch_bytes(int64_t n_rays);
  * mask_at_box (R) bytes or NULL. */
 int hl_camera_rays(const double *h_Kinv, const double *h_R, const double *h_T, const double *h_bounds, int H, int W,
                    float *rays_o, float *rays_d, float *near, float *far, unsigned char *mask_at_box, void *stream);
+/* The same view in the arithmetic of the reference's TRAINING split (recon_NeRF/lib/if_nerf_data_utils.py:146-149, 163-167): get_near_far
+ * runs on the float64 rays (float64 |ray_d|, an exact float64 zero of ray_d becomes 1e-8) and everything is rounded to float32
+ * afterwards, where hl_camera_rays - like the reference's test split and SynBodyView_datasets.py - rounds the rays first.  Same
+ * arguments; rays_o / rays_d are the same bits, near / far differ by a few float32 ulp.  This is what hl_ray_batch writes per sampled pixel. */
+int hl_camera_rays_train(const double *h_Kinv, const double *h_R, const double *h_T, const double *h_bounds, int H, int W,
+                         float *rays_o, float *rays_d, float *near, float *far, unsigned char *mask_at_box, void *stream);
 
 /* Canonical-space deformation of query points.  Replaces Renderer.deform_target2c /
  * deform_target2c_op (human_diffusion/NeRF/renderer.py:52-132, recon_NeRF/lib/renderer.py:60-140) including the external
@@ -709,6 +715,34 @@ size_t hl_image_metrics_workspace_bytes(int V, int H, int W);
 int hl_image_metrics(const float *pred, const float *gt, const unsigned char *mask, int V, int H, int W, double data_range, unsigned flags,
                      unsigned char *pred_u8, unsigned char *gt_u8, hl_metrics_record *results, void *workspace, size_t workspace_bytes,
                      void *stream);
+
+/* ---- training ray batches from resident views (recon_NeRF/lib/if_nerf_data_utils.py:87-170: sample_ray_batch, split == 'train') ----
+ * Contract: DESIGN.md 4g; csrc/hl_ray_batch.hip.  Contiguous device arrays unless marked h_ (host); enqueue-only on `stream`.
+ *   hl_camera_table_row: HOST.  One row of the camera table (HL_CAMERA_ROW float64: inv(K) 9, R 9, T 3, the camera centre -(R^T T) 3,
+ *     the bounds padded by 0.01 6) from the arguments of that call, derived exactly as it derives them.
+ *   hl_ray_views_prepare: per view, from corners (V, 8, 2) int32 - the 8 projected bound corners (x, y) in get_bound_corners' order,
+ *     rounded on the host like np.round(project(...)).astype(int), |value| < 2^30 - and body (V, H, W) uint8 (non-zero where msk == 1):
+ *     bound_mask = the union of get_bound_2d_mask's six quads, a pixel being set when it lies inside or on the boundary of the closed
+ *     quad (exact integer arithmetic; cv2.fillPoly's own outline pixels could not be compared).  Class 0 = bound & body, class 1 =
+ *     bound & ~body.  bitmaps (V, 2, H, ceil(W / 64)) uint64: bit x % 64 of word x / 64; row_table (V, 2, H + 1) int32: the exclusive
+ *     prefix of a class's set bits per row, the total at [H].
+ *   hl_ray_batch: one workgroup per entry b of image_idx (bs) int64.  images (V, H, W, 3) float32, or uint8 when images_u8 != 0 (then
+ *     rgb = (float)u8 / 255.0f).  Round r with m rows missing takes n_body = (int)((double)m * ratio) candidates of class 0, then
+ *     m - n_body of class 1; candidate `slot` of a class is that class's k-th pixel in row-major (np.argwhere) order, k =
+ *     picks[b][r][class][slot] with picks (bs, max_rounds, 2, n_rays) int32, or with picks NULL k = mulhi(x, count), x the first word of
+ *     Philox4x32-10 with key (seed low, seed high ^ step high) and counter (slot, b, 2 r + class, step low).  Its ray is the one
+ *     hl_camera_rays_train writes for that pixel; candidates whose ray crosses the padded box exactly twice are appended in candidate order
+ *     until n_rays rows are filled or max_rounds rounds are done.  Outputs per entry: rgb, ray_o, ray_d (n_rays, 3), near, far,
+ *     bkgd_msk (1 = class 0) (n_rays) float32, mask_at_box (n_rays) uint8, coord (n_rays, 2) int32 (y, x); rows not filled are zeros
+ *     with near 0 and far 1; n_valid (bs) int32 = rows filled, or -1 for an image_idx outside [0, V) or a pick outside its class. */
+#define HL_CAMERA_ROW 30
+int hl_camera_table_row(const double *h_Kinv, const double *h_R, const double *h_T, const double *h_bounds, double *h_row);
+int hl_ray_views_prepare(const int32_t *corners, const unsigned char *body, int64_t V, int H, int W, uint64_t *bitmaps, int32_t *row_table,
+                         void *stream);
+int hl_ray_batch(const int64_t *image_idx, int bs, const void *images, int images_u8, const uint64_t *bitmaps, const int32_t *row_table,
+                 const double *cameras, int64_t V, int H, int W, int n_rays, double ratio, const int32_t *picks, uint64_t seed, uint64_t step,
+                 int max_rounds, float *rgb, float *ray_o, float *ray_d, float *near, float *far, float *bkgd_msk,
+                 unsigned char *mask_at_box, int32_t *coord, int32_t *n_valid, void *stream);
 
 #ifdef __cplusplus
 }

@@ -4,7 +4,10 @@
         --triplane_ch 27 --lrate_decay 10 --tri_plane_lrate 1e-1 --tv_loss --tv_loss_coef 1e-2 --l1_loss_coef 5e-4 --use_clamp --n_iteration 1000
     python scripts/triplane_fit.py --expname ft --ft_triplane_only --lrate 0 --batch_size 8 --num_instance 1 ...
 
-No dataset ships with the project: the batches are humanliff_amd.synthetic.fit_batch (orbit rays, random targets), a fresh one per step.
+No dataset ships with the project.  --data synthetic (default): the batches are humanliff_amd.synthetic.fit_batch (orbit rays, random
+targets), a fresh one per step.  --data rendered: --views orbit views of a seeded tri-plane inside a box of 0.6 x the world bounds are rendered (render_view),
+acc > 0.5 is their body mask, all but --heldout of them go into a device-resident ViewStore and a FRESH tri-plane is fitted to them through
+RayBatchLoader (rays sampled on the device, csrc/hl_ray_batch.hip); evaluate_views' PSNR on the held-out views is printed before and after.
 --tv_loss is accepted and ignored: FitLoop always computes both regularisers (a coefficient of 0 switches a term off).
 """
 import argparse
@@ -47,6 +50,10 @@ def parse():
     a.add_argument("--i_print", type=int, default=100)
     a.add_argument("--i_weights", type=int, default=10000)
     a.add_argument("--seed", type=int, default=0)
+    a.add_argument("--data", choices=["synthetic", "rendered"], default="synthetic")
+    a.add_argument("--views", type=int, default=24, help="--data rendered: orbit views rendered from the hidden tri-plane")
+    a.add_argument("--heldout", type=int, default=4, help="--data rendered: of which this many (evenly spaced) are only scored")
+    a.add_argument("--image_size", type=int, default=128, help="--data rendered: side of the rendered views")
     return a.parse_args()
 
 
@@ -56,6 +63,63 @@ def batches(args, dev):
         tp = syn.fit_batch(args.batch_size, args.n_rand, args.num_instance, seed=args.seed * 1000003 + step)
         yield {k: v.to(dev, non_blocking=True) for k, v in tp.items()}
         step += 1
+
+
+def rendered_views(args, dev):
+    """Render the views of a hidden tri-plane and split them: (ViewStore of the training views, store of the held-out ones)."""
+    from humanliff_amd.NeRF import Renderer as ViewRenderer
+    from humanliff_amd.NeRF.renderer import render_view
+    from humanliff_amd.SynBodyView_datasets import camera_rays
+    from humanliff_amd.recon_NeRF.lib.if_nerf_data_utils import ViewStore
+    S = args.image_size
+    hidden = ViewRenderer(use_canonical_space=False, triplane_dim=args.triplane_dim, triplane_ch=args.triplane_ch, smpl_type='smpl', test=True)
+    hidden.load_state_dict(syn.render_mlp_state(3), strict=False)
+    hidden = hidden.to(dev)
+    planes = syn.triplane(seed=11 + args.seed, H=args.triplane_dim, W=args.triplane_dim).to(dev)
+    # the hidden subject fills a box of 0.6 x the world bounds (a seeded tri-plane is opaque everywhere inside its box): the rest of
+    # the world box is the empty space the background class is drawn from
+    inner = (0.6 * torch.tensor(syn.WORLD_BOUNDS)).tolist()
+    tp = {"world_bounds": torch.tensor(inner, device=dev)[None]}
+    held = set(range(0, args.views, max(args.views // max(args.heldout, 1), 1))[:args.heldout])
+    train, test = ViewStore(S, S, dev), ViewStore(S, S, dev)
+    with torch.no_grad():
+        for v in range(args.views):
+            K, c2w, cam = syn.orbit_camera(v, args.views, S, S)
+            R = c2w.T.copy()
+            rgb, acc, _, _ = render_view(S, S, K, R, -R @ cam, planes, tp, hidden, n_samples=args.n_samples, n_importance=args.n_importance)
+            hit = camera_rays(S, S, K, R, -R @ cam, inner, dev)[4].reshape(S, S)          # rays that cross the subject's box
+            (test if v in held else train).add((rgb * hit[..., None])[None].contiguous(), ((acc > 0.5) & hit)[None], K[None], R[None],
+                                               (-R @ cam)[None], syn.WORLD_BOUNDS, 0, 0)
+    return train.prepare(), test.prepare()
+
+
+def heldout_tp(store):
+    """The held-out views as evaluate_views' tp_input dicts (ViewStore.test_view: the reference's split != 'train' tuple)."""
+    for v in range(len(store)):
+        rgb, ray_o, ray_d, near, far, _, mask_at_box, _ = store.test_view(v)
+        yield {"rgb_all": rgb[None, None], "ray_o_all": ray_o[None, None], "ray_d_all": ray_d[None, None], "near_all": near[None, None, :, None],
+               "far_all": far[None, None, :, None], "mask_at_box_all": mask_at_box[None, None], "instance_idx": store.instance_idx[v:v + 1],
+               "cloth_layer_index": store.cloth_layer_index[v:v + 1], "pose_index": torch.tensor([0]), "world_bounds": store.world_bounds[v:v + 1],
+               "view_id": v, "H": store.H, "W": store.W}
+
+
+def fit_rendered(args, model, dev, kw):
+    from humanliff_amd.recon_NeRF.lib.all_test import evaluate_views
+    from humanliff_amd.recon_NeRF.lib.if_nerf_data_utils import RayBatchLoader
+    train, test = rendered_views(args, dev)
+    print(f"rendered {len(train)} training and {len(test)} held-out views of {args.image_size} x {args.image_size}; "
+          f"class counts (body, background) of the first: {train.class_counts()[0].tolist()}", flush=True)
+
+    def score(tag):
+        model.test = True
+        m = evaluate_views(model, heldout_tp(test), n_samples=args.n_samples, n_importance=args.n_importance, human_names=["hidden"])
+        model.test = False
+        print(f"[{tag}] held-out views: mse {m['novel_view_mean_human'][0]:.6f} psnr {m['novel_view_mean_human'][1]:.3f} "
+              f"ssim {m['novel_view_mean_human'][2]:.4f}", flush=True)
+
+    score("before")
+    FitLoop(model, RayBatchLoader(train, args.batch_size, args.n_rand, seed=args.seed), **kw).run_loop()
+    score("after")
 
 
 def main():
@@ -68,11 +132,14 @@ def main():
                      triplane_ch=args.triplane_ch, test=False)
     model.load_state_dict(syn.render_mlp_state(3), strict=False)
     model = model.to(dev)
-    FitLoop(model, batches(args, dev), lrate=args.lrate, tri_plane_lrate=args.tri_plane_lrate, lrate_decay=args.lrate_decay,
-            tv_loss_coef=args.tv_loss_coef, l1_loss_coef=args.l1_loss_coef, use_clamp=args.use_clamp, n_samples=args.n_samples,
-            n_importance=args.n_importance, perturb=args.perturb, chunk=args.chunk, ft_triplane_only=args.ft_triplane_only,
-            n_iteration=args.n_iteration, i_print=args.i_print, i_weights=args.i_weights, basedir=args.basedir, expname=args.expname,
-            ft_path=args.ft_path, no_reload=args.no_reload).run_loop()
+    kw = dict(lrate=args.lrate, tri_plane_lrate=args.tri_plane_lrate, lrate_decay=args.lrate_decay,
+              tv_loss_coef=args.tv_loss_coef, l1_loss_coef=args.l1_loss_coef, use_clamp=args.use_clamp, n_samples=args.n_samples,
+              n_importance=args.n_importance, perturb=args.perturb, chunk=args.chunk, ft_triplane_only=args.ft_triplane_only,
+              n_iteration=args.n_iteration, i_print=args.i_print, i_weights=args.i_weights, basedir=args.basedir, expname=args.expname,
+              ft_path=args.ft_path, no_reload=args.no_reload)
+    if args.data == "rendered":
+        return fit_rendered(args, model, dev, kw)
+    FitLoop(model, batches(args, dev), **kw).run_loop()
 
 
 if __name__ == "__main__":
