@@ -192,7 +192,7 @@ __global__ __launch_bounds__(256, 1) void k_conv_h16(const ConvK p) {
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(
         (void *)p.in, (short)0, (int)((long)p.N * p.Hin * p.Win * pitch4 * (p.in16 == 2 ? 2 : 1)), 0x00020000);
     const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)p.w_bf3, (short)0, (int)((long)p.n_nblocks * nch * 18 * 6144), 0x00020000);
+        (void *)p.wf, (short)0, (int)((long)p.n_nblocks * nch * 18 * 6144), 0x00020000);
 
     // ---- patch staging: unit u = (pixel of the 18x18 patch, group of 8 channels) -> two 16-byte fp32 loads, one 16-byte LDS write ----
     unsigned sv[NUT], sl[NUT];
@@ -468,7 +468,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_h2s(const ConvK p) {
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(
         (void *)p.in, (short)0, (int)((long)p.N * p.Hin * p.Win * pitch4 * (p.in16 == 2 ? 2 : 1)), 0x00020000);
     const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)p.w_bf3, (short)0, (int)((long)p.n_nblocks * nch * 18 * 6144 * 2), 0x00020000);
+        (void *)p.wf, (short)0, (int)((long)p.n_nblocks * nch * 18 * 6144 * 2), 0x00020000);
 
     // GroupNorm affine (+ SiLU) of the INPUT applied while staging (ConvK::cA / cB arrays, or ConvK::gn: coefficients formed here from the producers' group
     // totals): no pre-pass over the tensor.  The table sits behind the stages; padding pixels are zero AFTER the activation (the convolution pads the activated tensor).
@@ -632,7 +632,7 @@ __global__ __launch_bounds__(256, 1) void k_conv1_h16(const ConvK p) {
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(
         (void *)p.in, (short)0, (int)((long)p.N * p.Hin * p.Win * pitch4), 0x00020000);
     const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)p.w_bf3, (short)0, (int)((long)p.n_nblocks * nch * 6 * 6144), 0x00020000);
+        (void *)p.wf, (short)0, (int)((long)p.n_nblocks * nch * 6 * 6144), 0x00020000);
 
     unsigned sv[NUT], sl[NUT];
 #pragma unroll
@@ -740,7 +740,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_h2d(const ConvK p) {
     const int nch = p.Cin >> 4;                                    // chunks of 16 input channels
     const unsigned pitch4 = (unsigned)p.in_pitch * 4u;
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void *)p.in, (short)0, (int)((long)p.N * p.Hin * p.Win * pitch4), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc((void *)p.w_bf3, (short)0, (int)((long)p.n_nblocks * (p.Cin >> 5) * 18 * 6144 * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc((void *)p.wf, (short)0, (int)((long)p.n_nblocks * (p.Cin >> 5) * 18 * 6144 * 2), 0x00020000);
     unsigned sv[NUT], sl[NUT];
 #pragma unroll
     for (int j = 0; j < NUT; ++j) {
@@ -871,7 +871,7 @@ __global__ __launch_bounds__(256, 2) void k_conv1_h2s(const ConvK p) {
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(
         (void *)p.in, (short)0, (int)((long)p.N * p.Hin * p.Win * pitch4), 0x00020000);
     const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)p.w_bf3, (short)0, (int)((long)p.n_nblocks * nch * 3 * 12288), 0x00020000);
+        (void *)p.wf, (short)0, (int)((long)p.n_nblocks * nch * 3 * 12288), 0x00020000);
     // GroupNorm affine (+ SiLU) of the input applied while staging, as in k_conv_h2s (ConvK::cA / cB arrays or ConvK::gn); a tile = 128 pixels of ONE image
     const bool aff = p.cA != nullptr || p.gn.gt != nullptr;
     float *sA = reinterpret_cast<float *>(lds + H2S1_LDS), *sB = sA + p.Cin;
@@ -1158,7 +1158,7 @@ int conv_pack_weights_h2(const float *w, int Cout, int Cin, int Cin_pad, int ks,
 }
 // the 3x3 / stride-1 layers with fp16x2 products on the 8x16-pixel tile (two workgroups per CU): p.n_mtiles = pixels / 128
 int conv3_h2s_launch(const ConvK &p, hipStream_t st, int splits) {
-    HL_REQUIRE(p.w_bf3 && p.ks == 3 && conv_h16_applies(p.Hout, p.Wout, p.Cin, p.Cout, p.ks, p.stride, p.ups) && (splits == 1 || p.partial), "k_conv_h2s: bad layer");
+    HL_REQUIRE(p.wf && p.ks == 3 && conv_h16_applies(p.Hout, p.Wout, p.Cin, p.Cout, p.ks, p.stride, p.ups) && (splits == 1 || p.partial), "k_conv_h2s: bad layer");
     constexpr int LDS_MAX = H2S_LDS + (2 * 4096 + COEF_SCR_FLOATS) * 4;         // + the coefficient table of a fused GroupNorm (<= 4096 input channels)
     static const bool attr_ok = hipFuncSetAttribute((const void *)k_conv_h2s, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX) == hipSuccess;
     HL_REQUIRE(attr_ok, "k_conv_h2s: cannot raise the dynamic LDS limit to %d bytes", LDS_MAX);
@@ -1172,7 +1172,7 @@ int conv3_h2s_launch(const ConvK &p, hipStream_t st, int splits) {
 // the 3x3 / stride-2 layers: p.n_mtiles = output pixels / 128
 bool conv3_h2d_applies(int Hout, int Wout, int Cin, int Cout) { return Hout % 8 == 0 && Wout % 16 == 0 && Cin % 32 == 0 && Cout % 192 == 0 && (long)Cout * Cin * 36 < (1L << 31); }
 int conv3_h2d_launch(const ConvK &p, hipStream_t st) {
-    HL_REQUIRE(p.w_bf3 && p.ks == 3 && p.stride == 2 && !p.ups && !p.in16 && !p.partial && conv3_h2d_applies(p.Hout, p.Wout, p.Cin, p.Cout) && p.cA == nullptr && p.gn.gt == nullptr,
+    HL_REQUIRE(p.wf && p.ks == 3 && p.stride == 2 && !p.ups && !p.in16 && !p.partial && conv3_h2d_applies(p.Hout, p.Wout, p.Cin, p.Cout) && p.cA == nullptr && p.gn.gt == nullptr,
                "k_conv_h2d: bad layer");
     static const bool attr_ok = hipFuncSetAttribute((const void *)k_conv_h2d, hipFuncAttributeMaxDynamicSharedMemorySize, H2D_LDS) == hipSuccess;
     HL_REQUIRE(attr_ok, "k_conv_h2d: cannot raise the dynamic LDS limit to %d bytes", H2D_LDS);
@@ -1182,7 +1182,7 @@ int conv3_h2d_launch(const ConvK &p, hipStream_t st) {
 
 // the 1x1 layers on 128-pixel tiles (two workgroups per CU): p.n_mtiles = pixels / 128
 int conv1_h2s_launch(const ConvK &p, hipStream_t st, int splits) {
-    HL_REQUIRE(p.w_bf3 && conv1_h2_applies(p.Hout, p.Wout, p.Cin, p.Cout, p.ks, p.stride, p.ups) && (splits == 1 || p.partial) && !p.in16 && p.kt_per >= 1, "k_conv1_h2s: bad layer");
+    HL_REQUIRE(p.wf && conv1_h2_applies(p.Hout, p.Wout, p.Cin, p.Cout, p.ks, p.stride, p.ups) && (splits == 1 || p.partial) && !p.in16 && p.kt_per >= 1, "k_conv1_h2s: bad layer");
     constexpr int LDS_MAX = H2S1_LDS + (2 * 4096 + COEF_SCR_FLOATS) * 4;        // + the coefficient table of a fused GroupNorm (<= 4096 input channels)
     static const bool attr_ok = hipFuncSetAttribute((const void *)k_conv1_h2s, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX) == hipSuccess;
     HL_REQUIRE(attr_ok, "k_conv1_h2s: cannot raise the dynamic LDS limit to %d bytes", LDS_MAX);
@@ -1196,7 +1196,7 @@ int conv1_h2s_launch(const ConvK &p, hipStream_t st, int splits) {
 size_t conv_h16_lds_bytes() { return (size_t)2 * H1_STAGE; }   // 104 KB: the two 1x1 stages (the epilogue exchange needs 98 KB, the 3x3 patch stages 45 KB)
 
 int conv_h16_launch(const ConvK &p, int f16, hipStream_t st, int splits) {
-    HL_REQUIRE(p.w_bf3 && conv_h16_applies(p.Hout, p.Wout, p.Cin, p.Cout, p.ks, p.stride, p.ups), "k_conv_h16: bad layer");
+    HL_REQUIRE(p.wf && conv_h16_applies(p.Hout, p.Wout, p.Cin, p.Cout, p.ks, p.stride, p.ups), "k_conv_h16: bad layer");
     HL_REQUIRE(splits == 1 || (p.ks == 3 && p.partial), "k_conv_h16: split-K is the 3x3 kernel's");
     const dim3 grid((unsigned)(p.n_mtiles * p.n_nblocks), 1, (unsigned)splits);
     const size_t sh = conv_h16_lds_bytes();

@@ -213,7 +213,7 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino4w(const ConvK p) {
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(
         (void *)p.in, (short)0, (int)((long)p.N * p.Hin * p.Win * p.in_pitch * 4), 0x00020000);
     const __amdgpu_buffer_rsrc_t rsU = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)p.w_wino, (short)0, (int)((long)(p.Cout >> 5) * nkt * 36 * 1024), 0x00020000);
+        (void *)p.wf, (short)0, (int)((long)(p.Cout >> 5) * nkt * 36 * 1024), 0x00020000);
 
     // accumulators [frequency f of the wave's 3x3 block][32-channel half cb]: tile f*2+cb; tiles 0..15 = the accumulator file, 16 / 17 here
     f32x16 accv[2];
@@ -518,7 +518,7 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino4w(const ConvK p) {
 size_t conv_wino4w_lds_bytes() { return (size_t)36 * 16 * 64 * sizeof(float); }   // 144 KB: the output exchange (the two patch stages + the dump slot need 41.5 KB)
 
 int conv_wino4w_launch(const ConvK &p, int ups, int blk, int splits, hipStream_t st) {
-    HL_REQUIRE(p.Cout % 64 == 0 && p.Cin % 8 == 0 && p.w_wino, "k_conv_wino4w: bad layer");
+    HL_REQUIRE(p.Cout % 64 == 0 && p.Cin % 8 == 0 && p.wf, "k_conv_wino4w: bad layer");
     HL_REQUIRE(!(ups && blk), "k_conv_wino4w: the upsampling convolution reads a raw NHWC tensor");
     const dim3 grid((unsigned)(p.n_mtiles * p.n_nblocks), 1, (unsigned)splits);
     const size_t sh = conv_wino4w_lds_bytes();

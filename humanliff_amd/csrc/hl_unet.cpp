@@ -22,34 +22,12 @@ using hl::View;
 
 static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
-bool conv_mode_known(int mode) {
-    return mode == HL_CONV_FP32 || mode == HL_CONV_FP32_MFMA || mode == HL_CONV_BF16X3 || mode == HL_CONV_FP32_DIRECT || mode == HL_CONV_FP32_F23 ||
-           mode == HL_CONV_BF16 || mode == HL_CONV_FP16;
-}
-// The packed weight forms (besides the fp32 one) a convolution may use under the HL_CONV_* `mode`.  bf16_h16: the caller can pack the 16-bit
-// form in bf16 - the network packs it in fp16 only, so its HL_CONV_BF16 never reaches k_conv_h16.  bwd_data: a backward-data call (tf = 1),
-// which never takes the fp16x2 forms (measured in round 6 with the scale-invariant planes - the training step at microbatch 2 went from 102.6
-// to 110.1 ms as a HIP graph: per call the gradient's abs-max pass, the weights' scale + pack, and kernels that at two rounds of workgroups are
-// no faster than F(4x4,3x3) on the fp32 pipe).
-struct ConvForms { bool bf3, wino, wino4, h2, h16; };
-ConvForms conv_forms(int mode, bool bf16_h16, bool bwd_data) {
-    const bool f32 = mode == HL_CONV_FP32 || mode == HL_CONV_FP32_MFMA || mode == HL_CONV_FP16;   // (HL_CONV_FP16: the other layers as HL_CONV_FP32)
-    ConvForms f;
-    f.bf3 = mode == HL_CONV_BF16X3 || mode == HL_CONV_BF16;
-    f.wino = f32 || mode == HL_CONV_FP32_F23;
-    f.wino4 = f32;
-    f.h2 = mode == HL_CONV_FP32 && !bwd_data;
-    f.h16 = mode == HL_CONV_FP16 || (bf16_h16 && mode == HL_CONV_BF16);
-    return f;
-}
+using hl::WeightForm;
+using hl::conv_forms;
+using hl::conv_mode_known;
 
 struct Conv {
-    const float *w = nullptr;  // packed
-    const void *w_bf3 = nullptr;  // packed split-bf16 copy (layers that take the DMA tile), used when Net::conv_mode == 1
-    const float *w_wino = nullptr;  // Winograd-domain copy (3x3 layers), used when Net::conv_mode == 0
-    const void *w_h2 = nullptr;     // 1x1 layers: two fp16 planes in MFMA-fragment order (k_conv1_h2: fp16x2 products), used when Net::conv_mode == HL_CONV_FP32
-    const void *w_h16 = nullptr;    // fp16 copy in MFMA-fragment order (3x3 layers k_conv_h16 covers), used when Net::conv_mode == HL_CONV_FP16
-    const float *w_wino4 = nullptr; // Winograd F(4x4,3x3) copy (3x3 layers up to 64 MB of it), used when Net::conv_mode == HL_CONV_FP32
+    hl::ConvWeights w;   // every packed form the layer has (make_conv_w); a forward uses those of conv_forms(Net::conv_mode)
     const float *bias = nullptr;
     int Cin = 0, Cin_pad = 0, Cout = 0, ks = 1;
 };
@@ -121,7 +99,7 @@ struct Net {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     std::vector<hipEvent_t> ev_block;   // main encoder block i finished (its output feeds the skip sum)
     bool overlap = true;
-    int conv_mode = 0;   // HL_CONV_*: 0 fp32 (Winograd where it applies), 1 bf16x3 emulation, 2 fp32 direct only
+    int conv_mode = HL_CONV_FP32;   // HL_CONV_* (hl_unet_set_conv_mode): which of the layers' packed forms a forward may use (hl::conv_forms)
     // optional per-category HIP-event timing of one forward (bench.py roofline leg)
     bool prof = false;
     std::vector<hipEvent_t> ev_pool;
@@ -162,6 +140,13 @@ const float *lookup(Net &n, const std::string &name, int64_t expect) {
     return it->second.first;
 }
 
+// floats a weight form of `bytes` takes in the packed buffer (every form starts on 256 bytes), and all the forms of a layer
+size_t form_floats(size_t bytes) { return (bytes / 4 + 63) / 64 * 64; }
+size_t conv_forms_floats(int Cout, int Cin_pad, int ks) {
+    size_t t = 0;
+    for (int f = 0; f < hl::kWeightForms; ++f) t += form_floats(hl::conv_form_bytes((WeightForm)f, Cout, Cin_pad, ks));
+    return t;
+}
 Conv make_conv_w(Net &n, const float *w, const float *bias, int Cin, int Cout, int ks);
 Conv make_conv(Net &n, const std::string &p, int Cin, int Cout, int ks, bool has_bias = true) {
     const float *w = lookup(n, p + ".weight", (int64_t)Cout * Cin * ks * ks);
@@ -173,28 +158,15 @@ Conv make_conv_w(Net &n, const float *w, const float *bias, int Cin, int Cout, i
     c.Cin = Cin; c.Cin_pad = round_up(Cin, 16); c.Cout = Cout; c.ks = ks;
     c.bias = n.dry ? nullptr : bias;
     const int cp = c.Cin_pad;
-    // F(4x4,3x3) weights are 4x the direct ones: kept for the layers that can reach a level wide enough for that kernel (up to 64 MB a layer)
-    size_t wino4 = hl::conv_packed_wino4_bytes(Cout, cp, ks);
-    if (wino4 > ((size_t)64 << 20)) wino4 = 0;
-    // every form the layer has, in buffer order (fp32, bf16x3, F(2x2), F(4x4), fp16x2, fp16), each starting on 256 bytes; 0 bytes: no such form
-    const size_t bytes[6] = {hl::conv_packed_floats(Cout, cp, ks) * sizeof(float), hl::conv_packed_bf3_bytes(Cout, cp, ks),
-                             hl::conv_packed_wino_bytes(Cout, cp, ks), wino4, hl::conv_packed_h2_bytes(Cout, cp, ks),
-                             hl::conv_packed_h16_bytes(Cout, cp, ks)};
-    for (int f = 0; f < 6; ++f) {
-        if (!bytes[f]) continue;
+    // every form the layer has, in buffer order
+    for (int f = 0; f < hl::kWeightForms; ++f) {
+        const size_t bytes = hl::conv_form_bytes((WeightForm)f, Cout, cp, ks);
+        if (!bytes) continue;
         float *dst = n.dry ? nullptr : n.packed + n.packed_off;
-        n.packed_off += (bytes[f] / 4 + 63) / 64 * 64;
+        n.packed_off += form_floats(bytes);
         if (n.dry || !w) continue;
-        int rc = 0;
-        switch (f) {
-        case 0: rc = hl::conv_pack_weights(w, Cout, Cin, cp, ks, dst, n.st); c.w = dst; break;
-        case 1: rc = hl::conv_pack_weights_bf3(w, Cout, Cin, cp, ks, dst, n.st); c.w_bf3 = dst; break;
-        case 2: rc = hl::conv_pack_weights_wino(w, Cout, Cin, cp, dst, n.st); c.w_wino = dst; break;
-        case 3: rc = hl::conv_pack_weights_wino4(w, Cout, Cin, cp, dst, n.st); c.w_wino4 = dst; break;
-        case 4: rc = hl::conv_pack_weights_h2(w, Cout, Cin, cp, ks, dst, n.st); c.w_h2 = dst; break;
-        default: rc = hl::conv_pack_weights_h16(w, Cout, Cin, cp, ks, dst, 1, n.st); c.w_h16 = dst; break;   // (fp16 only: conv_forms)
-        }
-        if (rc != 0 && n.err.empty()) n.err = hl_last_error();
+        c.w.p[f] = dst;
+        if (hl::conv_pack_form((WeightForm)f, w, Cout, Cin, cp, ks, dst, n.st) != 0 && n.err.empty()) n.err = hl_last_error();   // (the 16-bit form in fp16: conv_forms)
     }
     return c;
 }
@@ -228,7 +200,10 @@ int add_res(Net &n, std::vector<EmbPiece> &emb, const std::string &p, int Cin, i
             if (it != n.sd.end() && it->second.second == (int64_t)Cout * Cin * 9) ks = 3;
         }
         r.skip = make_conv(n, p + ".skip_connection", Cin, Cout, ks);
-        if (n.dry) n.packed_off += hl::conv_packed_floats(Cout, round_up(Cin, 16), 3) * 5;  // size for the worst case (fp32 + bf16x3 + Winograd copies)
+        if (n.dry) {   // sized as 1x1 above: room for the 3x3 one where that is larger
+            const size_t f1 = conv_forms_floats(Cout, round_up(Cin, 16), 1), f3 = conv_forms_floats(Cout, round_up(Cin, 16), 3);
+            if (f3 > f1) n.packed_off += f3 - f1;
+        }
     }
     n.res.push_back(r);
     return (int)n.res.size() - 1;
@@ -499,11 +474,7 @@ struct Exec {
         if (!run) return;
         ConvArgs a{};
         a.in = in; a.in.C = c.Cin_pad;
-        const ConvForms f = conv_forms(n.conv_mode, false, false);
-        a.w = c.w; a.w_bf3 = f.bf3 ? c.w_bf3 : nullptr; a.bf16_single = n.conv_mode == HL_CONV_BF16;
-        a.w_wino = f.wino ? c.w_wino : nullptr; a.w_wino4 = f.wino4 ? c.w_wino4 : nullptr;
-        a.w_h16 = f.h16 ? c.w_h16 : nullptr; a.h16_fp16 = 1;
-        a.w_h2 = f.h2 ? c.w_h2 : nullptr;
+        a.w = c.w.only(conv_forms(n.conv_mode, false, false)); a.mode = n.conv_mode;
         a.bias = c.bias; a.Cout = c.Cout; a.ks = c.ks; a.stride = stride; a.ups = ups;
         a.coefA = cA; a.coefB = cB; a.act = act; a.gn = af.gn;
         a.out = out; a.res = res; a.res_pitch = res_pitch;
@@ -511,7 +482,7 @@ struct Exec {
         a.splitk_ws = splitk_ws; a.splitk_ws_bytes = hl::conv_splitk_ws_bytes();
         a.act_ws = act_ws; a.act_ws_bytes = act_need * sizeof(float);
         a.stats = st1; a.stats2 = st2;
-        if (af.cA == nullptr && af.gn.gt == nullptr) a.in_stats = raw_totals(in);     // (a raw input: the fp16x2 kernels scale it by a power of two from its sum x^2)
+        if (af.cA == nullptr && af.gn.gt == nullptr) a.in_stats = totals_of(in, false);     // (a raw input: the fp16x2 kernels scale it by a power of two from its sum x^2)
         a.st_cg = pi1.viewC / 32; a.st_c0 = pi1.c0; a.st2_cg = pi2.viewC / 32; a.st2_c0 = pi2.c0;
         const size_t e0 = span_begin();
         size_t emid = 0;
@@ -542,11 +513,12 @@ struct Exec {
             if (out2) stat_reg.erase(out2);
         }
     }
-    // the group totals the producer(s) of x left, whatever view they were grouped for, if they cover exactly x's channels (both halves of a decoder
-    // "concat" when x is one): complete when a consumer of x runs, since it is ordered behind every producer of x
-    const float *raw_totals(const View &x) const {
+    // the group totals the producer(s) of x left if they cover exactly x's channels (both halves of a decoder "concat" when x is one), whatever view
+    // they were grouped for or - need_view_match - only those formed for exactly this view: complete when a consumer of x runs, since it is ordered
+    // behind every producer of x
+    const float *totals_of(const View &x, bool need_view_match) const {
         auto it = stat_reg.find(x.p);
-        if (it == stat_reg.end() || it->second.c0 != 0) return nullptr;
+        if (it == stat_reg.end() || it->second.c0 != 0 || (need_view_match && it->second.viewC != x.C)) return nullptr;
         if (it->second.covered == x.C) return it->second.buf;
         auto it2 = stat_reg.find(x.p + it->second.covered);
         if (it2 != stat_reg.end() && it2->second.buf == it->second.buf && it2->second.c0 == it->second.covered &&
@@ -560,18 +532,7 @@ struct Exec {
         af.cA = alloc((size_t)B * x.C);
         af.cB = alloc((size_t)B * x.C);
         if (!run) return af;
-        // group totals left by the producer(s) of x, if they were formed for exactly this view and cover every channel of it; otherwise one
-        // pass over the tensor
-        const float *gt = nullptr;
-        auto it = stat_reg.find(x.p);
-        if (it != stat_reg.end() && it->second.viewC == x.C && it->second.c0 == 0) {
-            if (it->second.covered == x.C) gt = it->second.buf;
-            else {
-                auto it2 = stat_reg.find(x.p + it->second.covered);
-                if (it2 != stat_reg.end() && it2->second.buf == it->second.buf && it2->second.c0 == it->second.covered &&
-                    it->second.covered + it2->second.covered == x.C) gt = it->second.buf;
-            }
-        }
+        const float *gt = totals_of(x, true);   // else one pass over the tensor
         if (gt && !force_arrays && !n.prof) {
             // the consumer kernels form the coefficients themselves from the totals the producers left: no launch here
             af.cA = af.cB = nullptr;
@@ -1045,25 +1006,23 @@ static int conv2d_single(int mode, const float *in, int N, int H, int W, int Cin
     if (Cin_w < 0) Cin_w = Cin;
     HL_REQUIRE(Cin_w <= Cin, "hl_conv2d_nhwc: the weight has more input channels than the tensor");
     hipStream_t st = (hipStream_t)stream;
-    const size_t need32 = (hl::conv_packed_floats(Cout, Cin, ks) * sizeof(float) + 255) / 256 * 256;
+    const size_t need32 = (hl::conv_form_bytes(WeightForm::Fp32, Cout, Cin, ks) + 255) / 256 * 256;
     // the second weight layout: room for the largest form the mode allows (only the one the plan reads is packed)
-    const ConvForms f = conv_forms(mode, true, tf != 0);
-    const size_t b_bf3 = f.bf3 ? hl::conv_packed_bf3_bytes(Cout, Cin, ks) : 0, b_wino = f.wino ? hl::conv_packed_wino_bytes(Cout, Cin, ks) : 0,
-                 b_wino4 = f.wino4 ? hl::conv_packed_wino4_bytes(Cout, Cin, ks) : 0, b_h2 = f.h2 ? hl::conv_packed_h2_bytes(Cout, Cin, ks) : 0,
-                 b_h16 = f.h16 ? hl::conv_packed_h16_bytes(Cout, Cin, ks) : 0;
-    const size_t extra = std::max({b_bf3, b_wino, b_wino4, b_h2, b_h16});
+    unsigned forms = conv_forms(mode, true, tf != 0);
+    size_t extra = 0;
+    for (int f = 1; f < hl::kWeightForms; ++f) {
+        const size_t b = forms >> f & 1u ? hl::conv_form_bytes((WeightForm)f, Cout, Cin, ks, false) : 0;
+        if (!b) forms &= ~(1u << f);   // (the layer has no such form)
+        extra = std::max(extra, b);
+    }
     const size_t need = need32 + (extra + 255) / 256 * 256;
     HL_REQUIRE(scratch && scratch_bytes >= need, "hl_conv2d_nhwc: scratch too small (%zu < %zu)", scratch_bytes, need);
     ConvArgs a{};
     void *extra_dst = static_cast<char *>(scratch) + need32;
     a.in.p = const_cast<float *>(in); a.in.N = N; a.in.H = H; a.in.W = W; a.in.C = Cin; a.in.pitch = Cin;
-    a.w = static_cast<float *>(scratch); a.bias = bias; a.Cout = Cout; a.ks = ks; a.stride = stride; a.ups = upsample;
+    a.bias = bias; a.Cout = Cout; a.ks = ks; a.stride = stride; a.ups = upsample; a.mode = mode;
     // every form the layer has under the mode points at that room, for plan_conv to choose from
-    if (b_bf3) { a.w_bf3 = extra_dst; a.bf16_single = mode == HL_CONV_BF16; }
-    if (b_wino) a.w_wino = static_cast<float *>(extra_dst);
-    if (b_wino4) a.w_wino4 = static_cast<float *>(extra_dst);
-    if (b_h16) { a.w_h16 = extra_dst; a.h16_fp16 = mode == HL_CONV_FP16; }
-    if (b_h2) a.w_h2 = extra_dst;
+    for (int f = 0; f < hl::kWeightForms; ++f) a.w.p[f] = f == 0 ? scratch : (forms >> f & 1u ? extra_dst : nullptr);
     a.coefA = coefA; a.coefB = coefB; a.act = silu;
     const int pad = ks / 2, Hv = upsample ? 2 * H : H, Wv = upsample ? 2 * W : W;
     a.out.p = out; a.out.N = N; a.out.H = (Hv + 2 * pad - ks) / stride + 1; a.out.W = (Wv + 2 * pad - ks) / stride + 1;
@@ -1089,22 +1048,11 @@ static int conv2d_single(int mode, const float *in, int N, int H, int W, int Cin
     a.stats = stats;
     if (stats) HL_HIP(hipMemsetAsync(stats, 0, hl::conv_stats_floats(N, (long)a.out.H * a.out.W) * sizeof(float), st));   // the epilogues ADD to the totals
     const hl::ConvPlan pl = hl::plan_conv(a);
-    int rc;
-    switch (pl.path) {
-    case hl::ConvPath::H16: rc = hl::conv_pack_weights_h16(w_oihw, Cout, Cin_w, Cin, ks, extra_dst, a.h16_fp16, st, tf); break;
-    case hl::ConvPath::Fp16x2: rc = hl::conv_pack_weights_h2(w_oihw, Cout, Cin_w, Cin, ks, extra_dst, st, tf); break;
-    case hl::ConvPath::Wino4: rc = hl::conv_pack_weights_wino4(w_oihw, Cout, Cin_w, Cin, static_cast<float *>(extra_dst), st, tf); break;
-    case hl::ConvPath::Wino2: rc = hl::conv_pack_weights_wino(w_oihw, Cout, Cin_w, Cin, static_cast<float *>(extra_dst), st, tf); break;
-    case hl::ConvPath::Bf16x3: rc = hl::conv_pack_weights_bf3(w_oihw, Cout, Cin_w, Cin, ks, extra_dst, st, tf); break;   // (k_conv_bf3 reads only these planes)
-    default: rc = hl::conv_pack_weights(w_oihw, Cout, Cin_w, Cin, ks, static_cast<float *>(scratch), st, tf); break;
-    }
-    if (rc) return rc;
     // the room holds that form only: no kernel argument points at the others
-    if (pl.path != hl::ConvPath::Bf16x3) a.w_bf3 = nullptr;
-    if (pl.path != hl::ConvPath::Wino2) a.w_wino = nullptr;
-    if (pl.path != hl::ConvPath::Wino4) a.w_wino4 = nullptr;
-    if (pl.path != hl::ConvPath::H16) a.w_h16 = nullptr;
-    if (pl.path != hl::ConvPath::Fp16x2) a.w_h2 = nullptr;
+    const WeightForm form = hl::form_of(pl.path);
+    a.w = a.w.only(hl::form_bit(WeightForm::Fp32) | hl::form_bit(form));
+    int rc = hl::conv_pack_form(form, w_oihw, Cout, Cin_w, Cin, ks, form == WeightForm::Fp32 ? scratch : extra_dst, st, tf, mode == HL_CONV_FP16);
+    if (rc) return rc;
     if (pl.path == hl::ConvPath::Fp16x2 && !coefA && tot_room) {   // fp16x2 products on a raw input: the largest |x| of every image fixes the power-of-two scale of the activation planes
         // (in the network the producers' sum x^2 bounds it; here one pass over the tensor - exact at any magnitude, which the backward-data calls need: gradients are 1e-4 ... 1e-9)
         if (g_single_op_scale_from_totals) {      // (test switch: the network's scale source - the group totals - on a single layer)
@@ -1123,7 +1071,7 @@ static int conv2d_single(int mode, const float *in, int N, int H, int W, int Cin
 
 int hl_conv2d_nhwc_bwd_data(int conv_mode, const float *dy, int N, int Ho, int Wo, int Cy, const float *w_oihw, int Cout, int Cin, int ks,
                             int stride, int upsample, float *dx, int Cx, void *scratch, size_t scratch_bytes, void *stream) {
-    HL_REQUIRE(conv_mode == HL_CONV_FP32 || conv_mode == HL_CONV_FP32_DIRECT || conv_mode == HL_CONV_FP32_F23 || conv_mode == HL_CONV_BF16 || conv_mode == HL_CONV_FP16, "hl_conv2d_nhwc_bwd_data: mode %d", conv_mode);
+    HL_REQUIRE(conv_mode_known(conv_mode) && conv_mode != HL_CONV_BF16X3 && conv_mode != HL_CONV_FP32_MFMA, "hl_conv2d_nhwc_bwd_data: mode %d", conv_mode);   // (the training path's modes)
     HL_REQUIRE(dy && w_oihw && dx && scratch, "hl_conv2d_nhwc_bwd_data: null argument");
     HL_REQUIRE(Cy % 16 == 0 && Cout <= Cy && Cin <= Cx && (ks == 1 || ks == 3) && (stride == 1 || (stride == 2 && !upsample && ks == 3)),
                "hl_conv2d_nhwc_bwd_data: bad argument");

@@ -1,4 +1,6 @@
 // Launchers of the UNet / sampler device kernels (hl_unet_kernels.hip). Internal header.
+// The packed weight forms of a convolution are one table: WeightForm names them in buffer order, conv_form_bytes / conv_pack_form size and
+// pack one, ConvWeights holds the pointers, conv_forms says which of them an HL_CONV_* mode may use and form_of which one a ConvPath reads.
 #pragma once
 #include "hl_common.h"
 
@@ -25,19 +27,86 @@ struct GnSrc {
     float eps;
 };
 
+// The kernel family a convolution runs on.  The values reach Python (hl_unet_dispatch_census, hl_unet_profile_dominant) and keep their numbers.
+enum class ConvPath : int {
+    Direct = 0,   // implicit GEMM on the fp32 matrix pipe: k_conv, k_conv_dma
+    Wino2 = 1,    // Winograd F(2x2,3x3): k_conv_wino
+    Bf16x3 = 2,   // fp32 emulated on the bf16 matrix pipe (or HL_CONV_BF16): k_conv_bf3
+    Wino4 = 3,    // Winograd F(4x4,3x3): k_conv_wino4, k_conv_wino4w
+    H16 = 5,      // 16-bit operands: k_conv_h16
+    Fp16x2 = 6,   // fp16x2 products: k_conv1_h2s, k_conv_h2s, k_conv_h2d
+};
+// row of hl_unet_dispatch_census: 0 direct, 1 F(2x2), 2 the 16-bit matrix pipe (bf16x3 and k_conv_h16), 3 F(4x4), 4 fp16x2
+constexpr int conv_census_row(ConvPath p) {
+    return p == ConvPath::Fp16x2 ? 4 : (p == ConvPath::H16 ? 2 : (int)p);
+}
+// FLOPs a family issues per algorithmic FLOP: Winograd F(2x2,3x3) 16 multiplies per 2x2 outputs instead of 36, F(4x4,3x3) a quarter,
+// bf16x3 six bf16 MFMA products per fp32 product
+constexpr double conv_issued_factor(ConvPath p) {
+    return p == ConvPath::Wino2 ? 16.0 / 36.0 : (p == ConvPath::Wino4 ? 0.25 : (p == ConvPath::Bf16x3 ? 6.0 : 1.0));
+}
+
+// The packed forms of one convolution's weights, in the order they lie in the network's packed buffer.
+enum class WeightForm : int {
+    Fp32,     // [Cout_pad][Ktot] floats, K order = kt_decode() in hl_unet_kernels.hip (groups of two 16-channel chunks, taps inside): k_conv, k_conv_dma; every layer has it
+    Bf16x3,   // three bf16 planes, [Cout_pad][K/16][plane*2 + k-half][8 bf16], 6 bytes per weight (layers that take the DMA tile: Cout_pad a multiple of 96): k_conv_bf3
+    Wino2,    // Winograd F(2x2,3x3) U = G g G^T, [Cout/64][Cin_pad/8][16][2][2][32][4] floats: k_conv_wino
+    Wino4,    // Winograd F(4x4,3x3) (points 0, +-3/4, +-3/2, inf), [Cout/32][Cin_pad/8][36][2][32][4] floats, a ragged Cout < 32 padded with zero rows: k_conv_wino4[w]
+    Fp16x2,   // two fp16 planes in MFMA-fragment order + the [Cout] inverse power-of-two scales behind them (conv_h2_wscale): k_conv1_h2s, k_conv_h2s, k_conv_h2d
+    H16,      // 16-bit weights (fp16, or bf16 on request) in MFMA-fragment order: k_conv_h16, k_conv1_h16
+    kCount
+};
+constexpr int kWeightForms = (int)WeightForm::kCount;
+constexpr unsigned form_bit(WeightForm f) { return 1u << (int)f; }
+// the form the kernels of a family read
+constexpr WeightForm form_of(ConvPath p) {
+    return p == ConvPath::Wino2 ? WeightForm::Wino2 : p == ConvPath::Bf16x3 ? WeightForm::Bf16x3 : p == ConvPath::Wino4 ? WeightForm::Wino4 :
+           p == ConvPath::H16 ? WeightForm::H16 : p == ConvPath::Fp16x2 ? WeightForm::Fp16x2 : WeightForm::Fp32;
+}
+// Bytes of one form; 0: the layer has no such form.  cap_wino4: F(4x4,3x3) weights are 4x the direct ones - the network keeps them only up to 64 MB a
+// layer (the single-op entry points, which pack one form per call, pass false).
+size_t conv_form_bytes(WeightForm f, int Cout, int Cin_pad, int ks, bool cap_wino4 = true);
+// packs w (Cout, Cin, ks, ks) into dst (conv_form_bytes of room).  tf = 1: the source is laid out (Cin, Cout, ks, ks) and is read flipped and
+// channel-transposed (backward-data weights).  f16 (WeightForm::H16 only): 1 fp16, 0 bf16.
+int conv_pack_form(WeightForm f, const float *w, int Cout, int Cin, int Cin_pad, int ks, void *dst, hipStream_t st, int tf = 0, int f16 = 1);
+const float *conv_h2_wscale(const void *packed, int Cout, int Cin_pad, int ks);   // the [Cout] inverse scales behind the Fp16x2 planes (ConvK::wsc)
+
+struct ConvWeights {
+    const void *p[kWeightForms] = {};
+    bool has(WeightForm f) const { return p[(int)f] != nullptr; }
+    const float *fp32() const { return static_cast<const float *>(p[(int)WeightForm::Fp32]); }
+    ConvWeights only(unsigned mask) const {   // the forms of `mask` (bits form_bit)
+        ConvWeights r;
+        for (int f = 0; f < kWeightForms; ++f) if (mask >> f & 1u) r.p[f] = p[f];
+        return r;
+    }
+};
+
+constexpr bool conv_mode_known(int mode) {
+    return mode == HL_CONV_FP32 || mode == HL_CONV_FP32_MFMA || mode == HL_CONV_BF16X3 || mode == HL_CONV_FP32_DIRECT || mode == HL_CONV_FP32_F23 ||
+           mode == HL_CONV_BF16 || mode == HL_CONV_FP16;
+}
+constexpr bool conv_mode_bf16(int mode) { return mode == HL_CONV_BF16X3 || mode == HL_CONV_BF16; }   // the modes of k_conv_bf3
+// The forms (bits form_bit) a convolution may use under the HL_CONV_* `mode`.  bf16_h16: the caller can pack the 16-bit form in bf16 - the network
+// packs it in fp16 only, so its HL_CONV_BF16 never reaches k_conv_h16.  bwd_data: a backward-data call (tf = 1), which never takes the fp16x2 form
+// (measured with the scale-invariant planes - the training step at microbatch 2 went from 102.6 to 110.1 ms as a HIP graph: per call the gradient's
+// abs-max pass, the weights' scale + pack, and kernels that at two rounds of workgroups are no faster than F(4x4,3x3) on the fp32 pipe).
+constexpr unsigned conv_forms(int mode, bool bf16_h16, bool bwd_data) {
+    const bool f32 = mode == HL_CONV_FP32 || mode == HL_CONV_FP32_MFMA || mode == HL_CONV_FP16;   // (HL_CONV_FP16: the other layers as HL_CONV_FP32)
+    return form_bit(WeightForm::Fp32) | (conv_mode_bf16(mode) ? form_bit(WeightForm::Bf16x3) : 0u) |
+           (f32 || mode == HL_CONV_FP32_F23 ? form_bit(WeightForm::Wino2) : 0u) | (f32 ? form_bit(WeightForm::Wino4) : 0u) |
+           (mode == HL_CONV_FP32 && !bwd_data ? form_bit(WeightForm::Fp16x2) : 0u) |
+           (mode == HL_CONV_FP16 || (bf16_h16 && mode == HL_CONV_BF16) ? form_bit(WeightForm::H16) : 0u);
+}
+
 struct ConvArgs {
     View in;             // C must be a multiple of 16 (pad channels are zero and have zero weights)
-    const float *w;      // packed [Cout_pad][Ktot], K order = kt_decode() in hl_unet_kernels.hip (groups of two 16-channel chunks, taps inside)
-    const void *w_bf3;   // optional: the same weights split into three bf16 planes (conv_pack_weights_bf3); selects k_conv_bf3
-    int bf16_single;     // with w_bf3: 1 = HL_CONV_BF16 (activations rounded to bf16 x the weights' two leading bf16 planes), 0 = bf16x3 emulation
-    const void *w_h2;    // optional (1x1 layers): two fp16 planes in MFMA-fragment order (conv_pack_weights_h2); selects k_conv1_h2s where it fills the chip
+    ConvWeights w;       // the forms plan_conv may choose from (Fp32 always; the others masked by conv_forms(mode, ...))
+    int mode;            // HL_CONV_*: says which kernel reads a form two modes share - HL_CONV_BF16 (activations rounded to bf16 x the weights' two leading bf16 planes)
+                         // against the bf16x3 emulation on Bf16x3; fp16 (HL_CONV_FP16) against bf16 operands on H16
     const float *in_absmax; // optional, instead of in_stats: [N] the largest |x| of every image of `in` (tensor_absmax)
     const float *in_stats; // optional: the group totals the producer(s) of `in` left for ANY view that covers it (conv_stats_floats(N, in.H * in.W) floats, complete
                          // when this launch starts): the fp16x2 kernels derive the power-of-two scale of the raw input from sum x^2 (ConvK::xs_gt); null: scale 1
-    const void *w_h16;   // optional: 16-bit weights in MFMA-fragment order (conv_pack_weights_h16); selects k_conv_h16 where conv_h16_applies
-    int h16_fp16;        // with w_h16: 1 = fp16 operands (HL_CONV_FP16), 0 = bf16 (HL_CONV_BF16)
-    const float *w_wino; // optional: Winograd-domain weights (conv_pack_weights_wino); selects k_conv_wino for large 3x3 layers
-    const float *w_wino4;// optional: Winograd F(4x4,3x3) weights (conv_pack_weights_wino4); selects k_conv_wino4 where it fills the chip
     const float *bias;   // [Cout] or null
     int Cout;            // real output channels
     int ks;              // 1 or 3 (pad = ks/2)
@@ -75,7 +144,9 @@ struct ConvArgs {
 struct ConvK {
     const float *in; long in_pitch; int N, Hin, Win, Cin;
     int Hout, Wout, ks, stride, ups, taps;
-    const float *w; const void *w_bf3; const float *w_wino; long Ktot; const float *bias; int Cout;
+    const float *w;    // WeightForm::Fp32 (the direct kernels)
+    const void *wf;    // the form of the planned path, form_of(ConvPlan::path): what every other kernel reads
+    long Ktot; const float *bias; int Cout;
     const float *cA; const float *cB; int act;
     GnSrc gn;          // (cA null and gn.t0 set: the coefficients are formed in the kernel, coef_to_lds)
     float *out; long out_pitch; const float *res; long res_pitch;
@@ -102,23 +173,18 @@ struct ConvK {
 };
 
 // k_conv_wino4w (hl_conv_wino4w.hip): Winograd F(4x4,3x3) with 64 output channels per workgroup, one wave per SIMD, 18 accumulator
-// tiles per wave in the accumulator registers; reads the weights conv_pack_weights_wino4 laid out.  LDS: conv_wino4w_lds_bytes().
+// tiles per wave in the accumulator registers; reads ConvK::wf = WeightForm::Wino4.  LDS: conv_wino4w_lds_bytes().
 size_t conv_wino4w_lds_bytes();
 int conv_wino4w_launch(const ConvK &p, int ups, int blk, int splits, hipStream_t st);
 
 // k_conv_h16 (hl_conv_h16.hip): 3x3 / stride-1 convolution with 16-bit operands (fp16 / bf16) and fp32 accumulation, 16x16 pixels x 192
-// channels per workgroup; reads ConvK::w_bf3 = the weights conv_pack_weights_h16 laid out (ConvK::n_mtiles = N (H/16)(W/16), n_nblocks = Cout/192).
+// channels per workgroup; reads ConvK::wf = WeightForm::H16 (ConvK::n_mtiles = N (H/16)(W/16), n_nblocks = Cout/192).
 bool conv_h16_applies(int Hout, int Wout, int Cin, int Cout, int ks, int stride, int ups);
-size_t conv_packed_h16_bytes(int Cout, int Cin_pad, int ks);
-int conv_pack_weights_h16(const float *w_oihw, int Cout, int Cin, int Cin_pad, int ks, void *packed, int f16, hipStream_t st, int tf = 0);
 int conv_h16_launch(const ConvK &p, int f16, hipStream_t st, int splits = 1);
 // k_conv1_h2s (hl_conv_h16.hip): the 1x1 / stride-1 convolutions of the default fp32 mode with fp16x2 products (two fp16 planes per operand, three partial
-// products, fp32 accumulation) on 128-pixel tiles, two workgroups per CU; weights conv_pack_weights_h2 laid out (ConvK::w_bf3), ConvK::n_mtiles = pixels / 128,
+// products, fp32 accumulation) on 128-pixel tiles, two workgroups per CU; reads ConvK::wf = WeightForm::Fp16x2, ConvK::n_mtiles = pixels / 128,
 // n_nblocks = Cout / 192.
 bool conv1_h2_applies(int Hout, int Wout, int Cin, int Cout, int ks, int stride, int ups);
-size_t conv_packed_h2_bytes(int Cout, int Cin_pad, int ks);
-int conv_pack_weights_h2(const float *w_oihw, int Cout, int Cin, int Cin_pad, int ks, void *packed, hipStream_t st, int tf = 0);
-const float *conv_h2_wscale(const void *packed, int Cout, int Cin_pad, int ks);   // the [Cout] inverse scales behind the planes (ConvK::wsc)
 int conv1_h2s_launch(const ConvK &p, hipStream_t st, int splits = 1);
 bool conv3_h2d_applies(int Hout, int Wout, int Cin, int Cout);        // 3x3 / stride 2 with fp16x2 products (k_conv_h2d)
 int conv3_h2d_launch(const ConvK &p, hipStream_t st);                 // p.n_mtiles = output pixels / 128
@@ -137,24 +203,6 @@ int tensor_totals(const View &x, float *totals, hipStream_t st);
 // [N] floats: the largest |x| of every image (zeroed here; non-negative floats order like their bit patterns: one integer atomicMax per workgroup)
 int tensor_absmax(const View &x, float *amax, hipStream_t st);
 
-// The kernel family a convolution runs on.  The values reach Python (hl_unet_dispatch_census, hl_unet_profile_dominant) and keep their numbers.
-enum class ConvPath : int {
-    Direct = 0,   // implicit GEMM on the fp32 matrix pipe: k_conv, k_conv_dma
-    Wino2 = 1,    // Winograd F(2x2,3x3): k_conv_wino
-    Bf16x3 = 2,   // fp32 emulated on the bf16 matrix pipe (or HL_CONV_BF16): k_conv_bf3
-    Wino4 = 3,    // Winograd F(4x4,3x3): k_conv_wino4, k_conv_wino4w
-    H16 = 5,      // 16-bit operands: k_conv_h16
-    Fp16x2 = 6,   // fp16x2 products: k_conv1_h2s, k_conv_h2s, k_conv_h2d
-};
-// row of hl_unet_dispatch_census: 0 direct, 1 F(2x2), 2 the 16-bit matrix pipe (bf16x3 and k_conv_h16), 3 F(4x4), 4 fp16x2
-constexpr int conv_census_row(ConvPath p) {
-    return p == ConvPath::Fp16x2 ? 4 : (p == ConvPath::H16 ? 2 : (int)p);
-}
-// FLOPs a family issues per algorithmic FLOP: Winograd F(2x2,3x3) 16 multiplies per 2x2 outputs instead of 36, F(4x4,3x3) a quarter,
-// bf16x3 six bf16 MFMA products per fp32 product
-constexpr double conv_issued_factor(ConvPath p) {
-    return p == ConvPath::Wino2 ? 16.0 / 36.0 : (p == ConvPath::Wino4 ? 0.25 : (p == ConvPath::Bf16x3 ? 6.0 : 1.0));
-}
 // the kernel within the family
 enum class ConvKernel { Conv, Dma, Bf3, Wino, Wino4, Wino4w, H16, H2s, H2s1, H2d };
 // GroupNorm(+SiLU) materialised into ConvArgs::act_ws before the convolution, and its format: dense fp32, fp32 channel-blocked [C/8][pixel][8]
@@ -176,21 +224,8 @@ struct ConvPlan {
     int stat_slots = 0;      // > 0: the launch adds the output statistics (ConvArgs::stats); 0: the consumer computes them from the tensor
 };
 ConvPlan plan_conv(const ConvArgs &a);
-// runs `pl` = plan_conv(a); a caller may change a weight pointer in between only to point it at the form the plan reads (conv2d_single)
+// runs `pl` = plan_conv(a); a caller may drop forms from a.w in between, all but the one the plan reads (conv2d_single)
 int conv2d(const ConvArgs &a, const ConvPlan &pl, hipStream_t st);
-size_t conv_packed_floats(int Cout, int Cin_pad, int ks);
-// tf = 1: the source is laid out (Cin, Cout, ks, ks) and is read flipped and channel-transposed (backward-data weights)
-int conv_pack_weights(const float *w_oihw, int Cout, int Cin, int Cin_pad, int ks, float *packed, hipStream_t st, int tf = 0);
-// split-bf16 copy for k_conv_bf3: [Cout_pad][K/16][plane*2 + k-half][8 bf16], 6 bytes per weight; 0 bytes if the layer
-// never takes the DMA tile (Cout_pad not a multiple of 96)
-// Winograd F(2x2,3x3) copy U = G g G^T: [Cout/64][Cin_pad/8][16][2][2][32][4] floats; 0 bytes if not applicable
-size_t conv_packed_wino_bytes(int Cout, int Cin_pad, int ks);
-int conv_pack_weights_wino(const float *w_oihw, int Cout, int Cin, int Cin_pad, float *packed, hipStream_t st, int tf = 0);
-// Winograd F(4x4,3x3) copy (points 0, +-3/4, +-3/2, inf): [Cout/32][Cin_pad/8][36][2][32][4] floats; 0 bytes if not applicable
-size_t conv_packed_wino4_bytes(int Cout, int Cin_pad, int ks);
-int conv_pack_weights_wino4(const float *w_oihw, int Cout, int Cin, int Cin_pad, float *packed, hipStream_t st, int tf = 0);
-size_t conv_packed_bf3_bytes(int Cout, int Cin_pad, int ks);
-int conv_pack_weights_bf3(const float *w_oihw, int Cout, int Cin, int Cin_pad, int ks, void *packed, hipStream_t st, int tf = 0);
 
 // GroupNorm(32 groups, eps 1e-5) statistics -> per-(n,c) affine  y = x*A + B   (nn.py:17-19,100)
 // optional scale/shift (ResBlock use_scale_shift_norm, unet.py:203-206): y = GN(x)*(1+scale)+shift,

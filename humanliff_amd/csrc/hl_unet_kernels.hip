@@ -676,7 +676,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_wino(const ConvK p) {
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(
         (void *)p.in, (short)0, (int)((long)p.N * p.Hin * p.Win * p.in_pitch * 4), 0x00020000);
     const __amdgpu_buffer_rsrc_t rsU = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)p.w_wino, (short)0, (int)((long)p.n_nblocks * nkt * U_F * 4), 0x00020000);
+        (void *)p.wf, (short)0, (int)((long)p.n_nblocks * nkt * U_F * 4), 0x00020000);
 
     // DMA instructions of a k-tile: 32 weight instructions (plain 1 KiB copies) then NP patch instructions; instruction
     // q = wave + NW*j: the first NU rounds are weights, the rest patch instructions q - 32 (< NP)
@@ -1040,7 +1040,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_wino4(const ConvK p) {
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(
         (void *)p.in, (short)0, (int)((long)p.N * p.Hin * p.Win * p.in_pitch * 4), 0x00020000);
     const __amdgpu_buffer_rsrc_t rsU = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)p.w_wino, (short)0, (int)((long)p.n_nblocks * nkt * U_F * 4), 0x00020000);
+        (void *)p.wf, (short)0, (int)((long)p.n_nblocks * nkt * U_F * 4), 0x00020000);
 
     f32x16 acc[9];
 #pragma unroll
@@ -1429,7 +1429,7 @@ __global__ __launch_bounds__(WM * 64, (WM == 8) ? 4 : 3) void k_conv_bf3(const C
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(
         (void *)p.in, (short)0, (int)((long)p.N * p.Hin * p.Win * p.in_pitch * 4), 0x00020000);
     const __amdgpu_buffer_rsrc_t rsB =
-        __builtin_amdgcn_make_buffer_rsrc((void *)p.w_bf3, (short)0, (int)((long)p.wrows * p.Ktot * 6), 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc((void *)p.wf, (short)0, (int)((long)p.wrows * p.Ktot * 6), 0x00020000);
 
     // DMA instruction i of a tile fills rows 16i..16i+15: A rows by instructions wave + WM*j (j = 0,1), the 96 B rows
     // by instructions BM/16 + b with b = wave + WM*j < 6.
@@ -2831,45 +2831,46 @@ static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
 size_t conv_splitk_ws_bytes() { return (size_t)64 << 20; }
 
-size_t conv_packed_floats(int Cout, int Cin_pad, int ks) { return (size_t)round_up(Cout, 64) * Cin_pad * ks * ks; }
+// The weight forms: sizes and packers, one row per WeightForm (the 16-bit and fp16x2 ones live next to their kernels in hl_conv_h16.hip).
+size_t conv_packed_h16_bytes(int Cout, int Cin_pad, int ks);
+int conv_pack_weights_h16(const float *w, int Cout, int Cin, int Cin_pad, int ks, void *packed, int f16, hipStream_t st, int tf);
+size_t conv_packed_h2_bytes(int Cout, int Cin_pad, int ks);
+int conv_pack_weights_h2(const float *w, int Cout, int Cin, int Cin_pad, int ks, void *packed, hipStream_t st, int tf);
 
-int conv_pack_weights(const float *w, int Cout, int Cin, int Cin_pad, int ks, float *packed, hipStream_t st, int tf) {
-    HL_REQUIRE(w && packed && Cin_pad % 16 == 0 && Cin <= Cin_pad && (ks == 1 || ks == 3), "conv_pack_weights: bad argument");
+size_t conv_form_bytes(WeightForm f, int Cout, int Cin_pad, int ks, bool cap_wino4) {
+    const size_t rows = round_up(Cout, 64), K = (size_t)Cin_pad * ks * ks;
+    switch (f) {
+    case WeightForm::Fp32: return rows * K * sizeof(float);
+    case WeightForm::Bf16x3: return rows % 96 == 0 ? rows * K * 6 : 0;
+    case WeightForm::Wino2: return (ks == 3 && Cout % 64 == 0 && Cin_pad % 8 == 0) ? (size_t)Cout * Cin_pad * 16 * sizeof(float) : 0;
+    case WeightForm::Wino4: {
+        const size_t b = (ks == 3 && (Cout % 32 == 0 || Cout < 32) && Cin_pad % 8 == 0) ? (size_t)round_up(Cout, 32) * Cin_pad * 36 * sizeof(float) : 0;
+        return cap_wino4 && b > ((size_t)64 << 20) ? 0 : b;
+    }
+    case WeightForm::Fp16x2: return conv_packed_h2_bytes(Cout, Cin_pad, ks);
+    case WeightForm::H16: return conv_packed_h16_bytes(Cout, Cin_pad, ks);
+    default: return 0;   // (kCount)
+    }
+}
+
+int conv_pack_form(WeightForm f, const float *w, int Cout, int Cin, int Cin_pad, int ks, void *dst, hipStream_t st, int tf, int f16) {
+    HL_REQUIRE(w && dst && Cin <= Cin_pad && (ks == 1 || ks == 3) && (f > WeightForm::Bf16x3 || Cin_pad % 16 == 0) && conv_form_bytes(f, Cout, Cin_pad, ks, false),
+               "conv_pack_form: bad argument (form %d)", (int)f);
     const int rows = round_up(Cout, 64);
-    hipLaunchKernelGGL(k_pack_conv, dim3(1024), dim3(256), 0, st, w, Cout, Cin, Cin_pad, ks, rows, packed, tf);
+    float *dstf = static_cast<float *>(dst);
+    switch (f) {
+    case WeightForm::Fp32: hipLaunchKernelGGL(k_pack_conv, dim3(1024), dim3(256), 0, st, w, Cout, Cin, Cin_pad, ks, rows, dstf, tf); break;
+    case WeightForm::Bf16x3: hipLaunchKernelGGL(k_pack_conv_bf3, dim3(1024), dim3(256), 0, st, w, Cout, Cin, Cin_pad, ks, rows, static_cast<unsigned short *>(dst), tf); break;
+    case WeightForm::Wino2:
+        hipLaunchKernelGGL(k_pack_conv_wino, dim3((unsigned)std::min<long>(8192, (long)(Cout >> 5) * (Cin_pad >> 3))), dim3(256), 0, st, w, Cout, Cin, Cin_pad, dstf, tf);
+        break;
+    case WeightForm::Wino4:
+        hipLaunchKernelGGL(k_pack_conv_wino4, dim3((unsigned)std::min<long>(8192, (long)(round_up(Cout, 32) >> 5) * (Cin_pad >> 3))), dim3(256), 0, st, w, Cout, Cin, Cin_pad, dstf, tf);
+        break;
+    case WeightForm::Fp16x2: return conv_pack_weights_h2(w, Cout, Cin, Cin_pad, ks, dst, st, tf);
+    default: return conv_pack_weights_h16(w, Cout, Cin, Cin_pad, ks, dst, f16, st, tf);   // (H16: conv_form_bytes is 0 for anything else)
+    }
     return check_launch("k_pack_conv");
-}
-
-size_t conv_packed_bf3_bytes(int Cout, int Cin_pad, int ks) {
-    const int rows = round_up(Cout, 64);
-    return rows % 96 == 0 ? (size_t)rows * Cin_pad * ks * ks * 6 : 0;
-}
-
-int conv_pack_weights_bf3(const float *w, int Cout, int Cin, int Cin_pad, int ks, void *packed, hipStream_t st, int tf) {
-    HL_REQUIRE(w && packed && Cin_pad % 16 == 0 && Cin <= Cin_pad && (ks == 1 || ks == 3), "conv_pack_weights_bf3: bad argument");
-    const int rows = round_up(Cout, 64);
-    hipLaunchKernelGGL(k_pack_conv_bf3, dim3(1024), dim3(256), 0, st, w, Cout, Cin, Cin_pad, ks, rows, static_cast<unsigned short *>(packed), tf);
-    return check_launch("k_pack_conv_bf3");
-}
-
-size_t conv_packed_wino_bytes(int Cout, int Cin_pad, int ks) {
-    return (ks == 3 && Cout % 64 == 0 && Cin_pad % 8 == 0) ? (size_t)Cout * Cin_pad * 16 * sizeof(float) : 0;
-}
-
-int conv_pack_weights_wino(const float *w, int Cout, int Cin, int Cin_pad, float *packed, hipStream_t st, int tf) {
-    HL_REQUIRE(w && packed && Cout % 64 == 0 && Cin_pad % 8 == 0 && Cin <= Cin_pad, "conv_pack_weights_wino: bad argument");
-    hipLaunchKernelGGL(k_pack_conv_wino, dim3((unsigned)std::min<long>(8192, (long)(Cout >> 5) * (Cin_pad >> 3))), dim3(256), 0, st, w, Cout, Cin, Cin_pad, packed, tf);
-    return check_launch("k_pack_conv_wino");
-}
-
-size_t conv_packed_wino4_bytes(int Cout, int Cin_pad, int ks) {   // (a ragged Cout - the 27-channel output convolution - is padded with zero rows to 32)
-    return (ks == 3 && (Cout % 32 == 0 || Cout < 32) && Cin_pad % 8 == 0) ? (size_t)round_up(Cout, 32) * Cin_pad * 36 * sizeof(float) : 0;
-}
-
-int conv_pack_weights_wino4(const float *w, int Cout, int Cin, int Cin_pad, float *packed, hipStream_t st, int tf) {
-    HL_REQUIRE(w && packed && (Cout % 32 == 0 || Cout < 32) && Cin_pad % 8 == 0 && Cin <= Cin_pad, "conv_pack_weights_wino4: bad argument");
-    hipLaunchKernelGGL(k_pack_conv_wino4, dim3((unsigned)std::min<long>(8192, (long)(round_up(Cout, 32) >> 5) * (Cin_pad >> 3))), dim3(256), 0, st, w, Cout, Cin, Cin_pad, packed, tf);
-    return check_launch("k_pack_conv_wino4");
 }
 
 // k_conv_h16 is taken from this many workgroups on.  The default (48) is what the network dispatch uses; the unit tests that run the
@@ -2896,6 +2897,8 @@ static SplitK split_k(const ConvArgs &a, int nk, int want, long blocks = 0, long
 ConvPlan plan_conv(const ConvArgs &a) {
     ConvPlan pl;
     const bool gn_on = a.coefA != nullptr || a.gn.gt != nullptr;      // a GroupNorm affine in front of the convolution (arrays, or formed in the kernels)
+    const bool bf16 = conv_mode_bf16(a.mode);                         // the bf16 modes keep every layer off the Winograd and fp16x2 kernels
+    const bool h2 = a.w.has(WeightForm::Fp16x2) && !bf16;
     pl.gn_mode = gn_on ? (a.act ? 2 : 1) : 0;
     const long M = (long)a.out.N * a.out.H * a.out.W, hw_o = (long)a.out.H * a.out.W;
     const int cpad = round_up(a.Cout, 64);
@@ -2939,7 +2942,7 @@ ConvPlan plan_conv(const ConvArgs &a) {
     // layer with fewer tiles splits its input channels into slabs of >= 2 chunks (k_splitk_finish sums them) until ~128 workgroups run
     const long h16_blocks = ((long)a.out.N * a.out.H * a.out.W / 256) * (a.Cout / 192);
     const int nk32 = a.in.C / 32;      // chunks of 32 input channels: the k-tiles of k_conv_h16 / k_conv_h2s
-    if (a.w_h16 && (!gn_on || (a.act_ws && !a.ups)) && !a.out_nchw && conv_h16_applies(a.out.H, a.out.W, a.in.C, a.Cout, a.ks, a.stride, a.ups) &&
+    if (a.w.has(WeightForm::H16) && (!gn_on || (a.act_ws && !a.ups)) && !a.out_nchw && conv_h16_applies(a.out.H, a.out.W, a.in.C, a.Cout, a.ks, a.stride, a.ups) &&
         in_31 && a.in.pitch % 4 == 0 && h16_blocks > 0) {
         const bool fills = h16_blocks >= h16_min_blocks();
         const int want = a.ks == 3 && !a.out2 && h16_blocks >= 4 ? (int)std::min<long>(std::min<long>(128 / h16_blocks, nk32 / 2), 16) : 0;
@@ -2954,7 +2957,7 @@ ConvPlan plan_conv(const ConvArgs &a) {
     // fp32 kernel takes twice as long.  From h2_min_blocks workgroups of 256 pixels x 192 channels on (fewer: the split-K fp32 path keeps the layer).
     constexpr long h2_min_blocks = 12;   // (12: with the 128-pixel tiles; 48 with the 256-pixel ones)
     const long h2_blocks = (M / 256) * (a.Cout / 192);
-    if (a.w_h2 && (!gn_on || a.act_ws) && !a.out_nchw && !a.w_bf3 && conv1_h2_applies(a.out.H, a.out.W, a.in.C, a.Cout, a.ks, a.stride, a.ups) &&
+    if (h2 && (!gn_on || a.act_ws) && !a.out_nchw && conv1_h2_applies(a.out.H, a.out.W, a.in.C, a.Cout, a.ks, a.stride, a.ups) &&
         in_31 && a.in.pitch % 4 == 0 && h2_blocks >= h2_min_blocks) {
         // few workgroups (the 16- and 32-pixel levels, batch 1): the input channels split into slabs of >= 4 chunks until ~256 workgroups run (k_splitk_finish[_st] sums them)
         constexpr long h2_split_max = 64;
@@ -2971,7 +2974,7 @@ ConvPlan plan_conv(const ConvArgs &a) {
     // round of workgroups: alone it beat k_conv_wino4w by 12 % on the 256-pixel level and the forward's wall time did not move - a kernel that owns whole CUs cannot fill
     // the other encoder tower's bubbles, and nothing overlapped its own prologue / staging / epilogue (profiles/r05_unet_fill_experiments.md, sections 6 - 8).
     constexpr long h3_min_blocks = 100;
-    if (a.w_h2 && a.ks == 3 && (!gn_on || (a.act_ws && !a.ups)) && !a.out_nchw && !a.w_bf3 &&
+    if (h2 && a.ks == 3 && (!gn_on || (a.act_ws && !a.ups)) && !a.out_nchw &&
         conv_h16_applies(a.out.H, a.out.W, a.in.C, a.Cout, a.ks, a.stride, a.ups) && in_31 && a.in.pitch % 4 == 0) {
         // below that: the input channels split into slabs of >= 2 chunks until about one round of 128-pixel workgroups runs (k_splitk_finish[_st] sums the slabs)
         constexpr long h3_split_min = 8;
@@ -2992,7 +2995,7 @@ ConvPlan plan_conv(const ConvArgs &a) {
     }
     // 3x3 / stride-2 layers (Downsample) of the default mode in the same arithmetic (k_conv_h2d), from h3d_min_blocks workgroups' worth of output (256 pixels x 192 channels) on
     constexpr long h3d_min_blocks = 32;
-    if (a.w_h2 && a.ks == 3 && a.stride == 2 && !a.ups && !gn_on && !a.out_nchw && !a.w_bf3 && conv3_h2d_applies(a.out.H, a.out.W, a.in.C, a.Cout) &&
+    if (h2 && a.ks == 3 && a.stride == 2 && !a.ups && !gn_on && !a.out_nchw && conv3_h2d_applies(a.out.H, a.out.W, a.in.C, a.Cout) &&
         in_31 && a.in.pitch % 4 == 0 && h16_blocks >= h3d_min_blocks) {
         take(ConvPath::Fp16x2, ConvKernel::H2d, {1, direct_sk.kt_per});   // one launch over the whole K (k_conv_h2d does not read kt_per)
         return done(a.stats, (int)(hw_o / 128));
@@ -3007,7 +3010,7 @@ ConvPlan plan_conv(const ConvArgs &a) {
     // (the 27-channel NCHW output convolution takes the F(4x4) kernel too: its weights are padded to 32 rows, the epilogue stores 27)
     const bool small_nchw = a.out_nchw && a.Cout < 32 && !a.res && !a.out2 && !a.stats && (!gn_on || a.act_ws) && in_31;
     const long wino4_blocks = (long)a.out.N * (a.out.H / 16) * (a.out.W / 32) * ((a.Cout + 31) / 32);
-    if ((dma || small_nchw) && a.w_wino4 && !a.w_bf3 && a.ks == 3 && a.stride == 1 && a.out.H % 16 == 0 && a.out.W % 32 == 0 &&
+    if ((dma || small_nchw) && a.w.has(WeightForm::Wino4) && !bf16 && a.ks == 3 && a.stride == 1 && a.out.H % 16 == 0 && a.out.W % 32 == 0 &&
         (a.Cout % 32 == 0 || small_nchw) && (long)round_up(a.Cout, 32) * a.in.C * 144 < (1L << 31)) {
         // k_conv_wino4w: the same arithmetic with 64 output channels per workgroup at ONE workgroup per CU (hl_conv_wino4w.hip).  With W
         // = 32x16-pixel x 64-channel workgroups it is taken
@@ -3037,7 +3040,7 @@ ConvPlan plan_conv(const ConvArgs &a) {
     constexpr long wino_thr = 512;    // Winograd: workgroups wanted per launch (smaller layers split the input channels)
     constexpr long wino_min = 384;    // fewer even after splitting: direct kernel
     const long wino_blocks = (long)a.out.N * (a.out.H / 8) * (a.out.W / 16) * (a.Cout / 64);
-    if (dma && a.w_wino && !a.w_bf3 && a.ks == 3 && a.stride == 1 && a.out.H % 8 == 0 && a.out.W % 16 == 0 &&
+    if (dma && a.w.has(WeightForm::Wino2) && !bf16 && a.ks == 3 && a.stride == 1 && a.out.H % 8 == 0 && a.out.W % 16 == 0 &&
         a.Cout % 64 == 0 && (long)a.Cout * a.in.C * 64 < (1L << 31)) {   // (stride 1: out = in, or 2x in when upsampling)
         const bool fills = wino_blocks >= wino_thr;
         // the most slabs that still fit ONE round of workgroups (2 per CU): rounding up instead put 576 workgroups on 512 slots - a second,
@@ -3051,7 +3054,7 @@ ConvPlan plan_conv(const ConvArgs &a) {
         }
     }
     if (dma) {
-        const bool bf3 = a.w_bf3 && (long)cpad * Ktot * 6 < (1L << 31);   // fp32 emulated on the bf16 matrix pipe (opt-in)
+        const bool bf3 = a.w.has(WeightForm::Bf16x3) && (long)cpad * Ktot * 6 < (1L << 31);   // fp32 emulated on the bf16 matrix pipe (opt-in)
         take(bf3 ? ConvPath::Bf16x3 : ConvPath::Direct, bf3 ? ConvKernel::Bf3 : ConvKernel::Dma, direct_sk);
         pl.pre = dense;
         return done(st_rows32 && !bf3, (int)(hw_o / 32));   // slot = a wave's 32 rows
@@ -3064,7 +3067,7 @@ ConvPlan plan_conv(const ConvArgs &a) {
 static int gn_prepass(const ConvArgs &a, ConvPrePass fmt, hipStream_t st) {
     HL_REQUIRE((size_t)a.in.pixels() * a.in.C * sizeof(float) <= a.act_ws_bytes, "conv2d: act scratch too small");
     const long npix = a.in.pixels();
-    const int out16 = fmt == ConvPrePass::TwoPlane ? 2 : a.h16_fp16;   // k_gn_apply_h16 / k_gn_apply_gs<1>: 2 = two fp16 planes, 1 fp16, 0 bf16
+    const int out16 = fmt == ConvPrePass::TwoPlane ? 2 : a.mode == HL_CONV_FP16;   // k_gn_apply_h16 / k_gn_apply_gs<1>: 2 = two fp16 planes, 1 fp16, 0 bf16
     if (fmt == ConvPrePass::Blocked) {
         const int tp = 8;   // (8 pixels = 256 contiguous bytes per plane; larger tiles cost occupancy: 64 pixels 93 us, 8 pixels 70 us = the plain pass)
         const int pad = ((4 - (a.in.C / 4) % 16 + 16) % 16) * 4;   // row length / 4 = 4 (mod 16): the read-back groups (8 pixels x 2 halves of two planes) hit 16 different slots
@@ -3144,7 +3147,7 @@ static int launch_conv(ConvK &p, const ConvArgs &a, const ConvPlan &pl, hipStrea
         p.n_nblocks = cpad / 96;
         p.n_mtiles = (int)((M + (pl.tile8 ? 255 : 127)) / (pl.tile8 ? 256 : 128));
         const dim3 grid((unsigned)(p.n_mtiles * p.n_nblocks), 1, pl.splits);
-        if (pl.kernel == ConvKernel::Bf3) return a.bf16_single ? launch_k_conv_bf3<1>(p, grid, pl.tile8, a.ups, st) : launch_k_conv_bf3<3>(p, grid, pl.tile8, a.ups, st);
+        if (pl.kernel == ConvKernel::Bf3) return a.mode == HL_CONV_BF16 ? launch_k_conv_bf3<1>(p, grid, pl.tile8, a.ups, st) : launch_k_conv_bf3<3>(p, grid, pl.tile8, a.ups, st);
         const size_t shm8 = (size_t)3 * 352 * 16 * sizeof(float), shm4 = (size_t)3 * 224 * 16 * sizeof(float);
         if (pl.tile8 && a.ups) hipLaunchKernelGGL((k_conv_dma<8, 3, true>), grid, dim3(512), shm8, st, p);
         else if (pl.tile8) hipLaunchKernelGGL((k_conv_dma<8, 3, false>), grid, dim3(512), shm8, st, p);
@@ -3162,7 +3165,6 @@ static int launch_conv(ConvK &p, const ConvArgs &a, const ConvPlan &pl, hipStrea
         return check_launch("k_conv_wino");
     }
     case ConvKernel::Wino4: {
-        p.w_wino = a.w_wino4;
         p.n_nblocks = (a.Cout + 31) / 32;
         p.n_mtiles = a.out.N * (a.out.H / 16) * (a.out.W / 32);
         const dim3 grid((unsigned)(p.n_mtiles * p.n_nblocks), 1, pl.splits);
@@ -3173,15 +3175,13 @@ static int launch_conv(ConvK &p, const ConvArgs &a, const ConvPlan &pl, hipStrea
         return check_launch("k_conv_wino4");
     }
     case ConvKernel::Wino4w:   // 64 output channels per workgroup, one wave per SIMD, accumulators in the accumulator registers (hl_conv_wino4w.hip)
-        p.w_wino = a.w_wino4;
         p.n_nblocks = a.Cout / 64;
         p.n_mtiles = a.out.N * (a.out.H / 16) * (a.out.W / 32);
         return conv_wino4w_launch(p, a.ups, pl.pre == ConvPrePass::Blocked ? 1 : 0, pl.splits, st);
     case ConvKernel::H16:
-        p.w_bf3 = a.w_h16;
         p.n_nblocks = a.Cout / 192;
         p.n_mtiles = (int)(M / 256);   // 16x16-pixel tiles (3x3) / runs of 256 pixels (1x1)
-        return conv_h16_launch(p, a.h16_fp16, st, pl.splits);
+        return conv_h16_launch(p, a.mode == HL_CONV_FP16, st, pl.splits);
     case ConvKernel::H2s:
         p.n_nblocks = a.Cout / 192;
         p.n_mtiles = (int)(M / 256) * 2;   // 8x16-pixel tiles, two workgroups per CU
@@ -3201,7 +3201,7 @@ static int launch_conv(ConvK &p, const ConvArgs &a, const ConvPlan &pl, hipStrea
 static void wire_stats(ConvK &p, const ConvArgs &a) { p.st1 = a.stats; p.st2 = a.out2 ? a.stats2 : nullptr; }
 
 int conv2d(const ConvArgs &a, const ConvPlan &pl, hipStream_t st) {
-    HL_REQUIRE(a.in.p && a.w && a.out.p, "conv2d: null tensor");
+    HL_REQUIRE(a.in.p && a.w.fp32() && a.out.p, "conv2d: null tensor");
     HL_REQUIRE(a.in.C % 16 == 0, "conv2d: Cin (%d) must be padded to a multiple of 16", a.in.C);
     HL_REQUIRE(a.ks == 1 || a.ks == 3, "conv2d: kernel size %d", a.ks);
     HL_REQUIRE(a.stride == 1 || (a.stride == 2 && !a.ups), "conv2d: stride/upsample combination");
@@ -3217,7 +3217,7 @@ int conv2d(const ConvArgs &a, const ConvPlan &pl, hipStream_t st) {
     ConvK p{};
     p.in = a.in.p; p.in_pitch = a.in.pitch; p.N = a.in.N; p.Hin = a.in.H; p.Win = a.in.W; p.Cin = a.in.C;
     p.Hout = a.out.H; p.Wout = a.out.W; p.ks = a.ks; p.stride = a.stride; p.ups = a.ups; p.taps = a.ks * a.ks;
-    p.w = a.w; p.w_bf3 = a.w_bf3; p.w_wino = a.w_wino; p.Ktot = (long)a.in.C * p.taps; p.bias = a.bias; p.Cout = a.Cout; p.wrows = round_up(a.Cout, 64);
+    p.w = a.w.fp32(); p.wf = a.w.p[(int)form_of(pl.path)]; p.Ktot = (long)a.in.C * p.taps; p.bias = a.bias; p.Cout = a.Cout; p.wrows = round_up(a.Cout, 64);
     p.cA = a.coefA; p.cB = a.coefB; p.act = a.act; p.gn = a.gn;
     p.st1_cg = a.st_cg > 0 ? a.st_cg : std::max(1, a.Cout / 32); p.st1_c0 = a.st_c0; p.st2_cg = a.st2_cg > 0 ? a.st2_cg : std::max(1, a.Cout / 32); p.st2_c0 = a.st2_c0;
     p.out = a.out.p; p.out_pitch = a.out.pitch; p.res = a.res; p.res_pitch = a.res_pitch;
@@ -3235,8 +3235,7 @@ int conv2d(const ConvArgs &a, const ConvPlan &pl, hipStream_t st) {
         if (a.ev_mid) hipEventRecord(a.ev_mid, st);
     }
     if (pl.path == ConvPath::Fp16x2) {
-        p.w_bf3 = a.w_h2;
-        p.wsc = conv_h2_wscale(a.w_h2, a.Cout, a.in.C, a.ks);
+        p.wsc = conv_h2_wscale(p.wf, a.Cout, a.in.C, a.ks);
         if (pl.gn_mode == 0) { p.xs_gt = a.in_stats; p.xs_hw = a.in.H * a.in.W; p.xs_max = a.in_absmax; }   // (raw input; a fused GroupNorm bounds its own output)
     }
     int rc = launch_conv(p, a, pl, st);

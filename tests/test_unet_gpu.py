@@ -494,6 +494,32 @@ def test_training_path_matches_inference_forward_and_twin():
     assert (hip - twin).abs().max() < 2e-4 * scale             # MIOpen vs the HIP kernels: different summation orders
 
 
+@pytest.mark.parametrize("mode", ["fp32", "fp32_direct"])
+def test_unet_with_3x3_resblock_skips_matches_twin(mode):
+    """ResBlocks whose skip convolution is 3x3 (the reference's use_conv=True; told apart from the shipped 1x1 by the weight's size): the packed
+    buffer is sized before the state_dict is seen, so its worst case must hold every form of the 3x3 layer."""
+    from humanliff_amd import synthetic as syn
+    from humanliff_amd.improved_diffusion.unet import ResBlock, UNetModel
+    model = UNetModel(in_channels=27, model_channels=32, out_channels=27, num_res_blocks=1, attention_resolutions=(), channel_mult=(1, 2), num_classes=4,
+                      num_heads=4, use_scale_shift_norm=True, cond_type="controlnet")
+    skips = [m for m in model.modules() if isinstance(m, ResBlock) and m.out_channels != m.channels]
+    assert skips
+    for m in skips:
+        m.skip_connection = torch.nn.Conv2d(m.channels, m.out_channels, 3, padding=1)
+    model.load_state_dict(syn.state_from_shapes([(k, tuple(v.shape)) for k, v in model.state_dict().items()], 1), strict=True)
+    model = model.to(dev).eval().set_conv_mode(mode)
+    g = torch.Generator().manual_seed(7)
+    x = torch.randn((1, 27, 16, 16), generator=g).to(dev)
+    xc = (torch.randn((1, 27, 16, 16), generator=g).clamp(-1, 1) * 0.7).to(dev)
+    t, y = torch.tensor([17], device=dev), torch.tensor([3], device=dev)
+    with torch.no_grad():
+        hip = model(x, t, xc, y=y)
+        twin = forward_autograd(model, x, t, xc, y=y)
+    scale = max(1.0, float(twin.abs().max()))
+    assert float(twin.abs().max()) > 1e-3                      # (synthetic weights: the output convolution is not zero)
+    assert (hip - twin).abs().max() < 2e-4 * scale             # the bound of test_training_path_matches_inference_forward_and_twin
+
+
 @pytest.mark.parametrize("N,C,H,W,Cout,ks,stride,ups,mode,with_gn,expect_stats", [
     (2, 64, 256, 128, 192, 3, 1, 0, 0, True, True),     # Winograd F(4x4) after the k_gn_apply pass, residual; slot = (32x16 block, round, wave)
     (2, 64, 256, 128, 192, 3, 1, 0, 3, True, True),     # Winograd F(2x2) (HL_CONV_FP32_F23); slot = (16x8 block, parity)
