@@ -50,6 +50,10 @@ class UNetCfg(C.Structure):
                 ("no_scale_shift", C.c_int)]
 
 
+class LpipsParams(C.Structure):
+    _fields_ = [("conv_w", C.c_void_p * 13), ("conv_b", C.c_void_p * 13), ("lin", C.c_void_p * 5), ("shift", C.c_float * 3), ("scale", C.c_float * 3)]
+
+
 _lib = None
 
 _p, _i, _i64, _u, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_uint, C.c_size_t
@@ -171,6 +175,10 @@ SIGNATURES = {
                                 C.c_float, _i, _p]),
     "hl_image_metrics_workspace_bytes": (_sz, [_i, _i, _i]),
     "hl_image_metrics": (_i, [_p, _p, _p, _i, _i, _i, C.c_double, _u, _p, _p, _p, _p, _sz, _p]),
+    "hl_lpips_workspace_bytes": (_sz, [_i, _i, _i]),
+    "hl_lpips_tap_shape": (_i, [_i, _i, _i, _i, C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "hl_lpips_features": (_i, [C.POINTER(LpipsParams), _p, _p, _i, _i, _i, _p, _sz, _p]),
+    "hl_lpips": (_i, [C.POINTER(LpipsParams), _p, _p, _i, _i, _i, _p, _p, _sz, _p]),
     "hl_camera_table_row": (_i, [_p, _p, _p, _p, _p]),
     "hl_ray_views_prepare": (_i, [_p, _p, _i64, _i, _i, _p, _p, _p]),
     "hl_ray_batch": (_i, [_p, _i, _p, _i, _p, _p, _p, _i64, _i, _i, _i, C.c_double, _p, C.c_uint64, C.c_uint64, _i, _p, _p, _p, _p, _p, _p,

@@ -716,6 +716,34 @@ int hl_image_metrics(const float *pred, const float *gt, const unsigned char *ma
                      unsigned char *pred_u8, unsigned char *gt_u8, hl_metrics_record *results, void *workspace, size_t workspace_bytes,
                      void *stream);
 
+/* ---- LPIPS(net='vgg', version='0.1') forward (the reference's loss_fn_vgg, recon_NeRF/lib/all_test.py) ----
+ * Contract: DESIGN.md 4f "LPIPS"; csrc/hl_lpips.hip.  Contiguous fp32, enqueue-only on `stream`, caller-owned workspace, exact fp32
+ * products.  The network: x = (in - shift) / scale per channel; torchvision VGG-16 features[0:30] (13 3 x 3 / pad 1 convolutions with
+ * bias + ReLU, widths 64 64 | 128 128 | 256 256 256 | 512 512 512 | 512 512 512, a 2 x 2 floor max-pool at each |); the taps are the
+ * last ReLU of each block (tap k is h >> k by w >> k); per tap d_k = mean_{y,x} sum_c lin_k[c] (n(f0) - n(f1))^2 with
+ * n(f) = f / (sqrt(sum_c f^2) + 1e-10), in float64 and a fixed order; the score is d_1 + ... + d_5.
+ *   params (HOST struct of DEVICE pointers): conv_w[l] is layer l's weight packed as (ceil(Cin / 16), Cout, 9, 16) - channel chunk,
+ *     output channel, tap ky * 3 + kx, channel within the chunk, zero where the channel is >= Cin (layer 0: Cin 3); conv_b[l] (Cout);
+ *     lin[k] (C_k); shift, scale: the scaling layer's constants, by value.
+ *   hl_lpips_features: the trunk of N images - in0 (B, 3, h, w) alone (in1 NULL, N = B) or followed by in1 (B, 3, h, w) (N = 2 B).  The
+ *     taps stay in the workspace as NHWC tensors (N, h_k, w_k, C_k) at the offsets hl_lpips_tap_shape gives for (N, h, w).
+ *   hl_lpips: the trunk of the 2 B images and the head; out (B, 6) float64: d_1 .. d_5 and their sum per pair.  The inputs are only read.
+ *   16 <= h, w <= 16384; workspace: hl_lpips_workspace_bytes(N, h, w) with N the number of images through the trunk (0: bad shape). */
+#define HL_LPIPS_CONVS 13
+#define HL_LPIPS_TAPS 5
+typedef struct hl_lpips_params {
+    const float *conv_w[HL_LPIPS_CONVS];
+    const float *conv_b[HL_LPIPS_CONVS];
+    const float *lin[HL_LPIPS_TAPS];
+    float shift[3], scale[3];
+} hl_lpips_params;
+size_t hl_lpips_workspace_bytes(int N, int h, int w);
+int hl_lpips_tap_shape(int N, int h, int w, int k, size_t *offset_bytes, int *hk, int *wk, int *channels);
+int hl_lpips_features(const hl_lpips_params *params, const float *in0, const float *in1, int B, int h, int w, void *workspace,
+                      size_t workspace_bytes, void *stream);
+int hl_lpips(const hl_lpips_params *params, const float *in0, const float *in1, int B, int h, int w, double *out, void *workspace,
+             size_t workspace_bytes, void *stream);
+
 /* ---- training ray batches from resident views (recon_NeRF/lib/if_nerf_data_utils.py:87-170: sample_ray_batch, split == 'train') ----
  * Contract: DESIGN.md 4g; csrc/hl_ray_batch.hip.  Contiguous device arrays unless marked h_ (host); enqueue-only on `stream`.
  *   hl_camera_table_row: HOST.  One row of the camera table (HL_CAMERA_ROW float64: inv(K) 9, R 9, T 3, the camera centre -(R^T T) 3,

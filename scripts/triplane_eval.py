@@ -10,7 +10,11 @@ optionally --test_layer_id); any other orbit needs --view_ids.  View id i is orb
 
 --views-npz loads real views: arrays ray_o_all, ray_d_all (N, R, 3), near_all, far_all (N, R), rgb_all (N, R, 3), mask_at_box_all (N, R),
 instance_idx, cloth_layer_index, pose_index, view_id (N), world_bounds (N, 2, 3) and optionally H, W; the N views must be grouped by
-instance_idx.  LPIPS is not computed (its VGG weights are not available offline); evaluate_views takes a hook for it.
+instance_idx.
+
+--lpips-weights PATH fills novel_view_lpips: PATH is a state dict of lpips.LPIPS(net='vgg') saved on a machine that has the package
+(torch.save(loss_fn_vgg.state_dict(), 'lpips_vgg.pt')); the network runs in HIP (humanliff_amd.lpips.LpipsVGG).  Without
+it the entries are NaN: no weights ship with the project.
 """
 import argparse
 import math
@@ -25,7 +29,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from humanliff_amd import synthetic as syn                                           # noqa: E402
 from humanliff_amd.SynBodyView_datasets import camera_rays                           # noqa: E402
 from humanliff_amd.recon_NeRF import Renderer                                        # noqa: E402
-from humanliff_amd.recon_NeRF.lib.all_test import evaluate_views, heldout_view_ids   # noqa: E402
+from humanliff_amd.recon_NeRF.lib.all_test import heldout_view_ids                   # noqa: E402
+from humanliff_amd.recon_NeRF.lib.lpips_views import evaluate_views_lpips           # noqa: E402
 
 
 def parse():
@@ -43,6 +48,7 @@ def parse():
     a.add_argument("--data_range", type=float, default=2.0)
     a.add_argument("--views-npz", dest="views_npz", type=str, default=None)
     a.add_argument("--seed", type=int, default=0)
+    a.add_argument("--lpips-weights", dest="lpips_weights", type=str, default=None, help="saved state dict of lpips.LPIPS(net='vgg')")
     return a.parse_args()
 
 
@@ -98,10 +104,17 @@ def main():
     torch.manual_seed(args.seed)
     humans = list(range(ni)) if args.humans is None else args.humans
     views = npz_views(args.views_npz) if args.views_npz else synthetic_views(args, humans, dev)
-    metric = evaluate_views(model, views, n_samples=args.n_samples, n_importance=args.n_importance, white_bkgd=args.white_bkgd,
-                            data_range=args.data_range, savedir=args.savedir)
+    lpips_fn = None
+    if args.lpips_weights:
+        from humanliff_amd.lpips import LpipsVGG
+        lpips_fn = LpipsVGG.from_state_dict(torch.load(args.lpips_weights, map_location="cpu"), dev)
+    # (evaluate_views_lpips is evaluate_views with the hook's device scores read back once per subject; without a hook they are the same)
+    metric = evaluate_views_lpips(model, views, lpips_fn, n_samples=args.n_samples, n_importance=args.n_importance, white_bkgd=args.white_bkgd,
+                                  data_range=args.data_range, savedir=args.savedir)
     mse, psnr, ssim = metric["novel_view_mean_human"]
-    print(f"mean over {metric['novel_view_mse'].size} views of {len(metric['all_human_names'])} subjects: mse {mse:.6f} psnr {psnr:.4f} ssim {ssim:.6f}")
+    lpips = float(np.mean(metric["novel_view_lpips"]))
+    print(f"mean over {metric['novel_view_mse'].size} views of {len(metric['all_human_names'])} subjects: mse {mse:.6f} psnr {psnr:.4f} ssim {ssim:.6f}"
+          f" lpips {lpips:.6f}")
 
 
 if __name__ == "__main__":
