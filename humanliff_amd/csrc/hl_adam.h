@@ -1,7 +1,7 @@
 // What the optimizer kernels share (hl_optim.hip, hl_fit.hip): Adam's per-element update in torch's multi-tensor op order, the host's
-// scalars for it, 16-byte accesses and the workgroup's fixed-order fp64 sum.
+// scalars for it and 16-byte accesses.  The workgroup's fixed-order fp64 sum is hl_reduce.h's.
 #pragma once
-#include "hl_common.h"
+#include "hl_reduce.h"
 
 #include <cmath>
 
@@ -40,20 +40,6 @@ __device__ __forceinline__ void adam_moments(float g, float &p, float &m, float 
 
 __device__ __forceinline__ f32x4 ld4(const float *p) { return *reinterpret_cast<const f32x4 *>(p); }
 __device__ __forceinline__ void st4(float *p, f32x4 v) { *reinterpret_cast<f32x4 *>(p) = v; }
-
-// fixed-shape tree over the workgroup's 256 fp64 values; every thread ends with the sum, and `sh` is free again on return
-__device__ __forceinline__ double block_sum(double x, double *sh) {
-    sh[threadIdx.x] = x;
-    __syncthreads();
-#pragma unroll
-    for (int s = kOptThreads / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-        __syncthreads();
-    }
-    const double tot = sh[0];
-    __syncthreads();
-    return tot;
-}
 #endif
 
 }  // namespace hl

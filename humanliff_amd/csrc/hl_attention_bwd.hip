@@ -12,6 +12,7 @@
 // Every output element is owned by one wave and summed in a fixed order: run-to-run identical bits.
 // Head sizes that are not a multiple of 32 (the tiny test networks: 8, 16) take a plain two-kernel path that materialises P and dS per head
 // in caller scratch.
+#include "hl_reduce.h"
 #include "hl_unet_kernels.h"
 
 namespace hl {
@@ -259,13 +260,13 @@ __global__ void k_attn_bwd_rows(const float *__restrict__ qkv, const float *__re
         prow[j] = s;
         mx = fmaxf(mx, s);
     }
-    for (int d = 32; d >= 1; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d));
+    mx = wave_xor_max(mx);
     float sum = 0.f;
     for (int j = lane; j < T; j += 64) { const float e = __expf(prow[j] - mx); prow[j] = e; sum += e; }
-    for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d);
+    sum = wave_xor_sum(sum);
     float D = 0.f;
     for (int c = lane; c < ch; c += 64) D = fmaf(drow[c], orow[c], D);
-    for (int d = 32; d >= 1; d >>= 1) D += __shfl_xor(D, d);
+    D = wave_xor_sum(D);
     const float inv = 1.f / sum;
     for (int j = lane; j < T; j += 64) {
         const float *vr = base + (long)j * pitch + 2 * ch;

@@ -3,8 +3,10 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
+#include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 
 #include "../../include/humanliff_hip.h"
 
@@ -27,6 +29,13 @@ inline int check_launch(const char *what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(HL_ERR_RUNTIME, "%s: %s", what, hipGetErrorString(e));
     return HL_OK;
+}
+
+// are all of these pointers 16-byte aligned (NULL counts as aligned: an absent optional tensor)
+inline bool aligned16(std::initializer_list<const void *> ps) {
+    uintptr_t u = 0;
+    for (const void *p : ps) u |= (uintptr_t)p;
+    return u % 16 == 0;
 }
 
 }  // namespace hl

@@ -81,8 +81,7 @@ extern "C" int hl_diffusion_step(int mode, const float *x, const float *eps, con
     const int x0_given = (mode >> 1) & 1, xprev_given = mode >> 2;
     mode &= 1;
     HL_REQUIRE(n_per_sample > 0 && B > 0 && T > 0, "hl_diffusion_step: bad sizes");
-    const bool vec = (n_per_sample % 4 == 0) && (((uintptr_t)x | (uintptr_t)eps | (uintptr_t)noise | (uintptr_t)sample |
-                                                   (uintptr_t)pred_xstart | (uintptr_t)log_variance) % 16 == 0);
+    const bool vec = n_per_sample % 4 == 0 && hl::aligned16({x, eps, noise, sample, pred_xstart, log_variance});
     const long work = vec ? n_per_sample / 4 : n_per_sample;
     long gx = (work + 255) / 256;
     if (gx > 1024) gx = 1024;

@@ -11,13 +11,12 @@
 // the reference's fp32 op order (file built with -ffp-contract=off); exp / log / tanh are the device's, so those terms agree with PyTorch-CPU
 // to a few ulp rather than bit for bit.  The per-sample means are accumulated in fp64 in a fixed order - per-workgroup partials into a
 // caller-provided scratch, then one fixed-order pass per sample - with no atomics, so repeated calls give bit-identical results.
-#include <initializer_list>
-
-#include "hl_common.h"
+#include "hl_reduce.h"
 
 namespace {
 
 constexpr int TPB = 256;
+static_assert(TPB == hl::kReduceThreads, "block_sum reduces a workgroup of kReduceThreads");
 constexpr long MAX_BLOCKS = 1024;     // workgroups per sample (the grid-stride loops cover the rest)
 constexpr int NCOL = 16;
 // eval table columns (include/humanliff_hip.h)
@@ -127,6 +126,7 @@ __device__ __forceinline__ float decoder_nll(float x, float mean, float logvar) 
 }
 
 struct Acc { double vb, xm, mse; };
+__device__ __forceinline__ Acc operator+(Acc a, Acc b) { return Acc{a.vb + b.vb, a.xm + b.xm, a.mse + b.mse}; }     // three sums through one tree
 
 // One element of one timestep: the selected vb term (decoder NLL at t == 0, else KL), (pred_xstart - x_start)^2, (eps_hat - noise)^2.
 struct VbElem {
@@ -160,30 +160,13 @@ struct VbElem {
     }
 };
 
-// Fixed-order block reduction of three fp64 sums (TPB = 256: a tree over LDS).
-__device__ __forceinline__ void block_reduce3(Acc a, double *__restrict__ dst) {
-    __shared__ double red[3][TPB];
-    red[0][threadIdx.x] = a.vb;
-    red[1][threadIdx.x] = a.xm;
-    red[2][threadIdx.x] = a.mse;
-    __syncthreads();
-    for (int s = TPB / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) {
-            red[0][threadIdx.x] += red[0][threadIdx.x + s];
-            red[1][threadIdx.x] += red[1][threadIdx.x + s];
-            red[2][threadIdx.x] += red[2][threadIdx.x + s];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { dst[0] = red[0][0]; dst[1] = red[1][0]; dst[2] = red[2][0]; }
-}
-
 // PRIOR: KL(q(x_T | x_0) || N(0, 1)) per element (:786-789) into the vb slot; x_t, noise, model output unused.
 template <bool VEC, bool PRIOR>
 __global__ __launch_bounds__(TPB) void k_vb_partial(const float *__restrict__ xs, const float *__restrict__ xt, const float *__restrict__ nz,
                                                      const float *__restrict__ mo, const float *__restrict__ vv, long out_stride,
                                                      const float *__restrict__ coef, const int64_t *__restrict__ t, long n, int T, int mean_type,
                                                      int var_type, int clip, double *__restrict__ partial) {
+    __shared__ Acc sh[TPB];
     const int b = blockIdx.y;
     const int64_t tb = PRIOR ? (int64_t)T - 1 : t[b];
     const bool in_range = tb >= 0 && tb < (int64_t)T;
@@ -220,31 +203,30 @@ __global__ __launch_bounds__(TPB) void k_vb_partial(const float *__restrict__ xs
                 f(xs[base + i], xt[base + i], nz[base + i], mo[mbase + i], vv ? vv[mbase + i] : 0.f, a);
         }
     }
-    block_reduce3(a, partial + ((long)b * gridDim.x + blockIdx.x) * 3);
+    a = hl::block_sum(a, sh);
+    if (threadIdx.x == 0) {
+        double *dst = partial + ((long)b * gridDim.x + blockIdx.x) * 3;
+        dst[0] = a.vb;
+        dst[1] = a.xm;
+        dst[2] = a.mse;
+    }
 }
 
 // One workgroup per sample: the sample's partials in a fixed order -> mean over n, / ln 2 for the vb term -> column j of the (B, ld) outputs.
 __global__ __launch_bounds__(TPB) void k_vb_final(const double *__restrict__ partial, long nparts, long n, float *__restrict__ vb,
                                                    float *__restrict__ xstart_mse, float *__restrict__ mse, long ld, long j) {
+    __shared__ Acc sh[TPB];
     const int b = blockIdx.x;
     Acc a{0.0, 0.0, 0.0};
     const double *p = partial + (long)b * nparts * 3;
-    for (long q = threadIdx.x; q < nparts; q += TPB) { a.vb += p[q * 3]; a.xm += p[q * 3 + 1]; a.mse += p[q * 3 + 2]; }
-    __shared__ double tot[3];
-    block_reduce3(a, tot);
-    __syncthreads();
+    for (long q = threadIdx.x; q < nparts; q += TPB) { a.vb += p[q * 3]; a.xm += p[q * 3 + 1]; a.mse += p[q * 3 + 2]; }      // (strided_sum's order, three sums at once)
+    a = hl::block_sum(a, sh);
     if (threadIdx.x == 0) {
         const double inv_n = 1.0 / (double)n, ln2 = 0.69314718055994530942;
-        vb[(long)b * ld + j] = (float)(tot[0] * inv_n / ln2);
-        if (xstart_mse) xstart_mse[(long)b * ld + j] = (float)(tot[1] * inv_n);
-        if (mse) mse[(long)b * ld + j] = (float)(tot[2] * inv_n);
+        vb[(long)b * ld + j] = (float)(a.vb * inv_n / ln2);
+        if (xstart_mse) xstart_mse[(long)b * ld + j] = (float)(a.xm * inv_n);
+        if (mse) mse[(long)b * ld + j] = (float)(a.mse * inv_n);
     }
-}
-
-bool aligned16(std::initializer_list<const void *> ps) {
-    uintptr_t u = 0;
-    for (const void *p : ps) u |= (uintptr_t)p;
-    return u % 16 == 0;
 }
 
 }  // namespace
@@ -253,7 +235,7 @@ extern "C" int hl_diffusion_q_sample(const float *x_start, const float *noise, c
                                      int64_t n_per_sample, int B, int T, void *stream) {
     HL_REQUIRE(x_start && noise && coef && t && x_t, "hl_diffusion_q_sample: null argument");
     HL_REQUIRE(n_per_sample > 0 && B > 0 && T > 0, "hl_diffusion_q_sample: bad sizes");
-    const bool vec = n_per_sample % 4 == 0 && aligned16({x_start, noise, x_t});
+    const bool vec = n_per_sample % 4 == 0 && hl::aligned16({x_start, noise, x_t});
     dim3 grid((unsigned)blocks_for(n_per_sample, vec), (unsigned)B);
     hipStream_t st = (hipStream_t)stream;
     if (vec) hipLaunchKernelGGL(k_q_sample<true>, grid, dim3(TPB), 0, st, x_start, noise, coef, t, x_t, (long)n_per_sample, T);
@@ -266,7 +248,7 @@ extern "C" int hl_diffusion_reverse_step(int mode, const float *x, const float *
     HL_REQUIRE(x && eps && coef && t && sample, "hl_diffusion_reverse_step: null argument");
     HL_REQUIRE(mode == 0 || mode == 1, "hl_diffusion_reverse_step: mode %d", mode);
     HL_REQUIRE(n_per_sample > 0 && B > 0 && T > 0, "hl_diffusion_reverse_step: bad sizes");
-    const bool vec = n_per_sample % 4 == 0 && aligned16({x, eps, sample, pred_xstart});
+    const bool vec = n_per_sample % 4 == 0 && hl::aligned16({x, eps, sample, pred_xstart});
     dim3 grid((unsigned)blocks_for(n_per_sample, vec), (unsigned)B);
     hipStream_t st = (hipStream_t)stream;
     if (vec) hipLaunchKernelGGL(k_reverse<true>, grid, dim3(TPB), 0, st, x, eps, coef, t, sample, pred_xstart, (long)n_per_sample, T, clip, mode);
@@ -290,7 +272,7 @@ extern "C" int hl_diffusion_vb_terms(int mean_type, int var_type, int clip, cons
     HL_REQUIRE(n_per_sample > 0 && B > 0 && T > 0 && out_stride >= n_per_sample, "hl_diffusion_vb_terms: bad sizes");
     HL_REQUIRE(ld > 0 && j >= 0 && j < ld, "hl_diffusion_vb_terms: column %lld outside a row of %lld", (long long)j, (long long)ld);
     HL_REQUIRE(scratch_bytes >= hl_diffusion_vb_scratch_bytes(n_per_sample, B), "hl_diffusion_vb_terms: scratch too small");
-    const bool vec = n_per_sample % 4 == 0 && out_stride % 4 == 0 && aligned16({x_start, x_t, noise, model_out, model_var});
+    const bool vec = n_per_sample % 4 == 0 && out_stride % 4 == 0 && hl::aligned16({x_start, x_t, noise, model_out, model_var});
     const long g = blocks_for(n_per_sample, vec);
     hipStream_t st = (hipStream_t)stream;
     double *partial = (double *)scratch;
@@ -309,7 +291,7 @@ extern "C" int hl_diffusion_prior_bpd(const float *x_start, const float *coef, i
     HL_REQUIRE(x_start && coef && prior_bpd && scratch, "hl_diffusion_prior_bpd: null argument");
     HL_REQUIRE(n_per_sample > 0 && B > 0 && T > 0, "hl_diffusion_prior_bpd: bad sizes");
     HL_REQUIRE(scratch_bytes >= hl_diffusion_vb_scratch_bytes(n_per_sample, B), "hl_diffusion_prior_bpd: scratch too small");
-    const bool vec = n_per_sample % 4 == 0 && aligned16({x_start});
+    const bool vec = n_per_sample % 4 == 0 && hl::aligned16({x_start});
     const long g = blocks_for(n_per_sample, vec);
     hipStream_t st = (hipStream_t)stream;
     double *partial = (double *)scratch;

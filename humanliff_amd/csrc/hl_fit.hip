@@ -28,6 +28,7 @@ constexpr int kThreads = kOptThreads;
 constexpr int64_t kChunk = HL_FIT_CHUNK;                   // elements of a slice per workgroup (k_fit_adam_planes)
 constexpr int64_t kRegChunk = HL_FIT_REG_CHUNK;            // texels of an image per workgroup (k_fit_reg)
 static_assert(kChunk % (4 * kThreads) == 0 && kRegChunk % (4 * kThreads) == 0, "a chunk is whole float4 rows of the workgroup");
+static_assert(kThreads == kReduceThreads, "block_sum / strided_sum reduce a workgroup of kReduceThreads");
 
 __device__ __forceinline__ float sgn(float d) { return d != d ? d : (float)((d > 0.f) - (d < 0.f)); }
 
@@ -104,13 +105,11 @@ __global__ __launch_bounds__(kThreads) void k_fit_reg(const float *__restrict__ 
     }
 }
 
-// one workgroup: out[k] = sum over the n workgroups of partial[3 i + k], thread t summing i = t, t + 256, ... in order, then the fixed tree
+// one workgroup: out[k] = sum over the n workgroups of partial[3 i + k] (strided_sum's order)
 __global__ __launch_bounds__(kThreads) void k_fit_reg_finish(const double *__restrict__ partial, int64_t n, double *__restrict__ out) {
     __shared__ double sh[kThreads];
     for (int k = 0; k < 3; ++k) {
-        double acc = 0.0;
-        for (int64_t i = threadIdx.x; i < n; i += kThreads) acc += partial[3 * i + k];
-        const double tot = block_sum(acc, sh);
+        const double tot = strided_sum(partial + k, n, 3, sh);
         if (threadIdx.x == 0) out[k] = tot;
     }
 }
@@ -173,8 +172,6 @@ __global__ __launch_bounds__(kThreads) void k_fit_adam_planes(PlanesArgs a, Adam
     }
 }
 
-inline bool aligned16(const void *q) { return ((uintptr_t)q & 15) == 0; }
-
 inline int64_t reg_blocks(int64_t nplanes, int H, int W) {
     if (nplanes <= 0 || H < 2 || W < 2 || (int64_t)H * W > (int64_t)0x7fffffff - kRegChunk) return -1;
     const int64_t cpp = ((int64_t)H * W + kRegChunk - 1) / kRegChunk;
@@ -205,7 +202,7 @@ int hl_fit_reg(const float *planes, float *grad, int64_t nplanes, int H, int W, 
     double *partial = static_cast<double *>(scratch);
     const hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)nb), block(kThreads);
-    if (W % 4 == 0 && aligned16(planes) && aligned16(grad))
+    if (W % 4 == 0 && aligned16({planes, grad}))
         hipLaunchKernelGGL(k_fit_reg<true>, grid, block, 0, st, planes, grad, H, W, cpp, c, partial);
     else
         hipLaunchKernelGGL(k_fit_reg<false>, grid, block, 0, st, planes, grad, H, W, cpp, c, partial);
@@ -229,7 +226,7 @@ int hl_fit_adam_planes(float *param, float *exp_avg, float *exp_avg_sq, const fl
                        clamp ? 1 : 0};
     const AdamCoef c = adam_coef(one_minus_beta1, beta2, one_minus_beta2, bc2_sqrt, eps, neg_step_size);
     const dim3 grid((unsigned)nb), block(kThreads);
-    if (slice_numel % 4 == 0 && aligned16(param) && aligned16(exp_avg) && aligned16(exp_avg_sq) && aligned16(grad))
+    if (slice_numel % 4 == 0 && aligned16({param, exp_avg, exp_avg_sq, grad}))
         hipLaunchKernelGGL(k_fit_adam_planes<true>, grid, block, 0, (hipStream_t)stream, a, c);
     else
         hipLaunchKernelGGL(k_fit_adam_planes<false>, grid, block, 0, (hipStream_t)stream, a, c);

@@ -6,12 +6,13 @@
 // The contract (signed distance, band, bounds, operator, stopping rule, corner rule, case table, ordering) is in DESIGN.md
 // ("Mesh extraction"); tests/geometry_restatement.py states it again in numpy.  Everything is fp64, the file is built with
 // -ffp-contract=off, and every reduction is integer or fixed-order, so results are bit-reproducible run to run.
-#include "hl_common.h"
+#include "hl_reduce.h"
 #include "hl_mc_table.h"
 
 namespace {
 
 constexpr int TPB = 256;
+static_assert(TPB == hl::kReduceThreads, "block_sum / strided_sum reduce a workgroup of kReduceThreads");
 constexpr int SCAN_ITEMS = 16;
 constexpr int SCAN_TILE = TPB * SCAN_ITEMS;
 constexpr int INF32 = 0x3fffffff;            // "no feature on this line yet" in the int32 squared-distance buffers
@@ -30,13 +31,8 @@ __global__ __launch_bounds__(TPB) void k_scan_reduce(F f, long n, unsigned long 
         const long i = base + (long)k * TPB + threadIdx.x;
         if (i < n) s += f(i);
     }
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = TPB / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) block_sums[blockIdx.x] = red[0];
+    s = hl::block_sum(s, red);
+    if (threadIdx.x == 0) block_sums[blockIdx.x] = s;
 }
 
 __device__ unsigned long long block_exclusive(unsigned long long v, unsigned long long *sh, unsigned long long *total) {
@@ -249,26 +245,14 @@ __global__ __launch_bounds__(TPB) void k_grad(const int *__restrict__ nbr, const
         }
     }
     if (!partial) return;
-    red[threadIdx.x] = e;
-    __syncthreads();
-    for (int w = TPB / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+    e = hl::block_sum(e, red);
+    if (threadIdx.x == 0) partial[blockIdx.x] = e;
 }
 
 __global__ __launch_bounds__(TPB) void k_energy_final(const double *__restrict__ partial, long nparts, double *__restrict__ energy) {
     __shared__ double red[TPB];
-    double e = 0.0;
-    for (long p = threadIdx.x; p < nparts; p += TPB) e += partial[p];
-    red[threadIdx.x] = e;
-    __syncthreads();
-    for (int w = TPB / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) energy[0] = 0.5 * red[0];
+    const double e = hl::strided_sum(partial, nparts, 1, red);
+    if (threadIdx.x == 0) energy[0] = 0.5 * e;
 }
 
 // (A x)_s = sum_a ( -m_a g[a][s] + sum_{band nb along a} g[a][nb] ), diag_s = sum_a (m_a^2 + m_a);

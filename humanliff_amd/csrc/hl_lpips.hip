@@ -17,14 +17,13 @@
 //   the workgroup its 4 waves in order -> one partial in a fixed slot.  No float atomics.
 // k_lpips_finish: grid (pairs).  Adds each tap's partials in a fixed order, divides by the tap's pixel count, writes the five d_k
 //   and their sum (d_1 + ... + d_5, left to right).
-#include "hl_common.h"
-
-#include <cstdint>
+#include "hl_reduce.h"
 
 namespace hl {
 namespace {
 
 constexpr int kThreads = 256;
+static_assert(kThreads == kReduceThreads, "strided_sum reduces a workgroup of kReduceThreads");
 constexpr int kTH = 8, kTW = 16;              // output pixels per workgroup (rows x columns)
 constexpr int kPH = kTH + 2, kPW = kTW + 2;   // the staged patch
 constexpr int kBN = 64;                       // output channels per workgroup
@@ -186,12 +185,6 @@ __global__ __launch_bounds__(kThreads, 2) void k_lpips_conv(const float *__restr
     }
 }
 
-__device__ __forceinline__ double wave_sum(double x) {       // xor butterfly: every lane ends with the same bits
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) x += __shfl_xor(x, s);
-    return x;
-}
-
 // f (N, hw, C) with C = 64 KC; pair b = images b and B + b
 template <int KC>
 __global__ __launch_bounds__(kThreads) void k_lpips_head(const float *__restrict__ f, int B, int64_t hw, const float *__restrict__ lin,
@@ -217,14 +210,14 @@ __global__ __launch_bounds__(kThreads) void k_lpips_head(const float *__restrict
             s0 += (double)a[t] * (double)a[t];
             s1 += (double)c[t] * (double)c[t];
         }
-        const double n0 = sqrt(wave_sum(s0)) + 1e-10, n1 = sqrt(wave_sum(s1)) + 1e-10;
+        const double n0 = sqrt(wave_xor_sum(s0)) + 1e-10, n1 = sqrt(wave_xor_sum(s1)) + 1e-10;
         double d = 0.0;
 #pragma unroll
         for (int t = 0; t < KC; ++t) {
             const double e = (double)a[t] / n0 - (double)c[t] / n1;
             d += (double)w[t] * (e * e);
         }
-        tot += wave_sum(d);
+        tot += wave_xor_sum(d);
     }
     if (lane == 0) sh[wave] = tot;
     __syncthreads();
@@ -243,17 +236,7 @@ __global__ __launch_bounds__(kThreads) void k_lpips_finish(const double *__restr
     const int tid = (int)threadIdx.x;
     double total = 0.0;
     for (int k = 0; k < kTaps; ++k) {
-        const double *src = partial + fa.off[k] + b * fa.chunks[k];
-        double acc = 0.0;
-        for (int i = tid; i < fa.chunks[k]; i += kThreads) acc += src[i];
-        sh[tid] = acc;
-        __syncthreads();
-        for (int s = kThreads / 2; s > 0; s >>= 1) {
-            if (tid < s) sh[tid] += sh[tid + s];
-            __syncthreads();
-        }
-        const double d = sh[0] / fa.hw[k];
-        __syncthreads();
+        const double d = strided_sum(partial + fa.off[k] + b * fa.chunks[k], fa.chunks[k], 1, sh) / fa.hw[k];
         total += d;
         if (tid == 0) out[b * (kTaps + 1) + k] = d;
     }

@@ -11,8 +11,8 @@
 //   sits in the image.  The 22 x 22 masked pixels it needs are staged in LDS as fp32 (exact), then per channel a row pass (7-sums of
 //   x, y, xx, yy, xy in float64) and a column pass (7-sums of those) give the 49-sums of every window; S follows skimage's
 //   expression order.  One partial of three channel sums per workgroup; a workgroup outside the crop's interior writes zeros.
-// k_metrics_ssim_finish: grid (V).  Adds the tiles' partials in a fixed order, the channels' means, their mean -> ssim of the record.
-#include "hl_common.h"
+// k_metrics_ssim_finish: grid (V).  Adds the tiles' partials in a fixed order (hl_reduce.h), the channels' means, their mean -> ssim of the record.
+#include "hl_reduce.h"
 
 #include <climits>
 #include <cmath>
@@ -27,6 +27,7 @@ constexpr int kTile = 16;                   // window origins per tile side
 constexpr int kWin = 7;                     // skimage's default win_size
 constexpr int kHalo = kTile + kWin - 1;     // 22 pixels per tile side
 static_assert(kTile * kTile == kThreads, "one thread per window origin of a tile");
+static_assert(kThreads == kReduceThreads, "block_reduce / strided_sum reduce a workgroup of kReduceThreads");
 
 struct PixPartial {
     double sse;
@@ -34,32 +35,6 @@ struct PixPartial {
 };
 static_assert(sizeof(PixPartial) == 32, "workspace layout");
 static_assert(sizeof(hl_metrics_record) == 48, "record layout (humanliff_amd/metrics.py reads it as 6 float64 / 12 int32)");
-
-// fixed-shape tree over the workgroup's 256 values; every thread ends with the result, and `sh` is free again on return
-template <class T, class Op>
-__device__ __forceinline__ T block_reduce(T x, T *sh, Op op) {
-    sh[threadIdx.x] = x;
-    __syncthreads();
-#pragma unroll
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) sh[threadIdx.x] = op(sh[threadIdx.x], sh[threadIdx.x + s]);
-        __syncthreads();
-    }
-    const T tot = sh[0];
-    __syncthreads();
-    return tot;
-}
-
-struct Add {
-    template <class T>
-    __device__ T operator()(T a, T b) const { return a + b; }
-};
-struct Min {
-    __device__ int operator()(int a, int b) const { return a < b ? a : b; }
-};
-struct Max {
-    __device__ int operator()(int a, int b) const { return a > b ? a : b; }
-};
 
 __device__ __forceinline__ unsigned char to8b(float x) {      // (255 * np.clip(x, 0, 1)).astype(np.uint8); NaN -> 0
     const float c = fminf(fmaxf(x, 0.f), 1.f);
@@ -109,8 +84,8 @@ __global__ __launch_bounds__(kThreads) void k_metrics_pixels(const float *__rest
         }
     }
     PixPartial out;
-    out.sse = block_reduce(sse, shd, Add());
-    out.count = block_reduce(count, shi, Add());
+    out.sse = block_sum(sse, shd);
+    out.count = block_sum(count, shi);
     out.x0 = block_reduce(x0, shi, Min());
     out.x1 = block_reduce(x1, shi, Max());
     out.y0 = block_reduce(y0, shi, Min());
@@ -119,25 +94,23 @@ __global__ __launch_bounds__(kThreads) void k_metrics_pixels(const float *__rest
     if (threadIdx.x == 0) partial[v * gridDim.x + blockIdx.x] = out;
 }
 
-// one workgroup per view: thread t takes partials t, t + 256, ... in order, then the fixed tree
+// one workgroup per view: thread t takes partials t, t + 256, ... in order, then the fixed tree (strided_sum for the squared error)
 __global__ __launch_bounds__(kThreads) void k_metrics_box(const PixPartial *__restrict__ partial, int chunks,
                                                           hl_metrics_record *__restrict__ rec) {
     __shared__ double shd[kThreads];
     __shared__ int shi[kThreads];
     const int64_t v = blockIdx.x;
-    double sse = 0.0;
+    const double sse = strided_sum(&partial[v * chunks].sse, chunks, sizeof(PixPartial) / sizeof(double), shd);
     int count = 0, x0 = INT_MAX, x1 = -1, y0 = INT_MAX, y1 = -1;
-    for (int i = (int)threadIdx.x; i < chunks; i += kThreads) {
+    for (int i = (int)threadIdx.x; i < chunks; i += kThreads) {      // (integers: any order gives the same result)
         const PixPartial q = partial[v * chunks + i];
-        sse += q.sse;
         count += q.count;
         x0 = q.x0 < x0 ? q.x0 : x0;
         x1 = q.x1 > x1 ? q.x1 : x1;
         y0 = q.y0 < y0 ? q.y0 : y0;
         y1 = q.y1 > y1 ? q.y1 : y1;
     }
-    sse = block_reduce(sse, shd, Add());
-    count = block_reduce(count, shi, Add());
+    count = block_sum(count, shi);
     x0 = block_reduce(x0, shi, Min());
     x1 = block_reduce(x1, shi, Max());
     y0 = block_reduce(y0, shi, Min());
@@ -225,7 +198,7 @@ __global__ __launch_bounds__(kThreads) void k_metrics_ssim(const float *__restri
         const double A1 = 2.0 * ux * uy + c1, A2 = 2.0 * vxy + c2, B1 = ux * ux + uy * uy + c1, B2 = vx + vy + c2;
         const double D = B1 * B2;
         const double S = (A1 * A2) / D;
-        const double tot = block_reduce(counted ? S : 0.0, shd, Add());      // (its barriers also free `row` for the next channel)
+        const double tot = block_sum(counted ? S : 0.0, shd);      // (its barriers also free `row` for the next channel)
         if (tid == 0) out[c] = tot;
     }
 }
@@ -237,11 +210,7 @@ __global__ __launch_bounds__(kThreads) void k_metrics_ssim_finish(const double *
     const int iw = rec[v].w - (kWin - 1), ih = rec[v].h - (kWin - 1);
     double ch[3];
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        double acc = 0.0;
-        for (int i = (int)threadIdx.x; i < tiles; i += kThreads) acc += partial[3 * (v * tiles + i) + c];
-        ch[c] = block_reduce(acc, shd, Add()) / ((double)iw * (double)ih);
-    }
+    for (int c = 0; c < 3; ++c) ch[c] = strided_sum(partial + 3 * v * tiles + c, tiles, 3, shd) / ((double)iw * (double)ih);
     // a crop smaller than the window has no interior: skimage raises, the record says NaN
     if (threadIdx.x == 0) rec[v].ssim = iw > 0 && ih > 0 ? (ch[0] + ch[1] + ch[2]) / 3.0 : NAN;
 }

@@ -28,6 +28,7 @@ namespace {
 constexpr int kThreads = kOptThreads;
 constexpr int64_t kChunk = HL_ADAMW_CHUNK;                 // elements per workgroup
 static_assert(kChunk % (4 * kThreads) == 0, "a chunk is whole float4 rows of the workgroup");
+static_assert(kThreads == kReduceThreads, "block_sum / strided_sum reduce a workgroup of kReduceThreads");
 
 struct OptTensor {            // 80 bytes, the table's first part (one per tensor)
     float *p;
@@ -147,12 +148,10 @@ __global__ __launch_bounds__(kThreads) void k_adamw_ema(const OptTensor *__restr
     if (tid == 0) partial[blockIdx.x] = tot;
 }
 
-// one workgroup: out = sum of n partials, thread i summing i, i + 256, ... in order, then the fixed tree
+// one workgroup: out = sum of n partials (strided_sum's order)
 __global__ __launch_bounds__(kThreads) void k_sum_partials(const double *__restrict__ partial, int64_t n, double *__restrict__ out) {
     __shared__ double sh[kThreads];
-    double acc = 0.0;
-    for (int64_t i = threadIdx.x; i < n; i += kThreads) acc += partial[i];
-    const double tot = block_sum(acc, sh);
+    const double tot = strided_sum(partial, n, 1, sh);
     if (threadIdx.x == 0) out[0] = tot;
 }
 

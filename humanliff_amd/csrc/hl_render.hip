@@ -25,7 +25,7 @@
 // Further down in this file: evaluate-once schedule (k_march<.., STORE> + k_composite), canonical-space deformation
 // (k_deform_rays_cull / k_deform_rays / k_deform_points, renderer.py:52-132), per-view ray generation (k_camera_rays), and the
 // training backward (k_march<.., ACTS>, k_composite_wave, k_mlp_bwd, k_plane_scatter, k_wgrad; recon_NeRF/run_nerf_batch.py:236-265).
-#include "hl_common.h"
+#include "hl_reduce.h"
 #include "hl_camera.h"
 
 #include <cstdlib>
@@ -2146,16 +2146,13 @@ __global__ __launch_bounds__(DC_WAVES * 64) void k_deform_rays_cull(const Deform
     const int V = c.V, NC = (V + 63) / 64;
     for (int i = threadIdx.x; i < NC * 64; i += DC_WAVES * 64) sv[i] = i < V ? c.verts[i] : make_float4(1.0e18f, 1.0e18f, 1.0e18f, 0.f);
     __syncthreads();
-    auto wsum = [](float v) { for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d); return v; };
-    auto wmax = [](float v) { for (int d = 32; d > 0; d >>= 1) v = fmaxf(v, __shfl_xor(v, d)); return v; };
-    auto wmin = [](float v) { for (int d = 32; d > 0; d >>= 1) v = fminf(v, __shfl_xor(v, d)); return v; };
     for (int k = wv; k < NC; k += DC_WAVES) {                        // bounding sphere of vertices 64k .. 64k+63
         const bool on = 64 * k + lane < V;
         const float4 v = sv[64 * k + lane];
-        const float n = wsum(on ? 1.f : 0.f);
-        const float cx = wsum(on ? v.x : 0.f) / n, cy = wsum(on ? v.y : 0.f) / n, cz = wsum(on ? v.z : 0.f) / n;
+        const float n = hl::wave_xor_sum(on ? 1.f : 0.f);
+        const float cx = hl::wave_xor_sum(on ? v.x : 0.f) / n, cy = hl::wave_xor_sum(on ? v.y : 0.f) / n, cz = hl::wave_xor_sum(on ? v.z : 0.f) / n;
         const float dx = v.x - cx, dy = v.y - cy, dz = v.z - cz;
-        const float r = wmax(on ? sqrtf(dx * dx + dy * dy + dz * dz) : 0.f);
+        const float r = hl::wave_xor_max(on ? sqrtf(dx * dx + dy * dy + dz * dz) : 0.f);
         if (lane == 0) scl[k] = make_float4(cx, cy, cz, r * 1.0001f + 1e-6f);
     }
     __syncthreads();
@@ -2191,8 +2188,8 @@ __global__ __launch_bounds__(DC_WAVES * 64) void k_deform_rays_cull(const Deform
         const float qy = (wx * c.R[1] + wy * c.R[4]) + wz * c.R[7];
         const float qz = (wx * c.R[2] + wy * c.R[5]) + wz * c.R[8];
         // group geometry
-        const float mx = wsum(qx) * (1.f / 64.f), my = wsum(qy) * (1.f / 64.f), mz = wsum(qz) * (1.f / 64.f);
-        const float rho = wmax(sqrtf((qx - mx) * (qx - mx) + (qy - my) * (qy - my) + (qz - mz) * (qz - mz))) * 1.0001f + 1e-6f;
+        const float mx = hl::wave_xor_sum(qx) * (1.f / 64.f), my = hl::wave_xor_sum(qy) * (1.f / 64.f), mz = hl::wave_xor_sum(qz) * (1.f / 64.f);
+        const float rho = hl::wave_xor_max(sqrtf((qx - mx) * (qx - mx) + (qy - my) * (qy - my) + (qz - mz) * (qz - mz))) * 1.0001f + 1e-6f;
         // U: m's distance to the body - one lane-parallel pass over the vertices (64 per step, loads independent of each other)
         float u2 = 3.0e38f;
 #pragma unroll 4
@@ -2200,7 +2197,7 @@ __global__ __launch_bounds__(DC_WAVES * 64) void k_deform_rays_cull(const Deform
             const float4 v = sv[64 * k + lane];
             u2 = fminf(u2, (v.x - mx) * (v.x - mx) + (v.y - my) * (v.y - my) + (v.z - mz) * (v.z - mz));
         }
-        const float lim = sqrtf(wmin(u2)) * 1.0001f + 2.f * rho + 1e-6f;     // |m - v*| <= lim for every point of the group
+        const float lim = sqrtf(hl::wave_xor_min(u2)) * 1.0001f + 2.f * rho + 1e-6f;     // |m - v*| <= lim for every point of the group
         const float lim2 = lim * lim * 1.0001f;
         // runs whose bounding sphere reaches into the ball
         unsigned long long runs[(DC_MAXV / 64 + 63) / 64];

@@ -19,6 +19,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "hl_reduce.h"
 #include "hl_stats.h"
 
 namespace hl {
@@ -2603,14 +2604,14 @@ __global__ void k_attention_generic(const float *__restrict__ qkv, int T, int C,
         sc[k] = s;
         mx = fmaxf(mx, s);
     }
-    for (int d = 32; d > 0; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d));
+    mx = wave_xor_max(mx);
     float sum = 0.f;
     for (int k = lane; k < T; k += 64) {
         const float e = __expf(sc[k] - mx);
         sc[k] = e;
         sum += e;
     }
-    for (int d = 32; d > 0; d >>= 1) sum += __shfl_xor(sum, d);
+    sum = wave_xor_sum(sum);
     __builtin_amdgcn_s_waitcnt(0);
     for (int c = lane; c < ch; c += 64) {
         float a = 0.f;
@@ -2715,13 +2716,11 @@ __global__ __launch_bounds__(256) void k_layernorm(const float *__restrict__ x, 
     const float *xp = x + pix * pitch;
     float sm = 0.f;
     for (int c = lane; c < C; c += 64) sm += xp[c];
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) sm += __shfl_xor(sm, d);
+    sm = wave_xor_sum(sm);
     const float mean = sm / (float)C;
     float sq = 0.f;
     for (int c = lane; c < C; c += 64) { const float dv = xp[c] - mean; sq = fmaf(dv, dv, sq); }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) sq += __shfl_xor(sq, d);
+    sq = wave_xor_sum(sq);
     const float rstd = 1.f / sqrtf(sq / (float)C + 1e-5f);
     for (int c = lane; c < C; c += 64) y[pix * C + c] = fmaf((xp[c] - mean) * rstd, gamma[c], beta[c]);
 }

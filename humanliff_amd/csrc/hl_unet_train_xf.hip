@@ -7,6 +7,7 @@
 // Every kernel here is enqueue-only (no host syncs, no allocations: scratch comes from the caller) and sums in a fixed order without
 // float atomics, so a training step gives the same bits run to run.  Contracts: include/humanliff_hip.h; the autograd.Functions that use
 // them: humanliff_amd/improved_diffusion/unet_train.py.
+#include "hl_reduce.h"
 #include "hl_unet_kernels.h"
 
 namespace hl {
@@ -129,13 +130,11 @@ __global__ __launch_bounds__(256) void k_ln_fwd(const float *__restrict__ x, lon
     const float *xp = x + pix * C;
     float sm = 0.f;
     for (int c = lane; c < C; c += 64) sm += xp[c];
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) sm += __shfl_xor(sm, d);
+    sm = wave_xor_sum(sm);
     const float mean = sm / (float)C;
     float sq = 0.f;
     for (int c = lane; c < C; c += 64) { const float dv = xp[c] - mean; sq = fmaf(dv, dv, sq); }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) sq += __shfl_xor(sq, d);
+    sq = wave_xor_sum(sq);
     const float rstd = 1.f / sqrtf(sq / (float)C + eps);
     for (int c = lane; c < C; c += 64) y[pix * C + c] = fmaf((xp[c] - mean) * rstd, gamma[c], beta[c]);
     if (lane == 0) { stat[pix * 2] = mean; stat[pix * 2 + 1] = rstd; }
@@ -155,8 +154,8 @@ __global__ __launch_bounds__(256) void k_ln_bwd_dx(const float *__restrict__ x, 
         a += gd;
         b = fmaf(gd, xh, b);
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) { a += __shfl_xor(a, d); b += __shfl_xor(b, d); }
+    a = wave_xor_sum(a);
+    b = wave_xor_sum(b);
     const float ma = a / (float)C, mb = b / (float)C;
     for (int c = lane; c < C; c += 64) {
         const float gd = dp[c] * gamma[c], xh = (xp[c] - mean) * rstd;
