@@ -118,6 +118,9 @@ SIGNATURES = {
     "hl_diffusion_vb_scratch_bytes": (_sz, [_i64, _i]),
     "hl_diffusion_vb_terms": (_i, [_i, _i, _i, _p, _p, _p, _p, _p, _i64, _p, _p, _i64, _i, _i, _p, _p, _p, _i64, _i64, _p, _sz, _p]),
     "hl_diffusion_prior_bpd": (_i, [_p, _p, _i64, _i, _i, _p, _p, _sz, _p]),
+    "hl_conv2d_scratch_bytes": (_sz, [_i] * 10),
+    "hl_conv2d_gn_scratch_bytes": (_sz, [_i] * 10),
+    "hl_conv2d_bwd_data_scratch_bytes": (_sz, [_i] * 11),
     "hl_conv2d_nhwc": (_i, [_p, _i, _i, _i, _i, _p, _p, _i, _i, _i, _i, _p, _p, _i, _p, _p, _p, _sz, _p]),
     "hl_conv2d_nhwc_mode": (_i, [_i, _p, _i, _i, _i, _i, _p, _p, _i, _i, _i, _i, _p, _p, _i, _p, _p, _p, _sz, _p]),
     "hl_conv2d_nhwc_gn": (_i, [_i, _p, _i, _i, _i, _i, _p, _p, _i, _i, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p, _p, C.POINTER(C.c_int), _p, _sz, _p]),
@@ -129,10 +132,13 @@ SIGNATURES = {
     "hl_gn_backward_scratch_bytes": (_sz, [_i, _i, _i]),
     "hl_gn_backward_reduce": (_i, [_p, _i64, _p, _i, _i, _i, _p, _p, _i, _p, _p, _sz, _p]),
     "hl_gn_backward_apply": (_i, [_p, _i64, _p, _i, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p, _p]),
+    "hl_groupnorm_scratch_bytes": (_sz, [_i]),
+    "hl_groupnorm_train_backward_scratch_bytes": (_sz, [_i, _i, _i]),
     "hl_groupnorm_train_forward": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _i, _p, _p, _p, _p, _p, _sz, _p]),
     "hl_groupnorm_train_backward": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "hl_upsample2_backward_nhwc": (_i, [_p, _i, _i, _i, _i, _p, _p]),
     "hl_zero_stuff2_nhwc": (_i, [_p, _i, _i, _i, _i, _p, _p]),
+    "hl_triplane_agg_backward_scratch_bytes": (_sz, [_i, _i, _i, _i]),
     "hl_triplane_agg_forward": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p]),
     "hl_triplane_agg_backward": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _sz, _p]),
     "hl_layernorm_train_forward": (_i, [_p, _i64, _i, _p, _p, C.c_float, _p, _p, _p]),

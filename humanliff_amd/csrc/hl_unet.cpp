@@ -993,6 +993,70 @@ int hl_unet_profile_dominant(void *handle, double *h_vals, int *h_key) {
 }
 
 // ---- single ops for tests ------------------------------------------------------------------------
+static size_t up256(size_t b) { return (b + 255) / 256 * 256; }
+
+static void conv_out_hw(int H, int W, int ks, int stride, int upsample, int *Ho, int *Wo) {
+    const int pad = ks / 2, Hv = upsample ? 2 * H : H, Wv = upsample ? 2 * W : W;
+    *Ho = (Hv + 2 * pad - ks) / stride + 1; *Wo = (Wv + 2 * pad - ks) / stride + 1;
+}
+
+// What plan_conv reads of a single-op layer: the geometry, the forms it may choose from and which rooms exist.  It asks only whether a
+// pointer is there, so they all point at `at` (the queries have no buffer; conv2d_single puts the real ones in afterwards), and it plans
+// with the conv_splitk_ws_bytes() every layer has inside hl_unet_forward.
+static void single_conv_plan_args(ConvArgs &a, float *at, int mode, unsigned forms, int N, int H, int W, int Cin, int Cout, int ks, int stride,
+                                  int upsample, bool with_gn) {
+    a.in.N = N; a.in.H = H; a.in.W = W; a.in.C = Cin; a.in.pitch = Cin;
+    a.Cout = Cout; a.ks = ks; a.stride = stride; a.ups = upsample; a.mode = mode;
+    a.out.N = N; conv_out_hw(H, W, ks, stride, upsample, &a.out.H, &a.out.W); a.out.C = Cout;
+    for (int f = 0; f < hl::kWeightForms; ++f) a.w.p[f] = forms >> f & 1u ? at : nullptr;
+    a.coefA = with_gn ? at : nullptr;
+    a.act_ws = with_gn ? at : nullptr;
+    a.act_ws_bytes = with_gn ? (size_t)N * H * W * Cin * sizeof(float) : 0;
+    a.splitk_ws = at;
+    a.splitk_ws_bytes = hl::conv_splitk_ws_bytes();
+}
+static size_t splitk_slab_bytes(const ConvArgs &a, const hl::ConvPlan &pl) {
+    return pl.splits > 1 ? (size_t)pl.splits * a.out.N * a.out.H * a.out.W * a.Cout * sizeof(float) : 0;
+}
+
+// The scratch of one single-op convolution, stated once: the size queries and conv2d_single's carve both read it.  Byte offsets of the
+// regions, each rounded to 256: the fp32 weight form at 0 | the largest other form the mode allows (only the one the plan reads is
+// packed) | the materialised GroupNorm input (exactly when coefA is given) | per-image totals / abs-max of a raw fp16x2 input | the
+// split-K slabs.  The plan is always made with the network's split-K room, so a single-op call takes the plan hl_unet_forward takes for
+// the layer whatever the caller allocated; the region holds the slabs that plan writes (splits x M x Cout floats, the bound split_k
+// itself cuts by), not the network's whole 64 MiB: the calls are made layer by layer with a fresh buffer each.  A GroupNorm in front can
+// change the kernel family and with it the slabs, so a forward layer gets the larger of the two: with_gn adds the GroupNorm input, nothing else.
+// Arguments no call accepts give a size of 0.
+struct SingleConvRoom {
+    size_t form, act, tot, splitk, total;
+    unsigned forms;   // the forms the layer has under the mode
+};
+static SingleConvRoom single_conv_room(int mode, int tf, int N, int H, int W, int Cin, int Cout, int ks, int stride, int upsample, bool with_gn) {
+    SingleConvRoom r{};
+    if (!conv_mode_known(mode) || N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cin % 16 || Cout <= 0 || (ks != 1 && ks != 3) || (stride != 1 && stride != 2))
+        return r;
+    r.forms = conv_forms(mode, true, tf != 0);
+    size_t extra = 0;
+    for (int f = 1; f < hl::kWeightForms; ++f) {
+        const size_t b = r.forms >> f & 1u ? hl::conv_form_bytes((WeightForm)f, Cout, Cin, ks, false) : 0;
+        if (!b) r.forms &= ~(1u << f);   // (the layer has no such form)
+        extra = std::max(extra, b);
+    }
+    r.form = up256(hl::conv_form_bytes(WeightForm::Fp32, Cout, Cin, ks));
+    r.act = r.form + up256(extra);
+    r.tot = r.act + (with_gn ? up256((size_t)N * H * W * Cin * sizeof(float)) : 0);
+    r.splitk = r.tot + up256(hl::conv_stats_floats(N, (long)H * W) * sizeof(float));
+    static float at;
+    size_t slabs = 0;
+    for (int gn = 0; gn <= (tf ? 0 : 1); ++gn) {      // (backward-data has no GroupNorm in front)
+        ConvArgs a{};
+        single_conv_plan_args(a, &at, mode, r.forms, N, H, W, Cin, Cout, ks, stride, upsample, gn != 0);
+        slabs = std::max(slabs, splitk_slab_bytes(a, hl::plan_conv(a)));
+    }
+    r.total = r.splitk + up256(slabs);
+    return r;
+}
+
 // One convolution through the kernels of the network.  Cin = channels of `in` (multiple of 16); the weight tensor covers
 // Cin_w <= Cin of them (the rest are zero-padded channels with zero weights).  tf = 1: `w` is laid out (Cin_w, Cout, ks, ks) and is
 // read flipped and channel-transposed - the backward-data convolution of the training path.  Only the weight layout the chosen
@@ -1006,54 +1070,34 @@ static int conv2d_single(int mode, const float *in, int N, int H, int W, int Cin
     if (Cin_w < 0) Cin_w = Cin;
     HL_REQUIRE(Cin_w <= Cin, "hl_conv2d_nhwc: the weight has more input channels than the tensor");
     hipStream_t st = (hipStream_t)stream;
-    const size_t need32 = (hl::conv_form_bytes(WeightForm::Fp32, Cout, Cin, ks) + 255) / 256 * 256;
-    // the second weight layout: room for the largest form the mode allows (only the one the plan reads is packed)
-    unsigned forms = conv_forms(mode, true, tf != 0);
-    size_t extra = 0;
-    for (int f = 1; f < hl::kWeightForms; ++f) {
-        const size_t b = forms >> f & 1u ? hl::conv_form_bytes((WeightForm)f, Cout, Cin, ks, false) : 0;
-        if (!b) forms &= ~(1u << f);   // (the layer has no such form)
-        extra = std::max(extra, b);
-    }
-    const size_t need = need32 + (extra + 255) / 256 * 256;
-    HL_REQUIRE(scratch && scratch_bytes >= need, "hl_conv2d_nhwc: scratch too small (%zu < %zu)", scratch_bytes, need);
+    const SingleConvRoom room = single_conv_room(mode, tf, N, H, W, Cin, Cout, ks, stride, upsample, coefA != nullptr);
+    HL_REQUIRE(room.total, "hl_conv2d_nhwc: bad argument (mode %d, N %d, H %d, W %d, Cin %d, Cout %d, ks %d, stride %d)", mode, N, H, W, Cin, Cout, ks, stride);
+    HL_REQUIRE(scratch && scratch_bytes >= room.total, "hl_conv2d_nhwc: scratch too small (%zu bytes, hl_conv2d_scratch_bytes says %zu)",
+               scratch_bytes, room.total);
+    char *sc = static_cast<char *>(scratch);
+    void *extra_dst = sc + room.form;
     ConvArgs a{};
-    void *extra_dst = static_cast<char *>(scratch) + need32;
-    a.in.p = const_cast<float *>(in); a.in.N = N; a.in.H = H; a.in.W = W; a.in.C = Cin; a.in.pitch = Cin;
-    a.bias = bias; a.Cout = Cout; a.ks = ks; a.stride = stride; a.ups = upsample; a.mode = mode;
+    single_conv_plan_args(a, static_cast<float *>(scratch), mode, room.forms, N, H, W, Cin, Cout, ks, stride, upsample, coefA != nullptr);
     // every form the layer has under the mode points at that room, for plan_conv to choose from
-    for (int f = 0; f < hl::kWeightForms; ++f) a.w.p[f] = f == 0 ? scratch : (forms >> f & 1u ? extra_dst : nullptr);
+    for (int f = 1; f < hl::kWeightForms; ++f) if (a.w.p[f]) a.w.p[f] = extra_dst;
+    if (coefA) a.act_ws = reinterpret_cast<float *>(sc + room.act);      // the materialised GroupNorm input (DMA path)
+    a.splitk_ws = reinterpret_cast<float *>(sc + room.splitk);
+    a.in.p = const_cast<float *>(in); a.bias = bias;
     a.coefA = coefA; a.coefB = coefB; a.act = silu;
-    const int pad = ks / 2, Hv = upsample ? 2 * H : H, Wv = upsample ? 2 * W : W;
-    a.out.p = out; a.out.N = N; a.out.H = (Hv + 2 * pad - ks) / stride + 1; a.out.W = (Wv + 2 * pad - ks) / stride + 1;
-    a.out.C = Cout; a.out.pitch = out_pitch ? out_pitch : Cout;
+    a.out.p = out; a.out.pitch = out_pitch ? out_pitch : Cout;
     a.res = residual; a.res_pitch = Cout;
-    // whatever scratch is left after the packed weights serves split-K (small-M shapes)
-    size_t used = (need + 255) / 256 * 256;
-    const size_t act_bytes = coefA ? (size_t)N * H * W * Cin * sizeof(float) : 0;
-    if (act_bytes && scratch_bytes >= used + act_bytes) {      // room for the materialised GroupNorm input (DMA path)
-        a.act_ws = reinterpret_cast<float *>(static_cast<char *>(scratch) + used);
-        a.act_ws_bytes = act_bytes;
-        used += (act_bytes + 255) / 256 * 256;
-    }
-    float *tot_room = nullptr;
-    {
-        const size_t tb = (hl::conv_stats_floats(N, (long)H * W) * sizeof(float) + 255) / 256 * 256;
-        if (scratch_bytes >= used + tb) { tot_room = reinterpret_cast<float *>(static_cast<char *>(scratch) + used); used += tb; }
-    }
-    if (scratch_bytes > used + (1u << 20)) {
-        a.splitk_ws = reinterpret_cast<float *>(static_cast<char *>(scratch) + used);
-        a.splitk_ws_bytes = scratch_bytes - used;
-    }
+    float *tot_room = reinterpret_cast<float *>(sc + room.tot);
     a.stats = stats;
     if (stats) HL_HIP(hipMemsetAsync(stats, 0, hl::conv_stats_floats(N, (long)a.out.H * a.out.W) * sizeof(float), st));   // the epilogues ADD to the totals
     const hl::ConvPlan pl = hl::plan_conv(a);
+    // (no tensor changes a split; a test switch of the dispatch flipped between the query and the call can: refused, never an overrun)
+    HL_REQUIRE(room.splitk + splitk_slab_bytes(a, pl) <= room.total, "hl_conv2d_nhwc: the plan splits K further than hl_conv2d_scratch_bytes planned");
     // the room holds that form only: no kernel argument points at the others
     const WeightForm form = hl::form_of(pl.path);
     a.w = a.w.only(hl::form_bit(WeightForm::Fp32) | hl::form_bit(form));
     int rc = hl::conv_pack_form(form, w_oihw, Cout, Cin_w, Cin, ks, form == WeightForm::Fp32 ? scratch : extra_dst, st, tf, mode == HL_CONV_FP16);
     if (rc) return rc;
-    if (pl.path == hl::ConvPath::Fp16x2 && !coefA && tot_room) {   // fp16x2 products on a raw input: the largest |x| of every image fixes the power-of-two scale of the activation planes
+    if (pl.path == hl::ConvPath::Fp16x2 && !coefA) {   // fp16x2 products on a raw input: the largest |x| of every image fixes the power-of-two scale of the activation planes
         // (in the network the producers' sum x^2 bounds it; here one pass over the tensor - exact at any magnitude, which the backward-data calls need: gradients are 1e-4 ... 1e-9)
         if (g_single_op_scale_from_totals) {      // (test switch: the network's scale source - the group totals - on a single layer)
             rc = hl::tensor_totals(a.in, tot_room, st);
@@ -1069,32 +1113,65 @@ static int conv2d_single(int mode, const float *in, int N, int H, int W, int Cin
     return hl::conv2d(a, pl, st);
 }
 
+size_t hl_conv2d_scratch_bytes(int conv_mode, int N, int H, int W, int Cin, int Cout, int ks, int stride, int upsample, int with_gn) {
+    return single_conv_room(conv_mode, 0, N, H, W, Cin, Cout, ks, stride, upsample, with_gn != 0).total;
+}
+
+// What hl_conv2d_nhwc_gn puts in front: the totals of the output and the scratch of a GroupNorm pass over it.
+struct GnPrefix { size_t gn, conv; };   // byte offsets of the GroupNorm scratch and of the convolution's room (the totals sit at 0)
+static GnPrefix conv_gn_prefix(int N, int H, int W, int ks, int stride, int upsample) {
+    int Ho, Wo;
+    conv_out_hw(H, W, ks, stride, upsample, &Ho, &Wo);
+    GnPrefix p;
+    p.gn = up256(hl::conv_stats_floats(N, (long)Ho * Wo) * sizeof(float));
+    p.conv = p.gn + up256(hl::gn_scratch_floats(N) * sizeof(float));
+    return p;
+}
+
+size_t hl_conv2d_gn_scratch_bytes(int conv_mode, int N, int H, int W, int Cin, int Cout, int ks, int stride, int upsample, int with_gn) {
+    const size_t conv = hl_conv2d_scratch_bytes(conv_mode, N, H, W, Cin, Cout, ks, stride, upsample, with_gn);
+    return conv ? conv_gn_prefix(N, H, W, ks, stride, upsample).conv + conv : 0;
+}
+
+// What hl_conv2d_nhwc_bwd_data puts in front: the zero-stuffed (stride 2) or upsampled (nearest x2) gradient.
+static size_t bwd_data_prefix(int N, int Ho, int Wo, int Cy, int stride, int upsample, int Cx) {
+    return stride == 2 ? up256((size_t)N * 4 * Ho * Wo * Cy * sizeof(float)) : upsample ? up256((size_t)N * Ho * Wo * Cx * sizeof(float)) : 0;
+}
+
+size_t hl_conv2d_bwd_data_scratch_bytes(int conv_mode, int N, int Ho, int Wo, int Cy, int Cout, int Cin, int ks, int stride, int upsample, int Cx) {
+    (void)Cout;   // (the weight's output channels: the convolution reads all Cy of the gradient)
+    const int s = stride == 2 ? 2 : 1;   // the convolution runs on the zero-stuffed grid
+    const size_t conv = Cx > 0 && (stride == 1 || stride == 2) ? single_conv_room(conv_mode, 1, N, s * Ho, s * Wo, Cy, Cin, ks, 1, 0, false).total : 0;
+    return conv ? bwd_data_prefix(N, Ho, Wo, Cy, stride, upsample, Cx) + conv : 0;
+}
+
 int hl_conv2d_nhwc_bwd_data(int conv_mode, const float *dy, int N, int Ho, int Wo, int Cy, const float *w_oihw, int Cout, int Cin, int ks,
                             int stride, int upsample, float *dx, int Cx, void *scratch, size_t scratch_bytes, void *stream) {
     HL_REQUIRE(conv_mode_known(conv_mode) && conv_mode != HL_CONV_BF16X3 && conv_mode != HL_CONV_FP32_MFMA, "hl_conv2d_nhwc_bwd_data: mode %d", conv_mode);   // (the training path's modes)
     HL_REQUIRE(dy && w_oihw && dx && scratch, "hl_conv2d_nhwc_bwd_data: null argument");
-    HL_REQUIRE(Cy % 16 == 0 && Cout <= Cy && Cin <= Cx && (ks == 1 || ks == 3) && (stride == 1 || (stride == 2 && !upsample && ks == 3)),
-               "hl_conv2d_nhwc_bwd_data: bad argument");
+    HL_REQUIRE(Cy % 16 == 0 && Cout <= Cy && Cin <= Cx && (ks == 1 || ks == 3) && (stride == 1 || (stride == 2 && !upsample && ks == 3)) &&
+               (!upsample || Cx % 4 == 0), "hl_conv2d_nhwc_bwd_data: bad argument");
+    const size_t need = hl_conv2d_bwd_data_scratch_bytes(conv_mode, N, Ho, Wo, Cy, Cout, Cin, ks, stride, upsample, Cx);
+    HL_REQUIRE(need, "hl_conv2d_nhwc_bwd_data: bad argument");
+    HL_REQUIRE(scratch_bytes >= need, "hl_conv2d_nhwc_bwd_data: scratch too small (%zu bytes, hl_conv2d_bwd_data_scratch_bytes says %zu)",
+               scratch_bytes, need);
     // d input = convolution of d output with W'[ci][co][ky][kx] = W[co][ci][ks-1-ky][ks-1-kx]  (packed straight from w, tf = 1);
     // stride 2: on the zero-stuffed gradient; nearest-x2 upsample in front of the conv: the 2x2 blocks of the result are summed
     hipStream_t st = (hipStream_t)stream;
     char *sc = static_cast<char *>(scratch);
+    const size_t pre = bwd_data_prefix(N, Ho, Wo, Cy, stride, upsample, Cx);
     int rc;
     if (stride == 2) {
-        const size_t zb = ((size_t)N * 4 * Ho * Wo * Cy * sizeof(float) + 255) / 256 * 256;
-        HL_REQUIRE(scratch_bytes > zb, "hl_conv2d_nhwc_bwd_data: scratch too small");
         float *z = reinterpret_cast<float *>(sc);
         rc = hl_zero_stuff2_nhwc(dy, N, Ho, Wo, Cy, z, stream);
         if (rc) return rc;
-        return conv2d_single(conv_mode, z, N, 2 * Ho, 2 * Wo, Cy, w_oihw, nullptr, Cin, ks, 1, 0, nullptr, nullptr, 0, nullptr, dx, sc + zb,
-                             scratch_bytes - zb, stream, nullptr, nullptr, 1, Cout, Cx);
+        return conv2d_single(conv_mode, z, N, 2 * Ho, 2 * Wo, Cy, w_oihw, nullptr, Cin, ks, 1, 0, nullptr, nullptr, 0, nullptr, dx, sc + pre,
+                             scratch_bytes - pre, stream, nullptr, nullptr, 1, Cout, Cx);
     }
     if (upsample) {      // dy lives on the (2H, 2W) grid = (Ho, Wo); dx on (Ho/2, Wo/2)
-        const size_t ub = ((size_t)N * Ho * Wo * Cx * sizeof(float) + 255) / 256 * 256;
-        HL_REQUIRE(scratch_bytes > ub && Cx % 4 == 0, "hl_conv2d_nhwc_bwd_data: scratch too small");
         float *du = reinterpret_cast<float *>(sc);
-        if (Cx != Cin) HL_HIP(hipMemsetAsync(du, 0, ub, st));
-        rc = conv2d_single(conv_mode, dy, N, Ho, Wo, Cy, w_oihw, nullptr, Cin, ks, 1, 0, nullptr, nullptr, 0, nullptr, du, sc + ub, scratch_bytes - ub,
+        if (Cx != Cin) HL_HIP(hipMemsetAsync(du, 0, pre, st));
+        rc = conv2d_single(conv_mode, dy, N, Ho, Wo, Cy, w_oihw, nullptr, Cin, ks, 1, 0, nullptr, nullptr, 0, nullptr, du, sc + pre, scratch_bytes - pre,
                            stream, nullptr, nullptr, 1, Cout, Cx);
         if (rc) return rc;
         return hl_upsample2_backward_nhwc(du, N, Ho / 2, Wo / 2, Cx, dx, stream);
@@ -1109,18 +1186,17 @@ int hl_conv2d_nhwc_gn(int conv_mode, const float *in, int N, int H, int W, int C
                       void *scratch, size_t scratch_bytes, void *stream) {
     HL_REQUIRE(conv_mode_known(conv_mode), "hl_conv2d_nhwc_gn: unknown mode %d", conv_mode);
     HL_REQUIRE(gamma && beta && next_coefA && next_coefB && scratch, "hl_conv2d_nhwc_gn: null argument");
-    const int pad = ks / 2, Hv = upsample ? 2 * H : H, Wv = upsample ? 2 * W : W;
-    const int Ho = (Hv + 2 * pad - ks) / stride + 1, Wo = (Wv + 2 * pad - ks) / stride + 1;
-    const size_t stf = (hl::conv_stats_floats(N, (long)Ho * Wo) * sizeof(float) + 255) / 256 * 256;
-    const size_t gnf = (hl::gn_scratch_floats(N) * sizeof(float) + 255) / 256 * 256;
-    HL_REQUIRE(scratch_bytes > stf + gnf, "hl_conv2d_nhwc_gn: scratch too small");
+    const size_t need = hl_conv2d_gn_scratch_bytes(conv_mode, N, H, W, Cin, Cout, ks, stride, upsample, coefA != nullptr);
+    HL_REQUIRE(need, "hl_conv2d_nhwc_gn: bad argument");
+    HL_REQUIRE(scratch_bytes >= need, "hl_conv2d_nhwc_gn: scratch too small (%zu bytes, hl_conv2d_gn_scratch_bytes says %zu)", scratch_bytes, need);
+    const GnPrefix pre = conv_gn_prefix(N, H, W, ks, stride, upsample);
     float *stats = static_cast<float *>(scratch);
-    float *gn_scr = reinterpret_cast<float *>(static_cast<char *>(scratch) + stf);
+    float *gn_scr = reinterpret_cast<float *>(static_cast<char *>(scratch) + pre.gn);
     int slots = 0;
     int rc = conv2d_single(conv_mode, in, N, H, W, Cin, w_oihw, bias, Cout, ks, stride, upsample, coefA, coefB, silu, residual, out,
-                           static_cast<char *>(scratch) + stf + gnf, scratch_bytes - stf - gnf, stream, stats, &slots);
+                           static_cast<char *>(scratch) + pre.conv, scratch_bytes - pre.conv, stream, stats, &slots);
     if (rc) return rc;
-    View v; v.p = out; v.N = N; v.H = Ho; v.W = Wo; v.C = Cout; v.pitch = Cout;
+    View v; v.p = out; v.N = N; conv_out_hw(H, W, ks, stride, upsample, &v.H, &v.W); v.C = Cout; v.pitch = Cout;
     if (h_used_stats) *h_used_stats = slots;
     if (slots > 0) {
         return hl::groupnorm_coef_stats(v, stats, gamma, beta, nullptr, 0, next_coefA, next_coefB, (hipStream_t)stream);
@@ -1131,8 +1207,7 @@ int hl_conv2d_nhwc_gn(int conv_mode, const float *in, int N, int H, int W, int C
 int hl_conv2d_nhwc(const float *in, int N, int H, int W, int Cin, const float *w_oihw, const float *bias, int Cout, int ks,
                    int stride, int upsample, const float *coefA, const float *coefB, int silu, const float *residual,
                    float *out, void *scratch, size_t scratch_bytes, void *stream) {
-    // (plain entry point: direct convolution only, so the scratch contract of round 1 - packed weights + optional split-K /
-    // activation room - is unchanged; hl_conv2d_nhwc_mode(HL_CONV_FP32, ...) adds the Winograd copy)
+    // (plain entry point: direct convolution only; hl_conv2d_nhwc_mode(HL_CONV_FP32, ...) adds the Winograd copy)
     return conv2d_single(HL_CONV_FP32_DIRECT, in, N, H, W, Cin, w_oihw, bias, Cout, ks, stride, upsample, coefA, coefB, silu, residual, out,
                          scratch, scratch_bytes, stream);
 }
@@ -1148,9 +1223,12 @@ int hl_conv2d_nhwc_mode(int conv_mode, const float *in, int N, int H, int W, int
 int hl_debug_set_h16_min_blocks(long v) { hl::set_h16_min_blocks(v); return HL_OK; }
 int hl_debug_set_single_op_scale_source(int from_totals) { g_single_op_scale_from_totals = from_totals != 0; return HL_OK; }
 
+size_t hl_groupnorm_scratch_bytes(int N) { return hl::gn_scratch_floats(N) * sizeof(float); }
+
 int hl_groupnorm_coef(const float *x, int N, int H, int W, int C, const float *gamma, const float *beta, const float *emb,
                       float *coefA, float *coefB, void *scratch, size_t scratch_bytes, void *stream) {
-    HL_REQUIRE(scratch && scratch_bytes >= hl::gn_scratch_floats(N) * sizeof(float), "hl_groupnorm_coef: scratch too small");
+    HL_REQUIRE(scratch && scratch_bytes >= hl_groupnorm_scratch_bytes(N), "hl_groupnorm_coef: scratch too small (%zu bytes, hl_groupnorm_scratch_bytes says %zu)",
+               scratch_bytes, hl_groupnorm_scratch_bytes(N));
     View v; v.p = const_cast<float *>(x); v.N = N; v.H = H; v.W = W; v.C = C; v.pitch = C;
     return hl::groupnorm_coef(v, gamma, beta, emb, 2L * C, coefA, coefB, static_cast<float *>(scratch), (hipStream_t)stream);
 }

@@ -759,22 +759,25 @@ int hl_gn_backward_apply(const float *x, long x_pitch, const float *dout, int N,
 int hl_groupnorm_train_forward(const float *x, int N, int H, int W, int C, const float *gamma, const float *beta, const float *scale_shift,
                                int silu, float *coefA, float *coefB, float *gstat, float *y, void *scratch, size_t scratch_bytes, void *stream) {
     HL_REQUIRE(x && gamma && beta && coefA && coefB && gstat && y, "hl_groupnorm_train_forward: null argument");
-    HL_REQUIRE(scratch && scratch_bytes >= gn_scratch_floats(N) * sizeof(float), "hl_groupnorm_train_forward: scratch too small");
+    HL_REQUIRE(scratch && scratch_bytes >= hl_groupnorm_scratch_bytes(N), "hl_groupnorm_train_forward: scratch too small (%zu bytes, hl_groupnorm_scratch_bytes says %zu)",
+               scratch_bytes, hl_groupnorm_scratch_bytes(N));
     View v; v.p = const_cast<float *>(x); v.N = N; v.H = H; v.W = W; v.C = C; v.pitch = C;
     int rc = groupnorm_coef(v, gamma, beta, scale_shift, 2L * C, coefA, coefB, static_cast<float *>(scratch), (hipStream_t)stream, gstat);
     if (rc) return rc;
     return gn_apply(v, coefA, coefB, silu, y, (hipStream_t)stream);
 }
 
+// S (N,C,2) and k1 / k2 / k3 (N,C each), then the partial sums of hl_gn_backward_reduce
+size_t hl_groupnorm_train_backward_scratch_bytes(int N, int HW, int C) { return (size_t)N * C * 5 * sizeof(float) + hl_gn_backward_scratch_bytes(N, HW, C); }
+
 int hl_groupnorm_train_backward(const float *x, const float *dout, int N, int H, int W, int C, const float *coefA, const float *coefB, int silu,
                                 const float *gstat, const float *gamma, const float *beta, const float *scale_shift, float *dx,
                                 float *dgamma, float *dbeta, float *dscale_shift, void *scratch, size_t scratch_bytes, void *stream) {
     HL_REQUIRE(x && dout && coefA && coefB && gstat && gamma && beta && dgamma && dbeta, "hl_groupnorm_train_backward: null argument");
     HL_REQUIRE(C % 32 == 0 && (scale_shift == nullptr) == (dscale_shift == nullptr), "hl_groupnorm_train_backward: bad argument");
-    const size_t part_bytes = hl_gn_backward_scratch_bytes(N, H * W, C);
-    HL_REQUIRE(scratch && scratch_bytes >= (size_t)N * C * 5 * sizeof(float) + part_bytes,
-               "hl_groupnorm_train_backward: scratch too small (%zu bytes; N*C*5 floats + hl_gn_backward_scratch_bytes = %zu)", scratch_bytes,
-               (size_t)N * C * 5 * sizeof(float) + part_bytes);
+    const size_t part_bytes = hl_gn_backward_scratch_bytes(N, H * W, C), need = hl_groupnorm_train_backward_scratch_bytes(N, H * W, C);
+    HL_REQUIRE(scratch && scratch_bytes >= need, "hl_groupnorm_train_backward: scratch too small (%zu bytes, hl_groupnorm_train_backward_scratch_bytes says %zu)",
+               scratch_bytes, need);
     float *S = static_cast<float *>(scratch), *k1 = S + (size_t)N * C * 2, *k2 = k1 + (size_t)N * C, *k3 = k2 + (size_t)N * C;
     int rc = hl_gn_backward_reduce(x, C, dout, N, H * W, C, coefA, coefB, silu, S, k3 + (size_t)N * C, part_bytes, stream);
     if (rc) return rc;

@@ -258,13 +258,17 @@ int hl_triplane_agg_forward(const float *g, int N, int H, int W, int C, float *r
     return check_launch("k_agg_fwd");
 }
 
+// the row and column sums of every plane's gradient: rg (N,3,H,C) | cg (N,3,W,C)
+size_t hl_triplane_agg_backward_scratch_bytes(int N, int H, int W, int C) { return (size_t)N * 3 * (H + W) * C * sizeof(float); }
+
 int hl_triplane_agg_backward(const float *dout, const float *g, const float *rmean, const float *cmean, int N, int H, int W, int C, float *dg,
                              void *scratch, size_t scratch_bytes, void *stream) {
     HL_REQUIRE(dout && g && rmean && cmean && dg && N > 0 && H > 0 && H == W && C > 0 && C % 4 == 0, "hl_triplane_agg_backward: bad argument "
                "(N %d, H %d, W %d, C %d)", N, H, W, C);
     HL_REQUIRE((long)N * H * 3 * W * 3 * C < (1L << 31), "hl_triplane_agg_backward: tensor too large");
-    const size_t need = (size_t)N * 3 * (H + W) * C * sizeof(float);
-    HL_REQUIRE(scratch && scratch_bytes >= need, "hl_triplane_agg_backward: scratch too small (%zu bytes, need %zu)", scratch_bytes, need);
+    const size_t need = hl_triplane_agg_backward_scratch_bytes(N, H, W, C);
+    HL_REQUIRE(scratch && scratch_bytes >= need, "hl_triplane_agg_backward: scratch too small (%zu bytes, hl_triplane_agg_backward_scratch_bytes says %zu)",
+               scratch_bytes, need);
     const hipStream_t st = (hipStream_t)stream;
     float *rg = static_cast<float *>(scratch), *cg = rg + (size_t)N * 3 * H * C;
     hipLaunchKernelGGL(k_plane_reduce<true>, dim3(H + W, 3, N), dim3(64), 0, st, dout, H, W, C, rmean, cmean, rg, cg);
@@ -322,7 +326,8 @@ int hl_groupnorm_train_forward_eps(const float *x, int N, int H, int W, int C, c
                                    int silu, float eps, float *coefA, float *coefB, float *gstat, float *y, void *scratch, size_t scratch_bytes,
                                    void *stream) {
     HL_REQUIRE(x && gamma && beta && coefA && coefB && gstat && y && eps > 0.f, "hl_groupnorm_train_forward_eps: bad argument");
-    HL_REQUIRE(scratch && scratch_bytes >= gn_scratch_floats(N) * sizeof(float), "hl_groupnorm_train_forward_eps: scratch too small");
+    HL_REQUIRE(scratch && scratch_bytes >= hl_groupnorm_scratch_bytes(N), "hl_groupnorm_train_forward_eps: scratch too small (%zu bytes, hl_groupnorm_scratch_bytes says %zu)",
+               scratch_bytes, hl_groupnorm_scratch_bytes(N));
     View v; v.p = const_cast<float *>(x); v.N = N; v.H = H; v.W = W; v.C = C; v.pitch = C;
     int rc = groupnorm_coef(v, gamma, beta, scale_shift, 2L * C, coefA, coefB, static_cast<float *>(scratch), (hipStream_t)stream, gstat, eps);
     if (rc) return rc;

@@ -32,6 +32,7 @@ do.  The PyTorch-op twin (tests/unet_autograd_twin.py, test infrastructure) rema
 both against the reference's vectors.
 """
 import ctypes as C
+import functools
 import math
 
 import threading
@@ -73,6 +74,12 @@ def _conv_mode():
     return _MODE if kind == "fp32" else _KIND_MODE[kind]
 
 
+@functools.lru_cache(maxsize=None)
+def _scratch_floats(query, *args):
+    """Floats of scratch an op asks for (the library's *_scratch_bytes queries; cached per geometry: the bf16 step is bound by host time)."""
+    return getattr(_lib.lib(), query)(*args) // 4
+
+
 def _conv_raw(x, w, b, ks, stride=1, ups=0, mode=None):
     """x (N,H,W,Cx) NHWC dense, Cx % 16 == 0; w (Cout, Cx, ks, ks) contiguous; -> (N,Ho,Wo,Cout)."""
     mode = _MODE if mode is None else mode
@@ -83,8 +90,7 @@ def _conv_raw(x, w, b, ks, stride=1, ups=0, mode=None):
     Hv, Wv = (2 * H, 2 * W) if ups else (H, W)
     Ho, Wo = (Hv + 2 * (ks // 2) - ks) // stride + 1, (Wv + 2 * (ks // 2) - ks) // stride + 1
     out = th.empty((N, Ho, Wo, Cout), device=x.device, dtype=th.float32)
-    rows = (Cout + 63) // 64 * 64
-    scratch = th.empty(rows * Cx * ks * ks * 5 + 256 + (16 << 20) + N * Cx * H * W, device=x.device, dtype=th.float32)
+    scratch = th.empty(_scratch_floats("hl_conv2d_scratch_bytes", mode, N, H, W, Cx, Cout, ks, stride, ups, 0), device=x.device, dtype=th.float32)
     with _lib.on(x.device):
         _lib.check(L.hl_conv2d_nhwc_mode(mode, _lib.ptr(x), N, H, W, Cx, _lib.ptr(w), _lib.ptr(b), Cout, ks, stride, ups, None, None, 0,
                                          None, _lib.ptr(out), _lib.ptr(scratch), scratch.numel() * 4, _lib.stream_ptr()), "hl_conv2d_nhwc_mode")
@@ -128,9 +134,8 @@ class _Conv(th.autograd.Function):
             # backward-data = forward conv kernels on dy with W'[ci][co][ky][kx] = W[co][ci][2-ky][2-kx], read in place from w4
             Cxp, Cyp = x.shape[-1], dyp.shape[-1]
             dx = th.empty_like(x) if Cxp == Cin else th.zeros_like(x)
-            rows = (Cin + 63) // 64 * 64
-            extra = N * 4 * Ho * Wo * Cyp if stride == 2 else (N * Ho * Wo * Cxp if ups else 0)
-            scratch = th.empty(rows * Cyp * ks * ks * 5 + 512 + (16 << 20) + extra, device=dy.device, dtype=th.float32)
+            scratch = th.empty(_scratch_floats("hl_conv2d_bwd_data_scratch_bytes", bmode, N, Ho, Wo, Cyp, Cout, Cin, ks, stride, ups, Cxp),
+                               device=dy.device, dtype=th.float32)
             with _lib.on(dy.device):
                 _lib.check(L.hl_conv2d_nhwc_bwd_data(bmode, _lib.ptr(dyp), N, Ho, Wo, Cyp, _lib.ptr(w4.contiguous()), Cout, Cin, ks, stride, ups,
                                                      _lib.ptr(dx), Cxp, _lib.ptr(scratch), scratch.numel() * 4, _lib.stream_ptr()),
@@ -166,7 +171,7 @@ class _GroupNormAct(th.autograd.Function):
         A, B = th.empty((N, Cc), device=dev), th.empty((N, Cc), device=dev)
         gstat = th.empty((N, 32, 2), device=dev)                      # (mean, rstd) per group
         y = th.empty((N, H, W, Cc), device=dev)
-        scr = th.empty(N * 8192, device=dev)
+        scr = th.empty(_scratch_floats("hl_groupnorm_scratch_bytes", N), device=dev)
         ssc = ss.contiguous() if ss is not None else None
         with _lib.on(dev):
             if eps is None:
@@ -192,7 +197,7 @@ class _GroupNormAct(th.autograd.Function):
         dx = th.empty_like(x) if ctx.needs_input_grad[0] else None
         dgamma, dbeta = th.empty(Cc, device=dev), th.empty(Cc, device=dev)
         dss = th.empty((N, 2 * Cc), device=dev) if has_ss else None
-        scr = th.empty(N * Cc * 5 + L.hl_gn_backward_scratch_bytes(N, H * W, Cc) // 4, device=dev)
+        scr = th.empty(_scratch_floats("hl_groupnorm_train_backward_scratch_bytes", N, H * W, Cc), device=dev)
         with _lib.on(dev):
             _lib.check(L.hl_groupnorm_train_backward(_lib.ptr(x), _lib.ptr(dy), N, H, W, Cc, _lib.ptr(A), _lib.ptr(B), 1 if ctx.silu else 0,
                                                      _lib.ptr(gstat), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(ss) if has_ss else None, _lib.ptr(dx),
@@ -229,7 +234,7 @@ class _Attention(th.autograd.Function):
         do = do.contiguous().float()
         dqkv = th.empty_like(qkv)
         nbytes = L.hl_attention_backward_scratch_bytes(N, T, Cc, ctx.heads)
-        scr = th.empty(nbytes // 4 + 16, device=qkv.device)
+        scr = th.empty(nbytes // 4, device=qkv.device)
         with _lib.on(qkv.device):
             _lib.check(L.hl_attention_nhwc_backward(_lib.ptr(qkv), _lib.ptr(out), _lib.ptr(do), N, T, Cc, ctx.heads, _lib.ptr(dqkv), _lib.ptr(scr),
                                                     scr.numel() * 4, _lib.stream_ptr()), "hl_attention_nhwc_backward")
@@ -259,7 +264,7 @@ class _TriplaneAgg(th.autograd.Function):
         N, H, W3, Cc = g.shape
         dout = dout.contiguous()
         dg = th.empty_like(g)
-        scr = th.empty(N * 3 * (H + W3 // 3) * Cc, device=g.device)
+        scr = th.empty(_scratch_floats("hl_triplane_agg_backward_scratch_bytes", N, H, W3 // 3, Cc), device=g.device)
         with _lib.on(g.device):
             _lib.check(_lib.lib().hl_triplane_agg_backward(_lib.ptr(dout), _lib.ptr(g), _lib.ptr(rmean), _lib.ptr(cmean), N, H, W3 // 3, Cc,
                                                            _lib.ptr(dg), _lib.ptr(scr), scr.numel() * 4, _lib.stream_ptr()),
@@ -292,7 +297,7 @@ class _LayerNorm(th.autograd.Function):
         dy = dy.contiguous()
         dx = th.empty_like(x) if ctx.needs_input_grad[0] else None
         dgamma, dbeta = th.empty(Cc, device=x.device), th.empty(Cc, device=x.device)
-        scr = th.empty(L.hl_layernorm_backward_scratch_bytes(npix, Cc) // 4 + 1, device=x.device)
+        scr = th.empty(L.hl_layernorm_backward_scratch_bytes(npix, Cc) // 4, device=x.device)
         with _lib.on(x.device):
             _lib.check(L.hl_layernorm_train_backward(_lib.ptr(x), _lib.ptr(dy), _lib.ptr(stat), npix, Cc, _lib.ptr(gamma), _lib.ptr(dx),
                                                      _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(scr), scr.numel() * 4, _lib.stream_ptr()),

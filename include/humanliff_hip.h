@@ -475,14 +475,20 @@ int hl_diffusion_vb_terms(int mean_type, int var_type, int clip, const float *x_
 int hl_diffusion_prior_bpd(const float *x_start, const float *coef, int64_t n_per_sample, int B, int T, float *prior_bpd,
                            void *scratch, size_t scratch_bytes, void *stream);
 
-/* Single ops of the UNet path, exposed for parity tests and profiling (NHWC fp32). */
+/* Single ops of the UNet path, exposed for parity tests and profiling (NHWC fp32).
+ * One convolution through the kernels of the network, planned as hl_unet_forward plans the same layer.  scratch: at least
+ * hl_conv2d_scratch_bytes(...) bytes (hl_conv2d_nhwc: at HL_CONV_FP32_DIRECT), with_gn = 1 exactly when coefA / coefB are given; less is
+ * refused with HL_ERR_ARG, more is ignored.  It holds the packed weights, the materialised GroupNorm input, the per-image scale of a raw
+ * fp16x2 input and the split-K slabs of the plan.  The plan is always the one the layer takes with the 64 MiB of split-K room it has
+ * inside hl_unet_forward; the scratch holds the slabs that plan writes (for a forward layer the larger of its plans with and without a
+ * GroupNorm in front, so with_gn adds the GroupNorm input and nothing else), not the whole 64 MiB.  The queries plan the layer on the
+ * host: a test switch of the dispatch (hl_debug_set_h16_min_blocks) set between a query and its call can make the call refuse.
+ * Arguments no call accepts (N, H, W, Cout <= 0, Cin not a positive multiple of 16, ks not 1 or 3, stride not 1 or 2, unknown mode) give 0. */
+size_t hl_conv2d_scratch_bytes(int conv_mode, int N, int H, int W, int Cin, int Cout, int ks, int stride, int upsample, int with_gn);
 int hl_conv2d_nhwc(const float *in, int N, int H, int W, int Cin, const float *w_oihw, const float *bias, int Cout,
                    int ks, int stride, int upsample, const float *coefA, const float *coefB, int silu,
                    const float *residual, float *out, void *scratch, size_t scratch_bytes, void *stream);
-/* hl_conv2d_nhwc with an explicit arithmetic mode (HL_CONV_*); the scratch also holds the mode's second weight layout:
- * scratch >= 4*Cout_pad*K (rounded up to 256) + extra, Cout_pad = Cout rounded up to 64, K = Cin*ks*ks; extra = 6*Cout_pad*K bytes
- * (HL_CONV_BF16X3), 64*Cout*Cin (HL_CONV_FP32_F23, 3x3 layers) or 144*Cout*Cin (HL_CONV_FP32, 3x3 layers); what is left beyond
- * that serves the materialised GroupNorm input (N*H*W*Cin floats, when coefA is given) and split-K partial sums. */
+/* hl_conv2d_nhwc with an explicit arithmetic mode (HL_CONV_*); scratch: hl_conv2d_scratch_bytes(conv_mode, ...). */
 int hl_conv2d_nhwc_mode(int conv_mode, const float *in, int N, int H, int W, int Cin, const float *w_oihw, const float *bias,
                         int Cout, int ks, int stride, int upsample, const float *coefA, const float *coefB, int silu,
                         const float *residual, float *out, void *scratch, size_t scratch_bytes, void *stream);
@@ -498,7 +504,9 @@ int hl_conv2d_nhwc_mode(int conv_mode, const float *in, int N, int H, int W, int
  * Cy >= Cout a multiple of 16 (zero-padded channels), w the convolution's own (Cout, Cin, ks, ks) weights - read flipped and
  * channel-transposed while they are re-laid for the kernel, no flipped copy is made -, dx (N,H,W,Cx) with Cx >= Cin (channels
  * [Cin, Cx) are not written).  stride 2 (ks 3): H = 2*Ho; upsample: the convolution ran on the nearest-x2 image, (Ho,Wo) = (2H,2W).
- * scratch: the re-laid weights (5 * round_up(Cin,64) * Cy * ks^2 floats) + 16 MiB + the zero-stuffed / upsampled gradient. */
+ * scratch: hl_conv2d_bwd_data_scratch_bytes(...) of the same arguments (the zero-stuffed / upsampled gradient in front of the
+ * convolution's own room); less is refused with HL_ERR_ARG, more is ignored. */
+size_t hl_conv2d_bwd_data_scratch_bytes(int conv_mode, int N, int Ho, int Wo, int Cy, int Cout, int Cin, int ks, int stride, int upsample, int Cx);
 int hl_conv2d_nhwc_bwd_data(int conv_mode, const float *dy, int N, int Ho, int Wo, int Cy, const float *w_oihw, int Cout, int Cin, int ks,
                             int stride, int upsample, float *dx, int Cx, void *scratch, size_t scratch_bytes, void *stream);
 /* hl_conv2d_wgrad_nhwc_ws: the weight / bias gradients, without atomics.  3x3 layers: k_conv_wgrad_t (a workgroup owns a 64x64 channel block of
@@ -529,9 +537,11 @@ int hl_gn_backward_apply(const float *x, long x_pitch, const float *dout, int N,
 /* The two as the training path uses them (unet_train.py), the (N,C) algebra between the passes in a kernel of its own:
  * forward   y = silu?( GroupNorm32(x) [* (1 + scale) + shift] ), x / y dense (N,H,W,C); scale_shift (N,2C) = [scale | shift] or NULL
  *           (unet.py:203-206); also returns the affine coefA / coefB (N,C) and gstat (N,32,2) = (mean, rstd) per group for the backward.
- *           scratch: N * 32 KiB.
- * backward  dx (may be NULL), dgamma / dbeta (C) (written, not accumulated), dscale_shift (N,2C) (iff scale_shift); scratch: N*C*5 floats
- *           + hl_gn_backward_scratch_bytes(N, H*W, C).  Deterministic (fixed-order sums). */
+ *           scratch: hl_groupnorm_scratch_bytes(N) (also hl_groupnorm_coef's and hl_groupnorm_train_forward_eps's).
+ * backward  dx (may be NULL), dgamma / dbeta (C) (written, not accumulated), dscale_shift (N,2C) (iff scale_shift); scratch:
+ *           hl_groupnorm_train_backward_scratch_bytes(N, H*W, C).  Deterministic (fixed-order sums). */
+size_t hl_groupnorm_scratch_bytes(int N);
+size_t hl_groupnorm_train_backward_scratch_bytes(int N, int HW, int C);
 int hl_groupnorm_train_forward(const float *x, int N, int H, int W, int C, const float *gamma, const float *beta, const float *scale_shift,
                                int silu, float *coefA, float *coefB, float *gstat, float *y, void *scratch, size_t scratch_bytes, void *stream);
 int hl_groupnorm_train_backward(const float *x, const float *dout, int N, int H, int W, int C, const float *coefA, const float *coefB, int silu,
@@ -552,7 +562,8 @@ int hl_zero_stuff2_nhwc(const float *dy, int N, int Ho, int Wo, int C, float *z,
  *           zy: [g, colmean(xy), colmean(xz)].  Also writes the means, rmean (N,3,H,C) and cmean (N,3,W,C), for the backward.
  * backward  dg (N,H,3W,C) from dout (N,H,3W,3C): the own slot times silu'(g), plus, for every mean, the sum of its slot's gradient
  *           along the broadcast axis times silu'(mean) / W (or / H), broadcast back onto the plane it came from.
- *           scratch: N*3*(H+W)*C floats. */
+ *           scratch: hl_triplane_agg_backward_scratch_bytes(N, H, W, C). */
+size_t hl_triplane_agg_backward_scratch_bytes(int N, int H, int W, int C);
 int hl_triplane_agg_forward(const float *g, int N, int H, int W, int C, float *rmean, float *cmean, float *out, void *stream);
 int hl_triplane_agg_backward(const float *dout, const float *g, const float *rmean, const float *cmean, int N, int H, int W, int C, float *dg,
                              void *scratch, size_t scratch_bytes, void *stream);
@@ -581,8 +592,9 @@ int hl_groupnorm_train_forward_eps(const float *x, int N, int H, int W, int C, c
  * that normalises `out` next): the statistics come from the epilogue of the kernel that stored `out` (fixed-point group totals added
  * with integer atomics: order-free, bit-reproducible) - the tensor is not read again; *h_used_stats returns nonzero when the epilogue
  * emitted them, 0 when the kernel
- * path taken emits none and the statistics were computed from the tensor instead.  scratch as hl_conv2d_nhwc_mode plus
- * (N*Hout*Wout/32 + 1)*Cout*8 + N*32 KiB bytes. */
+ * path taken emits none and the statistics were computed from the tensor instead.  scratch: hl_conv2d_gn_scratch_bytes(...), the
+ * arguments of hl_conv2d_scratch_bytes (the output's totals and a GroupNorm pass's scratch in front of the convolution's own room). */
+size_t hl_conv2d_gn_scratch_bytes(int conv_mode, int N, int H, int W, int Cin, int Cout, int ks, int stride, int upsample, int with_gn);
 int hl_conv2d_nhwc_gn(int conv_mode, const float *in, int N, int H, int W, int Cin, const float *w_oihw, const float *bias, int Cout,
                       int ks, int stride, int upsample, const float *coefA, const float *coefB, int silu, const float *residual,
                       float *out, const float *gamma, const float *beta, float *next_coefA, float *next_coefB, int *h_used_stats,

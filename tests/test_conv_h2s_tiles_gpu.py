@@ -49,8 +49,12 @@ def _reference(x, w, b, ups, cA, cB, silu, res):
 
 
 def _scratch(N, H, W, C, Cout, ups):
-    Ho, Wo = (2 * H, 2 * W) if ups else (H, W)
-    return torch.empty(Cout * C * 9 * 8 + 256 + (64 << 20) + N * H * W * C + N * Ho * Wo * Cout + N * 8192, device=dev)
+    """One buffer for every call of a test: the largest hl_conv2d_nhwc_gn asks for over both modes, with and without a GroupNorm in front
+    (the room of the plain call sits behind its prefix)."""
+    from humanliff_amd import _lib
+    need = max(_lib.lib().hl_conv2d_gn_scratch_bytes(m, N, H, W, C, Cout, 3, 1, ups, gn)
+               for m in (_lib.HL_CONV_FP32, _lib.HL_CONV_FP32_DIRECT) for gn in (0, 1))
+    return torch.empty(need // 4, device=dev)
 
 
 def _run(L, _lib, mode, x, w, b, Cout, ups, cA, cB, silu, res, scratch):

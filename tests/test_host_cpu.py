@@ -97,6 +97,75 @@ def test_library_exports_every_declared_symbol():
     assert L.hl_planes_packed_bytes(256, 256) == 9 * 256 * 256 * 16
 
 
+_CONV_LAYERS = [   # (N, H, W, Cin, Cout, ks, stride, upsample)
+    (2, 8, 8, 384, 1152, 1, 1, 0), (4, 8, 8, 768, 768, 3, 1, 0), (2, 32, 32, 192, 192, 3, 1, 0), (2, 16, 16, 64, 64, 3, 2, 0),
+    (2, 8, 8, 64, 64, 3, 1, 1), (1, 12, 20, 96, 27, 3, 1, 0), (3, 5, 7, 16, 80, 1, 1, 0),
+    (4, 8, 8, 256, 192, 3, 1, 1), (4, 16, 16, 256, 192, 3, 1, 0), (2, 32, 32, 384, 384, 3, 1, 0), (1, 16, 16, 384, 1152, 1, 1, 0)]   # a GroupNorm in front changes the kernel family
+
+
+@pytest.mark.parametrize("layer", _CONV_LAYERS)
+def test_conv_scratch_queries(layer):
+    """The scratch queries of the single-op convolutions are host arithmetic: every region is rounded to 256 bytes, the GroupNorm input
+    adds exactly its own size, and the entry points with a prefix never ask for less than the plain call."""
+    from humanliff_amd import _lib
+    from humanliff_amd.build import build
+    build()
+    L = _lib.lib()
+    N, H, W, Cin, Cout, ks, stride, ups = layer
+    Hv, Wv = (2 * H, 2 * W) if ups else (H, W)
+    Ho, Wo = (Hv + 2 * (ks // 2) - ks) // stride + 1, (Wv + 2 * (ks // 2) - ks) // stride + 1
+    act = (N * H * W * Cin * 4 + 255) // 256 * 256
+    for mode in (_lib.HL_CONV_FP32, _lib.HL_CONV_FP32_DIRECT, _lib.HL_CONV_BF16, _lib.HL_CONV_FP16):
+        plain = L.hl_conv2d_scratch_bytes(mode, N, H, W, Cin, Cout, ks, stride, ups, 0)
+        with_gn = L.hl_conv2d_scratch_bytes(mode, N, H, W, Cin, Cout, ks, stride, ups, 1)
+        assert plain >= (Cout + 63) // 64 * 64 * Cin * ks * ks * 4 and plain % 256 == 0 and with_gn == plain + act
+        for gn in (0, 1):
+            fused = L.hl_conv2d_gn_scratch_bytes(mode, N, H, W, Cin, Cout, ks, stride, ups, gn)
+            assert fused % 256 == 0 and fused >= (with_gn if gn else plain)
+        # the backward-data of this layer: d output (N,Ho,Wo,Cout) -> d input (N,H,W,Cin), a convolution Cout -> Cin on the gradient's grid
+        Cy = (Cout + 15) // 16 * 16
+        back = L.hl_conv2d_bwd_data_scratch_bytes(mode, N, Ho, Wo, Cy, Cout, Cin, ks, stride, ups, Cin)
+        # the zero-stuffed / upsampled gradient in front of the room of the convolution it runs: Cy -> Cin on the gradient's grid, flipped weights,
+        # no GroupNorm.  Flipped weights have no fp16x2 form and a forward layer keeps room for the slabs of either plan (with / without
+        # GroupNorm), so this is not "the plain query plus a prefix": between the packed fp32 weights and the forward query of that geometry
+        s = 2 if stride == 2 else 1
+        front = (N * 4 * Ho * Wo * Cy * 4 + 255) // 256 * 256 if stride == 2 else (N * Ho * Wo * Cin * 4 + 255) // 256 * 256 if ups else 0
+        w32 = (Cin + 63) // 64 * 64 * Cy * ks * ks * 4
+        assert back % 256 == 0 and back >= front + w32
+        if mode != _lib.HL_CONV_FP32:
+            assert back <= front + L.hl_conv2d_scratch_bytes(mode, N, s * Ho, s * Wo, Cy, Cin, ks, 1, 0, 0)
+    # hl_conv2d_nhwc is the query at HL_CONV_FP32_DIRECT: its refusal (the size check comes before any use of a pointer) names both numbers
+    rc = L.hl_conv2d_nhwc(None, N, H, W, Cin, None, None, Cout, ks, stride, ups, None, None, 0, None, None, None, 0, None)
+    msg = L.hl_last_error().decode()
+    want = L.hl_conv2d_scratch_bytes(_lib.HL_CONV_FP32_DIRECT, N, H, W, Cin, Cout, ks, stride, ups, 0)
+    assert rc == -1 and "hl_conv2d_scratch_bytes" in msg and re.search(r"\(0 bytes, hl_conv2d_scratch_bytes says (\d+)\)", msg).group(1) == str(want)
+
+
+def test_conv_scratch_queries_give_zero_for_arguments_no_call_accepts():
+    from humanliff_amd import _lib
+    from humanliff_amd.build import build
+    build()
+    L = _lib.lib()
+    good = dict(mode=0, N=2, H=8, W=8, Cin=64, Cout=64, ks=3, stride=1, ups=0)
+    assert L.hl_conv2d_scratch_bytes(*good.values(), 0) > 0
+    for bad in (dict(stride=0), dict(stride=3), dict(N=0), dict(H=0), dict(W=-1), dict(Cin=24), dict(Cin=0), dict(Cout=0), dict(ks=2), dict(mode=99)):
+        a = list({**good, **bad}.values())
+        assert L.hl_conv2d_scratch_bytes(*a, 0) == 0 and L.hl_conv2d_gn_scratch_bytes(*a, 1) == 0, bad
+        mode, N, H, W, Cin, Cout, ks, stride, ups = a
+        assert L.hl_conv2d_bwd_data_scratch_bytes(mode, N, H, W, Cin, Cin, Cout, ks, stride, ups, Cout) == 0, bad
+
+
+def test_training_scratch_queries():
+    from humanliff_amd import _lib
+    from humanliff_amd.build import build
+    build()
+    L = _lib.lib()
+    for N in (1, 3):
+        assert L.hl_groupnorm_scratch_bytes(N) == N * 8192 * 4      # 128 chunks x 32 groups x (sum, sum of squares) per image
+        assert L.hl_groupnorm_train_backward_scratch_bytes(N, 256, 64) == N * 64 * 5 * 4 + L.hl_gn_backward_scratch_bytes(N, 256, 64)
+        assert L.hl_triplane_agg_backward_scratch_bytes(N, 16, 16, 24) == N * 3 * 32 * 24 * 4
+
+
 def test_no_cpu_fallback():
     """CPU tensors must fail loudly, never silently route to PyTorch."""
     from humanliff_amd.NeRF import Renderer

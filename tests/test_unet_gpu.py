@@ -23,6 +23,15 @@ def nchw(t):
     return t.permute(0, 3, 1, 2).contiguous()
 
 
+def conv_scratch(N, H, W, C, Cout, ks, stride=1, ups=0, gn=False, modes=None, query="hl_conv2d_scratch_bytes"):
+    """The scratch a single-op convolution asks for: the largest over `modes` for a buffer that serves several calls (default: HL_CONV_FP32 and
+    HL_CONV_FP32_DIRECT, whose plans differ)."""
+    from humanliff_amd import _lib
+    modes = (_lib.HL_CONV_FP32, _lib.HL_CONV_FP32_DIRECT) if modes is None else modes
+    need = max(getattr(_lib.lib(), query)(m, N, H, W, C, Cout, ks, stride, ups, int(bool(gn))) for m in modes)
+    return torch.empty(need // 4, device=dev)
+
+
 def hip_conv(x, w, b, ks, stride=1, ups=0, cA=None, cB=None, silu=0, res=None, mode=0):
     from humanliff_amd import _lib
     L = _lib.lib()
@@ -32,8 +41,7 @@ def hip_conv(x, w, b, ks, stride=1, ups=0, cA=None, cB=None, silu=0, res=None, m
     Hv, Wv = (2 * H, 2 * W) if ups else (H, W)
     Ho, Wo = (Hv + 2 * (ks // 2) - ks) // stride + 1, (Wv + 2 * (ks // 2) - ks) // stride + 1
     out = torch.empty((N, Ho, Wo, Cout), device=dev)
-    # packed weights + room for split-K partial sums (taken for shapes that would under-fill the chip)
-    scratch = torch.empty(((Cout + 63) // 64 * 64) * C * ks * ks * 5 + 256 + (8 << 20) + N * C * H * W, device=dev)
+    scratch = conv_scratch(N, H, W, C, Cout, ks, stride, ups, gn=cA is not None, modes=(mode,))
     d = lambda t: None if t is None else t.contiguous().to(dev)  # noqa: E731
     wd, bd, cAd, cBd = d(w), d(b), d(cA), d(cB)
     rd = d(nhwc(res)) if res is not None else None
@@ -206,7 +214,7 @@ def test_conv_fused_groupnorm_silu_residual():
     res = torch.randn((N, Cout, H, W), generator=g)
     xd = nhwc(x).to(dev)
     cA, cB = torch.empty((N, C), device=dev), torch.empty((N, C), device=dev)
-    scratch = torch.empty(N * 128 * 64 + 64, device=dev)
+    scratch = torch.empty(L.hl_groupnorm_scratch_bytes(N) // 4, device=dev)
     gd_, bd_, ed_ = gamma.to(dev), beta.to(dev), emb.to(dev)
     _lib.check(L.hl_groupnorm_coef(_lib.ptr(xd), N, H, W, C, _lib.ptr(gd_), _lib.ptr(bd_), _lib.ptr(ed_), _lib.ptr(cA),
                                    _lib.ptr(cB), _lib.ptr(scratch), scratch.numel() * 4, _lib.stream_ptr()))
@@ -235,7 +243,7 @@ def test_groupnorm_affine_matches_torch(N, C, H, W, use_emb):
     emb = torch.randn((N, 2 * C), generator=g) * 0.3
     xd, gd_, bd_, ed_ = nhwc(x).to(dev), gamma.to(dev), beta.to(dev), emb.to(dev)
     cA, cB = torch.empty((N, C), device=dev), torch.empty((N, C), device=dev)
-    scratch = torch.empty(N * 128 * 64 + 64, device=dev)
+    scratch = torch.empty(L.hl_groupnorm_scratch_bytes(N) // 4, device=dev)
     _lib.check(L.hl_groupnorm_coef(_lib.ptr(xd), N, H, W, C, _lib.ptr(gd_), _lib.ptr(bd_), _lib.ptr(ed_) if use_emb else None,
                                    _lib.ptr(cA), _lib.ptr(cB), _lib.ptr(scratch), scratch.numel() * 4, _lib.stream_ptr()))
     torch.cuda.synchronize()
@@ -556,8 +564,7 @@ def test_conv_epilogue_groupnorm_statistics(N, C, H, W, Cout, ks, stride, ups, m
     rd = d(nhwc(res)) if res is not None else None
     out = torch.empty((N, Ho, Wo, Cout), device=dev)
     nA, nB = torch.empty((N, Cout), device=dev), torch.empty((N, Cout), device=dev)
-    scratch = torch.empty(((Cout + 63) // 64 * 64) * C * ks * ks * 5 + 256 + (8 << 20) + N * C * H * W + N * Ho * Wo * Cout // 8 + N * 8192,
-                          device=dev)
+    scratch = conv_scratch(N, H, W, C, Cout, ks, stride, ups, gn=cA is not None, modes=(mode,), query="hl_conv2d_gn_scratch_bytes")
     import ctypes
     used = ctypes.c_int(-1)
     _lib.check(L.hl_conv2d_nhwc_gn(mode, _lib.ptr(xin), N, H, W, C, _lib.ptr(wd), _lib.ptr(bd), Cout, ks, stride, ups, _lib.ptr(cAd),
@@ -601,7 +608,7 @@ def test_conv1x1_fp16x2_products_match_float64(N, H, W, C, Cout, res, gn):
         ref = ref + r.double()
     xd, wd, bd, rd, ad, bd2 = (t.to(dev) for t in (x, w, b, r, cA, cB))
     out = torch.zeros((N, H, W, Cout), device=dev)
-    scratch = torch.empty(Cout * C * 8 + 256 + (8 << 20) + N * H * W * C, device=dev)
+    scratch = conv_scratch(N, H, W, C, Cout, 1, gn=gn)
     import ctypes
     plan = ctypes.c_int(-1)
     _lib.check(L.hl_conv2d_nhwc_mode(_lib.HL_CONV_FP32, _lib.ptr(xd), N, H, W, C, _lib.ptr(wd), _lib.ptr(bd), Cout, 1, 1, 0, _lib.ptr(ad) if gn else None,
@@ -649,7 +656,7 @@ def test_conv3x3_fp16x2_products_match_float64(N, H, W, C, Cout, res, gn, ups):
     if res:
         ref = ref + r.double()
     xd, wd, bd, rd, ad, bd2 = (t.to(dev) for t in (x, w, b, r, cA, cB))
-    scratch = torch.empty(Cout * C * 9 * 8 + 256 + (64 << 20) + N * H * W * C, device=dev)
+    scratch = conv_scratch(N, H, W, C, Cout, 3, 1, ups, gn=gn)
     outs = {}
     for mode in (_lib.HL_CONV_FP32, _lib.HL_CONV_FP32_DIRECT):
         out = torch.zeros((N, Ho, Wo, Cout), device=dev)
@@ -682,7 +689,7 @@ def test_conv3x3_stride2_fp16x2_products_match_float64(N, H, W, C, Cout):
     torch.set_num_threads(min(32, torch.get_num_threads()))
     ref = F.conv2d(x.permute(0, 3, 1, 2).double(), w.double(), b.double(), stride=2, padding=1).permute(0, 2, 3, 1)
     xd, wd, bd = (t.to(dev) for t in (x, w, b))
-    scratch = torch.empty(Cout * C * 9 * 8 + 256 + (64 << 20), device=dev)
+    scratch = conv_scratch(N, H, W, C, Cout, 3, 2)
     outs = {}
     for mode in (_lib.HL_CONV_FP32, _lib.HL_CONV_FP32_DIRECT):
         out = torch.zeros((N, H // 2, W // 2, Cout), device=dev)
@@ -731,7 +738,7 @@ def test_conv_fp16x2_products_are_scale_invariant(kind, N, H, W, C, Cout, gn):
     torch.set_num_threads(min(32, torch.get_num_threads()))
     ref = F.conv2d(xin.permute(0, 3, 1, 2).double(), w.double(), b.double(), stride=stride, padding=ks // 2).permute(0, 2, 3, 1)
     Ho, Wo = ref.shape[1], ref.shape[2]
-    scratch = torch.empty(Cout * C * ks * ks * 8 + 256 + (64 << 20) + N * H * W * C, device=dev)
+    scratch = conv_scratch(N, H, W, C, Cout, ks, stride, gn=gn)
     rows = []
     for a, bx in _SCALE_CASES:
         if gn and bx != 0:
@@ -772,7 +779,7 @@ def test_conv_fp16x2_scale_from_group_totals(kind, N, H, W, C, Cout):
     torch.set_num_threads(min(32, torch.get_num_threads()))
     ref = F.conv2d(x.permute(0, 3, 1, 2).double(), w.double(), b.double(), stride=stride, padding=ks // 2).permute(0, 2, 3, 1)
     Ho, Wo = ref.shape[1], ref.shape[2]
-    scratch = torch.empty(Cout * C * ks * ks * 8 + 256 + (64 << 20), device=dev)
+    scratch = conv_scratch(N, H, W, C, Cout, ks, stride)
     wd = w.to(dev)
     rows = {}
     try:
@@ -812,7 +819,7 @@ def test_conv_fp16x2_activations_beyond_fp16_range_match_fp32():
     b = torch.randn(Cout, generator=g)
     ref = torch.einsum("nhwc,oc->nhwo", x.double(), w[:, :, 0, 0].double()) + b.double()
     xd, wd, bd = x.to(dev), w.to(dev), b.to(dev)
-    scratch = torch.empty(Cout * C * 8 + 256 + (16 << 20), device=dev)
+    scratch = conv_scratch(N, H, W, C, Cout, 1)
     outs = {}
     for mode in (_lib.HL_CONV_FP32, _lib.HL_CONV_FP32_DIRECT):
         out = torch.zeros((N, H, W, Cout), device=dev)

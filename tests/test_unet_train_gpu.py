@@ -23,6 +23,11 @@ def nchw(t):
     return t.permute(0, 3, 1, 2).contiguous()
 
 
+def _conv_scratch(mode, N, H, W, C, Cout, ks, ups=0, gn=False):
+    from humanliff_amd import _lib
+    return torch.empty(_lib.lib().hl_conv2d_scratch_bytes(mode, N, H, W, C, Cout, ks, 1, ups, int(bool(gn))) // 4, device=dev)
+
+
 @pytest.mark.parametrize("N,Cin,H,W,Cout,ks,stride,ups", [
     (2, 64, 32, 32, 64, 3, 1, 0),       # one 64x64 block per tap
     (2, 192, 64, 64, 192, 3, 1, 0),     # production channel count: 3 x 3 blocks x 9 taps, K slabs
@@ -476,7 +481,7 @@ def test_conv_h16_equals_the_convolution_of_the_rounded_operands(f16, h16_single
             ref = ref + res.double()
         xd, wd, bd, rd, ad, bd2 = (t.to(dev) for t in (x, w, b, res, cA, cB))
         out = torch.zeros((N, Ho, Wo, Co), device=dev)
-        scratch = torch.empty(Co * C * 9 * 6 + 256 + (8 << 20) + N * H * W * C, device=dev)
+        scratch = _conv_scratch(mode, N, H, W, C, Co, 3, ups, gn)
         with _lib.on(dev):
             _lib.check(L.hl_conv2d_nhwc_mode(mode, _lib.ptr(xd), N, H, W, C, _lib.ptr(wd), _lib.ptr(bd), Co, 3, 1, ups, _lib.ptr(ad) if gn else None,
                                              _lib.ptr(bd2) if gn else None, gn, _lib.ptr(rd) if use_res else None, _lib.ptr(out), _lib.ptr(scratch),
@@ -608,7 +613,7 @@ def test_conv1_h16_equals_the_product_of_the_rounded_operands(f16, h16_single_ti
             ref = ref + res.double()
         xd, wd, bd, rd, ad, bd2 = (t.to(dev) for t in (x, w, b, res, cA, cB))
         out = torch.zeros((N, H, W, Co), device=dev)
-        scratch = torch.empty(Co * C * 6 + 256 + (8 << 20) + N * H * W * C, device=dev)
+        scratch = _conv_scratch(mode, N, H, W, C, Co, 1, 0, gn)
         with _lib.on(dev):
             _lib.check(L.hl_conv2d_nhwc_mode(mode, _lib.ptr(xd), N, H, W, C, _lib.ptr(wd), _lib.ptr(bd), Co, 1, 1, 0, _lib.ptr(ad) if gn else None,
                                              _lib.ptr(bd2) if gn else None, 0, _lib.ptr(rd) if use_res else None, _lib.ptr(out), _lib.ptr(scratch),
@@ -659,7 +664,7 @@ def test_conv_h16_split_k_on_small_layers(f16):
         outs = []
         for _ in range(2):
             out = torch.zeros((N, H, W, Co), device=dev)
-            scratch = torch.empty(Co * C * 9 * 6 + 256 + (16 << 20), device=dev)
+            scratch = _conv_scratch(mode, N, H, W, C, Co, 3)
             with _lib.on(dev):
                 _lib.check(L.hl_conv2d_nhwc_mode(mode, _lib.ptr(xd), N, H, W, C, _lib.ptr(wd), _lib.ptr(bd), Co, 3, 1, 0, None, None, 0,
                                                  _lib.ptr(rd) if use_res else None, _lib.ptr(out), _lib.ptr(scratch), scratch.numel() * 4, _lib.stream_ptr()),
