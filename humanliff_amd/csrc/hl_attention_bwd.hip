@@ -2,11 +2,14 @@
 // (probabilities recomputed, never stored).  Replaces the five torch.bmm (rocBLAS) of round 3's _Attention.backward.
 //
 // Per (sample, head):  S = (s q)(s k)^T with s = ch^-1/4 on q AND k,  P = softmax_rows(S),  O = P v.   Given dO:
-//   dV = P^T dO      dP = dO V^T      D_i = sum_j P_ij dP_ij = dO_i . O_i      dS = P o (dP - D)      dQ = s dS (s k)      dK = s dS^T (s q)
+//   dV = P^T dO      dP = dO V^T      D_i = sum_j P_ij dP_ij  (= dO_i . O_i)      dS = P o (dP - D)      dQ = s dS (s k)      dK = s dS^T (s q)
+// D is formed as sum_j P_ij dP_ij from the SAME P and dP the dS of the query kernel is formed from, not as dO_i . O_i: the two agree to fp32 rounding only, and
+// dQ multiplies dP - D by k.  On a saturated row (one key holds all the probability) the exact dS is 0; with D = dP_top bit for bit it is 0 here too, where
+// dO . O left |dO| |v| 2^-24 sqrt(ch) times |k| in dQ.
 //
 // Two kernels, both in the register-resident transposed style of k_attention / k_march (v_mfma_f32_32x32x2_f32; an accumulator tile IS
 // the next product's B operand):
-//   k_attn_bwd_q   one wave = 32 queries.  Pass A over the key tiles: row maximum and sum (the forward kernels do not emit them).  Pass B:
+//   k_attn_bwd_q   one wave = 32 queries.  Pass A over the key tiles: row maximum, sum (the forward kernels do not emit them) and D, online.  Pass B:
 //                  S^T -> P^T, dP^T = V dO^T, dS^T in registers, dQ^T += K^T dS^T.  Writes dQ and per query (max, 1/sum, D) for the second kernel.
 //   k_attn_bwd_kv  one wave = 32 keys, loop over the query tiles: S -> P, dP = dO V^T, dS; dV^T += dO^T P, dK^T += Q^T dS.
 // Every output element is owned by one wave and summed in a fixed order: run-to-run identical bits.
@@ -29,7 +32,7 @@ __global__ __launch_bounds__(KS_ * 64, 1) void k_attn_bwd_q(const float *__restr
     extern __shared__ float lds_q[];                    // per wave: K tile, V tile (2 x 32 x LDK); reused for the partial dQ tiles at the end
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5;
     float *sK = lds_q + wave * 2 * TILE, *sV = sK + TILE;
-    __shared__ float sML[KS_ * 2 * 32];
+    __shared__ float sML[KS_ * 3 * 32];
     const int nh = blockIdx.y, n = nh / heads, head = nh % heads;
     const int q0 = blockIdx.x * 32;
     const float scale = 1.f / sqrtf(sqrtf((float)CH));
@@ -37,17 +40,15 @@ __global__ __launch_bounds__(KS_ * 64, 1) void k_attn_bwd_q(const float *__restr
     const float *base = qkv + (long)n * T * pitch + (long)head * 3 * CH;
     const int qi = q0 + (lane & 31), qj = min(qi, T - 1);
     float qreg[KS], doreg[KS];
-    float D = 0.f;
     {
-        const float *orow = out + ((long)n * T + qj) * C + head * CH, *drow = dout + ((long)n * T + qj) * C + head * CH;
+        const float *drow = dout + ((long)n * T + qj) * C + head * CH;
 #pragma unroll
         for (int s = 0; s < KS; ++s) {
             qreg[s] = base[(long)qj * pitch + 2 * s + half] * scale;
             doreg[s] = drow[2 * s + half];
-            D = fmaf(doreg[s], orow[2 * s + half], D);
         }
-        D += __shfl_xor(D, 32);
     }
+    (void)out;                                          // (the forward's output is not needed: D comes from P and dP, see the head of the file)
     auto load_tile = [&](int k0, bool with_v) {   // wave-private: the wave's own LDS reads of the previous tile are behind it in program order
         for (int e = lane; e < 32 * (CH / 4); e += 64) {
             const int key = e / (CH / 4), c = (e - key * (CH / 4)) * 4;
@@ -75,35 +76,56 @@ __global__ __launch_bounds__(KS_ * 64, 1) void k_attn_bwd_q(const float *__restr
             if (k0 + (r & 3) + 8 * (r >> 2) + 4 * half >= T) st[r] = -3.0e38f;
         return st;
     };
-    // pass A: row maximum and sum over this wave's key tiles, then over the waves
-    float mrun = -3.0e38f, lrun = 0.f;
+    auto dprobs = [&]() -> f32x16 {   // dP^T = V dO^T of the staged tile, the layout of scores()
+        f32x16 dp;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dp[r] = 0.f;
+#pragma unroll
+        for (int s = 0; s < KS; ++s) dp = __builtin_amdgcn_mfma_f32_32x32x2f32(sV[(lane & 31) * LDK + 2 * s + half], doreg[s], dp, 0, 0, 0);
+        return dp;
+    };
+    // pass A: row maximum, sum and sum_j exp(S_ij - max) dP_ij over this wave's key tiles (online, rescaled when the maximum moves), then over the waves
+    float mrun = -3.0e38f, lrun = 0.f, drun = 0.f;
     for (int k0 = wave * 32; k0 < T; k0 += 32 * KS_) {
-        load_tile(k0, false);
+        load_tile(k0, true);
         const f32x16 st = scores(k0);
+        const f32x16 dp = dprobs();
         float mx = -3.0e38f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) mx = fmaxf(mx, st[r]);
         mx = fmaxf(mx, __shfl_xor(mx, 32));
         const float mnew = fmaxf(mrun, mx);
-        float psum = 0.f;
+        float psum = 0.f, dsum = 0.f;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) psum += __expf(st[r] - mnew);
+        for (int r = 0; r < 16; ++r) {
+            const float e = __expf(st[r] - mnew);     // masked keys: 0 (their dP is that of the clamped key: finite)
+            psum += e;
+            dsum += e * dp[r];
+        }
         psum += __shfl_xor(psum, 32);
-        lrun = lrun * __expf(mrun - mnew) + psum;
+        dsum += __shfl_xor(dsum, 32);
+        const float alpha = __expf(mrun - mnew);
+        lrun = lrun * alpha + psum;
+        drun = drun * alpha + dsum;
         mrun = mnew;
         __builtin_amdgcn_wave_barrier();
     }
-    if (half == 0) { sML[(wave * 2) * 32 + lane] = mrun; sML[(wave * 2 + 1) * 32 + lane] = lrun; }
+    if (half == 0) { sML[(wave * 3) * 32 + lane] = mrun; sML[(wave * 3 + 1) * 32 + lane] = lrun; sML[(wave * 3 + 2) * 32 + lane] = drun; }
     __syncthreads();
     {
-        float m = -3.0e38f, l = 0.f;
+        float m = -3.0e38f, l = 0.f, d = 0.f;
 #pragma unroll
-        for (int w = 0; w < KS_; ++w) m = fmaxf(m, sML[(w * 2) * 32 + (lane & 31)]);
+        for (int w = 0; w < KS_; ++w) m = fmaxf(m, sML[(w * 3) * 32 + (lane & 31)]);
 #pragma unroll
-        for (int w = 0; w < KS_; ++w) l += sML[(w * 2 + 1) * 32 + (lane & 31)] * __expf(sML[(w * 2) * 32 + (lane & 31)] - m);   // waves without keys: l = 0
-        mrun = m; lrun = l;
+        for (int w = 0; w < KS_; ++w) {
+            const float a = __expf(sML[(w * 3) * 32 + (lane & 31)] - m);     // waves without keys: l = d = 0
+            l += sML[(w * 3 + 1) * 32 + (lane & 31)] * a;
+            d += sML[(w * 3 + 2) * 32 + (lane & 31)] * a;
+        }
+        mrun = m; lrun = l; drun = d;
     }
     const float invl = 1.f / lrun;
+    const float D = drun * invl;
     if (wave == 0 && half == 0 && qi < T) {
         float *sp = stat + ((long)nh * T + qi) * 3;
         sp[0] = mrun; sp[1] = invl; sp[2] = D;
@@ -117,11 +139,7 @@ __global__ __launch_bounds__(KS_ * 64, 1) void k_attn_bwd_q(const float *__restr
     for (int k0 = wave * 32; k0 < T; k0 += 32 * KS_) {
         load_tile(k0, true);
         f32x16 st = scores(k0);
-        f32x16 dp;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) dp[r] = 0.f;
-#pragma unroll
-        for (int s = 0; s < KS; ++s) dp = __builtin_amdgcn_mfma_f32_32x32x2f32(sV[(lane & 31) * LDK + 2 * s + half], doreg[s], dp, 0, 0, 0);
+        const f32x16 dp = dprobs();
 #pragma unroll
         for (int r = 0; r < 16; ++r) st[r] = __expf(st[r] - mrun) * invl * (dp[r] - D);    // masked keys: exp(-inf) = 0
 #pragma unroll
@@ -264,18 +282,20 @@ __global__ void k_attn_bwd_rows(const float *__restrict__ qkv, const float *__re
     float sum = 0.f;
     for (int j = lane; j < T; j += 64) { const float e = __expf(prow[j] - mx); prow[j] = e; sum += e; }
     sum = wave_xor_sum(sum);
-    float D = 0.f;
-    for (int c = lane; c < ch; c += 64) D = fmaf(drow[c], orow[c], D);
-    D = wave_xor_sum(D);
+    (void)orow;                                         // (D = sum_j P_ij dP_ij from the same P and dP as dS below, not dO . O: see the head of the file)
     const float inv = 1.f / sum;
+    float D = 0.f;
     for (int j = lane; j < T; j += 64) {
         const float *vr = base + (long)j * pitch + 2 * ch;
         float dp = 0.f;
         for (int c = 0; c < ch; ++c) dp = fmaf(drow[c], vr[c], dp);
         const float p = prow[j] * inv;
         prow[j] = p;
-        srow[j] = p * (dp - D);
+        srow[j] = dp;
+        D = fmaf(p, dp, D);
     }
+    D = wave_xor_sum(D);
+    for (int j = lane; j < T; j += 64) srow[j] = prow[j] * (srow[j] - D);
 }
 __global__ void k_attn_bwd_products(const float *__restrict__ qkv, const float *__restrict__ dout, const float *__restrict__ P, const float *__restrict__ dS,
                                     int N, int T, int C, int heads, int ch, float *__restrict__ dqkv) {

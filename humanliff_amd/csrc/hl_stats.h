@@ -7,12 +7,18 @@
 // (coef_to_lds), so no coefficient launch sits between producer and consumer.  The producer is told the grouping of the view its tensor is
 // normalised in (ConvK::st_cg channels per group, st_c0 = the tensor's first channel inside the view: the two producers of a decoder
 // "concat" add into the SAME 32 groups).  Scales: sum 2^30 (resolution 1e-9; capacity +-8.6e9 per group and image), sum of squares 2^24
-// (resolution 6e-8; capacity 2.7e11).  A contribution that is not finite or beyond the capacity sets bit 62 of the sum-of-squares word:
+// (resolution 6e-8; capacity 2.7e11) from 4096 pixels per image on, up to 2^30 below (stat_sq_bits: the capacity shrinks with the count it has to hold).  A contribution that is not finite or beyond the capacity sets bit 62 of the sum-of-squares word:
 // consumers turn that (and an overflowed total) into NaN coefficients.  Limits, stated plainly: the reference's fp32 GroupNorm keeps working where these
 // totals give up - a tensor whose sum x^2 per (image, group, shard) exceeds 2.7e11 (rms ~1e3 at the 256-pixel level with 6 channels per group) normalises to NaN here,
 // loudly.  One hole remains: a total can wrap past 2^64 unnoticed if more than 1.1e12 of sum x^2 arrives in pieces that each stay under the 1e11 cap (eleven or more
 // workgroups at rms ~2e3 and beyond) and the wrapped value happens to land under 2^62; closing it needs a returning atomic per contribution (its latency at the end of
 // every producer workgroup) or a third word, and was not built.
+// Accuracy envelope, as measured against float64 GroupNorm (tests/test_norm_offset_gpu.py; DESIGN.md, "GroupNorm statistics away from zero mean"): the integers are exact,
+// but a contribution (s, q) is an fp32 sum of raw x and x^2 (stat_add, stat_add_run, wg_stat_put / wg_group_flush, k_tensor_totals), so q carries fp32 rounding at the
+// magnitude of mean^2 and the error of the normalised output grows as (mean/std)^2: within 4x the reference's own fp32 error (+ 2e-6) up to mean/std ~ 10 on every
+// producer, 1.3e-5 ... 1.5e-4 at ~25 and 2.1e-4 ... 2.2e-3 at ~80 (reference: 3e-6 and 1.3e-5).  k_splitk_finish_st alone un-pivots in double (stat_add_run_d) and holds to
+// mean/std ~ 100.  The resolution of q used to be a second limit: at 2^-24 on every level a tensor at |x| ~ 1e-2 whose
+// variance is below eps lost 1e-5 of var + eps on the 256-pixel levels (1.2e-5 on the normalised output where the reference has 5e-7); with stat_sq_bits 8e-7.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -21,7 +27,25 @@
 namespace hl {
 
 constexpr double STAT_SC_SUM = 1073741824.0;   // 2^30
-constexpr double STAT_SC_SQ = 16777216.0;      // 2^24
+// Fractional bits of the sum-of-squares word: 24 from 4096 pixels per image on, one more per halving of the image below that (at most 30).  A level with fewer
+// pixels has fewer values to hold, so the bits go to resolution instead: the capacity in rms terms, 2^62 / (2^bits HW cg), never falls below the 4096-pixel
+// level's (rms 1.1e3 at 48 channels per group; the 65536-pixel level with 6: 830), while a tensor at |x| ~ 1e-2 whose variance is below eps keeps 1e-7 of var + eps
+// on the 256-pixel levels where 24 bits left 1e-5.  Producer and consumer derive it from the same HW they already share for stat_shards.
+// (a handful of integer instructions and no division where it runs: the head of every consumer workgroup, the tail of every producer's)
+__host__ __device__ constexpr int stat_sq_bits(long HW) {
+    if (HW > 2048) return 24;
+    const int cl = HW <= 1 ? 0 : 64 - __builtin_clzl((unsigned long)(HW - 1));     // ceil(log2(HW))
+    const int e = 12 - cl;                                                          // floor(log2(4096 / HW))
+    return 24 + (e > 6 ? 6 : e);
+}
+static_assert(stat_sq_bits(65536) == 24 && stat_sq_bits(4096) == 24 && stat_sq_bits(4095) == 24 && stat_sq_bits(2048) == 25 && stat_sq_bits(1025) == 25 &&
+              stat_sq_bits(1024) == 26 && stat_sq_bits(256) == 28 && stat_sq_bits(144) == 28 && stat_sq_bits(64) == 30 && stat_sq_bits(1) == 30, "stat_sq_bits");
+__host__ __device__ constexpr double stat_pow2(int e) { return __builtin_bit_cast(double, (unsigned long long)(1023 + e) << 52); }   // 2^e from its exponent field
+__host__ __device__ constexpr double stat_sq_scale(long HW) { return stat_pow2(stat_sq_bits(HW)); }
+__host__ __device__ constexpr double stat_sq_inv_scale(long HW) { return stat_pow2(-stat_sq_bits(HW)); }
+static_assert(stat_sq_scale(65536) == 16777216.0 && stat_sq_inv_scale(256) * 268435456.0 == 1.0, "stat_sq_scale");
+// a contribution beyond this poisons the word (1e11 at 24 bits: the conversion and the hole above scale with the word)
+__host__ __device__ constexpr double stat_sq_cap(long HW) { return 1.0e11 * stat_pow2(24 - stat_sq_bits(HW)); }
 constexpr unsigned long long STAT_POISON = 1ull << 62;
 
 __device__ __forceinline__ unsigned long long *stat_word(float *st, int N, long img, int g, long HW) {
@@ -33,9 +57,9 @@ __device__ __forceinline__ unsigned long long *stat_word(float *st, int N, long 
 // serialise); consumers add the copies up - exact integers.
 __device__ __forceinline__ void stat_add(float *st, int N, long img, int g, long HW, float s, float q) {
     unsigned long long *t = stat_word(st, N, img, g, HW);
-    if (!(q < 1.0e11f)) { atomicOr(t + 1, STAT_POISON); return; }
+    if (!(q < (float)stat_sq_cap(HW))) { atomicOr(t + 1, STAT_POISON); return; }
     atomicAdd(t, (unsigned long long)__double2ll_rn((double)s * STAT_SC_SUM));
-    atomicAdd(t + 1, (unsigned long long)__double2ll_rn((double)q * STAT_SC_SQ));
+    atomicAdd(t + 1, (unsigned long long)__double2ll_rn((double)q * stat_sq_scale(HW)));
 }
 
 // The lanes of a wave hold the (s, q) of CONSECUTIVE channels (g = the group of the lane's channel, non-decreasing over the lanes that
@@ -55,6 +79,31 @@ __device__ __forceinline__ void stat_add_run(float *st, int N, long img, int g, 
     const int kn = __shfl_down(key, 1);
     const bool next_same = lane < 63 && ((act >> (lane + 1)) & 1) && kn == key;
     if (take && !next_same) stat_add(st, N, img, g, HW, s, q);
+}
+
+// The same for contributions kept in double: a producer whose lanes sum about a pivot (their own first value) un-pivots each lane's pair in
+// double - S = n K + s, Q = q + 2 K s + n K^2 - and merges in double, so what reaches the integers carries no fp32 rounding at the magnitude
+// of mean^2 (k_splitk_finish_st).
+__device__ __forceinline__ void stat_add_d(float *st, int N, long img, int g, long HW, double s, double q) {
+    unsigned long long *t = stat_word(st, N, img, g, HW);
+    if (!(q < stat_sq_cap(HW))) { atomicOr(t + 1, STAT_POISON); return; }
+    atomicAdd(t, (unsigned long long)__double2ll_rn(s * STAT_SC_SUM));
+    atomicAdd(t + 1, (unsigned long long)__double2ll_rn(q * stat_sq_scale(HW)));
+}
+__device__ __forceinline__ void stat_add_run_d(float *st, int N, long img, int g, bool take, long HW, double s, double q) {
+    const int lane = threadIdx.x & 63;
+    const unsigned long long act = __ballot(1);
+    const int key = take ? g : -1 - lane;
+    if (!take) { s = 0.0; q = 0.0; }
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const double sp = __shfl_up(s, d), qp = __shfl_up(q, d);
+        const int kp = __shfl_up(key, d);
+        if (lane >= d && ((act >> (lane - d)) & 1) && kp == key) { s += sp; q += qp; }
+    }
+    const int kn = __shfl_down(key, 1);
+    const bool next_same = lane < 63 && ((act >> (lane + 1)) & 1) && kn == key;
+    if (take && !next_same) stat_add_d(st, N, img, g, HW, s, q);
 }
 
 // Workgroup-level pre-reduction: sub-part `sub` (a wave / round) deposits the (s, q) of local channel lc in `red` (2 * NSUB * NC floats of
@@ -79,10 +128,10 @@ __device__ __forceinline__ void wg_group_flush(const float *red, unsigned long l
             q += v.y;
         }
         const int gl = (c0 + n0 + tid) / cg - g0;
-        if (!(q < 1.0e11f)) atomicOr(lg + gl * 2 + 1, STAT_POISON);
+        if (!(q < (float)stat_sq_cap(HW))) atomicOr(lg + gl * 2 + 1, STAT_POISON);
         else {
             atomicAdd(lg + gl * 2, (unsigned long long)__double2ll_rn((double)s * STAT_SC_SUM));
-            atomicAdd(lg + gl * 2 + 1, (unsigned long long)__double2ll_rn((double)q * STAT_SC_SQ));
+            atomicAdd(lg + gl * 2 + 1, (unsigned long long)__double2ll_rn((double)q * stat_sq_scale(HW)));
         }
     }
     __syncthreads();
@@ -123,7 +172,7 @@ __device__ __forceinline__ void group_mean_rstd(const float *gt, int N, int n, i
     bad |= Q < 0 || (unsigned long long)Q >= STAT_POISON;
     const double cnt = (double)HW * cg;
     const double mean = (double)S * (1.0 / STAT_SC_SUM) / cnt;
-    double var = (double)Q * (1.0 / STAT_SC_SQ) / cnt - mean * mean;
+    double var = (double)Q * stat_sq_inv_scale(HW) / cnt - mean * mean;
     var = var < 0.0 ? 0.0 : var;
     mean_f = (float)mean;
     rstd = bad ? __builtin_nanf("") : (float)(1.0 / sqrt(var + (double)eps));
@@ -175,7 +224,7 @@ __device__ __forceinline__ float act_scale_totals(const float *gt, int N, int n,
     const float Qt = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, Q), 0)) +
                      __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, Q), 16));
     // (a poisoned / overflowed block says nothing about the magnitudes: scale 1, and the planes' own range decides)
-    return __ballot(bad) ? 1.f : pow2_scale_for_bound(sqrtf(Qt * (float)(1.0 / STAT_SC_SQ)) * 1.0001f + 1e-30f);
+    return __ballot(bad) ? 1.f : pow2_scale_for_bound(sqrtf(Qt * (float)stat_sq_inv_scale(HW)) * 1.0001f + 1e-30f);
 }
 
 // sum over the wave's 64 lanes, the same in every lane's return, in a fixed order (four DPP steps inside each row of 16, then the four rows)

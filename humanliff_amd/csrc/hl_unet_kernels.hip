@@ -1862,11 +1862,13 @@ __global__ void k_splitk_finish(const ConvK p, int splits) {
 // channels (grid (M/32, Cout/64)); its 4 waves take 8 pixels each, a lane one channel; the four partial (sum, sumsq) pairs of a
 // channel meet in LDS in a fixed order.  Same arithmetic and order of the slab sum as k_splitk_finish.
 __global__ __launch_bounds__(256) void k_splitk_finish_st(const ConvK p, int splits) {
-    __shared__ float red[2][4][2][64];
+    __shared__ double red[2][4][2][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int n = blockIdx.y * 64 + lane;
     const long total = p.M * p.Cout;
-    float s1 = 0.f, q1 = 0.f, s2 = 0.f, q2 = 0.f;
+    // (sum, sumsq) of the lane's 8 values about a pivot - its first value - and un-pivoted in double BEFORE lanes and waves with other pivots
+    // merge: the fp32 sums stay at the scale of the values' spread, so a channel far from zero loses nothing to mean^2 (hl_stats.h)
+    double S1 = 0.0, Q1 = 0.0, S2 = 0.0, Q2 = 0.0;
     if (n < p.Cout) {
         const float bs = p.bias ? p.bias[n] : 0.f;
         float v[8], r1[8], r2[8];
@@ -1883,24 +1885,38 @@ __global__ __launch_bounds__(256) void k_splitk_finish_st(const ConvK p, int spl
             v[k] += bs;
             if (p.res) v[k] += r1[k];
             p.out[(mb + k) * p.out_pitch + n] = v[k];
-            s1 += v[k]; q1 += v[k] * v[k];
-            if (p.out2) {
-                const float w = v[k] + r2[k];
-                p.out2[(mb + k) * p.out2_pitch + n] = w;
-                s2 += w; q2 += w * w;
+        }
+        float s = 0.f, q = 0.f;
+#pragma unroll
+        for (int k = 1; k < 8; ++k) { const float d = v[k] - v[0]; s += d; q += d * d; }
+        const double K1 = (double)v[0];
+        S1 = 8.0 * K1 + (double)s;
+        Q1 = (double)q + 2.0 * K1 * (double)s + 8.0 * K1 * K1;
+        if (p.out2) {
+            float w[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                w[k] = v[k] + r2[k];
+                p.out2[(mb + k) * p.out2_pitch + n] = w[k];
             }
+            s = 0.f; q = 0.f;
+#pragma unroll
+            for (int k = 1; k < 8; ++k) { const float d = w[k] - w[0]; s += d; q += d * d; }
+            const double K2 = (double)w[0];
+            S2 = 8.0 * K2 + (double)s;
+            Q2 = (double)q + 2.0 * K2 * (double)s + 8.0 * K2 * K2;
         }
     }
-    red[0][wave][0][lane] = s1; red[0][wave][1][lane] = q1;
-    red[1][wave][0][lane] = s2; red[1][wave][1][lane] = q2;
+    red[0][wave][0][lane] = S1; red[0][wave][1][lane] = Q1;
+    red[1][wave][0][lane] = S2; red[1][wave][1][lane] = Q2;
     __syncthreads();
     if (wave < 2) {   // (wave-uniform: wave 0 finishes out's statistics, wave 1 out2's; its 64 lanes = 64 consecutive channels)
         float *st = wave == 0 ? p.st1 : p.st2;
         if (st) {
-            const float s = ((red[wave][0][0][lane] + red[wave][1][0][lane]) + red[wave][2][0][lane]) + red[wave][3][0][lane];
-            const float q = ((red[wave][0][1][lane] + red[wave][1][1][lane]) + red[wave][2][1][lane]) + red[wave][3][1][lane];
-            stat_add_run(st, p.N, ((long)blockIdx.x * 32) / ((long)p.Hout * p.Wout), ((wave == 0 ? p.st1_c0 : p.st2_c0) + n) / (wave == 0 ? p.st1_cg : p.st2_cg),
-                         n < p.Cout, (long)p.Hout * p.Wout, s, q);
+            const double s = ((red[wave][0][0][lane] + red[wave][1][0][lane]) + red[wave][2][0][lane]) + red[wave][3][0][lane];
+            const double q = ((red[wave][0][1][lane] + red[wave][1][1][lane]) + red[wave][2][1][lane]) + red[wave][3][1][lane];
+            stat_add_run_d(st, p.N, ((long)blockIdx.x * 32) / ((long)p.Hout * p.Wout), ((wave == 0 ? p.st1_c0 : p.st2_c0) + n) / (wave == 0 ? p.st1_cg : p.st2_cg),
+                           n < p.Cout, (long)p.Hout * p.Wout, s, q);
         }
     }
 }
@@ -1956,10 +1972,13 @@ __global__ void k_pack_conv_bf3(const float *__restrict__ w, int Cout, int Cin, 
 // ---------------------------------------------------------------------------------------------
 // GroupNorm statistics
 // ---------------------------------------------------------------------------------------------
-// grid (nchunks, N); blockDim = (C/4) * k threads; thread owns one float4 channel column.
-__global__ void k_gn_partial(const float *__restrict__ x, long pitch, int HW, int C, int nchunks, float *__restrict__ partial,
-                             const float *__restrict__ gamma, const float *__restrict__ beta, const float *__restrict__ emb,
-                             long emb_pitch, float *__restrict__ cA, float *__restrict__ cB, float *__restrict__ gstat, float eps) {
+// Every statistic below is taken ABOUT A PIVOT: K = the group's first stored value (pixel 0, first channel of the group), the same for every
+// thread, chunk and workgroup that works on the (image, group).  The fp32 sums are of (x - K) and (x - K)^2, then mean = K + s / cnt and
+// var = q / cnt - (s / cnt)^2 in double: the cancellation in the variance is at the scale of the group's spread about K, not of mean^2, so a
+// group far from zero (mean / std of 100 and beyond) keeps the accuracy of a centred one.  A raw E[x^2] - mean^2 loses (mean / std)^2 of it.
+//
+// grid (nchunks, N), nchunks > 1; blockDim = (C/4) * k threads; thread owns one float4 channel column.
+__global__ void k_gn_partial(const float *__restrict__ x, long pitch, int HW, int C, int nchunks, float *__restrict__ partial) {
     extern __shared__ float sh[];  // [k][C] sums then [k][C] sumsq
     const int cq = C >> 2;
     const int k = blockDim.x / cq;
@@ -1967,22 +1986,27 @@ __global__ void k_gn_partial(const float *__restrict__ x, long pitch, int HW, in
     const int n = blockIdx.y, chunk = blockIdx.x;
     const int per = (HW + nchunks - 1) / nchunks;
     const int p0 = chunk * per, p1 = min(HW, p0 + per);
+    const int cg = C / 32;
     f32x4 s = f32x4{0.f, 0.f, 0.f, 0.f}, ss = f32x4{0.f, 0.f, 0.f, 0.f};
     if (prow < k) {
-        const float *base = x + (long)n * HW * pitch + c4 * 4;
+        const float *img = x + (long)n * HW * pitch;
+        f32x4 K;                                 // (a float4 column may straddle groups: one pivot per channel, its group's)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) K[j] = img[((c4 * 4 + j) / cg) * cg];
+        const float *base = img + c4 * 4;
         int pp = p0 + prow;
         for (; pp + 3 * k < p1; pp += 4 * k) {   // four independent loads in flight
-            const f32x4 v0 = *reinterpret_cast<const f32x4 *>(base + (long)pp * pitch);
-            const f32x4 v1 = *reinterpret_cast<const f32x4 *>(base + (long)(pp + k) * pitch);
-            const f32x4 v2 = *reinterpret_cast<const f32x4 *>(base + (long)(pp + 2 * k) * pitch);
-            const f32x4 v3 = *reinterpret_cast<const f32x4 *>(base + (long)(pp + 3 * k) * pitch);
+            const f32x4 v0 = *reinterpret_cast<const f32x4 *>(base + (long)pp * pitch) - K;
+            const f32x4 v1 = *reinterpret_cast<const f32x4 *>(base + (long)(pp + k) * pitch) - K;
+            const f32x4 v2 = *reinterpret_cast<const f32x4 *>(base + (long)(pp + 2 * k) * pitch) - K;
+            const f32x4 v3 = *reinterpret_cast<const f32x4 *>(base + (long)(pp + 3 * k) * pitch) - K;
             s += v0; ss += v0 * v0;
             s += v1; ss += v1 * v1;
             s += v2; ss += v2 * v2;
             s += v3; ss += v3 * v3;
         }
         for (; pp < p1; pp += k) {
-            const f32x4 v = *reinterpret_cast<const f32x4 *>(base + (long)pp * pitch);
+            const f32x4 v = *reinterpret_cast<const f32x4 *>(base + (long)pp * pitch) - K;
             s += v;
             ss += v * v;
         }
@@ -1992,37 +2016,12 @@ __global__ void k_gn_partial(const float *__restrict__ x, long pitch, int HW, in
         d2[0] = ss[0]; d2[1] = ss[1]; d2[2] = ss[2]; d2[3] = ss[3];
     }
     __syncthreads();
-    const int cg = C / 32;
-    __shared__ float gs[64];
     if (threadIdx.x < 64) {
         const int g = threadIdx.x & 31, which = threadIdx.x >> 5;
         float t = 0.f;
         for (int r = 0; r < k; ++r)
             for (int c = 0; c < cg; ++c) t += sh[(long)(which * k + r) * C + g * cg + c];
         partial[(((long)n * nchunks + chunk) * 32 + g) * 2 + which] = t;
-        gs[which * 32 + g] = t;
-    }
-    if (nchunks != 1 || cA == nullptr) return;
-    // one workgroup saw the whole image: finish the affine here (saves the k_gn_coef launch)
-    __syncthreads();
-    const double cnt = (double)HW * cg;
-    for (int c = threadIdx.x; c < C; c += blockDim.x) {
-        const int g = c / cg;
-        const double mean = (double)gs[g] / cnt;
-        double var = (double)gs[32 + g] / cnt - mean * mean;
-        var = var < 0.0 ? 0.0 : var;
-        const float rstd = (float)(1.0 / sqrt(var + (double)eps));
-        float a = rstd * gamma[c];
-        float b = beta[c] - (float)mean * a;
-        if (emb) {
-            const float sc = 1.f + emb[(long)n * emb_pitch + c];
-            const float sf = emb[(long)n * emb_pitch + C + c];
-            a = a * sc;
-            b = b * sc + sf;
-        }
-        cA[(long)n * C + c] = a;
-        cB[(long)n * C + c] = b;
-        if (gstat && c % cg == 0) { gstat[((long)n * 32 + c / cg) * 2] = (float)mean; gstat[((long)n * 32 + c / cg) * 2 + 1] = rstd; }
     }
 }
 
@@ -2036,21 +2035,24 @@ __global__ __launch_bounds__(256) void k_gn_small(const float *__restrict__ x, l
     const int g = blockIdx.x, n = blockIdx.y, tid = threadIdx.x;
     const int cg = C / 32, per = cg / V;
     const float *base = x + (long)n * HW * pitch + g * cg;
+    const float K = base[0];                     // the pivot (above): the group's first value, one broadcast load
     float s = 0.f, ss = 0.f;
     const int items = HW * per;
     for (int i = tid; i < items; i += 256) {
         const int pix = i / per, sub = i - pix * per;
         const float *q = base + (long)pix * pitch + sub * V;
         if (V == 4) {
-            const f32x4 v = *reinterpret_cast<const f32x4 *>(q);
+            f32x4 v = *reinterpret_cast<const f32x4 *>(q);
+            v -= f32x4{K, K, K, K};
             s += (v[0] + v[1]) + (v[2] + v[3]);
             ss += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
         } else if (V == 2) {
-            const float2 v = *reinterpret_cast<const float2 *>(q);
+            float2 v = *reinterpret_cast<const float2 *>(q);
+            v.x -= K; v.y -= K;
             s += v.x + v.y;
             ss += v.x * v.x + v.y * v.y;
         } else {
-            const float v = *q;
+            const float v = *q - K;
             s += v;
             ss += v * v;
         }
@@ -2067,8 +2069,8 @@ __global__ __launch_bounds__(256) void k_gn_small(const float *__restrict__ x, l
     ds = (red[0] + red[2]) + (red[4] + red[6]);
     dss = (red[1] + red[3]) + (red[5] + red[7]);
     const double cnt = (double)HW * cg;
-    const double mean = ds / cnt;
-    double var = dss / cnt - mean * mean;
+    const double dm = ds / cnt, mean = (double)K + dm;
+    double var = dss / cnt - dm * dm;
     var = var < 0.0 ? 0.0 : var;
     const float rstd = (float)(1.0 / sqrt(var + (double)eps));
     for (int j = tid; j < cg; j += 256) {
@@ -2087,9 +2089,9 @@ __global__ __launch_bounds__(256) void k_gn_small(const float *__restrict__ x, l
     }
 }
 
-// grid (32 groups, N), one wave each: lanes sum the chunk partials (double), then lanes < C/32 write
-// A = rstd*gamma [*(1+scale)], B = (beta - mean*rstd*gamma) [*(1+scale) + shift] for the group's channels
-__global__ __launch_bounds__(64) void k_gn_coef(const float *__restrict__ partial, int nchunks, int HW, int C,
+// grid (32 groups, N), one wave each: lanes sum the chunk partials (double; sums about the group's pivot, read from x again), then lanes
+// < C/32 write A = rstd*gamma [*(1+scale)], B = (beta - mean*rstd*gamma) [*(1+scale) + shift] for the group's channels
+__global__ __launch_bounds__(64) void k_gn_coef(const float *__restrict__ x, long pitch, const float *__restrict__ partial, int nchunks, int HW, int C,
                                                 const float *__restrict__ gamma, const float *__restrict__ beta,
                                                 const float *__restrict__ emb, long emb_pitch, float *__restrict__ cA,
                                                 float *__restrict__ cB, float *__restrict__ gstat, float eps) {
@@ -2107,8 +2109,8 @@ __global__ __launch_bounds__(64) void k_gn_coef(const float *__restrict__ partia
         ss += __shfl_xor(ss, d);
     }
     const double cnt = (double)HW * cg;
-    const double mean = s / cnt;
-    double var = ss / cnt - mean * mean;
+    const double dm = s / cnt, mean = (double)x[(long)n * HW * pitch + g * cg] + dm;
+    double var = ss / cnt - dm * dm;
     var = var < 0.0 ? 0.0 : var;
     const float rstd = (float)(1.0 / sqrt(var + (double)eps));
     for (int j = lane; j < cg; j += 64) {
@@ -3250,7 +3252,7 @@ int conv2d(const ConvArgs &a, const ConvPlan &pl, hipStream_t st) {
 }
 
 static int gn_chunks(int HW, int C) {
-    if ((long)HW * C <= 524288) return 1;   // one 1024-thread workgroup per image: statistics + affine in one launch
+    if ((long)HW * C <= 524288) return 1;   // k_gn_small: one workgroup per (group, image), statistics + affine in one launch
     int c = HW / 256;
     if (c < 1) c = 1;
     if (c > 128) c = 128;
@@ -3275,16 +3277,15 @@ int groupnorm_coef(const View &x, const float *gamma, const float *beta, const f
             hipLaunchKernelGGL(k_gn_small<1>, grid, dim3(256), 0, st, x.p, x.pitch, HW, x.C, gamma, beta, emb, emb_pitch, cA, cB, gstat, eps);
         return check_launch("k_gn_small");
     }
-    int k = (nch == 1 ? 1024 : 512) / cq;
+    int k = 512 / cq;
     if (k < 1) k = 1;
     HL_REQUIRE(cq <= 1024, "groupnorm_coef: C too large");
     const int threads = cq * k > 64 ? cq * k : 64;
     const size_t shm = (size_t)2 * k * x.C * sizeof(float);
-    hipLaunchKernelGGL(k_gn_partial, dim3(nch, x.N), dim3(threads), shm, st, x.p, x.pitch, HW, x.C, nch, scratch, gamma, beta, emb,
-                       emb_pitch, cA, cB, gstat, eps);
+    hipLaunchKernelGGL(k_gn_partial, dim3(nch, x.N), dim3(threads), shm, st, x.p, x.pitch, HW, x.C, nch, scratch);
     int rc = check_launch("k_gn_partial");
-    if (rc || nch == 1) return rc;
-    hipLaunchKernelGGL(k_gn_coef, dim3(32, x.N), dim3(64), 0, st, scratch, nch, HW, x.C, gamma, beta, emb, emb_pitch, cA, cB, gstat, eps);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_gn_coef, dim3(32, x.N), dim3(64), 0, st, x.p, x.pitch, scratch, nch, HW, x.C, gamma, beta, emb, emb_pitch, cA, cB, gstat, eps);
     return check_launch("k_gn_coef");
 }
 

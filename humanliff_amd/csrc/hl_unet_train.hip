@@ -450,13 +450,15 @@ __global__ __launch_bounds__(256) void k_wgrad_finish(const float *__restrict__ 
 // ---------------------------------------------------------------------------------------------
 // forward: u = A[n,c] * x + B[n,c]  (A, B fold GroupNorm32 statistics, affine and the ResBlock's scale / shift), out = act ? silu(u) : u.
 // With du = dout * (act ? silu'(u) : 1) the two reductions everything else follows from are, per (n, c):
-//     S1 = sum_p du,    S2 = sum_p du * x
+//     S1 = sum_p du,    S2 = sum_p du * x        (gstat given - the training backward: S2 = sum_p du * (x - mean of the channel's group), so that
+//                                                 x_hat's sum needs no S2 - mean * S1, a cancellation at the magnitude of mean * S1)
 // (parameter gradients, the scale / shift gradients and the three per-(n,c) coefficients of dx = k1*du + k2*x + k3 are small (N,C)
 // tensor algebra done by the caller).  grid (chunks, N); a thread owns a float4 of channels.  No atomics: the k pixel rows of a workgroup
 // meet in LDS and are added in row order, every workgroup stores its 2C sums to part[n][chunk][2C], and k_gn_bwd_fin adds the chunks
 // in chunk order - the same bits on every run.
 __global__ void k_gn_bwd_reduce(const float *__restrict__ x, long x_pitch, const float *__restrict__ dout, long d_pitch, int HW, int C,
-                                int nchunks, const float *__restrict__ cA, const float *__restrict__ cB, int act, float *__restrict__ part) {
+                                int nchunks, const float *__restrict__ cA, const float *__restrict__ cB, int act, const float *__restrict__ gstat,
+                                float *__restrict__ part) {
     const int cq = C >> 2;
     const int k = blockDim.x / cq;
     const int c4 = threadIdx.x % cq, prow = threadIdx.x / cq;
@@ -466,6 +468,12 @@ __global__ void k_gn_bwd_reduce(const float *__restrict__ x, long x_pitch, const
     const int p0 = chunk * per, p1 = min(HW, p0 + per);
     const f32x4 a = *reinterpret_cast<const f32x4 *>(cA + (long)n * C + c4 * 4), b = *reinterpret_cast<const f32x4 *>(cB + (long)n * C + c4 * 4);
     f32x4 s1 = f32x4{0.f, 0.f, 0.f, 0.f}, s2 = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 mv = f32x4{0.f, 0.f, 0.f, 0.f};                        // (a float4 of channels may straddle groups: each channel its group's mean)
+    if (gstat) {
+        const int cg = C / 32;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) mv[i] = gstat[((long)n * 32 + (c4 * 4 + i) / cg) * 2];
+    }
     auto accum = [&](const f32x4 xv, f32x4 dv) {
         if (act) {
 #pragma unroll
@@ -475,7 +483,7 @@ __global__ void k_gn_bwd_reduce(const float *__restrict__ x, long x_pitch, const
             }
         }
         s1 += dv;
-        s2 += dv * xv;
+        s2 += dv * (xv - mv);
     };
     auto ldx = [&](int pp) { return *reinterpret_cast<const f32x4 *>(x + ((long)n * HW + pp) * x_pitch + c4 * 4); };
     auto ldd = [&](int pp) { return *reinterpret_cast<const f32x4 *>(dout + ((long)n * HW + pp) * d_pitch + c4 * 4); };
@@ -546,10 +554,11 @@ __global__ void k_gn_bwd_apply(const float *__restrict__ x, long x_pitch, const 
 //     k1 = rstd * g,   k2 = -rstd^2 * M2,   k3 = -rstd * M1 + rstd^2 * mean * M2,   M1 = sum_c g S1 / m,  M2 = sum_c g xhS / m,
 //     xhS = sum_p du * x_hat = rstd * (S2 - mean * S1),   m = (C/32) * HW;
 // d gamma = sum_n (1 + scale) xhS,  d beta = sum_n (1 + scale) S1,  d scale = gamma * xhS + beta * S1,  d shift = S1.
+// centred: S2 arrives as sum_p du * (x - mean) (k_gn_bwd_reduce with gstat), xhS = rstd * S2.
 __global__ __launch_bounds__(64) void k_gn_bwd_coef(const float *__restrict__ S, const float *__restrict__ gstat, const float *__restrict__ gamma,
                                                     const float *__restrict__ beta, const float *__restrict__ ss, int N, int HW, int C,
                                                     float *__restrict__ k1, float *__restrict__ k2, float *__restrict__ k3,
-                                                    float *__restrict__ dgamma, float *__restrict__ dbeta, float *__restrict__ dss) {
+                                                    float *__restrict__ dgamma, float *__restrict__ dbeta, float *__restrict__ dss, int centred) {
     const int g = blockIdx.x, lane = threadIdx.x, cg = C / 32;
     const float m = (float)cg * (float)HW;
     for (int c0 = 0; c0 < cg; c0 += 64) {                          // (cg <= 64 for every C <= 2048: one trip)
@@ -565,7 +574,7 @@ __global__ __launch_bounds__(64) void k_gn_bwd_coef(const float *__restrict__ S,
                 const float s1 = S[((long)n * C + cc) * 2], s2 = S[((long)n * C + cc) * 2 + 1];
                 const float gh = gamma[cc] * (ss ? 1.f + ss[(long)n * 2 * C + cc] : 1.f);
                 a1 += gh * s1;
-                a2 += gh * (rstd * (s2 - mean * s1));
+                a2 += gh * (rstd * (centred ? s2 : s2 - mean * s1));
             }
 #pragma unroll
             for (int d = 32; d > 0; d >>= 1) { a1 += __shfl_xor(a1, d); a2 += __shfl_xor(a2, d); }
@@ -573,7 +582,7 @@ __global__ __launch_bounds__(64) void k_gn_bwd_coef(const float *__restrict__ S,
             if (on) {
                 const float s1 = S[((long)n * C + c) * 2], s2 = S[((long)n * C + c) * 2 + 1];
                 const float one_s = ss ? 1.f + ss[(long)n * 2 * C + c] : 1.f;
-                const float xhS = rstd * (s2 - mean * s1);
+                const float xhS = rstd * (centred ? s2 : s2 - mean * s1);
                 k1[(long)n * C + c] = rstd * gamma[c] * one_s;
                 k2[(long)n * C + c] = -rstd * rstd * M2;
                 k3[(long)n * C + c] = -rstd * M1 + rstd * rstd * mean * M2;
@@ -728,8 +737,8 @@ static int gn_bwd_chunks(int HW, int C) {
 
 size_t hl_gn_backward_scratch_bytes(int N, int HW, int C) { return (size_t)N * gn_bwd_chunks(HW, C) * 2 * C * sizeof(float); }
 
-int hl_gn_backward_reduce(const float *x, long x_pitch, const float *dout, int N, int HW, int C, const float *coefA, const float *coefB,
-                          int silu, float *S, void *scratch, size_t scratch_bytes, void *stream) {
+static int gn_backward_reduce(const float *x, long x_pitch, const float *dout, int N, int HW, int C, const float *coefA, const float *coefB,
+                              int silu, const float *gstat, float *S, void *scratch, size_t scratch_bytes, void *stream) {
     HL_REQUIRE(x && dout && coefA && coefB && S && C % 4 == 0 && x_pitch % 4 == 0 && C <= 4096, "hl_gn_backward_reduce: bad argument");
     HL_REQUIRE(scratch && scratch_bytes >= hl_gn_backward_scratch_bytes(N, HW, C),
                "hl_gn_backward_reduce: scratch too small (%zu bytes, hl_gn_backward_scratch_bytes says %zu)", scratch_bytes,
@@ -739,11 +748,16 @@ int hl_gn_backward_reduce(const float *x, long x_pitch, const float *dout, int N
     const int threads = cq * k, chunks = gn_bwd_chunks(HW, C);
     float *part = static_cast<float *>(scratch);
     hipLaunchKernelGGL(k_gn_bwd_reduce, dim3(chunks, N), dim3(threads), (size_t)k * 2 * C * sizeof(float), (hipStream_t)stream, x, x_pitch, dout,
-                       (long)C, HW, C, chunks, coefA, coefB, silu, part);
+                       (long)C, HW, C, chunks, coefA, coefB, silu, gstat, part);
     int rc = check_launch("k_gn_bwd_reduce");
     if (rc) return rc;
     hipLaunchKernelGGL(k_gn_bwd_fin, dim3((2 * C + 63) / 64, N), dim3(256), 0, (hipStream_t)stream, part, chunks, 2 * C, S);
     return check_launch("k_gn_bwd_fin");
+}
+
+int hl_gn_backward_reduce(const float *x, long x_pitch, const float *dout, int N, int HW, int C, const float *coefA, const float *coefB,
+                          int silu, float *S, void *scratch, size_t scratch_bytes, void *stream) {
+    return gn_backward_reduce(x, x_pitch, dout, N, HW, C, coefA, coefB, silu, nullptr, S, scratch, scratch_bytes, stream);
 }
 
 int hl_gn_backward_apply(const float *x, long x_pitch, const float *dout, int N, int HW, int C, const float *coefA, const float *coefB,
@@ -779,10 +793,10 @@ int hl_groupnorm_train_backward(const float *x, const float *dout, int N, int H,
     HL_REQUIRE(scratch && scratch_bytes >= need, "hl_groupnorm_train_backward: scratch too small (%zu bytes, hl_groupnorm_train_backward_scratch_bytes says %zu)",
                scratch_bytes, need);
     float *S = static_cast<float *>(scratch), *k1 = S + (size_t)N * C * 2, *k2 = k1 + (size_t)N * C, *k3 = k2 + (size_t)N * C;
-    int rc = hl_gn_backward_reduce(x, C, dout, N, H * W, C, coefA, coefB, silu, S, k3 + (size_t)N * C, part_bytes, stream);
+    int rc = gn_backward_reduce(x, C, dout, N, H * W, C, coefA, coefB, silu, gstat, S, k3 + (size_t)N * C, part_bytes, stream);
     if (rc) return rc;
     hipLaunchKernelGGL(k_gn_bwd_coef, dim3(32), dim3(64), 0, (hipStream_t)stream, S, gstat, gamma, beta, scale_shift, N, H * W, C, k1, k2, k3, dgamma,
-                       dbeta, dscale_shift);
+                       dbeta, dscale_shift, 1);
     rc = check_launch("k_gn_bwd_coef");
     if (rc || !dx) return rc;
     return hl_gn_backward_apply(x, C, dout, N, H * W, C, coefA, coefB, silu, k1, k2, k3, nullptr, dx, stream);

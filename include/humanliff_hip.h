@@ -593,12 +593,17 @@ int hl_groupnorm_train_forward_eps(const float *x, int N, int H, int W, int C, c
  * with integer atomics: order-free, bit-reproducible) - the tensor is not read again; *h_used_stats returns nonzero when the epilogue
  * emitted them, 0 when the kernel
  * path taken emits none and the statistics were computed from the tensor instead.  scratch: hl_conv2d_gn_scratch_bytes(...), the
- * arguments of hl_conv2d_scratch_bytes (the output's totals and a GroupNorm pass's scratch in front of the convolution's own room). */
+ * arguments of hl_conv2d_scratch_bytes (the output's totals and a GroupNorm pass's scratch in front of the convolution's own room).
+ * Accuracy: the epilogue totals are sums of raw x and x^2 - within 4x the error of the reference's fp32 F.group_norm (+ 2e-6) while the stored tensor's groups sit at
+ * mean/std <= 10, (mean/std)^2 beyond (1.5e-4 at 25, 2.2e-3 at 80) (csrc/hl_stats.h). */
 size_t hl_conv2d_gn_scratch_bytes(int conv_mode, int N, int H, int W, int Cin, int Cout, int ks, int stride, int upsample, int with_gn);
 int hl_conv2d_nhwc_gn(int conv_mode, const float *in, int N, int H, int W, int Cin, const float *w_oihw, const float *bias, int Cout,
                       int ks, int stride, int upsample, const float *coefA, const float *coefB, int silu, const float *residual,
                       float *out, const float *gamma, const float *beta, float *next_coefA, float *next_coefB, int *h_used_stats,
                       void *scratch, size_t scratch_bytes, void *stream);
+/* GroupNorm32 of x folded to y = x*A[n,c] + B[n,c] (nn.py:17-19,100; emb = the ResBlock's [scale | shift] rows, unet.py:203-206).  Accuracy: the statistics are taken about a
+ * pivot (the group's first value), so x*A + B stays within 4x the error of the reference's fp32 F.group_norm (+ 2e-6) against float64 up to mean/std = 100 and for
+ * constant groups; scratch: hl_groupnorm_scratch_bytes(N). */
 int hl_groupnorm_coef(const float *x, int N, int H, int W, int C, const float *gamma, const float *beta,
                       const float *emb /* (N,2C) or NULL */, float *coefA, float *coefB, void *scratch,
                       size_t scratch_bytes, void *stream);
@@ -609,9 +614,9 @@ int hl_attention_nhwc(const float *qkv, int N, int T, int C, int heads, float *o
  * are split as they are (their error enters the scores absolutely and the softmax flattens it). */
 int hl_attention_nhwc_mode(int conv_mode, const float *qkv, int N, int T, int C, int heads, float *out, void *stream);
 /* Backward of hl_attention_nhwc (QKVAttention, unet.py:255-274, under train_util.py:200-246): qkv as in the forward, out = the forward's
- * output (N,T,C), dout = its gradient -> dqkv (N,T,3C).  fp32 MFMA, probabilities recomputed (flash-style), every output summed by one wave in
- * a fixed order (deterministic).  scratch: hl_attention_backward_scratch_bytes() (per query: row maximum, 1/row sum, dO.O; head sizes that are
- * not a multiple of 32 materialise P and dS there instead). */
+ * output (N,T,C; required non-NULL, no longer read: D below comes from P and dP), dout = its gradient -> dqkv (N,T,3C).  fp32 MFMA, probabilities recomputed
+ * (flash-style), every output summed by one wave in a fixed order (deterministic).  scratch: hl_attention_backward_scratch_bytes() (per query: row maximum,
+ * 1/row sum, D = sum_j P_ij dP_ij; head sizes that are not a multiple of 32 materialise P and dS there instead). */
 size_t hl_attention_backward_scratch_bytes(int N, int T, int C, int heads);
 int hl_attention_nhwc_backward(const float *qkv, const float *out, const float *dout, int N, int T, int C, int heads, float *dqkv,
                                void *scratch, size_t scratch_bytes, void *stream);

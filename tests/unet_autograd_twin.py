@@ -30,8 +30,13 @@ def _silu(x):
     return x * th.sigmoid(x)
 
 
+def _f32(x):
+    """fp32 as the reference computes - except that a float64 tensor (a float64 model: the high-precision restatement some tests use) stays."""
+    return x if x.dtype == th.float64 else x.float()
+
+
 def _norm(m, x):
-    return F.group_norm(x.float(), m.num_groups, m.weight, m.bias, m.eps)
+    return F.group_norm(_f32(x), m.num_groups, m.weight, m.bias, m.eps)
 
 
 def _res_block(m, x, emb):
@@ -60,7 +65,7 @@ def _attention(m, x):
     ch = qkv.shape[1] // 3
     q, k, v = qkv.split(ch, dim=1)
     s = 1.0 / math.sqrt(math.sqrt(ch))
-    w = th.softmax(th.einsum("bct,bcs->bts", q * s, k * s).float(), dim=-1)
+    w = th.softmax(_f32(th.einsum("bct,bcs->bts", q * s, k * s)), dim=-1)
     a = th.einsum("bts,bcs->bct", w, v).reshape(b, -1, hh * ww)
     return (xf + m.proj_out(a)).reshape(b, c, hh, ww)
 
@@ -80,7 +85,7 @@ def _xattn(a, x, context):
 def _spatial_transformer(m, x, context):
     """SpatialTransformer.forward (spatial_transformer.py:165-178) with its BasicTransformerBlock (:128-134)."""
     b, c, hh, ww = x.shape
-    h = m.proj_in(F.group_norm(x.float(), 32, m.norm.weight, m.norm.bias, m.norm.eps))
+    h = m.proj_in(F.group_norm(_f32(x), 32, m.norm.weight, m.norm.bias, m.norm.eps))
     h = h.reshape(b, c, hh * ww).permute(0, 2, 1)
     for blk in m.transformer_blocks:
         h = _xattn(blk.attn1, blk.norm1(h), None) + h
@@ -120,11 +125,11 @@ def forward_autograd(model, x, timesteps, x_cond=None, y=None):
             x_cond = roll(x_cond)
     if model.cond_type == "concat" and x_cond is not None:   # unet.py:572-573
         x, x_cond = th.cat([x, x_cond], dim=1), None
-    emb = model.time_embed[2](_silu(model.time_embed[0](_embedding(timesteps, model.model_channels))))
+    emb = model.time_embed[2](_silu(model.time_embed[0](_embedding(timesteps, model.model_channels).to(_f32(x).dtype))))
     context = None
     if model.cond_type in ("AdaGN", "cross_attention"):   # unet.py:574-582
         assert x_cond is not None, f"cond_type='{model.cond_type}' needs x_cond"
-        xp = model.conv_proj_2(model.conv_proj_1(x_cond.float()))
+        xp = model.conv_proj_2(model.conv_proj_1(_f32(x_cond)))
         xp = model.linear(xp.reshape(xp.shape[0], -1))
         if model.cond_type == "AdaGN":
             emb = emb + xp
@@ -133,7 +138,7 @@ def forward_autograd(model, x, timesteps, x_cond=None, y=None):
     if model.num_classes is not None:
         emb = emb + model.label_emb(y)
     hs = []
-    h = x.float()
+    h = _f32(x)
     for blk in model.input_blocks:
         h = _run(blk, h, emb, context)
         hs.append(h)
@@ -141,7 +146,7 @@ def forward_autograd(model, x, timesteps, x_cond=None, y=None):
     if model.cond_type == "controlnet":
         assert x_cond is not None, "cond_type='controlnet' needs x_cond (zeros for the first layer)"
         hs_cond = []
-        hc = x.float() + x_cond.float()
+        hc = _f32(x) + _f32(x_cond)
         for blk, proj in zip(model.input_blocks_cond, model.input_blocks_proj_cond):
             hc = proj(_run(blk, hc, emb))
             hs_cond.append(hc)
