@@ -120,13 +120,32 @@ def deform_tables(model, params, t_params, vertices):
     return out
 
 
+def prebuilt_tables(tp_input, b=0):
+    """tp_input['deform'] of entry b, or None without the key: tables made ahead of the render call (humanliff_amd/body.py:
+    PosedBody.tp_input), as deform_tables returns them - (verts4 (V,4), table (V,36), R host (3,3), Th host (3,)).  One such tuple
+    (batch 1) or a sequence of them, indexed by entry like `params`.  With it the caller skips deform_tables and its host fingerprint."""
+    d = tp_input.get('deform') if hasattr(tp_input, 'get') else None
+    if d is None:
+        return None
+    if not (len(d) == 4 and torch.is_tensor(d[0]) and d[0].dim() == 2):
+        d = d[b]
+    elif b != 0:
+        raise ValueError("tp_input['deform'] holds the tables of one subject, the batch has more: pass one tuple per entry")
+    verts4, table, Rh, Th = d
+    if not (verts4.is_cuda and verts4.dim() == 2 and verts4.shape[1] == 4 and tuple(table.shape) == (verts4.shape[0], 36)):
+        raise ValueError("tp_input['deform']: verts4 (V,4) and table (V,36) device tensors expected")
+    return (verts4.contiguous(), table.contiguous(), np.ascontiguousarray(Rh, dtype=np.float32).reshape(3, 3),
+            np.ascontiguousarray(Th, dtype=np.float32).reshape(3))
+
+
 def deform_target2c(model, tp_input, pts, viewdir=None, return_ids=False):
     """Renderer.deform_target2c for use_canonical_space=True, batch 1: pts (1,P,3) [, viewdir (1,P,3)] on the device ->
     (canonical_pts (1,P,3), canonical_viewdir (1,P,3) or None, box_warp = tp_input['t_world_bounds'])."""
     assert pts.dim() == 3 and pts.shape[0] == 1, "batch size 1 (one posed subject per call)"
     if not pts.is_cuda:
         raise RuntimeError("deform_target2c needs CUDA(HIP) tensors; there is no CPU path")
-    verts4, table, Rh, Th = deform_tables(model, tp_input["params"], tp_input["t_params"], tp_input["vertices"].to(pts.device))
+    verts4, table, Rh, Th = prebuilt_tables(tp_input) or \
+        deform_tables(model, tp_input["params"], tp_input["t_params"], tp_input["vertices"].to(pts.device))
     P = pts.shape[1]
     p = pts[0].to(torch.float32).contiguous()
     d = viewdir[0].to(torch.float32).contiguous() if viewdir is not None else None

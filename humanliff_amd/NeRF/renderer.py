@@ -44,7 +44,7 @@ _SIDE_STREAMS = {}   # device -> HIP streams of Renderer.subject_streams (proces
 
 class Renderer(nn.Module):
     def __init__(self, use_canonical_space=True, num_instances=1, triplane_dim=256, triplane_ch=18,
-                 smpl_type='smpl', test=False):
+                 smpl_type='smpl', test=False, body_model=None):
         super().__init__()
         self.use_canonical_space = use_canonical_space
         self.num_instances = num_instances
@@ -64,8 +64,12 @@ class Renderer(nn.Module):
         # The reference loads the SMPL(-X) asset here (renderer.py:41-50: assets/SMPL_NEUTRAL.pkl -> SMPL_to_tensor); it is only
         # used by the canonical-space deformation.  The asset is licensed data and not shipped: assign the dict of tensors
         # (keys v_template, shapedirs, posedirs, J_regressor, kintree_table, weights) to `SMPL_NEUTRAL` before rendering with
-        # use_canonical_space=True.
+        # use_canonical_space=True - or hand the file, a dict or a humanliff_amd.body.BodyModel to
+        # `load_body_model` / the `body_model` keyword, which loads it the way the reference does.
         self.SMPL_NEUTRAL = None
+        self.body_model = None
+        if body_model is not None:
+            self.load_body_model(body_model)
         # depth_map = (depth - near) / (far - near + 1e-5), clamped to [0,1] by this twin (renderer.py:271-274); the recon_NeRF twin
         # (recon_NeRF/lib/renderer.py:288) does not clamp and clears the second flag
         self._depth_flags = _lib.HL_RENDER_NORMALIZE_DEPTH | _lib.HL_RENDER_CLAMP_DEPTH
@@ -85,6 +89,17 @@ class Renderer(nn.Module):
                                              # planes, six partial products (k_march_plw<3>, HL_RENDER_MLP_BF16X3); "fp32" = v_mfma_f32_32x32x2_f32
                                              # (k_march).  Same tolerances, tested on all three; rgb of the three within 7e-7 of each other on full views.
         self._ws = None
+
+    def load_body_model(self, path_or_dict, device=None):
+        """What the reference's constructor does with assets/SMPL_NEUTRAL.pkl (renderer.py:41-45): SMPL_NEUTRAL = the SMPL_to_tensor
+        dict on the device, faces = its 'f'.  Takes a path (.pkl / .npz), a dict, or a BodyModel; keeps the BodyModel, whose pose()
+        makes the tp_input of a posed frame (humanliff_amd/body.py)."""
+        from ..body import BodyModel, load_body_model
+        model = path_or_dict if isinstance(path_or_dict, BodyModel) else load_body_model(path_or_dict, device)
+        self.body_model = model
+        self.SMPL_NEUTRAL = model.tensors
+        self.faces = self.SMPL_NEUTRAL['f']
+        return model
 
     # ---- packing caches ------------------------------------------------------------------------
     def _mlp_tensors(self):
@@ -323,7 +338,7 @@ class Renderer(nn.Module):
             return t
         dfm = None
         if tp_canonical is not None:      # per-subject deformation tables (NeRF/deform.py); `bounds` is t_world_bounds here
-            from .deform import deform_tables
+            from .deform import deform_tables, prebuilt_tables
             if self.SMPL_NEUTRAL is None:
                 raise RuntimeError("use_canonical_space=True needs the body model: set renderer.SMPL_NEUTRAL to the SMPL_to_tensor dict")
             def rec(t):                   # inputs of the caller's stream that this subject's (side) stream reads
@@ -333,8 +348,12 @@ class Renderer(nn.Module):
             one = lambda d: {k: rec(v[b:b + 1]) for k, v in d.items()}  # noqa: E731
             for v in self.SMPL_NEUTRAL.values():
                 rec(v)
-            dfm = deform_tables(self.SMPL_NEUTRAL, one(tp_canonical['params']), one(tp_canonical['t_params']),
-                                rec(tp_canonical['vertices'][b:b + 1].to(dev)))
+            dfm = prebuilt_tables(tp_canonical, b)      # tables posed ahead (humanliff_amd/body.py): no op chain, no host read
+            if dfm is not None:
+                rec(dfm[0]), rec(dfm[1])
+            else:
+                dfm = deform_tables(self.SMPL_NEUTRAL, one(tp_canonical['params']), one(tp_canonical['t_params']),
+                                    rec(tp_canonical['vertices'][b:b + 1].to(dev)))
         parts = []
         for i in range(0, R, rc):
             sl = slice(i, min(R, i + rc))
@@ -348,7 +367,7 @@ class Renderer(nn.Module):
         """use_canonical_space=True (renderer.py:114-132, 192-201, 242-246): every sample point and its unit ray direction go through
         deform_target2c (1-NN body vertex, inverse LBS, blend-shape offsets, forward LBS into the big pose) before the tri-plane
         lookup in tp_input['t_world_bounds'].  One posed subject per call (batch 1)."""
-        from .deform import deform_tables
+        from .deform import deform_tables, prebuilt_tables
         if self.SMPL_NEUTRAL is None:
             raise RuntimeError("use_canonical_space=True needs the body model: set renderer.SMPL_NEUTRAL to the SMPL_to_tensor dict")
         if self.triplane_ch != 27:
@@ -371,8 +390,8 @@ class Renderer(nn.Module):
                 from .cpu_rng import rand_like_cpu
                 u, pending_draw = rand_like_cpu([R, n_importance], dev)
         try:                                      # (the generator is advanced whatever happens below: see render)
-            verts4, table, Rh, Th = deform_tables(self.SMPL_NEUTRAL, tp_input['params'], tp_input['t_params'],
-                                                  tp_input['vertices'].to(dev))
+            verts4, table, Rh, Th = prebuilt_tables(tp_input) or \
+                deform_tables(self.SMPL_NEUTRAL, tp_input['params'], tp_input['t_params'], tp_input['vertices'].to(dev))
             L = _lib.lib()
             packed, pp = self._packed_mlp(dev), self._packed_planes(tri_planes[0])
             ws = self._workspace(L.hl_render_canonical_workspace_bytes(R, n_samples, n_importance), dev)
@@ -430,10 +449,11 @@ class Renderer(nn.Module):
             # renderer.py:311-314: the lattice spans world_bounds, every point goes through deform_target2c and is looked up in
             # t_world_bounds.  Same column-rays; hl_deform_rays writes their canonical points, hl_render_eval_points evaluates them
             # (full MLP: the density is the first value of the record)
-            from .deform import deform_tables
+            from .deform import deform_tables, prebuilt_tables
             if self.SMPL_NEUTRAL is None:
                 raise RuntimeError("use_canonical_space=True needs the body model: set renderer.SMPL_NEUTRAL to the SMPL_to_tensor dict")
-            verts4, table, Rh, Th = deform_tables(self.SMPL_NEUTRAL, tp_input['params'], tp_input['t_params'], tp_input['vertices'].to(dev))
+            verts4, table, Rh, Th = prebuilt_tables(tp_input) or \
+                deform_tables(self.SMPL_NEUTRAL, tp_input['params'], tp_input['t_params'], tp_input['vertices'].to(dev))
             tb = tp_input['t_world_bounds'].reshape(-1, 2, 3)[0].to(device=dev, dtype=torch.float32).contiguous()
             pc, dc = torch.empty((T32 * N, 4), device=dev), torch.empty((T32 * N, 4), device=dev)
             rec, scr = torch.empty((T32 * N, 4), device=dev), torch.empty(4, device=dev)

@@ -59,3 +59,14 @@ def get_rays(H, W, K, R, T, device=None):
     float32 before use, :422-423); bounds are irrelevant here, so a unit box is passed."""
     ro, rd, _, _, _ = camera_rays(H, W, K, R, T, [[-1.0, -1.0, -1.0], [1.0, 1.0, 1.0]], device, return_mask=False)
     return ro.view(H, W, 3), rd.view(H, W, 3)
+
+
+def prepare_input(body_model, params):
+    """prepare_input (:141-182) for smpl_type='smpl' on the device: `params` holds 'poses' (1,72) or (F,72) and 'shapes' (device
+    tensors), 'R' (3,3) and 'Th' (1,3) (host arrays, as prepare_smpl_params makes them) -> (world_bounds (2,3), vertices (V,3), params,
+    joints (J,3)) as device float32 tensors, with a leading frame axis when poses has more than one row.  The PosedBody behind them
+    (tables for the renderer included) is body_model.pose(...) of the same arguments (humanliff_amd/body.py)."""
+    posed = body_model.pose(params['poses'], params['shapes'], params.get('R'), params.get('Th'))
+    if posed.F == 1:
+        return posed.world_bounds[0], posed.vertices[0], params, posed.joints[0]
+    return posed.world_bounds, posed.vertices, params, posed.joints

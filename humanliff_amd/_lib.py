@@ -189,6 +189,11 @@ SIGNATURES = {
     "hl_ray_views_prepare": (_i, [_p, _p, _i64, _i, _i, _p, _p, _p]),
     "hl_ray_batch": (_i, [_p, _i, _p, _i, _p, _p, _p, _i64, _i, _i, _i, C.c_double, _p, C.c_uint64, C.c_uint64, _i, _p, _p, _p, _p, _p, _p,
                           _p, _p, _p, _p]),
+    "hl_body_packed_bytes": (_sz, [_i, _i, _i]),
+    "hl_body_pack": (_i, [_p, _p, _i, _p, _p, _p, _i, _i, _i, _p, _p]),
+    "hl_body_chunk_frames": (_i, []),
+    "hl_body_pose_workspace_bytes": (_sz, [_i, _i]),
+    "hl_body_pose": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _i, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
 }
 
 

@@ -789,6 +789,35 @@ int hl_ray_batch(const int64_t *image_idx, int bs, const void *images, int image
                  int max_rounds, float *rgb, float *ray_o, float *ray_d, float *near, float *far, float *bkgd_msk,
                  unsigned char *mask_at_box, int32_t *coord, int32_t *n_valid, void *stream);
 
+/* ---- posing the body model: linear blend skinning, world bounds and the deformation tables (smpl/smpl_numpy.py SMPL.__call__,
+ *      SynBodyView_datasets.py:141-182 prepare_input, and the per-vertex tables of NeRF/deform.py: deform_tables) ----
+ * Contract: DESIGN.md "Body model"; csrc/hl_body.hip.  Contiguous fp32 device arrays, enqueue-only on `stream`, nothing allocated,
+ * every sum in a fixed order (no float atomics): the same inputs give the same bits, alone or inside a batch of frames.
+ * V vertices, 2 <= J <= 64 joints, P = 9 (J - 1) pose features, 1 <= S <= Sp <= 16 shape coefficients, F >= 1 frames.
+ *   hl_body_pack (once per model): v_template (V,3), shapedirs (V,3,sd_cols) of which the first Sp columns are kept, posedirs (V,3,P),
+ *     J_regressor (J,V), weights (V,J) -> packed, hl_body_packed_bytes(V, J, Sp) bytes, as floats in this order:
+ *       posedirs (P,3,V) | shapedirs (Sp,3,V) | weights (J,V) | v_template (3,V) | J_regressor v_template (J,3) |
+ *       J_regressor shapedirs (J,3,Sp)
+ *     - coefficient-major, so a thread per vertex reads neighbouring addresses in neighbouring lanes.
+ *   hl_body_pose: parents (J) int32 with parents[i] < i for i >= 1 (parents[0] is not read).  poses (F,3J) axis-angle; shapes (S) with
+ *     shapes_stride 0 (shared) or (F,S) with shapes_stride S; rt: per frame 12 floats, the row-major 3x3 R and then Th, rt_stride 0 or 12.
+ *     big (V,16), optional: a big-pose row per vertex as big_out writes it; needed for `table`.  Outputs, each optional (NULL):
+ *       vertices (F,V,3) world = v_smpl R^T + Th;  joints (F,J,3) posed joints in the world;  bounds (F,2,3) min / max of the frame's
+ *       vertices, - / + 0.05, y once more by 0.05 (needs vertices);  verts4 (F,V,4) = (vertices - Th) R, w = 0;  table (F,V,36), the row
+ *       of hl_deform_points: t[3] Rinv[9] pose_off[3] shape_off[3] pose_off_big[3] Rbig[9] tbig[3] pad[3];
+ *       big_out (F,V,16): blended R[9] t[3] pose_off[3] pad[1].
+ *     workspace: hl_body_pose_workspace_bytes(J, F) bytes; afterwards it holds A (F,J,16), the joints' 4x4 transforms with the rest-joint
+ *     term removed, followed by the pose features (F,P).  hl_body_chunk_frames(): frames a workgroup of the skinning pass keeps in
+ *     registers per pass over posedirs. */
+size_t hl_body_packed_bytes(int V, int J, int Sp);
+int hl_body_pack(const float *v_template, const float *shapedirs, int sd_cols, const float *posedirs, const float *J_regressor,
+                 const float *weights, int V, int J, int Sp, float *packed, void *stream);
+int hl_body_chunk_frames(void);
+size_t hl_body_pose_workspace_bytes(int J, int F);
+int hl_body_pose(const float *packed, const int32_t *parents, int V, int J, int Sp, int S, int F, const float *poses, const float *shapes,
+                 int shapes_stride, const float *rt, int rt_stride, const float *big, float *vertices, float *joints, float *bounds,
+                 float *verts4, float *table, float *big_out, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
