@@ -309,6 +309,8 @@ __global__ __launch_bounds__(256, 1) void k_conv_h16(const ConvK p) {
 // two-plane activation image; weight ring two k-steps deep; the epilogue exchange in two channel halves of 128 slots x 96 channels (50 KB).
 // Round 7: the 4 waves split N only (1 x 4), each owns all 128 pixels x 48 channels as 8 x 3 tiles of v_mfma_f32_16x16x32_f16 - a weight fragment
 // feeds 8 tiles instead of 2, which halves the weight bytes per FLOP (2048-workgroup launch at B = 4: 525 -> 479 us, profiles/r07_h2s_16x16x32_ab.md).
+// k_conv_h2s_ph: the same body for the Upsample layers, four 2x2-tap phases of the source instead of nine taps of the upsampled image (256 px, B = 4: 463 -> 231 us,
+// profiles/upsample_phases_ab.md).
 // ---------------------------------------------------------------------------------------------------------------------------------------------
 constexpr int H2S_PH = 10, H2S_NPIX = H2S_PH * H16_PW;               // patch of an 8x16 tile: 10 rows x 18 columns
 constexpr int H2S_PLANE = H2S_PH * H16_LP * 64, H2S_STG = 2 * H2S_PLANE;   // bytes per plane / per stage (both planes)
@@ -446,11 +448,20 @@ __device__ __forceinline__ void h2s_epilogue(const ConvK &p, char *lds, ScatterF
 __device__ __forceinline__ float h2s_silu(float v, float kq) { return v * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(kq * v)); }
 __device__ __forceinline__ float wave_uniform(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); }
 
-__global__ __launch_bounds__(256, 2) void k_conv_h2s(const ConvK p) {
+// PH (k_conv_h2s_ph): the nearest-x2 upsample + 3x3 convolution as four 2x2-tap phase convolutions of the SOURCE image.  The nine taps of output
+// pixel (2i + py, 2j + px) read only the four source pixels (i - 1 + py + a, j - 1 + px + b), a, b in {0, 1}, and the source's zero border is the upsampled
+// image's; the weights of tap (a, b) are the sums of the 3x3 ones that fall on it (h2p_taps, packed once by k_pack_conv_h2p) - 4 / 9 of the products for
+// the same mathematics.  A workgroup = the 8x16 source positions of ONE phase (tile index & 3: the four phases of a tile are neighbours in the grid, so
+// they run on one XCD and share the patch in L2), its 128 pixels stored at (2i + py, 2j + px); patch = the 9x17 source pixels from (i0 - 1 + py,
+// j0 - 1 + px) in the same [plane][10x18] layout, tap (a, b) = row mf + a, aoff[b]; a chunk of 32 channels is 4 k-steps.
 #if __HIP_DEVICE_COMPILE__
+template <bool PH>
+__device__ __forceinline__ void conv_h2s_body(const ConvK &p) {
     constexpr unsigned OOB = 0x80000000u;
-    constexpr int NU = H2S_NPIX * 4, NUT = (NU + 255) / 256;      // staging units (pixel, 8-channel group): 720 -> 3 per thread
-    constexpr int ST0 = 6;                                         // k-step behind which the next chunk's patch goes to LDS (3 units, one per step)
+    constexpr int PW = PH ? H16_PW - 1 : H16_PW, PR = PH ? H2S_PH - 1 : H2S_PH;   // patch columns / rows
+    constexpr int NU = PR * PW * 4, NUT = (NU + 255) / 256;       // staging units (pixel, 8-channel group): 720 (PH: 612) -> 3 per thread
+    constexpr int NS = PH ? 4 : 9;                                 // k-steps (taps) per chunk
+    constexpr int ST0 = NS - NUT;                                  // k-step from which the next chunk's patch goes to LDS (3 units, one per step: the last three)
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -459,8 +470,10 @@ __global__ __launch_bounds__(256, 2) void k_conv_h2s(const ConvK p) {
     const int q8 = total >> 3, r8 = total & 7;
     const int wi = xcd * q8 + (xcd < r8 ? xcd : r8) + slot;
     const int tb = __builtin_amdgcn_readfirstlane(wi / p.n_nblocks), nb = wi - tb * p.n_nblocks;
-    const int bw = p.Wout >> 4, bh = p.Hout >> 3;
-    const int img = tb / (bw * bh), brem = tb - img * (bw * bh);
+    const int ph = PH ? tb & 3 : 0, phy = ph >> 1, phx = ph & 1;   // PH: the workgroup's phase; its tiles lie on the source grid
+    const int tl = PH ? tb >> 2 : tb, Ht = PH ? p.Hin : p.Hout, Wt = PH ? p.Win : p.Wout;
+    const int bw = Wt >> 4, bh = Ht >> 3;
+    const int img = tl / (bw * bh), brem = tl - img * (bw * bh);
     const int y0 = (brem / bw) * 8, x0 = (brem - (brem / bw) * bw) * 16;
     const int nch = p.Cin >> 5;
     const unsigned pitch4 = (unsigned)p.in_pitch * (p.in16 ? 2u : 4u);
@@ -468,21 +481,21 @@ __global__ __launch_bounds__(256, 2) void k_conv_h2s(const ConvK p) {
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(
         (void *)p.in, (short)0, (int)((long)p.N * p.Hin * p.Win * pitch4 * (p.in16 == 2 ? 2 : 1)), 0x00020000);
     const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)p.wf, (short)0, (int)((long)p.n_nblocks * nch * 18 * 6144 * 2), 0x00020000);
+        (void *)p.wf, (short)0, (int)((long)(PH ? 4 : 1) * p.n_nblocks * nch * NS * 24576), 0x00020000);
 
     // GroupNorm affine (+ SiLU) of the INPUT applied while staging (ConvK::cA / cB arrays, or ConvK::gn: coefficients formed here from the producers' group
     // totals): no pre-pass over the tensor.  The table sits behind the stages; padding pixels are zero AFTER the activation (the convolution pads the activated tensor).
-    const bool aff = p.cA != nullptr || p.gn.gt != nullptr;
+    const bool aff = !PH && (p.cA != nullptr || p.gn.gt != nullptr);      // (an Upsample convolution follows a raw tensor)
     float *sA = reinterpret_cast<float *>(lds + H2S_LDS), *sB = sA + p.Cin;
     float sx = 1.f, kq = -1.44269504088896341f;                    // power-of-two scale of the staged activations (hl_stats.h), -log2(e) / sx
     unsigned sv[NUT], sl[NUT];
 #pragma unroll
     for (int j = 0; j < NUT; ++j) {
         const int u = tid + 256 * j, pix = u >> 2, grp = u & 3;
-        const int py = pix / H16_PW, px = pix - py * H16_PW;
-        const int y = y0 - 1 + py, x = x0 - 1 + px;
-        const bool ok = u < NU && y >= 0 && y < p.Hout && x >= 0 && x < p.Wout;
-        const int ys = p.ups ? y >> 1 : y, xs = p.ups ? x >> 1 : x;
+        const int py = pix / PW, px = pix - py * PW;
+        const int y = y0 - 1 + phy + py, x = x0 - 1 + phx + px;
+        const bool ok = u < NU && y >= 0 && y < Ht && x >= 0 && x < Wt;
+        const int ys = !PH && p.ups ? y >> 1 : y, xs = !PH && p.ups ? x >> 1 : x;
         sv[j] = ok ? (unsigned)((img * p.Hin + ys) * p.Win + xs) * pitch4 + grp * (p.in16 ? 16 : 32) : OOB;
         sl[j] = u < NU ? (unsigned)((py * H16_LP + px) * 64 + ((grp ^ ((px >> 2) & 3)) << 4)) : (unsigned)(2 * H2S_STG + (tid & 63) * 16);
     }
@@ -534,11 +547,11 @@ __global__ __launch_bounds__(256, 2) void k_conv_h2s(const ConvK p) {
     unsigned wof[3];
 #pragma unroll
     for (int f = 0; f < 3; ++f) wof[f] = h2s_wfrag_off(wave, f, lane);
-    const int wbase = nb * nch * 18 * 6144 * 2;
+    const int wbase = (ph * p.n_nblocks + nb) * nch * NS * 24576;   // (PH: [phase][channel block][chunk][tap 4]...)
     u32x4 ring[2][2][3];                                           // [k-step slot S & 1][plane][fragment]: two k-steps of weights in flight
     const int c0 = (int)blockIdx.z * p.kt_per, c1 = min(nch, c0 + p.kt_per);
     auto w_load = [&](int slot_, int chunk, int tap) {
-        const int so = wbase + (chunk * 9 + tap) * 24576;
+        const int so = wbase + (chunk * NS + tap) * 24576;
 #pragma unroll
         for (int pl = 0; pl < 2; ++pl)
 #pragma unroll
@@ -569,9 +582,10 @@ __global__ __launch_bounds__(256, 2) void k_conv_h2s(const ConvK p) {
     u32x4 af[2][2];                                                // [buffer][plane]: fragment row mf + 1 is read while the MFMAs of row mf run
     auto a_read = [&](const char *st, int tap, int mf, u32x4 (&dst)[2]) {
 #pragma unroll
-        for (int pl = 0; pl < 2; ++pl) dst[pl] = *reinterpret_cast<const u32x4 *>(st + pl * H2S_PLANE + (mf + tap / 3) * (H16_LP * 64) + aoff[tap % 3]);
+        for (int pl = 0; pl < 2; ++pl)
+            dst[pl] = *reinterpret_cast<const u32x4 *>(st + pl * H2S_PLANE + (mf + (PH ? tap >> 1 : tap / 3)) * (H16_LP * 64) + aoff[PH ? tap & 1 : tap % 3]);
     };
-    // one chunk = 9 k-steps (one tap x 32 channels) of 8 x 3 tiles x 3 products
+    // one chunk = NS k-steps (one tap x 32 channels) of 8 x 3 tiles x 3 products
     for (int c = c0; c < c1; ++c) {
         const char *st = lds + ((c - c0) & 1) * H2S_STG;
         const int cc = c, ccn = cc + 1 < nch ? cc + 1 : 0;
@@ -580,7 +594,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_h2s(const ConvK p) {
         auto row = [&](auto s_, auto m_) {                           // fragment row M of k-step S
             constexpr int S = decltype(s_)::value, M = decltype(m_)::value, rs = S & 1, cur = M & 1;
             if constexpr (M + 1 < 8) a_read(st, S, M + 1, af[cur ^ 1]);
-            else if constexpr (S + 1 < 9) a_read(st, S + 1, 0, af[cur ^ 1]);
+            else if constexpr (S + 1 < NS) a_read(st, S + 1, 0, af[cur ^ 1]);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int pr = 0; pr < 3; ++pr)                              // smallest partial product first: h1 w0, h0 w1, h0 w0 into every tile
@@ -593,17 +607,38 @@ __global__ __launch_bounds__(256, 2) void k_conv_h2s(const ConvK p) {
         auto kstep = [&](auto s_) {
             constexpr int S = decltype(s_)::value, rs = S & 1;
             [&]<int... M>(std::integer_sequence<int, M...>) { (row(s_, std::integral_constant<int, M>{}), ...); }(std::make_integer_sequence<int, 8>{});
-            // two steps ahead; 9 steps per chunk, so steps 7 and 8 fetch the next chunk's steps 1 and 0 (each keeps its slot parity)
-            w_load(rs, S + 2 < 9 ? cc : ccn, S + 2 < 9 ? S + 2 : 8 - S);
+            // two steps ahead, each into its own slot parity: of 9 steps per chunk, steps 7 and 8 fetch the next chunk's steps 1 and 0; of 4 (an even
+            // count keeps the parity across chunks), steps 2 and 3 fetch its steps 0 and 1
+            w_load(rs, S + 2 < NS ? cc : ccn, S + 2 < NS ? S + 2 : (PH ? S + 2 - NS : 8 - S));
             if constexpr (S >= ST0 && S < ST0 + NUT) a_store((c - c0 + 1) & 1, S - ST0, ccn);
             __builtin_amdgcn_sched_barrier(0);
         };
-        [&]<int... S>(std::integer_sequence<int, S...>) { (kstep(std::integral_constant<int, S>{}), ...); }(std::make_integer_sequence<int, 9>{});
+        [&]<int... S>(std::integer_sequence<int, S...>) { (kstep(std::integral_constant<int, S>{}), ...); }(std::make_integer_sequence<int, NS>{});
         __syncthreads();
     }
-    h2s_epilogue(p, lds, h2s_scatter_1x4(acc, lane, wave), tid, nb * 192, (long)tb, rsx, [&](int pc) {
-        return ((long)img * p.Hout + y0 + (pc >> 4)) * p.Wout + x0 + (pc & 15);
-    });
+    if constexpr (PH) {   // a phase has its own weight scales ([phase][Cout]); slot pc = source position (y0 + pc / 16, x0 + pc % 16) -> its output pixel of the phase
+        ConvK pp = p;
+        pp.wsc = p.wsc + ph * p.Cout;
+        h2s_epilogue(pp, lds, h2s_scatter_1x4(acc, lane, wave), tid, nb * 192, (long)tb, rsx, [&](int pc) {
+            return ((long)img * p.Hout + 2 * (y0 + (pc >> 4)) + phy) * p.Wout + 2 * (x0 + (pc & 15)) + phx;
+        });
+    } else {
+        h2s_epilogue(p, lds, h2s_scatter_1x4(acc, lane, wave), tid, nb * 192, (long)tb, rsx, [&](int pc) {
+            return ((long)img * p.Hout + y0 + (pc >> 4)) * p.Wout + x0 + (pc & 15);
+        });
+    }
+}
+#endif
+
+// (two plain entry points over the one body: a kernel trace and the compiled metadata keep the name k_conv_h2s for the nine-tap kernel)
+__global__ __launch_bounds__(256, 2) void k_conv_h2s(const ConvK p) {
+#if __HIP_DEVICE_COMPILE__
+    conv_h2s_body<false>(p);
+#endif
+}
+__global__ __launch_bounds__(256, 2) void k_conv_h2s_ph(const ConvK p) {
+#if __HIP_DEVICE_COMPILE__
+    conv_h2s_body<true>(p);
 #endif
 }
 
@@ -1038,6 +1073,64 @@ __global__ void k_pack_conv_h2(const float *__restrict__ w, int Cout, int Cin, i
     }
 }
 
+// The phase form of an Upsample convolution (k_conv_h2s_ph).  Output row 2i + q reads, through the nearest-x2 upsample, source rows i - 1 + q + t, t in {0, 1}:
+//   q = 0:  t = 0 <- W[0,.]           t = 1 <- W[1,.] + W[2,.]
+//   q = 1:  t = 0 <- W[0,.] + W[1,.]  t = 1 <- W[2,.]
+// and columns alike.  h2p_taps(q, t) = the 3x3 rows (or columns) that parity q's tap t sums, as a bit mask.
+__host__ __device__ constexpr unsigned h2p_taps(int q, int t) { return q == 0 ? (t == 0 ? 1u : 6u) : (t == 0 ? 3u : 4u); }
+// weight of tap (a, b) = tap >> 1, tap & 1 of phase (py, px) = ph >> 1, ph & 1: the sum formed in double and rounded once
+__device__ __forceinline__ float h2p_weight(const float *__restrict__ w9, int ph, int tap) {
+    const unsigned rows = h2p_taps(ph >> 1, tap >> 1), cols = h2p_taps(ph & 1, tap & 1);
+    double s = 0.0;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) if ((rows >> (k / 3) & 1u) && (cols >> (k % 3) & 1u)) s += (double)w9[k];
+    return (float)s;
+}
+// the scales of k_wscale_h2 per (phase, output channel): inv[ph * Cout + o] from the largest |summed tap| of the phase
+__global__ void k_wscale_h2p(const float *__restrict__ w, int Cout, int Cin, float *__restrict__ inv) {
+    __shared__ float red[256];
+    const int o = blockIdx.x, ph = blockIdx.y;
+    float m = 0.f;
+    for (int i = threadIdx.x; i < Cin * 4; i += 256) m = fmaxf(m, fabsf(h2p_weight(w + ((long)o * Cin + (i >> 2)) * 9, ph, i & 3)));
+    red[threadIdx.x] = m;
+    __syncthreads();
+    for (int d = 128; d > 0; d >>= 1) {
+        if ((int)threadIdx.x < d) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + d]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        m = red[0];
+        int e = (int)((__float_as_uint(m) >> 23) & 0xff) - 127;
+        float r = 1.f;
+        if (m > 0.f && e < 128) {
+            e = e < -100 ? -100 : e;
+            r = __uint_as_float((unsigned)(e - 13 + 127) << 23);
+        }
+        inv[ph * Cout + o] = r;
+    }
+}
+// [phase 4][channel block of 192][chunk of 32 inputs][tap 4][k-half][plane 2][wn][fragment nf][lane][8], then 4 x Cout floats = the inverse scales:
+// per phase the image of k_pack_conv_h2 with four taps
+__global__ void k_pack_conv_h2p(const float *__restrict__ w, int Cout, int Cin, int Cin_pad, unsigned short *__restrict__ dst, const float *__restrict__ inv) {
+    const int nch = Cin_pad >> 5, nbs = Cout / 192;
+    const long n = (long)4 * nbs * nch * 8 * 2 * 3072;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const int j = (int)(i & 7), l = (int)((i >> 3) & 63);
+        long t = i >> 9;
+        const int nf = (int)(t % 3); t /= 3;
+        const int wn = (int)(t & 1); t >>= 1;
+        const int pl = (int)(t & 1); t >>= 1;
+        const int k2 = (int)(t & 1); t >>= 1;
+        const int tap = (int)(t & 3); t >>= 2;
+        const int chunk = (int)(t % nch); t /= nch;
+        const int nb = (int)(t % nbs);
+        const int ph = (int)(t / nbs);
+        const int o = nb * 192 + wn * 96 + nf * 32 + (l & 31), cin = chunk * 32 + k2 * 16 + (l >> 5) * 8 + j;
+        const float v = cin < Cin ? h2p_weight(w + ((long)o * Cin + cin) * 9, ph, tap) : 0.f;
+        dst[i] = h2_plane(v, inv[ph * Cout + o], pl);
+    }
+}
+
 // fp16x2 weights of a 1x1 layer: [channel block of 192][chunk of 48 inputs][k-step 3][plane 2][wn][fragment nf][lane][8], then Cout floats = the inverse scales
 __global__ void k_pack_conv1_h2(const float *__restrict__ w, int Cout, int Cin, int Cin_pad, unsigned short *__restrict__ dst, int tf, const float *__restrict__ inv) {
     const int nch = Cin_pad / 48;
@@ -1156,6 +1249,36 @@ int conv_pack_weights_h2(const float *w, int Cout, int Cin, int Cin_pad, int ks,
     else hipLaunchKernelGGL(k_pack_conv1_h2, dim3(512), dim3(256), 0, st, w, Cout, Cin, Cin_pad, static_cast<unsigned short *>(packed), tf, inv);
     return check_launch("k_pack_conv_h2");
 }
+// The phase form (WeightForm::Fp16x2Up): four phases x four taps = 16 / 9 of the 3x3 planes, + the [4][Cout] inverse scales
+static size_t h2p_plane_bytes(int Cout, int Cin_pad) { return (Cout % 192 == 0 && Cin_pad % 32 == 0) ? (size_t)Cout * Cin_pad * 16 * 4 : 0; }
+size_t conv_packed_h2p_bytes(int Cout, int Cin_pad, int ks) {
+    const size_t b = ks == 3 ? h2p_plane_bytes(Cout, Cin_pad) : 0;
+    return b ? b + (size_t)4 * Cout * sizeof(float) : 0;
+}
+const float *conv_h2p_wscale(const void *packed, int Cout, int Cin_pad) {
+    return reinterpret_cast<const float *>(static_cast<const char *>(packed) + h2p_plane_bytes(Cout, Cin_pad));
+}
+int conv_pack_weights_h2p(const float *w, int Cout, int Cin, int Cin_pad, int ks, void *packed, hipStream_t st, int tf) {
+    HL_REQUIRE(w && packed && conv_packed_h2p_bytes(Cout, Cin_pad, ks) && Cin <= Cin_pad && !tf, "conv_pack_weights_h2p: bad argument");
+    float *inv = reinterpret_cast<float *>(static_cast<char *>(packed) + h2p_plane_bytes(Cout, Cin_pad));
+    hipLaunchKernelGGL(k_wscale_h2p, dim3((unsigned)Cout, 4), dim3(256), 0, st, w, Cout, Cin, inv);
+    hipLaunchKernelGGL(k_pack_conv_h2p, dim3(1024), dim3(256), 0, st, w, Cout, Cin, Cin_pad, static_cast<unsigned short *>(packed), inv);
+    return check_launch("k_pack_conv_h2p");
+}
+// the Upsample convolutions as four 2x2-tap phases: low-resolution tiles of 8x16, so the output is a multiple of 16 x 32
+bool conv3_h2s_ph_applies(int Hout, int Wout, int Cin, int Cout, int ks, int stride, int ups) {
+    return ups && conv_h16_applies(Hout, Wout, Cin, Cout, ks, stride, ups) && Wout % 32 == 0 && (long)Cout * Cin * 64 < (1L << 31);
+}
+// k_conv_h2s_ph: p.n_mtiles = output pixels / 128 = 4 phases x low-resolution tiles; p.wf = WeightForm::Fp16x2Up, p.wsc = its [4][Cout] scales
+int conv3_h2s_ph_launch(const ConvK &p, hipStream_t st, int splits) {
+    HL_REQUIRE(p.wf && p.wsc && conv3_h2s_ph_applies(p.Hout, p.Wout, p.Cin, p.Cout, p.ks, p.stride, p.ups) && p.Hout == 2 * p.Hin && p.Wout == 2 * p.Win &&
+                   (splits == 1 || p.partial) && !p.in16 && p.cA == nullptr && p.gn.gt == nullptr, "k_conv_h2s_ph: bad layer");
+    static const bool attr_ok = hipFuncSetAttribute((const void *)k_conv_h2s_ph, hipFuncAttributeMaxDynamicSharedMemorySize, H2S_LDS) == hipSuccess;
+    HL_REQUIRE(attr_ok, "k_conv_h2s_ph: cannot raise the dynamic LDS limit to %d bytes", H2S_LDS);
+    hipLaunchKernelGGL(k_conv_h2s_ph, dim3((unsigned)(p.n_mtiles * p.n_nblocks), 1, (unsigned)splits), dim3(256), (size_t)H2S_LDS, st, p);
+    return check_launch("k_conv_h2s_ph");
+}
+
 // the 3x3 / stride-1 layers with fp16x2 products on the 8x16-pixel tile (two workgroups per CU): p.n_mtiles = pixels / 128
 int conv3_h2s_launch(const ConvK &p, hipStream_t st, int splits) {
     HL_REQUIRE(p.wf && p.ks == 3 && conv_h16_applies(p.Hout, p.Wout, p.Cin, p.Cout, p.ks, p.stride, p.ups) && (splits == 1 || p.partial), "k_conv_h2s: bad layer");

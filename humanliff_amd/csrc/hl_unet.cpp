@@ -147,20 +147,21 @@ size_t conv_forms_floats(int Cout, int Cin_pad, int ks) {
     for (int f = 0; f < hl::kWeightForms; ++f) t += form_floats(hl::conv_form_bytes((WeightForm)f, Cout, Cin_pad, ks));
     return t;
 }
-Conv make_conv_w(Net &n, const float *w, const float *bias, int Cin, int Cout, int ks);
-Conv make_conv(Net &n, const std::string &p, int Cin, int Cout, int ks, bool has_bias = true) {
+// ups: the convolution of an Upsample layer (it alone has the phase form, WeightForm::Fp16x2Up)
+Conv make_conv_w(Net &n, const float *w, const float *bias, int Cin, int Cout, int ks, bool ups = false);
+Conv make_conv(Net &n, const std::string &p, int Cin, int Cout, int ks, bool has_bias = true, bool ups = false) {
     const float *w = lookup(n, p + ".weight", (int64_t)Cout * Cin * ks * ks);
     const float *b = has_bias ? lookup(n, p + ".bias", Cout) : nullptr;
-    return make_conv_w(n, w, b, Cin, Cout, ks);
+    return make_conv_w(n, w, b, Cin, Cout, ks, ups);
 }
-Conv make_conv_w(Net &n, const float *w, const float *bias, int Cin, int Cout, int ks) {
+Conv make_conv_w(Net &n, const float *w, const float *bias, int Cin, int Cout, int ks, bool ups) {
     Conv c;
     c.Cin = Cin; c.Cin_pad = round_up(Cin, 16); c.Cout = Cout; c.ks = ks;
     c.bias = n.dry ? nullptr : bias;
     const int cp = c.Cin_pad;
     // every form the layer has, in buffer order
     for (int f = 0; f < hl::kWeightForms; ++f) {
-        const size_t bytes = hl::conv_form_bytes((WeightForm)f, Cout, cp, ks);
+        const size_t bytes = hl::conv_form_bytes((WeightForm)f, Cout, cp, ks, true, ups);
         if (!bytes) continue;
         float *dst = n.dry ? nullptr : n.packed + n.packed_off;
         n.packed_off += form_floats(bytes);
@@ -250,8 +251,8 @@ int add_xf(Net &n, const std::string &p, int C, int heads) {
     n.xf.push_back(a);
     return (int)n.xf.size() - 1;
 }
-int add_conv(Net &n, const std::string &p, int Cin, int Cout, int ks) {
-    n.convs.push_back(make_conv(n, p, Cin, Cout, ks));
+int add_conv(Net &n, const std::string &p, int Cin, int Cout, int ks, bool ups = false) {
+    n.convs.push_back(make_conv(n, p, Cin, Cout, ks, true, ups));
     return (int)n.convs.size() - 1;
 }
 bool has_ds(const hl_unet_cfg &c, int ds) {
@@ -352,7 +353,7 @@ void build(Net &n) {
                 else b.layers.push_back({K_ATTN, add_attn(n, p + "." + std::to_string(li++), ch, c.num_heads_upsample)});
             }
             if (level && i == c.num_res_blocks) {
-                b.layers.push_back({K_UP, add_conv(n, p + "." + std::to_string(li++) + ".conv", ch, ch, 3)});
+                b.layers.push_back({K_UP, add_conv(n, p + "." + std::to_string(li++) + ".conv", ch, ch, 3, true)});
                 ds /= 2;
             }
             b.Cout = ch; b.ds_out = ds;
@@ -503,7 +504,7 @@ struct Exec {
             span_key[0] = (int)pl.path; span_key[1] = lvl; span_key[2] = ups ? 1 : 0; span_key[3] = c.Cout; span_key[4] = c.ks;
         }
         const double fl = 2.0 * (double)out.pixels() * c.Cout * c.Cin * c.ks * c.ks;
-        span_end(CAT_CONV, e0, fl, fl * hl::conv_issued_factor(pl.path));
+        span_end(CAT_CONV, e0, fl, fl * hl::conv_issued_factor(pl.path) * (pl.kernel == hl::ConvKernel::H2sUp ? 4.0 / 9.0 : 1.0));   // (four of the nine taps)
         // whoever stored the tensor last owns its statistics
         if (pl.stat_slots > 0) {
             stat_reg[out.p] = {st1, pi1.viewC, pi1.c0, c.Cout};
@@ -1038,7 +1039,7 @@ static SingleConvRoom single_conv_room(int mode, int tf, int N, int H, int W, in
     r.forms = conv_forms(mode, true, tf != 0);
     size_t extra = 0;
     for (int f = 1; f < hl::kWeightForms; ++f) {
-        const size_t b = r.forms >> f & 1u ? hl::conv_form_bytes((WeightForm)f, Cout, Cin, ks, false) : 0;
+        const size_t b = r.forms >> f & 1u ? hl::conv_form_bytes((WeightForm)f, Cout, Cin, ks, false, upsample != 0) : 0;
         if (!b) r.forms &= ~(1u << f);   // (the layer has no such form)
         extra = std::max(extra, b);
     }
@@ -1093,7 +1094,7 @@ static int conv2d_single(int mode, const float *in, int N, int H, int W, int Cin
     // (no tensor changes a split; a test switch of the dispatch flipped between the query and the call can: refused, never an overrun)
     HL_REQUIRE(room.splitk + splitk_slab_bytes(a, pl) <= room.total, "hl_conv2d_nhwc: the plan splits K further than hl_conv2d_scratch_bytes planned");
     // the room holds that form only: no kernel argument points at the others
-    const WeightForm form = hl::form_of(pl.path);
+    const WeightForm form = pl.form;
     a.w = a.w.only(hl::form_bit(WeightForm::Fp32) | hl::form_bit(form));
     int rc = hl::conv_pack_form(form, w_oihw, Cout, Cin_w, Cin, ks, form == WeightForm::Fp32 ? scratch : extra_dst, st, tf, mode == HL_CONV_FP16);
     if (rc) return rc;
@@ -1115,6 +1116,18 @@ static int conv2d_single(int mode, const float *in, int N, int H, int W, int Cin
 
 size_t hl_conv2d_scratch_bytes(int conv_mode, int N, int H, int W, int Cin, int Cout, int ks, int stride, int upsample, int with_gn) {
     return single_conv_room(conv_mode, 0, N, H, W, Cin, Cout, ks, stride, upsample, with_gn != 0).total;
+}
+
+int hl_conv2d_plan(int conv_mode, int N, int H, int W, int Cin, int Cout, int ks, int stride, int upsample, int with_gn, int *h_kernel, int *h_splits) {
+    HL_REQUIRE(h_kernel && h_splits, "hl_conv2d_plan: null argument");
+    const SingleConvRoom room = single_conv_room(conv_mode, 0, N, H, W, Cin, Cout, ks, stride, upsample, with_gn != 0);
+    HL_REQUIRE(room.total, "hl_conv2d_plan: bad argument (mode %d, N %d, H %d, W %d, Cin %d, Cout %d, ks %d, stride %d)", conv_mode, N, H, W, Cin, Cout, ks, stride);
+    static float at;
+    ConvArgs a{};
+    single_conv_plan_args(a, &at, conv_mode, room.forms, N, H, W, Cin, Cout, ks, stride, upsample, with_gn != 0);
+    const hl::ConvPlan pl = hl::plan_conv(a);      // (host arithmetic: no HIP call)
+    *h_kernel = (int)pl.kernel; *h_splits = pl.splits;
+    return HL_OK;
 }
 
 // What hl_conv2d_nhwc_gn puts in front: the totals of the output and the scratch of a GroupNorm pass over it.

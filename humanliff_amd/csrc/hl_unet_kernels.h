@@ -54,6 +54,8 @@ enum class WeightForm : int {
     Wino4,    // Winograd F(4x4,3x3) (points 0, +-3/4, +-3/2, inf), [Cout/32][Cin_pad/8][36][2][32][4] floats, a ragged Cout < 32 padded with zero rows: k_conv_wino4[w]
     Fp16x2,   // two fp16 planes in MFMA-fragment order + the [Cout] inverse power-of-two scales behind them (conv_h2_wscale): k_conv1_h2s, k_conv_h2s, k_conv_h2d
     H16,      // 16-bit weights (fp16, or bf16 on request) in MFMA-fragment order: k_conv_h16, k_conv1_h16
+    Fp16x2Up, // the Upsample convolutions only (conv_form_bytes(.., ups = true)): nearest-x2 + 3x3 as four 2x2-tap phase convolutions, the summed taps as
+              // Fp16x2 planes [phase 4][..][tap 4].. + the [4][Cout] inverse scales (conv_h2p_wscale): k_conv_h2s_ph
     kCount
 };
 constexpr int kWeightForms = (int)WeightForm::kCount;
@@ -64,12 +66,14 @@ constexpr WeightForm form_of(ConvPath p) {
            p == ConvPath::H16 ? WeightForm::H16 : p == ConvPath::Fp16x2 ? WeightForm::Fp16x2 : WeightForm::Fp32;
 }
 // Bytes of one form; 0: the layer has no such form.  cap_wino4: F(4x4,3x3) weights are 4x the direct ones - the network keeps them only up to 64 MB a
-// layer (the single-op entry points, which pack one form per call, pass false).
-size_t conv_form_bytes(WeightForm f, int Cout, int Cin_pad, int ks, bool cap_wino4 = true);
+// layer (the single-op entry points, which pack one form per call, pass false).  ups: the layer reads its input through the nearest-x2 upsample
+// (only such a layer has WeightForm::Fp16x2Up).
+size_t conv_form_bytes(WeightForm f, int Cout, int Cin_pad, int ks, bool cap_wino4 = true, bool ups = false);
 // packs w (Cout, Cin, ks, ks) into dst (conv_form_bytes of room).  tf = 1: the source is laid out (Cin, Cout, ks, ks) and is read flipped and
 // channel-transposed (backward-data weights).  f16 (WeightForm::H16 only): 1 fp16, 0 bf16.
 int conv_pack_form(WeightForm f, const float *w, int Cout, int Cin, int Cin_pad, int ks, void *dst, hipStream_t st, int tf = 0, int f16 = 1);
 const float *conv_h2_wscale(const void *packed, int Cout, int Cin_pad, int ks);   // the [Cout] inverse scales behind the Fp16x2 planes (ConvK::wsc)
+const float *conv_h2p_wscale(const void *packed, int Cout, int Cin_pad);          // the [4 phases][Cout] inverse scales behind the Fp16x2Up planes
 
 struct ConvWeights {
     const void *p[kWeightForms] = {};
@@ -95,7 +99,7 @@ constexpr unsigned conv_forms(int mode, bool bf16_h16, bool bwd_data) {
     const bool f32 = mode == HL_CONV_FP32 || mode == HL_CONV_FP32_MFMA || mode == HL_CONV_FP16;   // (HL_CONV_FP16: the other layers as HL_CONV_FP32)
     return form_bit(WeightForm::Fp32) | (conv_mode_bf16(mode) ? form_bit(WeightForm::Bf16x3) : 0u) |
            (f32 || mode == HL_CONV_FP32_F23 ? form_bit(WeightForm::Wino2) : 0u) | (f32 ? form_bit(WeightForm::Wino4) : 0u) |
-           (mode == HL_CONV_FP32 && !bwd_data ? form_bit(WeightForm::Fp16x2) : 0u) |
+           (mode == HL_CONV_FP32 && !bwd_data ? form_bit(WeightForm::Fp16x2) | form_bit(WeightForm::Fp16x2Up) : 0u) |
            (mode == HL_CONV_FP16 || (bf16_h16 && mode == HL_CONV_BF16) ? form_bit(WeightForm::H16) : 0u);
 }
 
@@ -145,7 +149,7 @@ struct ConvK {
     const float *in; long in_pitch; int N, Hin, Win, Cin;
     int Hout, Wout, ks, stride, ups, taps;
     const float *w;    // WeightForm::Fp32 (the direct kernels)
-    const void *wf;    // the form of the planned path, form_of(ConvPlan::path): what every other kernel reads
+    const void *wf;    // the form the planned kernel reads, ConvPlan::form: what every other kernel reads
     long Ktot; const float *bias; int Cout;
     const float *cA; const float *cB; int act;
     GnSrc gn;          // (cA null and gn.t0 set: the coefficients are formed in the kernel, coef_to_lds)
@@ -190,6 +194,9 @@ bool conv3_h2d_applies(int Hout, int Wout, int Cin, int Cout);        // 3x3 / s
 int conv3_h2d_launch(const ConvK &p, hipStream_t st);                 // p.n_mtiles = output pixels / 128
 int conv3_h2s_launch(const ConvK &p, hipStream_t st, int splits = 1);  // 3x3 / stride 1 on 8x16-pixel tiles, two workgroups per CU (p.n_mtiles = pixels / 128;
                                                                        // ConvK::in16 = 2: a two-plane image from the GroupNorm pass)
+// k_conv_h2s_ph: nearest-x2 + 3x3 as four 2x2-tap phase convolutions of the source (reads WeightForm::Fp16x2Up); output a multiple of 16 x 32 pixels
+bool conv3_h2s_ph_applies(int Hout, int Wout, int Cin, int Cout, int ks, int stride, int ups);
+int conv3_h2s_ph_launch(const ConvK &p, hipStream_t st, int splits = 1);   // p.n_mtiles = output pixels / 128 (phase = tile & 3)
 void set_h16_min_blocks(long v);   // developer / test switch: workgroups from which the dispatch takes k_conv_h16 (< 0: the default, 48)
 
 // Statistics block of one normalised VIEW (ConvArgs::stats): [shard][N][32 groups][2] 64-bit fixed-point totals.  Levels with many
@@ -204,7 +211,8 @@ int tensor_totals(const View &x, float *totals, hipStream_t st);
 int tensor_absmax(const View &x, float *amax, hipStream_t st);
 
 // the kernel within the family
-enum class ConvKernel { Conv, Dma, Bf3, Wino, Wino4, Wino4w, H16, H2s, H2s1, H2d };
+// (the numbers reach Python through hl_conv2d_plan and stay)
+enum class ConvKernel : int { Conv = 0, Dma = 1, Bf3 = 2, Wino = 3, Wino4 = 4, Wino4w = 5, H16 = 6, H2s = 7, H2s1 = 8, H2d = 9, H2sUp = 10 };
 // GroupNorm(+SiLU) materialised into ConvArgs::act_ws before the convolution, and its format: dense fp32, fp32 channel-blocked [C/8][pixel][8]
 // (k_conv_wino4 / k_conv_wino4w read it), the 16-bit image (k_conv_h16) or the two-plane fp16 image (k_conv_h2s)
 enum class ConvPrePass { None, Dense, Blocked, Half, TwoPlane };
@@ -215,6 +223,7 @@ enum class ConvStatsBy { None, Epilogue, Finish };
 struct ConvPlan {
     ConvPath path = ConvPath::Direct;
     ConvKernel kernel = ConvKernel::Conv;
+    WeightForm form = WeightForm::Fp32;   // the form the kernel reads: form_of(path), except k_conv_h2s_ph's Fp16x2Up
     int cfg = 0;             // k_conv tile config: 0 = 128x96, 1 = 128x32 (Cout <= 32), 2 = 64x64
     bool tile8 = false;      // k_conv_dma / k_conv_bf3: the 8-wave 256x96 tile (else 4 waves x 128x96)
     int gn_mode = 0;         // GroupNorm in front of the convolution: 0 none, 1 the affine, 2 the affine + SiLU

@@ -2837,8 +2837,10 @@ size_t conv_packed_h16_bytes(int Cout, int Cin_pad, int ks);
 int conv_pack_weights_h16(const float *w, int Cout, int Cin, int Cin_pad, int ks, void *packed, int f16, hipStream_t st, int tf);
 size_t conv_packed_h2_bytes(int Cout, int Cin_pad, int ks);
 int conv_pack_weights_h2(const float *w, int Cout, int Cin, int Cin_pad, int ks, void *packed, hipStream_t st, int tf);
+size_t conv_packed_h2p_bytes(int Cout, int Cin_pad, int ks);
+int conv_pack_weights_h2p(const float *w, int Cout, int Cin, int Cin_pad, int ks, void *packed, hipStream_t st, int tf);
 
-size_t conv_form_bytes(WeightForm f, int Cout, int Cin_pad, int ks, bool cap_wino4) {
+size_t conv_form_bytes(WeightForm f, int Cout, int Cin_pad, int ks, bool cap_wino4, bool ups) {
     const size_t rows = round_up(Cout, 64), K = (size_t)Cin_pad * ks * ks;
     switch (f) {
     case WeightForm::Fp32: return rows * K * sizeof(float);
@@ -2850,12 +2852,14 @@ size_t conv_form_bytes(WeightForm f, int Cout, int Cin_pad, int ks, bool cap_win
     }
     case WeightForm::Fp16x2: return conv_packed_h2_bytes(Cout, Cin_pad, ks);
     case WeightForm::H16: return conv_packed_h16_bytes(Cout, Cin_pad, ks);
+    case WeightForm::Fp16x2Up: return ups ? conv_packed_h2p_bytes(Cout, Cin_pad, ks) : 0;
     default: return 0;   // (kCount)
     }
 }
 
 int conv_pack_form(WeightForm f, const float *w, int Cout, int Cin, int Cin_pad, int ks, void *dst, hipStream_t st, int tf, int f16) {
-    HL_REQUIRE(w && dst && Cin <= Cin_pad && (ks == 1 || ks == 3) && (f > WeightForm::Bf16x3 || Cin_pad % 16 == 0) && conv_form_bytes(f, Cout, Cin_pad, ks, false),
+    HL_REQUIRE(w && dst && Cin <= Cin_pad && (ks == 1 || ks == 3) && (f > WeightForm::Bf16x3 || Cin_pad % 16 == 0) &&
+                   conv_form_bytes(f, Cout, Cin_pad, ks, false, f == WeightForm::Fp16x2Up),
                "conv_pack_form: bad argument (form %d)", (int)f);
     const int rows = round_up(Cout, 64);
     float *dstf = static_cast<float *>(dst);
@@ -2869,6 +2873,7 @@ int conv_pack_form(WeightForm f, const float *w, int Cout, int Cin, int Cin_pad,
         hipLaunchKernelGGL(k_pack_conv_wino4, dim3((unsigned)std::min<long>(8192, (long)(round_up(Cout, 32) >> 5) * (Cin_pad >> 3))), dim3(256), 0, st, w, Cout, Cin, Cin_pad, dstf, tf);
         break;
     case WeightForm::Fp16x2: return conv_pack_weights_h2(w, Cout, Cin, Cin_pad, ks, dst, st, tf);
+    case WeightForm::Fp16x2Up: return conv_pack_weights_h2p(w, Cout, Cin, Cin_pad, ks, dst, st, tf);
     default: return conv_pack_weights_h16(w, Cout, Cin, Cin_pad, ks, dst, f16, st, tf);   // (H16: conv_form_bytes is 0 for anything else)
     }
     return check_launch("k_pack_conv");
@@ -2917,7 +2922,10 @@ ConvPlan plan_conv(const ConvArgs &a) {
         }
         return pl;
     };
-    auto take = [&](ConvPath path, ConvKernel kernel, SplitK sk) { pl.path = path; pl.kernel = kernel; pl.splits = sk.splits; pl.kt_per = sk.kt_per; };
+    auto take = [&](ConvPath path, ConvKernel kernel, SplitK sk) {
+        pl.path = path; pl.kernel = kernel; pl.splits = sk.splits; pl.kt_per = sk.kt_per;
+        pl.form = kernel == ConvKernel::H2sUp ? WeightForm::Fp16x2Up : form_of(path);
+    };
 
     // tile configs: 0 = 128x96 (4 waves of 32x96: 48 accumulators -> 4 waves/SIMD, 4 workgroups/CU = 1024 slots),
     // 1 = 128x32 (Cout <= 32), 2 = 64x64.  Small-M layers keep the efficient main tile and split K instead
@@ -2986,7 +2994,10 @@ ConvPlan plan_conv(const ConvArgs &a) {
         const int want = h16_blocks >= h3_split_min && !a.out2 ? (int)std::min<long>(std::min<long>(h3_target / h16_blocks, nk32 / h3_min_chunks), h3_max_splits) : 0;
         const SplitK sk = split_k(a, nk32, fills ? 1 : want);
         if (fills || sk.splits > 1) {
-            take(ConvPath::Fp16x2, ConvKernel::H2s, sk);
+            // an Upsample convolution with whole 8x16 source tiles: four 2x2-tap phases of the source instead of nine taps (k_conv_h2s_ph) - same tiles per launch,
+            // same slabs, same statistics slots
+            const bool phases = a.w.has(WeightForm::Fp16x2Up) && conv3_h2s_ph_applies(a.out.H, a.out.W, a.in.C, a.Cout, a.ks, a.stride, a.ups);
+            take(ConvPath::Fp16x2, phases ? ConvKernel::H2sUp : ConvKernel::H2s, sk);
             // GroupNorm(+SiLU) of the input: applied by k_conv_h2s while it stages the patch (its two workgroups per CU hide the VALU) - no pass over the tensor;
             // beyond 4096 channels materialised once, as the two-plane image the kernel stages without conversion (the same bytes as fp32)
             const bool fuse = !a.ups && a.in.C <= 4096;
@@ -3187,6 +3198,10 @@ static int launch_conv(ConvK &p, const ConvArgs &a, const ConvPlan &pl, hipStrea
         p.n_nblocks = a.Cout / 192;
         p.n_mtiles = (int)(M / 256) * 2;   // 8x16-pixel tiles, two workgroups per CU
         return conv3_h2s_launch(p, st, pl.splits);
+    case ConvKernel::H2sUp:
+        p.n_nblocks = a.Cout / 192;
+        p.n_mtiles = (int)(M / 128);       // 4 phases x 8x16-pixel tiles of the source
+        return conv3_h2s_ph_launch(p, st, pl.splits);
     case ConvKernel::H2s1:
         p.n_nblocks = a.Cout / 192;
         p.n_mtiles = (int)(M / 256) * 2;   // 128-pixel tiles, two workgroups per CU
@@ -3218,7 +3233,7 @@ int conv2d(const ConvArgs &a, const ConvPlan &pl, hipStream_t st) {
     ConvK p{};
     p.in = a.in.p; p.in_pitch = a.in.pitch; p.N = a.in.N; p.Hin = a.in.H; p.Win = a.in.W; p.Cin = a.in.C;
     p.Hout = a.out.H; p.Wout = a.out.W; p.ks = a.ks; p.stride = a.stride; p.ups = a.ups; p.taps = a.ks * a.ks;
-    p.w = a.w.fp32(); p.wf = a.w.p[(int)form_of(pl.path)]; p.Ktot = (long)a.in.C * p.taps; p.bias = a.bias; p.Cout = a.Cout; p.wrows = round_up(a.Cout, 64);
+    p.w = a.w.fp32(); p.wf = a.w.p[(int)pl.form]; p.Ktot = (long)a.in.C * p.taps; p.bias = a.bias; p.Cout = a.Cout; p.wrows = round_up(a.Cout, 64);
     p.cA = a.coefA; p.cB = a.coefB; p.act = a.act; p.gn = a.gn;
     p.st1_cg = a.st_cg > 0 ? a.st_cg : std::max(1, a.Cout / 32); p.st1_c0 = a.st_c0; p.st2_cg = a.st2_cg > 0 ? a.st2_cg : std::max(1, a.Cout / 32); p.st2_c0 = a.st2_c0;
     p.out = a.out.p; p.out_pitch = a.out.pitch; p.res = a.res; p.res_pitch = a.res_pitch;
@@ -3236,7 +3251,7 @@ int conv2d(const ConvArgs &a, const ConvPlan &pl, hipStream_t st) {
         if (a.ev_mid) hipEventRecord(a.ev_mid, st);
     }
     if (pl.path == ConvPath::Fp16x2) {
-        p.wsc = conv_h2_wscale(p.wf, a.Cout, a.in.C, a.ks);
+        p.wsc = pl.form == WeightForm::Fp16x2Up ? conv_h2p_wscale(p.wf, a.Cout, a.in.C) : conv_h2_wscale(p.wf, a.Cout, a.in.C, a.ks);
         if (pl.gn_mode == 0) { p.xs_gt = a.in_stats; p.xs_hw = a.in.H * a.in.W; p.xs_max = a.in_absmax; }   // (raw input; a fused GroupNorm bounds its own output)
     }
     int rc = launch_conv(p, a, pl, st);

@@ -485,6 +485,10 @@ int hl_diffusion_prior_bpd(const float *x_start, const float *coef, int64_t n_pe
  * host: a test switch of the dispatch (hl_debug_set_h16_min_blocks) set between a query and its call can make the call refuse.
  * Arguments no call accepts (N, H, W, Cout <= 0, Cin not a positive multiple of 16, ks not 1 or 3, stride not 1 or 2, unknown mode) give 0. */
 size_t hl_conv2d_scratch_bytes(int conv_mode, int N, int H, int W, int Cin, int Cout, int ks, int stride, int upsample, int with_gn);
+/* The plan behind that size (host arithmetic, no HIP call): *h_kernel = the kernel the call launches - 0 k_conv, 1 k_conv_dma, 2 k_conv_bf3,
+ * 3 k_conv_wino, 4 k_conv_wino4, 5 k_conv_wino4w, 6 k_conv_h16 / k_conv1_h16, 7 k_conv_h2s, 8 k_conv1_h2s, 9 k_conv_h2d, 10 k_conv_h2s_ph (an
+ * Upsample convolution as four 2x2-tap phases); the numbers stay - *h_splits = its split-K slabs (1: none). */
+int hl_conv2d_plan(int conv_mode, int N, int H, int W, int Cin, int Cout, int ks, int stride, int upsample, int with_gn, int *h_kernel, int *h_splits);
 int hl_conv2d_nhwc(const float *in, int N, int H, int W, int Cin, const float *w_oihw, const float *bias, int Cout,
                    int ks, int stride, int upsample, const float *coefA, const float *coefB, int silu,
                    const float *residual, float *out, void *scratch, size_t scratch_bytes, void *stream);
