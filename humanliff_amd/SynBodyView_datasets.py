@@ -5,7 +5,7 @@ The reference builds every view's rays with numpy on the host (get_rays :316-329
 sample_ray_batch :405-436) and uploads 6.3 MB per 512x512 view; here one kernel writes the same float32 arrays directly
 in HBM.  The image / mask half of sample_ray_batch (bound mask, body / background pixel classes, the rejection loop, rgb) runs on the
 device as well: recon_NeRF/lib/if_nerf_data_utils.py (ViewStore, sample_ray_batch), which shares this file's per-pixel ray function.
-Reading and resizing image files stays dataset code.
+Image files are read and resized by recon_NeRF/lib/SynBody_dataset.py (load_view_store).
 """
 import ctypes as C
 

@@ -195,6 +195,12 @@ SIGNATURES = {
     "hl_body_chunk_frames": (_i, []),
     "hl_body_pose_workspace_bytes": (_sz, [_i, _i]),
     "hl_body_pose": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _i, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "hl_area_max_taps": (_i, [_i, _i]),
+    "hl_area_taps": (_i, [_i, _i, _i, _p, _p, _p]),
+    "hl_nearest_taps": (_i, [_i, _i, _p]),
+    "hl_view_ingest_table_words": (_sz, [_i, _i]),
+    "hl_view_ingest_table": (_i, [_i, _i, _p]),
+    "hl_view_ingest": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
 }
 
 

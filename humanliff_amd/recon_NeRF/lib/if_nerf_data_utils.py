@@ -9,7 +9,7 @@ without its per-call host work (csrc/hl_ray_batch.hip; contract: DESIGN.md 4g).
 
 The reference runs this in a DataLoader worker per item: float64 rays for the whole image, cv2.fillPoly, np.argwhere twice, a
 rejection loop.  Here the views stay in HBM, everything that depends on the view alone is computed once by prepare(), and a batch is one
-launch with no host work and no upload.  Reading and resizing image files stays dataset code.  There is no CPU path.
+launch with no host work and no upload.  SynBody_dataset.load_view_store fills a store from a dataset on disk.  There is no CPU path.
 """
 import ctypes as C
 

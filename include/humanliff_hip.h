@@ -822,6 +822,32 @@ int hl_body_pose(const float *packed, const int32_t *parents, int V, int J, int 
                  int shapes_stride, const float *rt, int rt_stride, const float *big, float *vertices, float *joints, float *bounds,
                  float *verts4, float *table, float *big_out, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- raw dataset views -> ViewStore arrays (recon_NeRF/lib/SynBody_dataset.py:266-278: imread / 255, img[msk == 0] = 0,
+ *      cv2.resize INTER_AREA of the image, INTER_NEAREST of the mask) ----
+ * Contract: DESIGN.md 4i; csrc/hl_view_ingest.hip.  The resize rule of one axis, src -> dst <= src, scale = src / dst in float64:
+ *   area: output d covers [f1, f2) = [d scale, d scale + scale), cell = min(scale, src - f1), s1 = ceil(f1), s2 = min(floor(f2), src - 1),
+ *     s1 = min(s1, s2); taps in this order: (s1 - 1, (s1 - f1) / cell) if s1 - f1 > 1e-3; (s, 1 / cell) for s1 <= s < s2;
+ *     (s2, min(min(f2 - s2, 1), cell) / cell) if f2 - s2 > 1e-3.  Weights are rounded to float32.  Agreement with cv2 itself is unverified.
+ *   nearest: min(floor(d scale), src - 1).
+ * HOST functions (no device work):
+ *   hl_area_max_taps: the most taps an output can have, ceil(src / dst) + 1 (0 for bad sizes or dst > src).
+ *   hl_area_taps: idx_out, w_out (dst, max_taps) and count_out (dst); unused slots are (0, 0.0f).  Fails if an output needs more than max_taps.
+ *   hl_nearest_taps: idx_out (dst).
+ *   hl_view_ingest_table: one axis packed for the kernel with T = hl_area_max_taps, hl_view_ingest_table_words(src, dst) int32 words:
+ *     count (dst) | nearest (dst) | idx (dst, T) | the bits of the float32 weights (dst, T).
+ * hl_view_ingest (enqueue-only): img_u8 (V, Hs, Ws, 3) and msk_u8 (V, Hs, Ws) uint8, xtab = the packed table of Ws -> W and ytab of Hs -> H
+ *   on the device (not read, and may be NULL, when H == Hs and W == Ws) -> out_image (V, H, W, 3) float32 = sum over the row taps of
+ *   beta * (sum over the column taps of alpha * p) in table order, p = msk != 0 ? (float)u8 / 255.0f : 0.0f, and out_body (V, H, W) uint8 =
+ *   the nearest source mask pixel != 0.  The four arrays must be 16-byte aligned.  No atomics; a view's bits do not depend on V.
+ *   H <= Hs, W <= Ws, H and V <= 65535, and a column reduction whose 256-output tile fits 64 KiB of LDS per source row (Ws / W up to ~60). */
+int hl_area_max_taps(int src, int dst);
+int hl_area_taps(int src, int dst, int max_taps, int32_t *idx_out, float *w_out, int32_t *count_out);
+int hl_nearest_taps(int src, int dst, int32_t *idx_out);
+size_t hl_view_ingest_table_words(int src, int dst);
+int hl_view_ingest_table(int src, int dst, int32_t *h_table);
+int hl_view_ingest(const unsigned char *img_u8, const unsigned char *msk_u8, int V, int Hs, int Ws, int H, int W, const int32_t *xtab,
+                   const int32_t *ytab, float *out_image, unsigned char *out_body, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,10 @@ cameras of humanliff_amd.synthetic (rays, near / far and mask_at_box by SynBodyV
 image - plumbing, not a quality number.  With --views_num 185 the view ids are the reference's held-out list (heldout_view_ids,
 optionally --test_layer_id); any other orbit needs --view_ids.  View id i is orbit position i % views_num of cloth layer i // views_num.
 
+--data synbody --data_root DIR --smpl_model PATH [--image_scaling S --views_num N --poses_num N --pose_interval N --layer_idx L] scores the
+same view ids on a SynBody directory tree: the files are decoded, resized on the device (csrc/hl_view_ingest.hip) and held in a ViewStore,
+whose test_view gives the rays and the ground truth (recon_NeRF/lib/SynBody_dataset.py).
+
 --views-npz loads real views: arrays ray_o_all, ray_d_all (N, R, 3), near_all, far_all (N, R), rgb_all (N, R, 3), mask_at_box_all (N, R),
 instance_idx, cloth_layer_index, pose_index, view_id (N), world_bounds (N, 2, 3) and optionally H, W; the N views must be grouped by
 instance_idx.
@@ -48,6 +52,15 @@ def parse():
     a.add_argument("--data_range", type=float, default=2.0)
     a.add_argument("--views-npz", dest="views_npz", type=str, default=None)
     a.add_argument("--seed", type=int, default=0)
+    a.add_argument("--data", choices=["synthetic", "synbody"], default="synthetic")
+    a.add_argument("--data_root", type=str, default=None, help="--data synbody: a subject's directory; human_list.txt lies beside it")
+    a.add_argument("--smpl_model", type=str, default=None, help="--data synbody: the SMPL asset (.pkl / .npz) load_body_model reads")
+    a.add_argument("--image_scaling", type=float, default=0.5)
+    a.add_argument("--poses_num", type=int, default=1)
+    a.add_argument("--pose_start", type=int, default=0)
+    a.add_argument("--pose_interval", type=int, default=5)
+    a.add_argument("--layer_idx", type=int, default=None)
+    a.add_argument("--decode_threads", type=int, default=8)
     a.add_argument("--lpips-weights", dest="lpips_weights", type=str, default=None, help="saved state dict of lpips.LPIPS(net='vgg')")
     return a.parse_args()
 
@@ -73,6 +86,25 @@ def synthetic_views(args, humans, dev):
                    "rgb_all": target_image(H, W, args.seed * 1000003 + view_id).reshape(1, 1, H * W, 3),
                    "instance_idx": torch.tensor([human]), "cloth_layer_index": torch.tensor([(view_id // args.views_num) % 4]),
                    "pose_index": torch.tensor([0]), "world_bounds": torch.tensor(syn.WORLD_BOUNDS)[None], "view_id": view_id, "H": H, "W": W}
+
+
+def synbody_views(args, humans, dev):
+    """The held-out views of a SynBody tree, read and resized on the device (recon_NeRF/lib/SynBody_dataset.py) and scored through
+    ViewStore.test_view.  View id i is view i % views_num of cloth layer i // views_num (with --layer_idx: of that layer), first pose."""
+    from humanliff_amd.body import load_body_model
+    from humanliff_amd.recon_NeRF.lib.SynBody_dataset import SynBodyIndex, load_view_store, store_test_views
+    if not args.data_root or not args.smpl_model:
+        raise SystemExit("--data synbody needs --data_root DIR and --smpl_model PATH")
+    ids = heldout_view_ids(args.views_num, args.test_layer_id, view_ids=args.view_ids)
+    index = SynBodyIndex(args.data_root, multi_person=True, num_instance=max(humans) + 1, pose_start=args.pose_start,
+                         pose_interval=args.pose_interval, poses_num=args.poses_num, views_num=args.views_num, layer_idx=args.layer_idx)
+    nv, per_layer = args.views_num, args.poses_num * args.views_num
+    per_human = index.cloth_layer_num * per_layer
+    layer_of = (lambda i: 0) if args.layer_idx is not None else (lambda i: (i // nv) % 4)
+    items = [h * per_human + layer_of(i) * per_layer + i % nv for h in humans for i in ids]
+    store = load_view_store(index, load_body_model(args.smpl_model, dev), image_scaling=args.image_scaling, device=dev, items=items,
+                            decode_threads=args.decode_threads)
+    return store_test_views(store, view_ids=[i for _ in humans for i in ids])
 
 
 def npz_views(path):
@@ -103,7 +135,10 @@ def main():
     model = model.to(dev)
     torch.manual_seed(args.seed)
     humans = list(range(ni)) if args.humans is None else args.humans
-    views = npz_views(args.views_npz) if args.views_npz else synthetic_views(args, humans, dev)
+    if args.views_npz:
+        views = npz_views(args.views_npz)
+    else:
+        views = synbody_views(args, humans, dev) if args.data == "synbody" else synthetic_views(args, humans, dev)
     lpips_fn = None
     if args.lpips_weights:
         from humanliff_amd.lpips import LpipsVGG

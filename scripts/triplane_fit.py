@@ -8,6 +8,13 @@ No dataset ships with the project.  --data synthetic (default): the batches are 
 targets), a fresh one per step.  --data rendered: --views orbit views of a seeded tri-plane inside a box of 0.6 x the world bounds are rendered (render_view),
 acc > 0.5 is their body mask, all but --heldout of them go into a device-resident ViewStore and a FRESH tri-plane is fitted to them through
 RayBatchLoader (rays sampled on the device, csrc/hl_ray_batch.hip); evaluate_views' PSNR on the held-out views is printed before and after.
+--data synbody: the views of a SynBody directory tree (--data_root DIR, the first subject's directory, with human_list.txt beside it;
+--smpl_model PATH, the body model asset) are decoded, resized by --image_scaling on the device (csrc/hl_view_ingest.hip) and held in a
+ViewStore (recon_NeRF/lib/SynBody_dataset.py); --num_instance subjects x 4 cloth layers (or --layer_idx) x --poses_num x --views_num views.
+With --ft_triplane_only it is run_nerf_batch_ft.py's flow (:348-360, 110-129): for every subject of human_list.txt[--start_idx:--end_idx] and
+every cloth layer, a one-subject tri-plane is fitted with the decoder of the run's checkpoint frozen - layer 0 starts from the checkpoint's
+first tri-plane, layer l from layer l - 1 of the subject's own file - and saved as {subject}_{n_iteration:06d}.tar.  (The learning rate
+follows FitLoop's schedule; the reference's separate 0.5 ^ (step / 500) decay of that script is not restated.)
 --tv_loss is accepted and ignored: FitLoop always computes both regularisers (a coefficient of 0 switches a term off).
 """
 import argparse
@@ -50,7 +57,19 @@ def parse():
     a.add_argument("--i_print", type=int, default=100)
     a.add_argument("--i_weights", type=int, default=10000)
     a.add_argument("--seed", type=int, default=0)
-    a.add_argument("--data", choices=["synthetic", "rendered"], default="synthetic")
+    a.add_argument("--data", choices=["synthetic", "rendered", "synbody"], default="synthetic")
+    a.add_argument("--data_root", type=str, default=None, help="--data synbody: a subject's directory; human_list.txt lies beside it")
+    a.add_argument("--smpl_model", type=str, default=None, help="--data synbody: the SMPL asset (.pkl / .npz) load_body_model reads")
+    a.add_argument("--image_scaling", type=float, default=0.5)
+    a.add_argument("--views_num", type=int, default=185)
+    a.add_argument("--poses_num", type=int, default=1)
+    a.add_argument("--pose_start", type=int, default=0)
+    a.add_argument("--pose_interval", type=int, default=5)
+    a.add_argument("--layer_idx", type=int, default=None)
+    a.add_argument("--single_person", action="store_true", help="--data synbody: only --data_root itself (multi_person=False)")
+    a.add_argument("--start_idx", type=int, default=0, help="--ft_triplane_only: first subject of human_list.txt")
+    a.add_argument("--end_idx", type=int, default=None)
+    a.add_argument("--decode_threads", type=int, default=8)
     a.add_argument("--views", type=int, default=24, help="--data rendered: orbit views rendered from the hidden tri-plane")
     a.add_argument("--heldout", type=int, default=4, help="--data rendered: of which this many (evenly spaced) are only scored")
     a.add_argument("--image_size", type=int, default=128, help="--data rendered: side of the rendered views")
@@ -122,6 +141,76 @@ def fit_rendered(args, model, dev, kw):
     score("after")
 
 
+def synbody_store(args, dev, body, data_root, multi_person, num_instance, layer_idx):
+    from humanliff_amd.recon_NeRF.lib.SynBody_dataset import SynBodyIndex, load_view_store
+    index = SynBodyIndex(data_root, multi_person=multi_person, num_instance=num_instance, pose_start=args.pose_start,
+                         pose_interval=args.pose_interval, poses_num=args.poses_num, views_num=args.views_num, layer_idx=layer_idx)
+    store = load_view_store(index, body, image_scaling=args.image_scaling, device=dev, decode_threads=args.decode_threads)
+    print(f"loaded {len(store)} views of {store.H} x {store.W} from {data_root}"
+          f"{'' if layer_idx is None else f' (cloth layer {layer_idx})'}; class counts (body, background) of the first: "
+          f"{store.class_counts()[0].tolist()}", flush=True)
+    return store
+
+
+def new_model(args, dev, num_instances):
+    model = Renderer(use_canonical_space=False, num_instances=num_instances, triplane_dim=args.triplane_dim, triplane_ch=args.triplane_ch, test=False)
+    model.load_state_dict(syn.render_mlp_state(3), strict=False)
+    return model.to(dev)
+
+
+def finetune_synbody(args, dev, body, kw):
+    """run_nerf_batch_ft.py:348-360 with create_nerf's tri-plane hand-over (:110-120)."""
+    from humanliff_amd.recon_NeRF.lib.if_nerf_data_utils import RayBatchLoader
+    logdir = os.path.join(args.basedir, args.expname)
+    if args.ft_path not in (None, 'None'):
+        base_ckpt = os.path.join(logdir, args.ft_path)
+    else:
+        runs = sorted(f for f in os.listdir(logdir) if f.endswith('.tar') and f[:-4].isdigit()) if os.path.isdir(logdir) else []
+        if not runs:
+            raise SystemExit(f"--ft_triplane_only needs the fitted decoder: no NNNNNN.tar checkpoint in {logdir} (fit without the flag first, or name one with --ft_path)")
+        base_ckpt = os.path.join(logdir, runs[-1])
+    root_dir = os.path.dirname(args.data_root)
+    with open(os.path.join(root_dir, 'human_list.txt')) as f:
+        names = [n.strip() for n in f.readlines()][args.start_idx:args.end_idx]
+    kw = dict(kw, ft_triplane_only=True, expname=None)                       # (the hand-over below replaces FitLoop's own reload)
+    for name in names:
+        own = os.path.join(logdir, f'{name}_{args.n_iteration:06d}.tar')
+        for layer in (range(4) if args.layer_idx is None else [args.layer_idx]):
+            state = torch.load(base_ckpt, map_location='cpu')['network_fn_state_dict']
+            if layer == 0 or not os.path.exists(own):
+                state['tri_planes'] = state['tri_planes'][0:1].clone()
+            else:
+                planes = torch.load(own, map_location='cpu')['network_fn_state_dict']['tri_planes']
+                planes[:, layer] = planes[:, layer - 1]
+                state['tri_planes'] = planes
+            model = new_model(args, dev, 1)
+            model.load_state_dict(state, strict=False)
+            store = synbody_store(args, dev, body, os.path.join(root_dir, name), False, 1, layer)
+            loop = FitLoop(model, RayBatchLoader(store, min(args.batch_size, len(store)), args.n_rand, seed=args.seed), **kw)
+            while loop.global_step < args.n_iteration:
+                for tp in loop.data:
+                    losses = loop.step(tp)
+                    if loop.global_step % args.i_print == 0 or loop.global_step == args.n_iteration:
+                        print(f"[FT] {name} layer {layer} iter {loop.global_step} loss {float(losses[0]):.5f} img loss {float(losses[1]):.5f}", flush=True)
+                    if loop.global_step >= args.n_iteration:
+                        break
+            os.makedirs(logdir, exist_ok=True)
+            torch.save({'network_fn_state_dict': {'tri_planes': model.tri_planes.detach().cpu().clone()}}, own)
+            print('Saved checkpoints at', own, flush=True)
+
+
+def fit_synbody(args, model, dev, kw):
+    from humanliff_amd.body import load_body_model
+    from humanliff_amd.recon_NeRF.lib.if_nerf_data_utils import RayBatchLoader
+    if not args.data_root or not args.smpl_model:
+        raise SystemExit("--data synbody needs --data_root DIR and --smpl_model PATH")
+    body = load_body_model(args.smpl_model, dev)
+    if args.ft_triplane_only:
+        return finetune_synbody(args, dev, body, kw)
+    store = synbody_store(args, dev, body, args.data_root, not args.single_person, 1 if args.single_person else args.num_instance, args.layer_idx)
+    FitLoop(model, RayBatchLoader(store, args.batch_size, args.n_rand, seed=args.seed), **kw).run_loop()
+
+
 def main():
     args = parse()
     if not torch.cuda.is_available():
@@ -139,6 +228,8 @@ def main():
               ft_path=args.ft_path, no_reload=args.no_reload)
     if args.data == "rendered":
         return fit_rendered(args, model, dev, kw)
+    if args.data == "synbody":
+        return fit_synbody(args, model, dev, kw)
     FitLoop(model, batches(args, dev), **kw).run_loop()
 
 
