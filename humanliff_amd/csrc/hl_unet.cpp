@@ -1005,10 +1005,10 @@ static void conv_out_hw(int H, int W, int ks, int stride, int upsample, int *Ho,
 // pointer is there, so they all point at `at` (the queries have no buffer; conv2d_single puts the real ones in afterwards), and it plans
 // with the conv_splitk_ws_bytes() every layer has inside hl_unet_forward.
 static void single_conv_plan_args(ConvArgs &a, float *at, int mode, unsigned forms, int N, int H, int W, int Cin, int Cout, int ks, int stride,
-                                  int upsample, bool with_gn) {
+                                  int upsample, bool with_gn, long out_pitch = 0) {
     a.in.N = N; a.in.H = H; a.in.W = W; a.in.C = Cin; a.in.pitch = Cin;
     a.Cout = Cout; a.ks = ks; a.stride = stride; a.ups = upsample; a.mode = mode;
-    a.out.N = N; conv_out_hw(H, W, ks, stride, upsample, &a.out.H, &a.out.W); a.out.C = Cout;
+    a.out.N = N; conv_out_hw(H, W, ks, stride, upsample, &a.out.H, &a.out.W); a.out.C = Cout; a.out.pitch = out_pitch ? out_pitch : Cout;
     for (int f = 0; f < hl::kWeightForms; ++f) a.w.p[f] = forms >> f & 1u ? at : nullptr;
     a.coefA = with_gn ? at : nullptr;
     a.act_ws = with_gn ? at : nullptr;
@@ -1078,14 +1078,14 @@ static int conv2d_single(int mode, const float *in, int N, int H, int W, int Cin
     char *sc = static_cast<char *>(scratch);
     void *extra_dst = sc + room.form;
     ConvArgs a{};
-    single_conv_plan_args(a, static_cast<float *>(scratch), mode, room.forms, N, H, W, Cin, Cout, ks, stride, upsample, coefA != nullptr);
+    single_conv_plan_args(a, static_cast<float *>(scratch), mode, room.forms, N, H, W, Cin, Cout, ks, stride, upsample, coefA != nullptr, out_pitch);
     // every form the layer has under the mode points at that room, for plan_conv to choose from
     for (int f = 1; f < hl::kWeightForms; ++f) if (a.w.p[f]) a.w.p[f] = extra_dst;
     if (coefA) a.act_ws = reinterpret_cast<float *>(sc + room.act);      // the materialised GroupNorm input (DMA path)
     a.splitk_ws = reinterpret_cast<float *>(sc + room.splitk);
     a.in.p = const_cast<float *>(in); a.bias = bias;
     a.coefA = coefA; a.coefB = coefB; a.act = silu;
-    a.out.p = out; a.out.pitch = out_pitch ? out_pitch : Cout;
+    a.out.p = out;
     a.res = residual; a.res_pitch = Cout;
     float *tot_room = reinterpret_cast<float *>(sc + room.tot);
     a.stats = stats;
@@ -1118,14 +1118,24 @@ size_t hl_conv2d_scratch_bytes(int conv_mode, int N, int H, int W, int Cin, int 
     return single_conv_room(conv_mode, 0, N, H, W, Cin, Cout, ks, stride, upsample, with_gn != 0).total;
 }
 
-int hl_conv2d_plan(int conv_mode, int N, int H, int W, int Cin, int Cout, int ks, int stride, int upsample, int with_gn, int *h_kernel, int *h_splits) {
-    HL_REQUIRE(h_kernel && h_splits, "hl_conv2d_plan: null argument");
-    const SingleConvRoom room = single_conv_room(conv_mode, 0, N, H, W, Cin, Cout, ks, stride, upsample, with_gn != 0);
-    HL_REQUIRE(room.total, "hl_conv2d_plan: bad argument (mode %d, N %d, H %d, W %d, Cin %d, Cout %d, ks %d, stride %d)", conv_mode, N, H, W, Cin, Cout, ks, stride);
+// The plan conv2d_single makes for the same arguments, without a buffer (the plan queries; host arithmetic: no HIP call).  false:
+// arguments no call accepts.
+static bool single_conv_query_plan(int mode, int tf, int N, int H, int W, int Cin, int Cout, int ks, int stride, int upsample, bool with_gn,
+                                   long out_pitch, hl::ConvPlan *pl) {
+    const SingleConvRoom room = single_conv_room(mode, tf, N, H, W, Cin, Cout, ks, stride, upsample, with_gn);
+    if (!room.total) return false;
     static float at;
     ConvArgs a{};
-    single_conv_plan_args(a, &at, conv_mode, room.forms, N, H, W, Cin, Cout, ks, stride, upsample, with_gn != 0);
-    const hl::ConvPlan pl = hl::plan_conv(a);      // (host arithmetic: no HIP call)
+    single_conv_plan_args(a, &at, mode, room.forms, N, H, W, Cin, Cout, ks, stride, upsample, with_gn, out_pitch);
+    *pl = hl::plan_conv(a);
+    return true;
+}
+
+int hl_conv2d_plan(int conv_mode, int N, int H, int W, int Cin, int Cout, int ks, int stride, int upsample, int with_gn, int *h_kernel, int *h_splits) {
+    HL_REQUIRE(h_kernel && h_splits, "hl_conv2d_plan: null argument");
+    hl::ConvPlan pl;
+    HL_REQUIRE(single_conv_query_plan(conv_mode, 0, N, H, W, Cin, Cout, ks, stride, upsample, with_gn != 0, 0, &pl),
+               "hl_conv2d_plan: bad argument (mode %d, N %d, H %d, W %d, Cin %d, Cout %d, ks %d, stride %d)", conv_mode, N, H, W, Cin, Cout, ks, stride);
     *h_kernel = (int)pl.kernel; *h_splits = pl.splits;
     return HL_OK;
 }
@@ -1151,19 +1161,43 @@ static size_t bwd_data_prefix(int N, int Ho, int Wo, int Cy, int stride, int ups
     return stride == 2 ? up256((size_t)N * 4 * Ho * Wo * Cy * sizeof(float)) : upsample ? up256((size_t)N * Ho * Wo * Cx * sizeof(float)) : 0;
 }
 
+// The forward convolution a backward-data call runs (tf = 1), stated once for the call, its scratch query and its plan query: on the
+// (H, W) grid - the zero-stuffed (2Ho, 2Wo) one for stride 2 - from the Cy channels of the gradient to the Cin input channels of the
+// layer, stride 1, nothing in front, stored with a pitch of Cx.  what: the refusal (null = the arguments are fine).
+struct BwdDataConv { int H, W; const char *what; };
+static BwdDataConv bwd_data_conv(int conv_mode, int Ho, int Wo, int Cy, int Cout, int Cin, int ks, int stride, int upsample, int Cx) {
+    BwdDataConv c{};
+    const int s = stride == 2 ? 2 : 1;
+    c.H = s * Ho; c.W = s * Wo;
+    if (!(conv_mode_known(conv_mode) && conv_mode != HL_CONV_BF16X3 && conv_mode != HL_CONV_FP32_MFMA)) c.what = "mode";   // (the training path's modes)
+    else if (!(Cy % 16 == 0 && Cout <= Cy && Cin <= Cx && (ks == 1 || ks == 3) && (stride == 1 || (stride == 2 && !upsample && ks == 3)) &&
+               (!upsample || (Cx % 4 == 0 && Ho % 2 == 0 && Wo % 2 == 0)) && Cx > 0))      // (an upsampled image has even sides)
+        c.what = "bad argument";
+    return c;
+}
+
 size_t hl_conv2d_bwd_data_scratch_bytes(int conv_mode, int N, int Ho, int Wo, int Cy, int Cout, int Cin, int ks, int stride, int upsample, int Cx) {
-    (void)Cout;   // (the weight's output channels: the convolution reads all Cy of the gradient)
-    const int s = stride == 2 ? 2 : 1;   // the convolution runs on the zero-stuffed grid
-    const size_t conv = Cx > 0 && (stride == 1 || stride == 2) ? single_conv_room(conv_mode, 1, N, s * Ho, s * Wo, Cy, Cin, ks, 1, 0, false).total : 0;
+    const BwdDataConv c = bwd_data_conv(conv_mode, Ho, Wo, Cy, Cout, Cin, ks, stride, upsample, Cx);   // (Cout: the weight's output channels - the convolution reads all Cy of the gradient)
+    const size_t conv = c.what ? 0 : single_conv_room(conv_mode, 1, N, c.H, c.W, Cy, Cin, ks, 1, 0, false).total;
     return conv ? bwd_data_prefix(N, Ho, Wo, Cy, stride, upsample, Cx) + conv : 0;
+}
+
+int hl_conv2d_bwd_data_plan(int conv_mode, int N, int Ho, int Wo, int Cy, int Cout, int Cin, int ks, int stride, int upsample, int Cx,
+                            int *h_kernel, int *h_splits) {
+    HL_REQUIRE(h_kernel && h_splits, "hl_conv2d_bwd_data_plan: null argument");
+    const BwdDataConv c = bwd_data_conv(conv_mode, Ho, Wo, Cy, Cout, Cin, ks, stride, upsample, Cx);
+    HL_REQUIRE(!c.what, "hl_conv2d_bwd_data_plan: %s (mode %d)", c.what, conv_mode);
+    hl::ConvPlan pl;
+    HL_REQUIRE(single_conv_query_plan(conv_mode, 1, N, c.H, c.W, Cy, Cin, ks, 1, 0, false, Cx, &pl), "hl_conv2d_bwd_data_plan: bad argument");
+    *h_kernel = (int)pl.kernel; *h_splits = pl.splits;
+    return HL_OK;
 }
 
 int hl_conv2d_nhwc_bwd_data(int conv_mode, const float *dy, int N, int Ho, int Wo, int Cy, const float *w_oihw, int Cout, int Cin, int ks,
                             int stride, int upsample, float *dx, int Cx, void *scratch, size_t scratch_bytes, void *stream) {
-    HL_REQUIRE(conv_mode_known(conv_mode) && conv_mode != HL_CONV_BF16X3 && conv_mode != HL_CONV_FP32_MFMA, "hl_conv2d_nhwc_bwd_data: mode %d", conv_mode);   // (the training path's modes)
+    const BwdDataConv c = bwd_data_conv(conv_mode, Ho, Wo, Cy, Cout, Cin, ks, stride, upsample, Cx);
+    HL_REQUIRE(!c.what, "hl_conv2d_nhwc_bwd_data: %s (mode %d)", c.what, conv_mode);
     HL_REQUIRE(dy && w_oihw && dx && scratch, "hl_conv2d_nhwc_bwd_data: null argument");
-    HL_REQUIRE(Cy % 16 == 0 && Cout <= Cy && Cin <= Cx && (ks == 1 || ks == 3) && (stride == 1 || (stride == 2 && !upsample && ks == 3)) &&
-               (!upsample || Cx % 4 == 0), "hl_conv2d_nhwc_bwd_data: bad argument");
     const size_t need = hl_conv2d_bwd_data_scratch_bytes(conv_mode, N, Ho, Wo, Cy, Cout, Cin, ks, stride, upsample, Cx);
     HL_REQUIRE(need, "hl_conv2d_nhwc_bwd_data: bad argument");
     HL_REQUIRE(scratch_bytes >= need, "hl_conv2d_nhwc_bwd_data: scratch too small (%zu bytes, hl_conv2d_bwd_data_scratch_bytes says %zu)",
@@ -1173,24 +1207,23 @@ int hl_conv2d_nhwc_bwd_data(int conv_mode, const float *dy, int N, int Ho, int W
     hipStream_t st = (hipStream_t)stream;
     char *sc = static_cast<char *>(scratch);
     const size_t pre = bwd_data_prefix(N, Ho, Wo, Cy, stride, upsample, Cx);
+    const float *in = dy;
+    float *out = dx;
     int rc;
     if (stride == 2) {
         float *z = reinterpret_cast<float *>(sc);
         rc = hl_zero_stuff2_nhwc(dy, N, Ho, Wo, Cy, z, stream);
         if (rc) return rc;
-        return conv2d_single(conv_mode, z, N, 2 * Ho, 2 * Wo, Cy, w_oihw, nullptr, Cin, ks, 1, 0, nullptr, nullptr, 0, nullptr, dx, sc + pre,
-                             scratch_bytes - pre, stream, nullptr, nullptr, 1, Cout, Cx);
+        in = z;
     }
     if (upsample) {      // dy lives on the (2H, 2W) grid = (Ho, Wo); dx on (Ho/2, Wo/2)
-        float *du = reinterpret_cast<float *>(sc);
-        if (Cx != Cin) HL_HIP(hipMemsetAsync(du, 0, pre, st));
-        rc = conv2d_single(conv_mode, dy, N, Ho, Wo, Cy, w_oihw, nullptr, Cin, ks, 1, 0, nullptr, nullptr, 0, nullptr, du, sc + pre, scratch_bytes - pre,
-                           stream, nullptr, nullptr, 1, Cout, Cx);
-        if (rc) return rc;
-        return hl_upsample2_backward_nhwc(du, N, Ho / 2, Wo / 2, Cx, dx, stream);
+        out = reinterpret_cast<float *>(sc);
+        if (Cx != Cin) HL_HIP(hipMemsetAsync(out, 0, pre, st));
     }
-    return conv2d_single(conv_mode, dy, N, Ho, Wo, Cy, w_oihw, nullptr, Cin, ks, 1, 0, nullptr, nullptr, 0, nullptr, dx, scratch, scratch_bytes, stream,
-                         nullptr, nullptr, 1, Cout, Cx);
+    rc = conv2d_single(conv_mode, in, N, c.H, c.W, Cy, w_oihw, nullptr, Cin, ks, 1, 0, nullptr, nullptr, 0, nullptr, out, sc + pre, scratch_bytes - pre,
+                       stream, nullptr, nullptr, 1, Cout, Cx);
+    if (rc || !upsample) return rc;
+    return hl_upsample2_backward_nhwc(out, N, Ho / 2, Wo / 2, Cx, dx, stream);
 }
 
 int hl_conv2d_nhwc_gn(int conv_mode, const float *in, int N, int H, int W, int Cin, const float *w_oihw, const float *bias, int Cout,

@@ -110,6 +110,9 @@ class _Conv(th.autograd.Function):
         ks = w4.shape[2]
         Cin = w4.shape[1]
         wp = w4 if x.shape[-1] == Cin else F.pad(w4, (0, 0, 0, 0, 0, x.shape[-1] - Cin))    # zero weights for the padded input channels
+        if stride == 2 and (x.shape[1] % 2 or x.shape[2] % 2):
+            # hl_conv2d_nhwc_bwd_data stores the whole zero-stuffed (2Ho, 2Wo) grid: one row / column more than an odd input has
+            raise ValueError(f"_Conv: a stride-2 convolution needs even H and W, got an input of shape {tuple(x.shape)} (N, H, W, C)")
         mode = _conv_mode()
         y = _conv_raw(x, wp.contiguous(), b, ks, stride, ups, mode)
         ctx.save_for_backward(x, w4)

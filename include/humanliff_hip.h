@@ -507,10 +507,18 @@ int hl_conv2d_nhwc_mode(int conv_mode, const float *in, int N, int H, int W, int
 /* hl_conv2d_nhwc_bwd_data: d input of a convolution from d output, through the forward kernels: dy (N,Ho,Wo,Cy) dense NHWC with
  * Cy >= Cout a multiple of 16 (zero-padded channels), w the convolution's own (Cout, Cin, ks, ks) weights - read flipped and
  * channel-transposed while they are re-laid for the kernel, no flipped copy is made -, dx (N,H,W,Cx) with Cx >= Cin (channels
- * [Cin, Cx) are not written).  stride 2 (ks 3): H = 2*Ho; upsample: the convolution ran on the nearest-x2 image, (Ho,Wo) = (2H,2W).
+ * [Cin, Cx) are not written).  stride 2 (ks 3): dx is (N, 2Ho, 2Wo, Cx) - the whole zero-stuffed grid is stored, so the layer's input had
+ * even H and W (an odd size has (H + 1) / 2 output rows: the caller refuses it, unet_train.py); upsample: the convolution ran on the
+ * nearest-x2 image, (Ho,Wo) = (2H,2W), both even, Cx a multiple of 4 - and the 2x2 block sums are stored for all Cx channels, so there
+ * the channels [Cin, Cx) come back zero.
  * scratch: hl_conv2d_bwd_data_scratch_bytes(...) of the same arguments (the zero-stuffed / upsampled gradient in front of the
- * convolution's own room); less is refused with HL_ERR_ARG, more is ignored. */
+ * convolution's own room); less is refused with HL_ERR_ARG, more is ignored; arguments the call refuses give 0. */
 size_t hl_conv2d_bwd_data_scratch_bytes(int conv_mode, int N, int Ho, int Wo, int Cy, int Cout, int Cin, int ks, int stride, int upsample, int Cx);
+/* The plan of that call (host arithmetic, no HIP call; the kernel numbers of hl_conv2d_plan): the forward convolution of the gradient,
+ * Cy -> Cin channels on the (Ho, Wo) grid - (2Ho, 2Wo) for stride 2 - with the forms a backward-data call may use (never the fp16x2
+ * ones; the 16-bit form in bf16 under HL_CONV_BF16).  Refuses what the call refuses. */
+int hl_conv2d_bwd_data_plan(int conv_mode, int N, int Ho, int Wo, int Cy, int Cout, int Cin, int ks, int stride, int upsample, int Cx,
+                            int *h_kernel, int *h_splits);
 int hl_conv2d_nhwc_bwd_data(int conv_mode, const float *dy, int N, int Ho, int Wo, int Cy, const float *w_oihw, int Cout, int Cin, int ks,
                             int stride, int upsample, float *dx, int Cx, void *scratch, size_t scratch_bytes, void *stream);
 /* hl_conv2d_wgrad_nhwc_ws: the weight / bias gradients, without atomics.  3x3 layers: k_conv_wgrad_t (a workgroup owns a 64x64 channel block of
