@@ -179,6 +179,32 @@ class Renderer(nn.Module):
             return self._render(tp_input, z_vals, rays_o, rays_d, near, far, tri_planes, n_importance, white_bkgd, n_samples, u,
                                 reevaluate, noise)
 
+    @staticmethod
+    def _maps(rgb, acc, depth):
+        # normal_map aliases rgb_map in the reference (renderer.py:228)
+        return {'rgb_map': rgb, 'acc_map': acc, 'normal_map': rgb, 'depth_map': depth}
+
+    def _deform_tables(self, tp, dev, b=None, side=None):
+        """(verts4, table, Rh, Th) of one posed subject (NeRF/deform.py): the tables posed ahead (tp['deform'], humanliff_amd/body.py: no op
+        chain, no host read) or, without them, built here.  b: the batch entry of a training batch (None: the one subject of a test-mode
+        call); side: that subject's stream, on which every input of the caller's stream that it reads is recorded."""
+        from .deform import deform_tables, prebuilt_tables
+        if self.SMPL_NEUTRAL is None:
+            raise RuntimeError("use_canonical_space=True needs the body model: set renderer.SMPL_NEUTRAL to the SMPL_to_tensor dict")
+        def rec(t):
+            if side is not None and torch.is_tensor(t) and t.is_cuda:
+                t.record_stream(side)
+            return t
+        for v in self.SMPL_NEUTRAL.values():
+            rec(v)
+        dfm = prebuilt_tables(tp, b or 0)
+        if dfm is not None:
+            rec(dfm[0]), rec(dfm[1])
+            return dfm
+        cut = (lambda v: v) if b is None else (lambda v: v[b:b + 1])
+        one = lambda d: {k: rec(cut(v)) for k, v in d.items()}  # noqa: E731
+        return deform_tables(self.SMPL_NEUTRAL, one(tp['params']), one(tp['t_params']), rec(cut(tp['vertices']).to(dev)))
+
     def _render(self, tp_input, z_vals, rays_o, rays_d, near, far, tri_planes, n_importance, white_bkgd, n_samples, u, reevaluate, noise):
         if self.use_canonical_space and self.SMPL_NEUTRAL is None:
             raise RuntimeError("use_canonical_space=True needs the body model: set renderer.SMPL_NEUTRAL to the SMPL_to_tensor dict")
@@ -259,8 +285,7 @@ class Renderer(nn.Module):
                     _lib.ptr(fr), _lib.ptr(zb), _lib.ptr(ub), u_ev, R, n_samples, n_importance, flags,
                     _lib.ptr(rgb[b]), _lib.ptr(acc[b]), _lib.ptr(depth[b]), _lib.ptr(ws), _lib.stream_ptr()),
                     "hl_render_rays")
-            # normal_map aliases rgb_map in the reference (renderer.py:228)
-            return {'rgb_map': rgb, 'acc_map': acc, 'normal_map': rgb, 'depth_map': depth}
+            return self._maps(rgb, acc, depth)
         finally:
             if pending_draw is not None:
                 pending_draw.finish()
@@ -317,7 +342,7 @@ class Renderer(nn.Module):
         rgb = torch.stack([o[0] for o in outs])
         acc = torch.stack([o[1] for o in outs])
         depth = torch.stack([o[2] for o in outs])
-        return {'rgb_map': rgb, 'acc_map': acc, 'normal_map': rgb, 'depth_map': depth}
+        return self._maps(rgb, acc, depth)
 
     def _subject_streams(self, dev, n):
         # (the pool lives outside the module: stream objects in an nn.Module's __dict__ would ride along into copy.deepcopy / torch.save)
@@ -336,24 +361,8 @@ class Renderer(nn.Module):
             if side is not None:
                 t.record_stream(side)
             return t
-        dfm = None
-        if tp_canonical is not None:      # per-subject deformation tables (NeRF/deform.py); `bounds` is t_world_bounds here
-            from .deform import deform_tables, prebuilt_tables
-            if self.SMPL_NEUTRAL is None:
-                raise RuntimeError("use_canonical_space=True needs the body model: set renderer.SMPL_NEUTRAL to the SMPL_to_tensor dict")
-            def rec(t):                   # inputs of the caller's stream that this subject's (side) stream reads
-                if side is not None and torch.is_tensor(t) and t.is_cuda:
-                    t.record_stream(side)
-                return t
-            one = lambda d: {k: rec(v[b:b + 1]) for k, v in d.items()}  # noqa: E731
-            for v in self.SMPL_NEUTRAL.values():
-                rec(v)
-            dfm = prebuilt_tables(tp_canonical, b)      # tables posed ahead (humanliff_amd/body.py): no op chain, no host read
-            if dfm is not None:
-                rec(dfm[0]), rec(dfm[1])
-            else:
-                dfm = deform_tables(self.SMPL_NEUTRAL, one(tp_canonical['params']), one(tp_canonical['t_params']),
-                                    rec(tp_canonical['vertices'][b:b + 1].to(dev)))
+        # per-subject deformation tables; `bounds` is t_world_bounds here
+        dfm = self._deform_tables(tp_canonical, dev, b, side) if tp_canonical is not None else None
         parts = []
         for i in range(0, R, rc):
             sl = slice(i, min(R, i + rc))
@@ -366,10 +375,7 @@ class Renderer(nn.Module):
     def _render_canonical(self, tp_input, z_vals, rays_o, rays_d, near, far, tri_planes, n_importance, white_bkgd, n_samples, u):
         """use_canonical_space=True (renderer.py:114-132, 192-201, 242-246): every sample point and its unit ray direction go through
         deform_target2c (1-NN body vertex, inverse LBS, blend-shape offsets, forward LBS into the big pose) before the tri-plane
-        lookup in tp_input['t_world_bounds'].  One posed subject per call (batch 1)."""
-        from .deform import deform_tables, prebuilt_tables
-        if self.SMPL_NEUTRAL is None:
-            raise RuntimeError("use_canonical_space=True needs the body model: set renderer.SMPL_NEUTRAL to the SMPL_to_tensor dict")
+        lookup in tp_input['t_world_bounds'].  One posed subject per call (batch 1); _render has checked that the body model is there."""
         if self.triplane_ch != 27:
             raise NotImplementedError("the HIP ray-march kernel is specialised for triplane_ch=27")
         assert tri_planes.dim() == 5 and tri_planes.shape[:3] == (1, 3, 9), "tri_planes must be (1, 3, 9, H, W)"
@@ -390,8 +396,7 @@ class Renderer(nn.Module):
                 from .cpu_rng import rand_like_cpu
                 u, pending_draw = rand_like_cpu([R, n_importance], dev)
         try:                                      # (the generator is advanced whatever happens below: see render)
-            verts4, table, Rh, Th = prebuilt_tables(tp_input) or \
-                deform_tables(self.SMPL_NEUTRAL, tp_input['params'], tp_input['t_params'], tp_input['vertices'].to(dev))
+            verts4, table, Rh, Th = self._deform_tables(tp_input, dev)
             L = _lib.lib()
             packed, pp = self._packed_mlp(dev), self._packed_planes(tri_planes[0])
             ws = self._workspace(L.hl_render_canonical_workspace_bytes(R, n_samples, n_importance), dev)
@@ -409,7 +414,7 @@ class Renderer(nn.Module):
                 _lib.ptr(ub), R, n_samples, n_importance, flags, Rh.ctypes.data, Th.ctypes.data, _lib.ptr(verts4), _lib.ptr(table),
                 int(verts4.shape[0]), _lib.ptr(rgb), _lib.ptr(acc), _lib.ptr(depth), _lib.ptr(ws), _lib.stream_ptr()),
                 "hl_render_rays_canonical")
-            return {'rgb_map': rgb, 'acc_map': acc, 'normal_map': rgb, 'depth_map': depth}
+            return self._maps(rgb, acc, depth)
         finally:
             if pending_draw is not None:
                 pending_draw.finish()
@@ -449,11 +454,7 @@ class Renderer(nn.Module):
             # renderer.py:311-314: the lattice spans world_bounds, every point goes through deform_target2c and is looked up in
             # t_world_bounds.  Same column-rays; hl_deform_rays writes their canonical points, hl_render_eval_points evaluates them
             # (full MLP: the density is the first value of the record)
-            from .deform import deform_tables, prebuilt_tables
-            if self.SMPL_NEUTRAL is None:
-                raise RuntimeError("use_canonical_space=True needs the body model: set renderer.SMPL_NEUTRAL to the SMPL_to_tensor dict")
-            verts4, table, Rh, Th = prebuilt_tables(tp_input) or \
-                deform_tables(self.SMPL_NEUTRAL, tp_input['params'], tp_input['t_params'], tp_input['vertices'].to(dev))
+            verts4, table, Rh, Th = self._deform_tables(tp_input, dev)
             tb = tp_input['t_world_bounds'].reshape(-1, 2, 3)[0].to(device=dev, dtype=torch.float32).contiguous()
             pc, dc = torch.empty((T32 * N, 4), device=dev), torch.empty((T32 * N, 4), device=dev)
             rec, scr = torch.empty((T32 * N, 4), device=dev), torch.empty(4, device=dev)

@@ -349,11 +349,9 @@ int attention_backward(const float *qkv, const float *out, const float *dout, in
     do {                                                                                                                                   \
         constexpr int KS_ = CH_ <= 96 ? 4 : 2;                                                                                             \
         constexpr size_t lq = (size_t)KS_ * 2 * 32 * (CH_ + 1) * sizeof(float), lk = (size_t)KS_ * (2 * 32 * (CH_ + 1) + 96) * sizeof(float);  \
-        static const bool ok_ = hipFuncSetAttribute((const void *)k_attn_bwd_q<CH_, KS_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lq) == hipSuccess && \
-                                hipFuncSetAttribute((const void *)k_attn_bwd_kv<CH_, KS_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lk) == hipSuccess;   \
-        HL_REQUIRE(ok_, "attention_backward: cannot raise the dynamic LDS limit");                                                         \
-        hipLaunchKernelGGL((k_attn_bwd_q<CH_, KS_>), grid, dim3(KS_ * 64), lq, st, qkv, out, dout, T, C, heads, dqkv, sc);                  \
-        hipLaunchKernelGGL((k_attn_bwd_kv<CH_, KS_>), grid, dim3(KS_ * 64), lk, st, qkv, dout, sc, T, C, heads, dqkv);                      \
+        int rc_ = launch_lds<k_attn_bwd_q<CH_, KS_>>("k_attn_bwd_q", lq, grid, dim3(KS_ * 64), lq, st, qkv, out, dout, T, C, heads, dqkv, sc);   \
+        if (rc_) return rc_;                                                                                                               \
+        return launch_lds<k_attn_bwd_kv<CH_, KS_>>("k_attn_bwd_kv", lk, grid, dim3(KS_ * 64), lk, st, qkv, dout, sc, T, C, heads, dqkv);     \
     } while (0)
     switch (attn_bwd_fast(C, ch) ? ch : -1) {
         case 32: HL_ATTB(32); break;

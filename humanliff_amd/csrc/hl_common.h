@@ -57,6 +57,22 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 #if defined(__HIPCC__)
+namespace hl {
+// A launch with more dynamic LDS than the default cap allows: raise Kernel's limit to `lds_limit` bytes once per kernel (the static
+// belongs to the instantiation), launch with `lds_bytes` (<= lds_limit; the two differ where the request depends on the layer), check.
+template <auto Kernel>
+inline bool lds_limit_raised(size_t lds_limit) {
+    static const bool ok = hipFuncSetAttribute((const void *)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_limit) == hipSuccess;
+    return ok;
+}
+template <auto Kernel, typename... Args>
+inline int launch_lds(const char *name, size_t lds_limit, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const Args &...args) {
+    HL_REQUIRE(lds_limit_raised<Kernel>(lds_limit), "%s: cannot raise the dynamic LDS limit to %zu bytes", name, lds_limit);
+    hipLaunchKernelGGL(Kernel, grid, block, lds_bytes, st, args...);
+    return check_launch(name);
+}
+}  // namespace hl
+
 // Two fp32 values -> the two packed fp16 planes of the fp16x2 products (round 6): h0 = the NEAREST fp16 (v_cvt_pk_f16_f32), h1 = the nearest fp16 of the residual
 // against h0 converted back (exact in fp32): |x - h0 - h1| <= 2^-23 |x| while both planes are normal; a value beyond fp16's range becomes inf / NaN (loud).
 // Four instructions per pair, written out: the residuals come from v_fma_mix_f32, which reads one fp16 half of the packed h0 as an operand (x - h0 = fma(h0, -1, x),

@@ -1273,23 +1273,17 @@ bool conv3_h2s_ph_applies(int Hout, int Wout, int Cin, int Cout, int ks, int str
 int conv3_h2s_ph_launch(const ConvK &p, hipStream_t st, int splits) {
     HL_REQUIRE(p.wf && p.wsc && conv3_h2s_ph_applies(p.Hout, p.Wout, p.Cin, p.Cout, p.ks, p.stride, p.ups) && p.Hout == 2 * p.Hin && p.Wout == 2 * p.Win &&
                    (splits == 1 || p.partial) && !p.in16 && p.cA == nullptr && p.gn.gt == nullptr, "k_conv_h2s_ph: bad layer");
-    static const bool attr_ok = hipFuncSetAttribute((const void *)k_conv_h2s_ph, hipFuncAttributeMaxDynamicSharedMemorySize, H2S_LDS) == hipSuccess;
-    HL_REQUIRE(attr_ok, "k_conv_h2s_ph: cannot raise the dynamic LDS limit to %d bytes", H2S_LDS);
-    hipLaunchKernelGGL(k_conv_h2s_ph, dim3((unsigned)(p.n_mtiles * p.n_nblocks), 1, (unsigned)splits), dim3(256), (size_t)H2S_LDS, st, p);
-    return check_launch("k_conv_h2s_ph");
+    return launch_lds<k_conv_h2s_ph>("k_conv_h2s_ph", H2S_LDS, dim3((unsigned)(p.n_mtiles * p.n_nblocks), 1, (unsigned)splits), dim3(256), H2S_LDS, st, p);
 }
 
 // the 3x3 / stride-1 layers with fp16x2 products on the 8x16-pixel tile (two workgroups per CU): p.n_mtiles = pixels / 128
 int conv3_h2s_launch(const ConvK &p, hipStream_t st, int splits) {
     HL_REQUIRE(p.wf && p.ks == 3 && conv_h16_applies(p.Hout, p.Wout, p.Cin, p.Cout, p.ks, p.stride, p.ups) && (splits == 1 || p.partial), "k_conv_h2s: bad layer");
     constexpr int LDS_MAX = H2S_LDS + (2 * 4096 + COEF_SCR_FLOATS) * 4;         // + the coefficient table of a fused GroupNorm (<= 4096 input channels)
-    static const bool attr_ok = hipFuncSetAttribute((const void *)k_conv_h2s, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX) == hipSuccess;
-    HL_REQUIRE(attr_ok, "k_conv_h2s: cannot raise the dynamic LDS limit to %d bytes", LDS_MAX);
     const bool aff = p.cA != nullptr || p.gn.gt != nullptr;
     HL_REQUIRE(!aff || (p.Cin <= 4096 && !p.in16 && !p.ups), "k_conv_h2s: fused GroupNorm needs a raw fp32 input of <= 4096 channels");
     const size_t lds_bytes = (size_t)H2S_LDS + (aff ? (size_t)(2 * p.Cin + COEF_SCR_FLOATS) * 4 : 0);
-    hipLaunchKernelGGL(k_conv_h2s, dim3((unsigned)(p.n_mtiles * p.n_nblocks), 1, (unsigned)splits), dim3(256), lds_bytes, st, p);
-    return check_launch("k_conv_h2s");
+    return launch_lds<k_conv_h2s>("k_conv_h2s", LDS_MAX, dim3((unsigned)(p.n_mtiles * p.n_nblocks), 1, (unsigned)splits), dim3(256), lds_bytes, st, p);
 }
 
 // the 3x3 / stride-2 layers: p.n_mtiles = output pixels / 128
@@ -1297,23 +1291,17 @@ bool conv3_h2d_applies(int Hout, int Wout, int Cin, int Cout) { return Hout % 8 
 int conv3_h2d_launch(const ConvK &p, hipStream_t st) {
     HL_REQUIRE(p.wf && p.ks == 3 && p.stride == 2 && !p.ups && !p.in16 && !p.partial && conv3_h2d_applies(p.Hout, p.Wout, p.Cin, p.Cout) && p.cA == nullptr && p.gn.gt == nullptr,
                "k_conv_h2d: bad layer");
-    static const bool attr_ok = hipFuncSetAttribute((const void *)k_conv_h2d, hipFuncAttributeMaxDynamicSharedMemorySize, H2D_LDS) == hipSuccess;
-    HL_REQUIRE(attr_ok, "k_conv_h2d: cannot raise the dynamic LDS limit to %d bytes", H2D_LDS);
-    hipLaunchKernelGGL(k_conv_h2d, dim3((unsigned)(p.n_mtiles * p.n_nblocks)), dim3(256), (size_t)H2D_LDS, st, p);
-    return check_launch("k_conv_h2d");
+    return launch_lds<k_conv_h2d>("k_conv_h2d", H2D_LDS, dim3((unsigned)(p.n_mtiles * p.n_nblocks)), dim3(256), H2D_LDS, st, p);
 }
 
 // the 1x1 layers on 128-pixel tiles (two workgroups per CU): p.n_mtiles = pixels / 128
 int conv1_h2s_launch(const ConvK &p, hipStream_t st, int splits) {
     HL_REQUIRE(p.wf && conv1_h2_applies(p.Hout, p.Wout, p.Cin, p.Cout, p.ks, p.stride, p.ups) && (splits == 1 || p.partial) && !p.in16 && p.kt_per >= 1, "k_conv1_h2s: bad layer");
     constexpr int LDS_MAX = H2S1_LDS + (2 * 4096 + COEF_SCR_FLOATS) * 4;        // + the coefficient table of a fused GroupNorm (<= 4096 input channels)
-    static const bool attr_ok = hipFuncSetAttribute((const void *)k_conv1_h2s, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX) == hipSuccess;
-    HL_REQUIRE(attr_ok, "k_conv1_h2s: cannot raise the dynamic LDS limit to %d bytes", LDS_MAX);
     const bool aff = p.cA != nullptr || p.gn.gt != nullptr;
     HL_REQUIRE(!aff || (p.Cin <= 4096 && ((long)p.Hout * p.Wout) % 128 == 0), "k_conv1_h2s: fused GroupNorm needs <= 4096 input channels and whole tiles per image");
     const size_t lds_bytes = (size_t)H2S1_LDS + (aff ? (size_t)(2 * p.Cin + COEF_SCR_FLOATS) * 4 : 0);
-    hipLaunchKernelGGL(k_conv1_h2s, dim3((unsigned)(p.n_mtiles * p.n_nblocks), 1, (unsigned)splits), dim3(256), lds_bytes, st, p);
-    return check_launch("k_conv1_h2s");
+    return launch_lds<k_conv1_h2s>("k_conv1_h2s", LDS_MAX, dim3((unsigned)(p.n_mtiles * p.n_nblocks), 1, (unsigned)splits), dim3(256), lds_bytes, st, p);
 }
 
 size_t conv_h16_lds_bytes() { return (size_t)2 * H1_STAGE; }   // 104 KB: the two 1x1 stages (the epilogue exchange needs 98 KB, the 3x3 patch stages 45 KB)
@@ -1323,22 +1311,12 @@ int conv_h16_launch(const ConvK &p, int f16, hipStream_t st, int splits) {
     HL_REQUIRE(splits == 1 || (p.ks == 3 && p.partial), "k_conv_h16: split-K is the 3x3 kernel's");
     const dim3 grid((unsigned)(p.n_mtiles * p.n_nblocks), 1, (unsigned)splits);
     const size_t sh = conv_h16_lds_bytes();
-    static const bool attr_ok = [] {
-        const int b = (int)conv_h16_lds_bytes();
-        return hipFuncSetAttribute((const void *)k_conv_h16<true>, hipFuncAttributeMaxDynamicSharedMemorySize, b) == hipSuccess &&
-               hipFuncSetAttribute((const void *)k_conv_h16<false>, hipFuncAttributeMaxDynamicSharedMemorySize, b) == hipSuccess &&
-               hipFuncSetAttribute((const void *)k_conv1_h16<true>, hipFuncAttributeMaxDynamicSharedMemorySize, b) == hipSuccess &&
-               hipFuncSetAttribute((const void *)k_conv1_h16<false>, hipFuncAttributeMaxDynamicSharedMemorySize, b) == hipSuccess;
-    }();
-    HL_REQUIRE(attr_ok, "k_conv_h16: cannot raise the dynamic LDS limit to %zu bytes", sh);
-    if (p.ks == 1) {
-        if (f16) hipLaunchKernelGGL((k_conv1_h16<true>), grid, dim3(256), sh, st, p);
-        else hipLaunchKernelGGL((k_conv1_h16<false>), grid, dim3(256), sh, st, p);
-        return check_launch("k_conv1_h16");
+    if (p.ks != 1) {
+        return f16 ? launch_lds<k_conv_h16<true>>("k_conv_h16", sh, grid, dim3(256), sh, st, p)
+                   : launch_lds<k_conv_h16<false>>("k_conv_h16", sh, grid, dim3(256), sh, st, p);
     }
-    if (f16) hipLaunchKernelGGL((k_conv_h16<true>), grid, dim3(256), sh, st, p);
-    else hipLaunchKernelGGL((k_conv_h16<false>), grid, dim3(256), sh, st, p);
-    return check_launch("k_conv_h16");
+    return f16 ? launch_lds<k_conv1_h16<true>>("k_conv1_h16", sh, grid, dim3(256), sh, st, p)
+               : launch_lds<k_conv1_h16<false>>("k_conv1_h16", sh, grid, dim3(256), sh, st, p);
 }
 
 }  // namespace hl

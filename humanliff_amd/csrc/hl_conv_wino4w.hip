@@ -521,18 +521,10 @@ int conv_wino4w_launch(const ConvK &p, int ups, int blk, int splits, hipStream_t
     HL_REQUIRE(p.Cout % 64 == 0 && p.Cin % 8 == 0 && p.wf, "k_conv_wino4w: bad layer");
     HL_REQUIRE(!(ups && blk), "k_conv_wino4w: the upsampling convolution reads a raw NHWC tensor");
     const dim3 grid((unsigned)(p.n_mtiles * p.n_nblocks), 1, (unsigned)splits);
-    const size_t sh = conv_wino4w_lds_bytes();
-    static const bool attr_ok = [] {   // 144 KB of dynamic LDS: above the default cap
-        const int b = (int)conv_wino4w_lds_bytes();
-        return hipFuncSetAttribute((const void *)k_conv_wino4w<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, b) == hipSuccess &&
-               hipFuncSetAttribute((const void *)k_conv_wino4w<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, b) == hipSuccess &&
-               hipFuncSetAttribute((const void *)k_conv_wino4w<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, b) == hipSuccess;
-    }();
-    HL_REQUIRE(attr_ok, "k_conv_wino4w: cannot raise the dynamic LDS limit to %zu bytes", sh);
-    if (ups) hipLaunchKernelGGL((k_conv_wino4w<true, false>), grid, dim3(256), sh, st, p);
-    else if (blk) hipLaunchKernelGGL((k_conv_wino4w<false, true>), grid, dim3(256), sh, st, p);
-    else hipLaunchKernelGGL((k_conv_wino4w<false, false>), grid, dim3(256), sh, st, p);
-    return check_launch("k_conv_wino4w");
+    const size_t sh = conv_wino4w_lds_bytes();   // 144 KB of dynamic LDS: above the default cap
+    if (ups) return launch_lds<k_conv_wino4w<true, false>>("k_conv_wino4w", sh, grid, dim3(256), sh, st, p);
+    if (blk) return launch_lds<k_conv_wino4w<false, true>>("k_conv_wino4w", sh, grid, dim3(256), sh, st, p);
+    return launch_lds<k_conv_wino4w<false, false>>("k_conv_wino4w", sh, grid, dim3(256), sh, st, p);
 }
 
 }  // namespace hl

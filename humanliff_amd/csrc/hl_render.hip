@@ -3406,11 +3406,28 @@ __global__ __launch_bounds__(256) void k_wgrad_finish(const WgradArgs a, int n_r
     }
 }
 
+// ---- the two packed MLP buffers: one row per section (it starts where the row above ends); every host pointer into them comes from the accessors ----
+constexpr size_t MLP_F16_OFF = (size_t)PACKED_FLOATS * sizeof(float);      // hl_render_mlp_pack: behind the fp32 image (k_march; its small block holds the fp16x2 layer scales)
+constexpr size_t MLP_B3_OFF = MLP_F16_OFF + (size_t)P16_FRAGS * 1024;      // behind the fp16 fragments of k_march16
+constexpr size_t MLP_H2_OFF = MLP_B3_OFF + B3_BYTES;                       // behind the three bf16 planes of k_march_plw<3>
+constexpr size_t MLP_BYTES = MLP_H2_OFF + (size_t)P16_FRAGS * 2 * 1024;    // behind the two fp16 planes of the fp16x2 products (k_march_plw<2>)
+constexpr size_t BWD_H2_OFF = (size_t)NCH_BWD * CHUNK_FLOATS * sizeof(float);   // hl_render_mlp_pack_bwd: behind the fp32 image
+constexpr size_t BWD_SCALES_OFF = 2 * BWD_H2_OFF;                          // behind the two fp16 planes (k_pack_mlp_bwd_h2)
+constexpr size_t BWD_BYTES = BWD_SCALES_OFF + 16 * sizeof(float);          // behind the planes' layer scales + inverses (k_mlp_scales_h2)
+// (the buffers are written by the pack entry points and read by every launcher: the accessors serve both)
+template <typename T> static inline T *section(const void *packed, size_t off) { return reinterpret_cast<T *>(static_cast<char *>(const_cast<void *>(packed)) + off); }
+static inline float *mlp_f32(const void *packed) { return section<float>(packed, 0); }
+static inline unsigned short *mlp_f16(const void *packed) { return section<unsigned short>(packed, MLP_F16_OFF); }
+static inline unsigned short *mlp_b3(const void *packed) { return section<unsigned short>(packed, MLP_B3_OFF); }
+static inline unsigned short *mlp_h2(const void *packed) { return section<unsigned short>(packed, MLP_H2_OFF); }
+static inline float *mlp_h2_scales(const void *packed) { return mlp_f32(packed) + NCH_FULL * CHUNK_FLOATS + SM_SC; }
+static inline float *bwd_f32(const void *packed) { return section<float>(packed, 0); }
+static inline unsigned short *bwd_h2(const void *packed) { return section<unsigned short>(packed, BWD_H2_OFF); }
+static inline float *bwd_scales(const void *packed) { return section<float>(packed, BWD_SCALES_OFF); }
+
 extern "C" {
 
-// fp32 image + the fp16 fragments of k_march16 + the three bf16 planes of k_march_plw<3>
-// (+ the two fp16 planes of the fp16x2 products)
-size_t hl_render_mlp_packed_bytes(void) { return (size_t)PACKED_FLOATS * sizeof(float) + (size_t)P16_FRAGS * 1024 + B3_BYTES + (size_t)P16_FRAGS * 2 * 1024; }
+size_t hl_render_mlp_packed_bytes(void) { return MLP_BYTES; }
 
 int hl_render_mlp_pack(const hl_render_mlp_params *p, void *packed, void *stream) {
     HL_REQUIRE(p && packed, "hl_render_mlp_pack: null argument");
@@ -3420,23 +3437,20 @@ int hl_render_mlp_pack(const hl_render_mlp_params *p, void *packed, void *stream
     a.alpha_w = p->alpha_w; a.alpha_b = p->alpha_b; a.rgb_w = p->rgb_w; a.rgb_b = p->rgb_b;
     for (int i = 0; i < 5; ++i) HL_REQUIRE(a.w[i] && a.b[i], "hl_render_mlp_pack: null weight %d", i);
     HL_REQUIRE(a.alpha_w && a.alpha_b && a.rgb_w && a.rgb_b, "hl_render_mlp_pack: null head weight");
-    a.out = (float *)packed;
+    a.out = mlp_f32(packed);
     hipLaunchKernelGGL(k_pack_mlp, dim3((PACKED_FLOATS + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
     int rc = hl::check_launch("k_pack_mlp");
     if (rc) return rc;
-    hipLaunchKernelGGL(k_pack_mlp16, dim3(P16_FRAGS * 2), dim3(256), 0, (hipStream_t)stream, a,
-                       reinterpret_cast<unsigned short *>(static_cast<float *>(packed) + PACKED_FLOATS));
+    hipLaunchKernelGGL(k_pack_mlp16, dim3(P16_FRAGS * 2), dim3(256), 0, (hipStream_t)stream, a, mlp_f16(packed));
     rc = hl::check_launch("k_pack_mlp16");
     if (rc) return rc;
-    hipLaunchKernelGGL(k_pack_mlp_b3, dim3(P16_FRAGS * 3 * 2), dim3(256), 0, (hipStream_t)stream, a,
-                       reinterpret_cast<unsigned short *>(static_cast<char *>(packed) + (size_t)PACKED_FLOATS * sizeof(float) + (size_t)P16_FRAGS * 1024));
+    hipLaunchKernelGGL(k_pack_mlp_b3, dim3(P16_FRAGS * 3 * 2), dim3(256), 0, (hipStream_t)stream, a, mlp_b3(packed));
     rc = hl::check_launch("k_pack_mlp_b3");
     if (rc) return rc;
-    hipLaunchKernelGGL(k_mlp_scales_h2, dim3(5), dim3(256), 0, (hipStream_t)stream, a, a.out + NCH_FULL * CHUNK_FLOATS + SM_SC);      // (behind k_pack_mlp, which wrote 1s there; in front of the planes that read them)
+    hipLaunchKernelGGL(k_mlp_scales_h2, dim3(5), dim3(256), 0, (hipStream_t)stream, a, mlp_h2_scales(packed));      // (behind k_pack_mlp, which wrote 1s there; in front of the planes that read them)
     rc = hl::check_launch("k_mlp_scales_h2");
     if (rc) return rc;
-    hipLaunchKernelGGL(k_pack_mlp_h2, dim3(P16_FRAGS * 2 * 2), dim3(256), 0, (hipStream_t)stream, a,
-                       reinterpret_cast<unsigned short *>(static_cast<char *>(packed) + (size_t)PACKED_FLOATS * sizeof(float) + (size_t)P16_FRAGS * 1024 + B3_BYTES));
+    hipLaunchKernelGGL(k_pack_mlp_h2, dim3(P16_FRAGS * 2 * 2), dim3(256), 0, (hipStream_t)stream, a, mlp_h2(packed));
     return hl::check_launch("k_pack_mlp_h2");
 }
 
@@ -3459,23 +3473,71 @@ static inline int imp_rays_per_wave(int64_t n_rays) {
     return rpw;
 }
 
-size_t hl_render_workspace_bytes(int64_t n_rays, int n_samples, int n_importance) {
-    if (n_rays <= 0 || n_importance <= 0) return 256;
-    // tile-major [ceil(R/32)][samples][32].  Evaluate-once pipeline: raw sample records (float4) of the n_samples coarse and
-    // the n_importance new points + the sorted new depths; HL_RENDER_REEVALUATE: sigma (n_samples) + z_all (both) - smaller
-    return (size_t)tiles32(n_rays) * 32 * ((size_t)(n_samples + n_importance) * 4 + n_importance) * sizeof(float) + 256;
+// ---- the render workspace: tile-major [ceil(R/32)][samples][32] buffers of one hl_render_rays* call, carved and sized in one place ----
+enum class Schedule { EvalOnce, Reevaluate, Canonical };
+struct Workspace {
+    float *vc, *vn, *zn;        // EvalOnce: raw sample records (float4) of the n_samples coarse and the n_importance new points, the sorted new depths
+    float *sigma, *z_all;       // Reevaluate (HL_RENDER_REEVALUATE): sigma (n_samples) + z_all (both) - the same memory, smaller
+    float *pc, *dc;             // Canonical, behind the EvalOnce buffers: canonical points of the pass in flight, then directions (256-byte aligned)
+    void *deform_counter;       // Canonical: work counter of the deformation kernel
+    size_t bytes;
+};
+static Workspace render_workspace(void *base, int64_t n_rays, int n_samples, int n_importance, Schedule sched) {   // base = null: the size query
+    Workspace w{};
+    w.bytes = 256;
+    if (n_rays <= 0 || (n_importance <= 0 && sched != Schedule::Canonical)) return w;
+    if (n_importance <= 0) n_importance = n_samples;   // (the canonical size query alone gets here: it sizes the evaluate-once part for equal counts)
+    const size_t T32 = (size_t)tiles32(n_rays) * 32;
+    const auto at = [&](size_t floats) { return (float *)((uintptr_t)base + floats * sizeof(float)); };
+    const size_t end = T32 * ((size_t)(n_samples + n_importance) * 4 + n_importance);   // floats of the evaluate-once buffers
+    w.vc = at(0); w.vn = at(T32 * n_samples * 4); w.zn = at(T32 * (n_samples + n_importance) * 4);
+    w.sigma = at(0); w.z_all = at(T32 * n_samples);
+    w.bytes = end * sizeof(float) + 256;
+    if (sched == Schedule::Canonical) {
+        const size_t each = T32 * (n_samples > n_importance ? n_samples : n_importance) * sizeof(float4);
+        const uintptr_t pc = ((uintptr_t)at(end) + 255) / 256 * 256;
+        w.pc = (float *)pc; w.dc = (float *)(pc + each); w.deform_counter = (void *)(pc + 2 * each);
+        w.bytes += 2 * each + 512;
+    }
+    return w;
 }
 
-static int fill_march(MarchArgs &a, const void *mlp, const void *planes, int H, int W, const float *bounds,
-                      const float *ro, const float *rd, const float *nr, const float *fr) {
-    HL_REQUIRE(mlp && planes && bounds && ro && rd && nr && fr, "render: null argument");
+size_t hl_render_workspace_bytes(int64_t n_rays, int n_samples, int n_importance) {
+    return render_workspace(nullptr, n_rays, n_samples, n_importance, Schedule::EvalOnce).bytes;
+}
+
+static inline int mlp_mode_of(unsigned flags) {   // 0 fp32 MFMA, 1 fp16 operands (opt-in), 2 bf16x3 split products, 3 fp16x2 products
+    return (flags & HL_RENDER_MLP_FP16) ? 1 : ((flags & HL_RENDER_MLP_FP16X2) ? 3 : ((flags & HL_RENDER_MLP_BF16X3) ? 2 : 0));
+}
+
+// ---- MarchArgs: what every march / MLP launch starts from.  `planes` may be null only with `bwd` (k_mlp_bwd reads the backward pack instead) ----
+static int fill_march(MarchArgs &a, const void *mlp, const void *planes, int H, int W, const float *bounds, const float *ro, const float *rd,
+                      const float *nr, const float *fr, const float *z, int z_tiled, int64_t n_rays, int n_samples, const void *bwd = nullptr) {
+    HL_REQUIRE(mlp && (planes || bwd) && bounds && ro && rd && nr && fr, "render: null argument");
     HL_REQUIRE(H > 0 && W > 0, "render: bad plane size %dx%d", H, W);
-    a.packed = (const float *)mlp;
+    a.packed = mlp_f32(mlp); a.bwd_packed = bwd ? bwd_f32(bwd) : nullptr;
     a.planes = (const float4 *)planes;
     a.H = H; a.W = W;
     a.bounds = bounds;
     a.rays_o = ro; a.rays_d = rd; a.near = nr; a.far = fr;
+    a.z = z; a.z_tiled = z_tiled; a.R = n_rays; a.S = n_samples;
     return HL_OK;
+}
+// the POINTS kernels read canonical points / directions, tile-major; they still load o, d, near, far of their ray unconditionally: placeholders
+static int fill_march_points(MarchArgs &a, const void *mlp, const void *planes, int H, int W, const float *bounds, const float *pts_c,
+                             const float *dirs_c, int64_t n_rays, int n_samples) {
+    a.pts_c = (const float4 *)pts_c; a.dirs_c = (const float4 *)dirs_c;
+    return fill_march(a, mlp, planes, H, W, bounds, pts_c, pts_c, pts_c, pts_c, nullptr, 0, n_rays, n_samples);
+}
+// The sample-split launches (the ACTS passes and k_mlp_bwd).  One workgroup per CU is resident (8 waves of ~240 VGPRs): aim at two rounds of
+// 256 workgroups.  Sets a.s_per; returns the grid (ray groups, sample ranges).
+static dim3 sample_split_grid(MarchArgs &a) {
+    const unsigned groups = (unsigned)((a.R + 255) / 256);
+    unsigned splits = (512 + groups - 1) / groups;
+    if (splits > (unsigned)a.S) splits = (unsigned)a.S;
+    if (splits < 1) splits = 1;
+    a.s_per = (a.S + (int)splits - 1) / (int)splits;
+    return dim3(groups, (unsigned)((a.S + a.s_per - 1) / a.s_per));
 }
 
 int hl_render_coarse(const void *mlp_packed, const void *planes_packed, int H, int W, const float *bounds,
@@ -3483,9 +3545,9 @@ int hl_render_coarse(const void *mlp_packed, const void *planes_packed, int H, i
                      const float *z_vals, int64_t n_rays, int n_samples, float *sigma_out, void *stream) {
     HL_REQUIRE(n_rays > 0 && n_samples >= 2 && sigma_out, "hl_render_coarse: bad argument");
     MarchArgs a{};
-    int rcode = fill_march(a, mlp_packed, planes_packed, H, W, bounds, rays_o, rays_d, near, far);
+    int rcode = fill_march(a, mlp_packed, planes_packed, H, W, bounds, rays_o, rays_d, near, far, z_vals, 0, n_rays, n_samples);
     if (rcode) return rcode;
-    a.z = z_vals; a.z_tiled = 0; a.R = n_rays; a.S = n_samples; a.flags = 0; a.sigma_out = sigma_out;
+    a.sigma_out = sigma_out;
     const unsigned grid = (unsigned)((n_rays + 255) / 256);
     hipLaunchKernelGGL(k_march<false>, dim3(grid), dim3(512), 0, (hipStream_t)stream, a);
     return hl::check_launch("k_march<coarse>");
@@ -3503,63 +3565,42 @@ int hl_render_importance(const float *sigma, const float *rays_d, const float *n
     return hl::check_launch("k_importance");
 }
 
-static int render_fine_impl(const void *mlp_packed, const void *planes_packed, int H, int W, const float *bounds,
-                            const float *rays_o, const float *rays_d, const float *near, const float *far, const float *z_all,
-                            int z_tiled, int64_t n_rays, int n_total_samples, unsigned flags, float *rgb, float *acc,
-                            float *depth, void *stream) {
+int hl_render_fine(const void *mlp_packed, const void *planes_packed, int H, int W, const float *bounds,
+                   const float *rays_o, const float *rays_d, const float *near, const float *far, const float *z_all,
+                   int z_tiled, int64_t n_rays, int n_total_samples, unsigned flags, float *rgb, float *acc, float *depth,
+                   void *stream) {
     HL_REQUIRE(n_rays > 0 && n_total_samples >= 2 && rgb && acc && depth, "hl_render_fine: bad argument");
     MarchArgs a{};
-    int rcode = fill_march(a, mlp_packed, planes_packed, H, W, bounds, rays_o, rays_d, near, far);
+    int rcode = fill_march(a, mlp_packed, planes_packed, H, W, bounds, rays_o, rays_d, near, far, z_all, z_tiled, n_rays, n_total_samples);
     if (rcode) return rcode;
-    a.z = z_all; a.z_tiled = z_tiled; a.R = n_rays; a.S = n_total_samples; a.flags = flags;
+    a.flags = flags;
     a.rgb = rgb; a.acc = acc; a.depth = depth;
     const unsigned grid = (unsigned)((n_rays + 255) / 256);
     hipLaunchKernelGGL(k_march<true>, dim3(grid), dim3(512), 0, (hipStream_t)stream, a);
     return hl::check_launch("k_march<fine>");
 }
 
-int hl_render_fine(const void *mlp_packed, const void *planes_packed, int H, int W, const float *bounds,
-                   const float *rays_o, const float *rays_d, const float *near, const float *far, const float *z_all,
-                   int z_tiled, int64_t n_rays, int n_total_samples, unsigned flags, float *rgb, float *acc, float *depth,
-                   void *stream) {
-    return render_fine_impl(mlp_packed, planes_packed, H, W, bounds, rays_o, rays_d, near, far, z_all, z_tiled, n_rays,
-                            n_total_samples, flags, rgb, acc, depth, stream);
-}
-
 static int render_eval_impl(const void *mlp_packed, const void *planes_packed, int H, int W, const float *bounds, const float *rays_o,
                             const float *rays_d, const float *near, const float *far, const float *z, int z_tiled, int64_t n_rays,
-                            int n_samples, float *records_out, int mlp_mode, void *stream) {   // mlp_mode: 0 fp32 MFMA, 1 fp16 operands (opt-in), 2 bf16x3 split products
+                            int n_samples, float *records_out, int mlp_mode, void *stream) {   // mlp_mode: see mlp_mode_of
     HL_REQUIRE(n_rays > 0 && n_samples >= 1 && records_out, "hl_render_eval: bad argument");
     MarchArgs a{};
-    int rcode = fill_march(a, mlp_packed, planes_packed, H, W, bounds, rays_o, rays_d, near, far);
+    int rcode = fill_march(a, mlp_packed, planes_packed, H, W, bounds, rays_o, rays_d, near, far, z, z_tiled, n_rays, n_samples);
     if (rcode) return rcode;
-    a.z = z; a.z_tiled = z_tiled; a.R = n_rays; a.S = n_samples; a.flags = 0; a.vals_out = (float4 *)records_out;
-    if (mlp_mode == 3) {   // HL_RENDER_MLP_FP16X2: two fp16 planes per operand, three partial products, fp32 accumulation
-        const unsigned short *ph2 = reinterpret_cast<const unsigned short *>(static_cast<const char *>(mlp_packed) + (size_t)PACKED_FLOATS * sizeof(float) + (size_t)P16_FRAGS * 1024 + B3_BYTES);
-        static const bool okh = hipFuncSetAttribute((const void *)k_march_plw<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PLW_LDS<2>) == hipSuccess;
-        HL_REQUIRE(okh, "k_march_plw<2>: cannot raise the dynamic LDS limit to %zu bytes", PLW_LDS<2>);
-        hipLaunchKernelGGL(k_march_plw<2>, dim3((unsigned)((n_rays + 255) / 256)), dim3(512), PLW_LDS<2>, (hipStream_t)stream, a, ph2);
-        return hl::check_launch("k_march_plw<2>");
-    }
-    if (mlp_mode == 2) {   // HL_RENDER_MLP_BF16X3: exact three-way bf16 split of both operands, six partial products, fp32 accumulation
-        const unsigned short *pb3 = reinterpret_cast<const unsigned short *>(static_cast<const char *>(mlp_packed) + (size_t)PACKED_FLOATS * sizeof(float) + (size_t)P16_FRAGS * 1024);
-        static const bool okw = hipFuncSetAttribute((const void *)k_march_plw<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)B3W_LDS) == hipSuccess;
-        HL_REQUIRE(okw, "k_march_b3w: cannot raise the dynamic LDS limit to %zu bytes", B3W_LDS);
-        hipLaunchKernelGGL(k_march_plw<3>, dim3((unsigned)((n_rays + 255) / 256)), dim3(512), B3W_LDS, (hipStream_t)stream, a, pb3);
-        return hl::check_launch("k_march_b3w");
-    }
+    a.vals_out = (float4 *)records_out;
+    const dim3 grid((unsigned)((n_rays + 255) / 256));
+    if (mlp_mode == 3)   // HL_RENDER_MLP_FP16X2: two fp16 planes per operand, three partial products, fp32 accumulation
+        return hl::launch_lds<k_march_plw<2>>("k_march_plw<2>", PLW_LDS<2>, grid, dim3(512), PLW_LDS<2>, (hipStream_t)stream, a, mlp_h2(mlp_packed));
+    if (mlp_mode == 2)   // HL_RENDER_MLP_BF16X3: exact three-way bf16 split of both operands, six partial products, fp32 accumulation
+        return hl::launch_lds<k_march_plw<3>>("k_march_plw<3>", B3W_LDS, grid, dim3(512), B3W_LDS, (hipStream_t)stream, a, mlp_b3(mlp_packed));
     if (mlp_mode == 1) {   // HL_RENDER_MLP_FP16 (opt-in): fp16 operands, all weights LDS-resident
-        const size_t sh = (size_t)P16_FRAGS * 1024 + SMALL_FLOATS * sizeof(float);
-        static const bool attr_ok = hipFuncSetAttribute((const void *)k_march16<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh) == hipSuccess;
-        HL_REQUIRE(attr_ok, "k_march16: cannot raise the dynamic LDS limit to %zu bytes", sh);
-        const unsigned short *p16 = reinterpret_cast<const unsigned short *>(static_cast<const float *>(mlp_packed) + PACKED_FLOATS);
+        const size_t sh = (MLP_B3_OFF - MLP_F16_OFF) + SMALL_FLOATS * sizeof(float);
         // 4 waves = one per SIMD (512 registers, no spills: 20.1 against 21.9 ms per view with 8)
-        hipLaunchKernelGGL(k_march16<4>, dim3((unsigned)((n_rays + 127) / 128)), dim3(256), sh, (hipStream_t)stream, a, p16);
-        return hl::check_launch("k_march16");
+        return hl::launch_lds<k_march16<4>>("k_march16", sh, dim3((unsigned)((n_rays + 127) / 128)), dim3(256), sh, (hipStream_t)stream, a, mlp_f16(mlp_packed));
     }
     // (4-wave workgroups, two per CU with independent barriers, measured equal - 74.5 vs 74.7 ms per view - at twice the weight
     //  traffic: 8 waves it is)
-    hipLaunchKernelGGL((k_march<true, true, 8>), dim3((unsigned)((n_rays + 255) / 256)), dim3(512), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL((k_march<true, true, 8>), grid, dim3(512), 0, (hipStream_t)stream, a);
     return hl::check_launch("k_march<eval>");
 }
 
@@ -3569,18 +3610,14 @@ static int render_onepass_fine(const void *mlp_packed, const void *planes_packed
                                unsigned flags, int npl, float *rgb, float *acc, float *depth, void *stream) {
     HL_REQUIRE(vc && u && zn_scratch && rgb && acc && depth && n_samples >= 3 && n_samples <= 128, "render_onepass_fine: bad argument");
     MarchArgs a{};
-    int rcode = fill_march(a, mlp_packed, planes_packed, H, W, bounds, rays_o, rays_d, near, far);
+    int rcode = fill_march(a, mlp_packed, planes_packed, H, W, bounds, rays_o, rays_d, near, far, zn_scratch, 1, n_rays, n_samples);
     if (rcode) return rcode;
-    a.z = zn_scratch; a.z_tiled = 1; a.R = n_rays; a.S = n_samples; a.flags = flags;
+    a.flags = flags;
     a.fz_vc = (const float4 *)vc; a.fz_u = u; a.fz_zn = zn_scratch; a.fz_N = n_samples;
     a.rgb = rgb; a.acc = acc; a.depth = depth;
     const dim3 grid((unsigned)((n_rays + 255) / 256));
     if (npl == 2) {
-        const unsigned short *ph2 = reinterpret_cast<const unsigned short *>(static_cast<const char *>(mlp_packed) + (size_t)PACKED_FLOATS * sizeof(float) + (size_t)P16_FRAGS * 1024 + B3_BYTES);
-        static const bool okh = hipFuncSetAttribute((const void *)k_march_plw<2, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PLW_LDS_FUSE<2>) == hipSuccess;
-        HL_REQUIRE(okh, "k_march_plw<2, one-pass>: cannot raise the dynamic LDS limit to %zu bytes", PLW_LDS_FUSE<2>);
-        hipLaunchKernelGGL((k_march_plw<2, false, true>), grid, dim3(512), PLW_LDS_FUSE<2>, (hipStream_t)stream, a, ph2);
-        return hl::check_launch("k_march_plw<2, one-pass>");
+        return hl::launch_lds<k_march_plw<2, false, true>>("k_march_plw<2, one-pass>", PLW_LDS_FUSE<2>, grid, dim3(512), PLW_LDS_FUSE<2>, (hipStream_t)stream, a, mlp_h2(mlp_packed));
     }
     return hl::fail(HL_ERR_UNSUPPORTED, "render_onepass_fine: the one-pass launch exists for the fp16x2 products only");
 }
@@ -3596,7 +3633,7 @@ int hl_render_eval_products(const void *mlp_packed, const void *planes_packed, i
                             const float *rays_d, const float *near, const float *far, const float *z, int z_tiled, int64_t n_rays,
                             int n_samples, unsigned flags, float *records_out, void *stream) {
     return render_eval_impl(mlp_packed, planes_packed, H, W, bounds, rays_o, rays_d, near, far, z, z_tiled, n_rays, n_samples, records_out,
-                            (flags & HL_RENDER_MLP_FP16) ? 1 : ((flags & HL_RENDER_MLP_FP16X2) ? 3 : ((flags & HL_RENDER_MLP_BF16X3) ? 2 : 0)), stream);
+                            mlp_mode_of(flags), stream);
 }
 
 int hl_render_importance_new(const float *records, const float *rays_d, const float *near, const float *far, const float *z_vals,
@@ -3641,29 +3678,22 @@ int hl_render_composite_noise(const float *near, const float *far, const float *
 }
 
 // ---- training: backward of the evaluate-once pipeline ----
-// one workgroup per CU is resident (8 waves of ~240 VGPRs): aim at two rounds of 256 workgroups
-static inline unsigned sample_splits(unsigned ray_groups, int n_samples) {
-    unsigned s = (512 + ray_groups - 1) / ray_groups;
-    if (s > (unsigned)n_samples) s = (unsigned)n_samples;
-    return s < 1 ? 1 : s;
-}
-size_t hl_render_mlp_bwd_packed_bytes(void) { return (size_t)(2 * NCH_BWD * CHUNK_FLOATS + 16) * sizeof(float); }   // the fp32 image, the two fp16 planes (k_pack_mlp_bwd_h2), the planes' layer scales + inverses
+size_t hl_render_mlp_bwd_packed_bytes(void) { return BWD_BYTES; }
 
 int hl_render_mlp_pack_bwd(const hl_render_mlp_params *p, void *packed, void *stream) {
     HL_REQUIRE(p && packed, "hl_render_mlp_pack_bwd: null argument");
     PackArgs a{};
     a.w[0] = p->pts0_w; a.w[1] = p->pts1_w; a.w[2] = p->pts2_w; a.w[3] = p->feat_w; a.w[4] = p->views_w;
     for (int i = 0; i < 5; ++i) HL_REQUIRE(a.w[i], "hl_render_mlp_pack_bwd: null weight %d", i);
-    a.out = (float *)packed;
+    a.out = bwd_f32(packed);
     hipLaunchKernelGGL(k_pack_mlp_bwd, dim3((NCH_BWD * CHUNK_FLOATS + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
     int rc_ = hl::check_launch("k_pack_mlp_bwd");
     if (rc_) return rc_;
-    float *wsc = static_cast<float *>(packed) + 2 * NCH_BWD * CHUNK_FLOATS;
-    hipLaunchKernelGGL(k_mlp_scales_h2, dim3(5), dim3(256), 0, (hipStream_t)stream, a, wsc);
+    hipLaunchKernelGGL(k_mlp_scales_h2, dim3(5), dim3(256), 0, (hipStream_t)stream, a, bwd_scales(packed));
     rc_ = hl::check_launch("k_mlp_scales_h2");
     if (rc_) return rc_;
-    hipLaunchKernelGGL(k_pack_mlp_bwd_h2, dim3((NCH_BWD * CHUNK_FLOATS * 2 + 255) / 256), dim3(256), 0, (hipStream_t)stream, a,
-                       reinterpret_cast<unsigned short *>(static_cast<float *>(packed) + NCH_BWD * CHUNK_FLOATS), wsc);
+    hipLaunchKernelGGL(k_pack_mlp_bwd_h2, dim3((NCH_BWD * CHUNK_FLOATS * 2 + 255) / 256), dim3(256), 0, (hipStream_t)stream, a, bwd_h2(packed),
+                       bwd_scales(packed));
     return hl::check_launch("k_pack_mlp_bwd_h2");
 }
 
@@ -3680,21 +3710,14 @@ int hl_render_eval_acts(const void *mlp_packed, const void *planes_packed, int H
     HL_REQUIRE((int64_t)ACT_ROWS * act_stride * 4 < (1LL << 32), "hl_render_eval_acts: activation matrix must stay below 4 GiB (row stride %lld)",
                (long long)act_stride);
     MarchArgs a{};
-    int rcode = fill_march(a, mlp_packed, planes_packed, H, W, bounds, rays_o, rays_d, near, far);
+    int rcode = fill_march(a, mlp_packed, planes_packed, H, W, bounds, rays_o, rays_d, near, far, z, z_tiled, n_rays, n_samples);
     if (rcode) return rcode;
-    a.z = z; a.z_tiled = z_tiled; a.R = n_rays; a.S = n_samples; a.flags = 0; a.vals_out = (float4 *)records_out;
+    a.vals_out = (float4 *)records_out;
     a.act = act; a.act_stride = act_stride; a.act_off = act_off;
-    const unsigned groups = (unsigned)((n_rays + 255) / 256);
-    const unsigned splits = sample_splits(groups, n_samples);
-    a.s_per = (n_samples + (int)splits - 1) / (int)splits;
     // round 5: the evaluate pass of the fitting step on the fp16x2 kernel (k_march_plw<2, ACTS>: the inference default's arithmetic; the backward reads the
     // activations it writes)
-    const dim3 grid(groups, (unsigned)((n_samples + a.s_per - 1) / a.s_per));
-    const unsigned short *ph2 = reinterpret_cast<const unsigned short *>(static_cast<const char *>(mlp_packed) + (size_t)PACKED_FLOATS * sizeof(float) + (size_t)P16_FRAGS * 1024 + B3_BYTES);
-    static const bool okh = hipFuncSetAttribute((const void *)k_march_plw<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PLW_LDS<2>) == hipSuccess;
-    HL_REQUIRE(okh, "k_march_plw<2, acts>: cannot raise the dynamic LDS limit to %zu bytes", PLW_LDS<2>);
-    hipLaunchKernelGGL((k_march_plw<2, true>), grid, dim3(512), PLW_LDS<2>, (hipStream_t)stream, a, ph2);
-    return hl::check_launch("k_march_plw<2, acts>");
+    const dim3 grid = sample_split_grid(a);
+    return hl::launch_lds<k_march_plw<2, true>>("k_march_plw<2, acts>", PLW_LDS<2>, grid, dim3(512), PLW_LDS<2>, (hipStream_t)stream, a, mlp_h2(mlp_packed));
 }
 
 size_t hl_render_composite_backward_scratch_bytes(int64_t n_rays, int n_samples, int n_importance) {
@@ -3738,17 +3761,13 @@ int hl_render_mlp_backward(const void *mlp_packed, const void *mlp_bwd_packed, i
     HL_REQUIRE((int64_t)ACT_ROWS * act_stride * 4 < (1LL << 32) && (int64_t)DEL_ROWS * del_stride * 4 < (1LL << 32),
                "hl_render_mlp_backward: activation / delta matrices must stay below 4 GiB");
     MarchArgs a{};
-    a.packed = (const float *)mlp_packed; a.bwd_packed = (const float *)mlp_bwd_packed;
-    a.H = H; a.W = W; a.bounds = bounds;
-    a.rays_o = rays_o; a.rays_d = rays_d; a.near = near; a.far = far;
-    a.z = z; a.z_tiled = z_tiled; a.R = n_rays; a.S = n_samples;
+    int rcode = fill_march(a, mlp_packed, nullptr, H, W, bounds, rays_o, rays_d, near, far, z, z_tiled, n_rays, n_samples, mlp_bwd_packed);
+    if (rcode) return rcode;
     a.d_rec = (const float4 *)d_records;
     a.act = const_cast<float *>(act); a.act_stride = act_stride; a.act_off = act_off;
     a.del = del; a.del_stride = del_stride; a.del_off = del_off;
-    const unsigned groups = (unsigned)((n_rays + 255) / 256);
-    const unsigned splits = sample_splits(groups, n_samples);
-    a.s_per = (n_samples + (int)splits - 1) / (int)splits;
-    hipLaunchKernelGGL((k_mlp_bwd<8, true>), dim3(groups, (unsigned)((n_samples + a.s_per - 1) / a.s_per)), dim3(512), 0, (hipStream_t)stream, a);
+    const dim3 grid = sample_split_grid(a);
+    hipLaunchKernelGGL((k_mlp_bwd<8, true>), grid, dim3(512), 0, (hipStream_t)stream, a);
     return hl::check_launch("k_mlp_bwd");
 }
 
@@ -3775,16 +3794,12 @@ int hl_render_eval_points_acts(const void *mlp_packed, const void *planes_packed
     HL_REQUIRE(act_off >= 0 && act_stride >= act_off + tiles32(n_rays) * 32 * n_samples, "hl_render_eval_points_acts: activation rows too short");
     HL_REQUIRE((int64_t)ACT_ROWS * act_stride * 4 < (1LL << 32), "hl_render_eval_points_acts: activation matrix must stay below 4 GiB");
     MarchArgs a{};
-    a.packed = (const float *)mlp_packed; a.planes = (const float4 *)planes_packed; a.H = H; a.W = W; a.bounds = bounds;
-    a.rays_o = pts_c; a.rays_d = pts_c; a.near = pts_c; a.far = pts_c;      // placeholders, as in hl_render_eval_points
-    a.z = nullptr; a.z_tiled = 0; a.R = n_rays; a.S = n_samples; a.flags = 0; a.vals_out = (float4 *)records_out;
-    a.pts_c = (const float4 *)pts_c; a.dirs_c = (const float4 *)dirs_c;
+    int rcode = fill_march_points(a, mlp_packed, planes_packed, H, W, bounds, pts_c, dirs_c, n_rays, n_samples);
+    if (rcode) return rcode;
+    a.vals_out = (float4 *)records_out;
     a.act = act; a.act_stride = act_stride; a.act_off = act_off;
-    const unsigned groups = (unsigned)((n_rays + 255) / 256);
-    const unsigned splits = sample_splits(groups, n_samples);
-    a.s_per = (n_samples + (int)splits - 1) / (int)splits;
-    hipLaunchKernelGGL((k_march<true, true, 8, true, true>), dim3(groups, (unsigned)((n_samples + a.s_per - 1) / a.s_per)), dim3(512), 0,
-                       (hipStream_t)stream, a);
+    const dim3 grid = sample_split_grid(a);
+    hipLaunchKernelGGL((k_march<true, true, 8, true, true>), grid, dim3(512), 0, (hipStream_t)stream, a);
     return hl::check_launch("k_march<eval points, acts>");
 }
 
@@ -3894,42 +3909,39 @@ int hl_render_rays_u_event(const void *mlp_packed, const void *planes_packed, in
             // depends only on (ray, depth), so here every point is evaluated exactly once with the full MLP - coarse points in pass
             // A, the new ones in pass B - and k_composite merges the two sorted lists: same values, same compositing order,
             // bit-identical images, 23 % fewer FLOPs (256 x 132 608 instead of 128 x 79 616 + 256 x 132 608 per ray).
-            const size_t T32 = (size_t)tiles32(n_rays) * 32;
-            float *vc = (float *)workspace, *vn = vc + T32 * n_samples * 4;
-            float *zn = vn + T32 * n_importance * 4;
-            const int h16 = (flags & HL_RENDER_MLP_FP16) ? 1 : ((flags & HL_RENDER_MLP_FP16X2) ? 3 : ((flags & HL_RENDER_MLP_BF16X3) ? 2 : 0));
+            const Workspace w = render_workspace(workspace, n_rays, n_samples, n_importance, Schedule::EvalOnce);
+            const int h16 = mlp_mode_of(flags);
             int rcode = render_eval_impl(mlp_packed, planes_packed, H, W, bounds, rays_o, rays_d, near, far, z_vals, 0, n_rays, n_samples,
-                                         vc, h16, stream);
+                                         w.vc, h16, stream);
             if (rcode) return rcode;
             rcode = wait_u();
             if (rcode) return rcode;
             // round 6: two launches per view - the fine launch draws its own importance depths and composites as it evaluates (no fine records, no merge kernel)
             // (fp16x2 products only: with the bf16x3 planes the fused kernel spills - measured 41.1 against 40.1 ms per view)
             if (!(flags & HL_RENDER_FOUR_LAUNCH) && h16 == 3 && n_samples <= 128 && z_vals == nullptr) {
-                return render_onepass_fine(mlp_packed, planes_packed, H, W, bounds, rays_o, rays_d, near, far, vc, u, zn, n_rays, n_samples, flags, 2,
+                return render_onepass_fine(mlp_packed, planes_packed, H, W, bounds, rays_o, rays_d, near, far, w.vc, u, w.zn, n_rays, n_samples, flags, 2,
                                            rgb, acc, depth, stream);
             }
-            rcode = hl_render_importance_new(vc, rays_d, near, far, z_vals, u, n_rays, n_samples, n_importance, zn, stream);
+            rcode = hl_render_importance_new(w.vc, rays_d, near, far, z_vals, u, n_rays, n_samples, n_importance, w.zn, stream);
             if (rcode) return rcode;
-            rcode = render_eval_impl(mlp_packed, planes_packed, H, W, bounds, rays_o, rays_d, near, far, zn, 1, n_rays, n_importance, vn,
+            rcode = render_eval_impl(mlp_packed, planes_packed, H, W, bounds, rays_o, rays_d, near, far, w.zn, 1, n_rays, n_importance, w.vn,
                                      h16, stream);
             if (rcode) return rcode;
-            return hl_render_composite(near, far, z_vals, zn, vc, vn, n_rays, n_samples, n_importance, flags, rgb, acc, depth, stream);
+            return hl_render_composite(near, far, z_vals, w.zn, w.vc, w.vn, n_rays, n_samples, n_importance, flags, rgb, acc, depth, stream);
         }
-        float *sigma = (float *)workspace;
-        float *z_all = sigma + (size_t)tiles32(n_rays) * 32 * n_samples;
+        const Workspace w = render_workspace(workspace, n_rays, n_samples, n_importance, Schedule::Reevaluate);
         int rcode = hl_render_coarse(mlp_packed, planes_packed, H, W, bounds, rays_o, rays_d, near, far, z_vals, n_rays,
-                                     n_samples, sigma, stream);
+                                     n_samples, w.sigma, stream);
         if (rcode) return rcode;
         rcode = wait_u();
         if (rcode) return rcode;
-        rcode = hl_render_importance(sigma, rays_d, near, far, z_vals, u, n_rays, n_samples, n_importance, z_all, stream);
+        rcode = hl_render_importance(w.sigma, rays_d, near, far, z_vals, u, n_rays, n_samples, n_importance, w.z_all, stream);
         if (rcode) return rcode;
-        return render_fine_impl(mlp_packed, planes_packed, H, W, bounds, rays_o, rays_d, near, far, z_all, 1, n_rays,
-                                n_samples + n_importance, flags, rgb, acc, depth, stream);
+        return hl_render_fine(mlp_packed, planes_packed, H, W, bounds, rays_o, rays_d, near, far, w.z_all, 1, n_rays,
+                              n_samples + n_importance, flags, rgb, acc, depth, stream);
     }
-    return render_fine_impl(mlp_packed, planes_packed, H, W, bounds, rays_o, rays_d, near, far, z_vals, 0, n_rays, n_samples,
-                            flags, rgb, acc, depth, stream);
+    return hl_render_fine(mlp_packed, planes_packed, H, W, bounds, rays_o, rays_d, near, far, z_vals, 0, n_rays, n_samples,
+                          flags, rgb, acc, depth, stream);
 }
 
 static int camera_rays_impl(bool train, const double *h_Kinv, const double *h_R, const double *h_T, const double *h_bounds, int H, int W,
@@ -3986,18 +3998,12 @@ int hl_deform_rays(const float *rays_o, const float *rays_d, const float *near, 
     static const bool brute = getenv("HL_DEFORM_BRUTE") != nullptr;    // developer switch: full scan for every sample point
     if (n_vertices <= DC_MAXV && !brute) {
         const size_t lds = (size_t)(DC_MAXV + DC_MAXV / 64 + DC_WAVES * DC_SLOTS * 2) * sizeof(float4);
-        static bool attr_set = false;
-        if (!attr_set) {
-            HL_HIP(hipFuncSetAttribute((const void *)k_deform_rays_cull, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            attr_set = true;
-        }
         const long long items = (long long)tiles32(n_rays) * 2 * ((n_samples + 3) / 4);
         const unsigned grid = (unsigned)(items / DC_WAVES + 1 < 256 ? items / DC_WAVES + 1 : 256);
         HL_REQUIRE(scratch, "hl_deform_rays: scratch (8 bytes of device memory) is required");
         a.counter = (unsigned long long *)scratch;
         HL_HIP(hipMemsetAsync(a.counter, 0, sizeof(unsigned long long), (hipStream_t)stream));
-        hipLaunchKernelGGL(k_deform_rays_cull, dim3(grid), dim3(DC_WAVES * 64), lds, (hipStream_t)stream, a);
-        return hl::check_launch("k_deform_rays_cull");
+        return hl::launch_lds<k_deform_rays_cull>("k_deform_rays_cull", lds, dim3(grid), dim3(DC_WAVES * 64), lds, (hipStream_t)stream, a);
     }
     const long long total = (long long)tiles32(n_rays) * 32 * ((n_samples + 1) / 2);   // two samples per thread
     hipLaunchKernelGGL(k_deform_rays, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
@@ -4009,20 +4015,15 @@ int hl_render_eval_points(const void *mlp_packed, const void *planes_packed, int
     HL_REQUIRE(mlp_packed && planes_packed && bounds && pts_c && dirs_c && records_out, "hl_render_eval_points: null argument");
     HL_REQUIRE(n_rays > 0 && n_samples >= 1 && H > 0 && W > 0, "hl_render_eval_points: bad sizes");
     MarchArgs a{};
-    a.packed = (const float *)mlp_packed; a.planes = (const float4 *)planes_packed; a.H = H; a.W = W; a.bounds = bounds;
-    // rays are not read in POINTS mode beyond the placeholders below (the kernel loads o, d, near, far of its ray unconditionally)
-    a.rays_o = pts_c; a.rays_d = pts_c; a.near = pts_c; a.far = pts_c;
-    a.z = nullptr; a.z_tiled = 0; a.R = n_rays; a.S = n_samples; a.flags = 0; a.vals_out = (float4 *)records_out;
-    a.pts_c = (const float4 *)pts_c; a.dirs_c = (const float4 *)dirs_c;
+    int rcode = fill_march_points(a, mlp_packed, planes_packed, H, W, bounds, pts_c, dirs_c, n_rays, n_samples);
+    if (rcode) return rcode;
+    a.vals_out = (float4 *)records_out;
     hipLaunchKernelGGL((k_march<true, true, 8, true>), dim3((unsigned)((n_rays + 255) / 256)), dim3(512), 0, (hipStream_t)stream, a);
     return hl::check_launch("k_march<eval points>");
 }
 
 size_t hl_render_canonical_workspace_bytes(int64_t n_rays, int n_samples, int n_importance) {
-    if (n_rays <= 0) return 256;
-    const size_t T32 = (size_t)tiles32(n_rays) * 32;
-    const int smax = n_samples > n_importance ? n_samples : n_importance;
-    return hl_render_workspace_bytes(n_rays, n_samples, n_importance > 0 ? n_importance : n_samples) + T32 * smax * 2 * sizeof(float4) + 512;
+    return render_workspace(nullptr, n_rays, n_samples, n_importance, Schedule::Canonical).bytes;
 }
 
 int hl_render_rays_canonical(const void *mlp_packed, const void *planes_packed, int H, int W, const float *t_bounds,
@@ -4035,27 +4036,20 @@ int hl_render_rays_canonical(const void *mlp_packed, const void *planes_packed, 
                n_samples);
     HL_REQUIRE(n_importance == 0 || u, "render: u is required when n_importance > 0");
     HL_REQUIRE(n_importance > 0, "hl_render_rays_canonical: n_importance = 0 is not built (the reference's configurations use 128)");
-    const size_t T32 = (size_t)tiles32(n_rays) * 32;
-    float *vc = (float *)workspace, *vn = vc + T32 * n_samples * 4;
-    float *zn = vn + T32 * n_importance * 4;
-    float *pc = zn + T32 * n_importance;                       // canonical points of the pass in flight, then directions
-    pc = (float *)(((uintptr_t)pc + 255) / 256 * 256);
-    const int smax = n_samples > n_importance ? n_samples : n_importance;
-    float *dc = pc + T32 * smax * 4;
-    void *dscr = dc + T32 * smax * 4;                           // work counter of the deformation kernel
-    int rc = hl_deform_rays(rays_o, rays_d, near, far, z_vals, 0, n_rays, n_samples, h_R, h_Th, verts_smpl4, table, n_vertices, pc, dc,
-                            dscr, stream);
+    const Workspace w = render_workspace(workspace, n_rays, n_samples, n_importance, Schedule::Canonical);
+    int rc = hl_deform_rays(rays_o, rays_d, near, far, z_vals, 0, n_rays, n_samples, h_R, h_Th, verts_smpl4, table, n_vertices, w.pc, w.dc,
+                            w.deform_counter, stream);
     if (rc) return rc;
-    rc = hl_render_eval_points(mlp_packed, planes_packed, H, W, t_bounds, pc, dc, n_rays, n_samples, vc, stream);
+    rc = hl_render_eval_points(mlp_packed, planes_packed, H, W, t_bounds, w.pc, w.dc, n_rays, n_samples, w.vc, stream);
     if (rc) return rc;
-    rc = hl_render_importance_new(vc, rays_d, near, far, z_vals, u, n_rays, n_samples, n_importance, zn, stream);
+    rc = hl_render_importance_new(w.vc, rays_d, near, far, z_vals, u, n_rays, n_samples, n_importance, w.zn, stream);
     if (rc) return rc;
-    rc = hl_deform_rays(rays_o, rays_d, near, far, zn, 1, n_rays, n_importance, h_R, h_Th, verts_smpl4, table, n_vertices, pc, dc,
-                        dscr, stream);
+    rc = hl_deform_rays(rays_o, rays_d, near, far, w.zn, 1, n_rays, n_importance, h_R, h_Th, verts_smpl4, table, n_vertices, w.pc, w.dc,
+                        w.deform_counter, stream);
     if (rc) return rc;
-    rc = hl_render_eval_points(mlp_packed, planes_packed, H, W, t_bounds, pc, dc, n_rays, n_importance, vn, stream);
+    rc = hl_render_eval_points(mlp_packed, planes_packed, H, W, t_bounds, w.pc, w.dc, n_rays, n_importance, w.vn, stream);
     if (rc) return rc;
-    return hl_render_composite(near, far, z_vals, zn, vc, vn, n_rays, n_samples, n_importance, flags, rgb, acc, depth, stream);
+    return hl_render_composite(near, far, z_vals, w.zn, w.vc, w.vn, n_rays, n_samples, n_importance, flags, rgb, acc, depth, stream);
 }
 
 }  // extern "C"

@@ -166,6 +166,38 @@ def test_training_scratch_queries():
         assert L.hl_triplane_agg_backward_scratch_bytes(N, 16, 16, 24) == N * 3 * 32 * 24 * 4
 
 
+def test_render_size_queries():
+    """The renderer's size queries are host arithmetic with closed forms: the tile-major workspace of a render call (rays rounded up to
+    tiles of 32, float4 records of both passes + the new depths, + 256), the canonical schedule's two float4 buffers behind it (+ 512),
+    the scratch of the backward kernels and the backward pack.  No byte of these layouts moves unnoticed."""
+    import ctypes
+    from humanliff_amd import _lib
+    from humanliff_amd.build import build
+    build()
+    L = _lib.lib()
+    ceil = lambda a, b: -(-a // b)  # noqa: E731
+    up256 = lambda b: ceil(b, 256) * 256  # noqa: E731
+    for R, N, Ni in [(1, 32, 32), (33, 32, 32), (257, 64, 64), (2048, 128, 128), (262144, 128, 128), (777, 3, 3)]:
+        T32 = ceil(R, 32) * 32
+        ws = T32 * ((N + Ni) * 4 + Ni) * 4 + 256
+        assert L.hl_render_workspace_bytes(R, N, Ni) == ws
+        assert L.hl_render_canonical_workspace_bytes(R, N, Ni) == ws + T32 * max(N, Ni) * 32 + 512
+        assert L.hl_render_composite_backward_scratch_bytes(R, N, Ni) == T32 * (N + Ni) * 8
+        pg = up256(T32 // 32 * 27 * 4)
+        assert L.hl_render_plane_grads_scratch_bytes(R) == pg
+        assert L.hl_render_plane_grads_points_scratch_bytes(R, N, Ni) == pg + R * (ceil(N, 64) + ceil(Ni, 64)) * 24 + 256
+        P = T32 * (N + Ni)
+        per = max(1024, ceil(ceil(P, 256), 32) * 32)
+        assert L.hl_render_weight_grads_scratch_bytes(P) == ceil(P, per) * 66884 * 4      # 66 884 = the MLP's parameter count
+    assert L.hl_render_workspace_bytes(0, 32, 32) == 256 and L.hl_render_workspace_bytes(64, 32, 0) == 256
+    assert L.hl_render_canonical_workspace_bytes(0, 32, 32) == 256 and L.hl_render_canonical_workspace_bytes(64, 32, 0) == 140032
+    assert L.hl_render_weight_grads_scratch_bytes(0) == 0
+    assert L.hl_render_mlp_bwd_packed_bytes() == 524352
+    act_rows, del_rows = ctypes.c_int(0), ctypes.c_int(0)
+    L.hl_render_train_rows(ctypes.byref(act_rows), ctypes.byref(del_rows))
+    assert (act_rows.value, del_rows.value) == (630, 634)
+
+
 def test_no_cpu_fallback():
     """CPU tensors must fail loudly, never silently route to PyTorch."""
     from humanliff_amd.NeRF import Renderer
