@@ -120,6 +120,7 @@ SIGNATURES = {
     "hl_diffusion_prior_bpd": (_i, [_p, _p, _i64, _i, _i, _p, _p, _sz, _p]),
     "hl_conv2d_scratch_bytes": (_sz, [_i] * 10),
     "hl_conv2d_plan": (_i, [_i] * 10 + [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "hl_conv2d_plan_ex": (_i, [_i] * 12 + [C.POINTER(C.c_int)]),
     "hl_conv2d_gn_scratch_bytes": (_sz, [_i] * 10),
     "hl_conv2d_bwd_data_scratch_bytes": (_sz, [_i] * 11),
     "hl_conv2d_nhwc": (_i, [_p, _i, _i, _i, _i, _p, _p, _i, _i, _i, _i, _p, _p, _i, _p, _p, _p, _sz, _p]),

@@ -1032,10 +1032,26 @@ struct SingleConvRoom {
     size_t form, act, tot, splitk, total;
     unsigned forms;   // the forms the layer has under the mode
 };
+// The arguments of a single-op convolution, checked once for the call (conv2d_single), its two size queries and its two plan queries:
+// null = the call accepts them, else what it refuses.  Beyond the ranges, conv2d's own refusals: a stride 2 behind the nearest-x2
+// upsample, a GroupNorm in front of an upsample (nearest x2 + conv only ever follows a raw tensor) and a SiLU without a GroupNorm.
+// A 1x1 convolution with stride 2 or behind an upsample is accepted: only k_conv / k_conv_dma / k_conv_bf3 take one (every other
+// family asks for stride 1 and no upsample, or for ks 3), and those index the input by (oy * stride - pad, ox * stride - pad) or
+// (y >> 1, x >> 1) with a bounds check per tap for any ks.
+static const char *single_conv_refusal(int mode, int N, int H, int W, int Cin, int Cout, int ks, int stride, int upsample, bool with_gn, bool silu) {
+    if (!conv_mode_known(mode)) return "unknown mode";
+    if (N <= 0 || H <= 0 || W <= 0 || Cout <= 0) return "N, H, W and Cout must be positive";
+    if (Cin <= 0 || Cin % 16) return "Cin must be a positive multiple of 16";
+    if (ks != 1 && ks != 3) return "ks must be 1 or 3";
+    if (stride != 1 && stride != 2) return "stride must be 1 or 2";
+    if (stride == 2 && upsample) return "stride 2 behind an upsample";
+    if (with_gn && upsample) return "a GroupNorm in front of an upsample";
+    if (silu && !with_gn) return "SiLU without a GroupNorm";
+    return nullptr;
+}
 static SingleConvRoom single_conv_room(int mode, int tf, int N, int H, int W, int Cin, int Cout, int ks, int stride, int upsample, bool with_gn) {
     SingleConvRoom r{};
-    if (!conv_mode_known(mode) || N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cin % 16 || Cout <= 0 || (ks != 1 && ks != 3) || (stride != 1 && stride != 2))
-        return r;
+    if (single_conv_refusal(mode, N, H, W, Cin, Cout, ks, stride, upsample, with_gn, false)) return r;
     r.forms = conv_forms(mode, true, tf != 0);
     size_t extra = 0;
     for (int f = 1; f < hl::kWeightForms; ++f) {
@@ -1067,7 +1083,9 @@ static int conv2d_single(int mode, const float *in, int N, int H, int W, int Cin
                          int ks, int stride, int upsample, const float *coefA, const float *coefB, int silu,
                          const float *residual, float *out, void *scratch, size_t scratch_bytes, void *stream,
                          float *stats = nullptr, int *stat_slots = nullptr, int tf = 0, int Cin_w = -1, long out_pitch = 0) {
-    HL_REQUIRE(Cin % 16 == 0, "hl_conv2d_nhwc: Cin must be a multiple of 16");
+    const char *refused = single_conv_refusal(mode, N, H, W, Cin, Cout, ks, stride, upsample, coefA != nullptr, silu != 0);
+    HL_REQUIRE(!refused, "hl_conv2d_nhwc: %s (mode %d, N %d, H %d, W %d, Cin %d, Cout %d, ks %d, stride %d, upsample %d)", refused, mode, N, H, W, Cin, Cout,
+               ks, stride, upsample);
     if (Cin_w < 0) Cin_w = Cin;
     HL_REQUIRE(Cin_w <= Cin, "hl_conv2d_nhwc: the weight has more input channels than the tensor");
     hipStream_t st = (hipStream_t)stream;
@@ -1118,15 +1136,19 @@ size_t hl_conv2d_scratch_bytes(int conv_mode, int N, int H, int W, int Cin, int 
     return single_conv_room(conv_mode, 0, N, H, W, Cin, Cout, ks, stride, upsample, with_gn != 0).total;
 }
 
-// The plan conv2d_single makes for the same arguments, without a buffer (the plan queries; host arithmetic: no HIP call).  false:
+// The plan conv2d_single makes for the same arguments, without a buffer (the plan queries; host arithmetic: no HIP call).  silu and
+// want_stats: what the call puts into ConvArgs::act and ::stats before it plans (hl_conv2d_nhwc_gn wants the statistics).  false:
 // arguments no call accepts.
 static bool single_conv_query_plan(int mode, int tf, int N, int H, int W, int Cin, int Cout, int ks, int stride, int upsample, bool with_gn,
-                                   long out_pitch, hl::ConvPlan *pl) {
+                                   long out_pitch, hl::ConvPlan *pl, bool silu = false, bool want_stats = false) {
+    if (single_conv_refusal(mode, N, H, W, Cin, Cout, ks, stride, upsample, with_gn, silu)) return false;
     const SingleConvRoom room = single_conv_room(mode, tf, N, H, W, Cin, Cout, ks, stride, upsample, with_gn);
     if (!room.total) return false;
     static float at;
     ConvArgs a{};
     single_conv_plan_args(a, &at, mode, room.forms, N, H, W, Cin, Cout, ks, stride, upsample, with_gn, out_pitch);
+    a.act = silu;
+    a.stats = want_stats ? &at : nullptr;
     *pl = hl::plan_conv(a);
     return true;
 }
@@ -1135,8 +1157,28 @@ int hl_conv2d_plan(int conv_mode, int N, int H, int W, int Cin, int Cout, int ks
     HL_REQUIRE(h_kernel && h_splits, "hl_conv2d_plan: null argument");
     hl::ConvPlan pl;
     HL_REQUIRE(single_conv_query_plan(conv_mode, 0, N, H, W, Cin, Cout, ks, stride, upsample, with_gn != 0, 0, &pl),
-               "hl_conv2d_plan: bad argument (mode %d, N %d, H %d, W %d, Cin %d, Cout %d, ks %d, stride %d)", conv_mode, N, H, W, Cin, Cout, ks, stride);
+               "hl_conv2d_plan: bad argument (mode %d, N %d, H %d, W %d, Cin %d, Cout %d, ks %d, stride %d, upsample %d, with_gn %d)", conv_mode, N, H, W, Cin,
+               Cout, ks, stride, upsample, with_gn);
     *h_kernel = (int)pl.kernel; *h_splits = pl.splits;
+    return HL_OK;
+}
+
+static_assert((int)hl::ConvPrePass::None == HL_PRE_NONE && (int)hl::ConvPrePass::Dense == HL_PRE_DENSE && (int)hl::ConvPrePass::Blocked == HL_PRE_BLOCKED &&
+                  (int)hl::ConvPrePass::Half == HL_PRE_HALF && (int)hl::ConvPrePass::TwoPlane == HL_PRE_TWO_PLANE,
+              "humanliff_hip.h documents ConvPrePass's numbers");
+static_assert((int)hl::ConvStatsBy::None == HL_STATS_BY_NONE && (int)hl::ConvStatsBy::Epilogue == HL_STATS_BY_EPILOGUE &&
+                  (int)hl::ConvStatsBy::Finish == HL_STATS_BY_FINISH,
+              "humanliff_hip.h documents ConvStatsBy's numbers");
+int hl_conv2d_plan_ex(int conv_mode, int N, int H, int W, int Cin, int Cout, int ks, int stride, int upsample, int with_gn, int silu, int want_stats,
+                      int *h_plan) {
+    HL_REQUIRE(h_plan, "hl_conv2d_plan_ex: null argument");
+    hl::ConvPlan pl;
+    HL_REQUIRE(single_conv_query_plan(conv_mode, 0, N, H, W, Cin, Cout, ks, stride, upsample, with_gn != 0, 0, &pl, silu != 0, want_stats != 0),
+               "hl_conv2d_plan_ex: bad argument (mode %d, N %d, H %d, W %d, Cin %d, Cout %d, ks %d, stride %d, upsample %d, with_gn %d, silu %d)", conv_mode, N,
+               H, W, Cin, Cout, ks, stride, upsample, with_gn, silu);
+    h_plan[HL_PLAN_KERNEL] = (int)pl.kernel; h_plan[HL_PLAN_SPLITS] = pl.splits; h_plan[HL_PLAN_CFG] = pl.cfg; h_plan[HL_PLAN_TILE8] = pl.tile8 ? 1 : 0;
+    h_plan[HL_PLAN_GN_MODE] = pl.gn_mode; h_plan[HL_PLAN_PRE] = (int)pl.pre; h_plan[HL_PLAN_STATS_BY] = (int)pl.stats_by;
+    h_plan[HL_PLAN_STAT_SLOTS] = pl.stat_slots; h_plan[HL_PLAN_KT_PER] = pl.kt_per;
     return HL_OK;
 }
 

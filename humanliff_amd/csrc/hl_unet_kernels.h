@@ -215,9 +215,10 @@ int tensor_absmax(const View &x, float *amax, hipStream_t st);
 enum class ConvKernel : int { Conv = 0, Dma = 1, Bf3 = 2, Wino = 3, Wino4 = 4, Wino4w = 5, H16 = 6, H2s = 7, H2s1 = 8, H2d = 9, H2sUp = 10 };
 // GroupNorm(+SiLU) materialised into ConvArgs::act_ws before the convolution, and its format: dense fp32, fp32 channel-blocked [C/8][pixel][8]
 // (k_conv_wino4 / k_conv_wino4w read it), the 16-bit image (k_conv_h16) or the two-plane fp16 image (k_conv_h2s)
-enum class ConvPrePass { None, Dense, Blocked, Half, TwoPlane };
-// which kernel adds the output statistics (ConvArgs::stats): the convolution's epilogue, or the split-K finish
-enum class ConvStatsBy { None, Epilogue, Finish };
+// (the numbers reach Python through hl_conv2d_plan_ex and stay: HL_PRE_* in humanliff_hip.h)
+enum class ConvPrePass : int { None = 0, Dense = 1, Blocked = 2, Half = 3, TwoPlane = 4 };
+// which kernel adds the output statistics (ConvArgs::stats): the convolution's epilogue, or the split-K finish (HL_STATS_BY_*)
+enum class ConvStatsBy : int { None = 0, Epilogue = 1, Finish = 2 };
 
 // Everything a convolution launch decides, made by plan_conv without any HIP call.
 struct ConvPlan {

@@ -483,12 +483,50 @@ int hl_diffusion_prior_bpd(const float *x_start, const float *coef, int64_t n_pe
  * inside hl_unet_forward; the scratch holds the slabs that plan writes (for a forward layer the larger of its plans with and without a
  * GroupNorm in front, so with_gn adds the GroupNorm input and nothing else), not the whole 64 MiB.  The queries plan the layer on the
  * host: a test switch of the dispatch (hl_debug_set_h16_min_blocks) set between a query and its call can make the call refuse.
- * Arguments no call accepts (N, H, W, Cout <= 0, Cin not a positive multiple of 16, ks not 1 or 3, stride not 1 or 2, unknown mode) give 0. */
+ * Arguments no call accepts (N, H, W, Cout <= 0, Cin not a positive multiple of 16, ks not 1 or 3, stride not 1 or 2, unknown mode, stride 2
+ * together with upsample, with_gn together with upsample) give 0: the call, its size queries and its plan queries read one check.  A 1x1
+ * convolution with stride 2 or behind the upsample is accepted (the direct kernels take it). */
 size_t hl_conv2d_scratch_bytes(int conv_mode, int N, int H, int W, int Cin, int Cout, int ks, int stride, int upsample, int with_gn);
 /* The plan behind that size (host arithmetic, no HIP call): *h_kernel = the kernel the call launches - 0 k_conv, 1 k_conv_dma, 2 k_conv_bf3,
  * 3 k_conv_wino, 4 k_conv_wino4, 5 k_conv_wino4w, 6 k_conv_h16 / k_conv1_h16, 7 k_conv_h2s, 8 k_conv1_h2s, 9 k_conv_h2d, 10 k_conv_h2s_ph (an
  * Upsample convolution as four 2x2-tap phases); the numbers stay - *h_splits = its split-K slabs (1: none). */
 int hl_conv2d_plan(int conv_mode, int N, int H, int W, int Cin, int Cout, int ks, int stride, int upsample, int with_gn, int *h_kernel, int *h_splits);
+/* The whole of that plan: which INSTANTIATION the call launches (host arithmetic, no HIP call).  silu: the call's silu (SiLU without a
+ * GroupNorm is refused, as by the call); want_stats = 1: the call is hl_conv2d_nhwc_gn, which asks the launch for the statistics of the
+ * output.  h_plan: HL_PLAN_FIELDS ints, in this order (the numbers stay):
+ *   [HL_PLAN_KERNEL]     the kernel, as *h_kernel of hl_conv2d_plan
+ *   [HL_PLAN_SPLITS]     split-K slabs (1: none; more: k_splitk_finish[_st] sums them)
+ *   [HL_PLAN_CFG]        k_conv's tile: 0 = 128 pixels x 96 channels, 1 = 128 x 32 (Cout <= 32), 2 = 64 x 64 (set for every kernel; only k_conv reads it)
+ *   [HL_PLAN_TILE8]      k_conv_dma / k_conv_bf3: 1 = the 8-wave 256 x 96 tile, 0 = 4 waves on 128 x 96
+ *   [HL_PLAN_GN_MODE]    the GroupNorm in front: 0 none, 1 the affine, 2 the affine + SiLU (k_conv's template mode when HL_PLAN_PRE is HL_PRE_NONE)
+ *   [HL_PLAN_PRE]        HL_PRE_*: the GroupNorm(+SiLU) materialised by a pass of its own before the convolution, and in which format - none
+ *                        (fused into the kernel's staging, or no GroupNorm), dense fp32 (k_gn_apply), fp32 channel-blocked [C/8][pixel][8]
+ *                        (k_gn_apply_blk; k_conv_wino4<., true> and the blk form of k_conv_wino4w read it), the 16-bit image (k_gn_apply_h16;
+ *                        k_conv_h16), the two-plane fp16 image (k_gn_apply_h16; k_conv_h2s)
+ *   [HL_PLAN_STATS_BY]   HL_STATS_BY_*: who adds the output statistics - nobody (the consumer computes them from the tensor), the kernel's
+ *                        epilogue, or the split-K finish (k_splitk_finish_st instead of k_splitk_finish)
+ *   [HL_PLAN_STAT_SLOTS] what hl_conv2d_nhwc_gn returns in *h_used_stats (0 unless want_stats)
+ *   [HL_PLAN_KT_PER]     k-tiles per slab */
+#define HL_PLAN_KERNEL 0
+#define HL_PLAN_SPLITS 1
+#define HL_PLAN_CFG 2
+#define HL_PLAN_TILE8 3
+#define HL_PLAN_GN_MODE 4
+#define HL_PLAN_PRE 5
+#define HL_PLAN_STATS_BY 6
+#define HL_PLAN_STAT_SLOTS 7
+#define HL_PLAN_KT_PER 8
+#define HL_PLAN_FIELDS 9
+#define HL_PRE_NONE 0
+#define HL_PRE_DENSE 1
+#define HL_PRE_BLOCKED 2
+#define HL_PRE_HALF 3
+#define HL_PRE_TWO_PLANE 4
+#define HL_STATS_BY_NONE 0
+#define HL_STATS_BY_EPILOGUE 1
+#define HL_STATS_BY_FINISH 2
+int hl_conv2d_plan_ex(int conv_mode, int N, int H, int W, int Cin, int Cout, int ks, int stride, int upsample, int with_gn, int silu, int want_stats,
+                      int *h_plan);
 int hl_conv2d_nhwc(const float *in, int N, int H, int W, int Cin, const float *w_oihw, const float *bias, int Cout,
                    int ks, int stride, int upsample, const float *coefA, const float *coefB, int silu,
                    const float *residual, float *out, void *scratch, size_t scratch_bytes, void *stream);

@@ -32,6 +32,16 @@ def conv_scratch(N, H, W, C, Cout, ks, stride=1, ups=0, gn=False, modes=None, qu
     return torch.empty(need // 4, device=dev)
 
 
+def conv_plan(mode, N, H, W, C, Cout, ks, stride=1, ups=0, gn=False):
+    """(kernel, split-K slabs) of the single-op convolution: hl_conv2d_plan, host arithmetic (the kernel names: tests/conv_fwd_cases.py)."""
+    import ctypes
+    from humanliff_amd import _lib
+    from tests.conv_fwd_cases import KERNELS
+    k, s = ctypes.c_int(-1), ctypes.c_int(-1)
+    _lib.check(_lib.lib().hl_conv2d_plan(mode, N, H, W, C, Cout, ks, stride, ups, int(bool(gn)), ctypes.byref(k), ctypes.byref(s)), "hl_conv2d_plan")
+    return KERNELS[k.value], s.value
+
+
 def hip_conv(x, w, b, ks, stride=1, ups=0, cA=None, cB=None, silu=0, res=None, mode=0):
     from humanliff_amd import _lib
     L = _lib.lib()
@@ -52,18 +62,18 @@ def hip_conv(x, w, b, ks, stride=1, ups=0, cA=None, cB=None, silu=0, res=None, m
     return nchw(out.cpu())
 
 
-@pytest.mark.parametrize("N,C,H,W,Cout,ks,stride,ups", [
-    (2, 32, 16, 16, 64, 3, 1, 0),      # small-tile config
-    (1, 192, 32, 32, 192, 3, 1, 0),    # production channel count
-    (4, 192, 64, 64, 192, 3, 1, 0),    # M=16384
-    (2, 192, 128, 128, 192, 3, 1, 0),  # main tile config (128x96, 4 waves/SIMD), 512 workgroups, XCD remap
-    (1, 96, 160, 96, 96, 3, 1, 0),     # main tile config with a ragged last pixel tile (M=15360) and Cout=96
-    (2, 64, 16, 16, 64, 3, 2, 0),      # Downsample (unet.py:100)
-    (2, 64, 8, 8, 64, 3, 1, 1),        # Upsample: nearest x2 then conv (unet.py:77-79)
-    (2, 96, 12, 20, 128, 1, 1, 0),     # 1x1 skip / zero-conv, ragged M
-    (1, 64, 16, 16, 27, 3, 1, 0),      # 27 output channels (N tile 32)
-    (2, 384, 8, 8, 1152, 1, 1, 0),     # qkv projection (split-K x3)
-    (4, 768, 8, 8, 768, 3, 1, 0),      # 8x8 level of the production UNet: K=6912, split-K
+@pytest.mark.parametrize("N,C,H,W,Cout,ks,stride,ups", [      # the kernel the default mode takes today (hl_conv2d_plan); per kernel: tests/test_conv_fwd_gpu.py
+    (2, 32, 16, 16, 64, 3, 1, 0),      # k_conv, 64x64 tile, 2 slabs
+    (1, 192, 32, 32, 192, 3, 1, 0),    # k_conv_dma, 4 waves, 12 slabs (production channel count)
+    (4, 192, 64, 64, 192, 3, 1, 0),    # k_conv_h2s (fp16x2 products), 3 slabs (M=16384)
+    (2, 192, 128, 128, 192, 3, 1, 0),  # k_conv_h2s, unsplit
+    (1, 96, 160, 96, 96, 3, 1, 0),     # k_conv, 64x64 tile, 2 slabs, Cout=96 (two 64-channel blocks, the second half filled)
+    (2, 64, 16, 16, 64, 3, 2, 0),      # k_conv, 4 slabs: Downsample (unet.py:100)
+    (2, 64, 8, 8, 64, 3, 1, 1),        # k_conv, 4 slabs: Upsample, nearest x2 then conv (unet.py:77-79)
+    (2, 96, 12, 20, 128, 1, 1, 0),     # k_conv unsplit: 1x1 skip / zero-conv, ragged M
+    (1, 64, 16, 16, 27, 3, 1, 0),      # k_conv, 128x32 tile, 4 slabs: 27 output channels
+    (2, 384, 8, 8, 1152, 1, 1, 0),     # k_conv, 3 slabs: qkv projection
+    (4, 768, 8, 8, 768, 3, 1, 0),      # k_conv_dma, 4 waves, 16 slabs: 8x8 level of the production UNet, K=6912
 ])
 def test_conv_matches_torch(N, C, H, W, Cout, ks, stride, ups):
     g = torch.Generator().manual_seed(N * 1000 + C + H + Cout)
@@ -77,30 +87,40 @@ def test_conv_matches_torch(N, C, H, W, Cout, ks, stride, ups):
     assert (got - want).abs().max() < 2e-5          # outputs O(1), K up to 3456: fp32 accumulation-order noise
 
 
+_BF16X3_KERNEL = {(1, 192, 32, 32, 192): ("k_conv_bf3", True), (2, 192, 128, 128, 192): ("k_conv_bf3", True), (4, 768, 8, 8, 768): ("k_conv_bf3", True),
+                  (1, 96, 160, 96, 96): ("k_conv", True), (2, 96, 16, 16, 96): ("k_conv", True), (2, 96, 24, 24, 96): ("k_conv", True), (2, 384, 8, 8, 1152): ("k_conv", True)}
+
+
 @pytest.mark.parametrize("N,C,H,W,Cout,ks,stride,ups", [
-    (1, 192, 32, 32, 192, 3, 1, 0),    # 128x96 tile, split-K
-    (2, 192, 128, 128, 192, 3, 1, 0),  # 256x96 tile (8 waves)
-    (1, 96, 160, 96, 96, 3, 1, 0),     # ragged last pixel tile, Cout=96
-    (2, 96, 16, 16, 96, 3, 2, 0),      # stride 2
-    (2, 96, 24, 24, 96, 3, 1, 1),      # nearest x2 upsample
-    (2, 384, 8, 8, 1152, 1, 1, 0),     # 1x1 (qkv), split-K
-    (4, 768, 8, 8, 768, 3, 1, 0),      # K = 6912, 16 slabs
+    (1, 192, 32, 32, 192, 3, 1, 0),    # k_conv_bf3, 128x96 tile, 12 slabs
+    (2, 192, 128, 128, 192, 3, 1, 0),  # k_conv_bf3, 256x96 tile (8 waves), 2 slabs
+    (1, 96, 160, 96, 96, 3, 1, 0),     # k_conv (Cout=96 pads to 128 rows, no multiple of 96: no bf16x3 form; so do the next two), ragged last pixel tile
+    (2, 96, 16, 16, 96, 3, 2, 0),      # k_conv: stride 2 (k_conv_bf3 with stride 2: tests/test_conv_fwd_gpu.py)
+    (2, 96, 24, 24, 96, 3, 1, 1),      # k_conv: nearest x2 upsample (k_conv_bf3<., true, .>: tests/test_conv_fwd_gpu.py)
+    (2, 384, 8, 8, 1152, 1, 1, 0),     # k_conv: 1x1 (qkv), 3 slabs
+    (4, 768, 8, 8, 768, 3, 1, 0),      # k_conv_bf3, K = 6912, 16 slabs
 ])
 def test_conv_bf16x3_emulation_matches_torch(N, C, H, W, Cout, ks, stride, ups):
-    """HL_CONV_BF16X3: fp32 products emulated with three bf16 planes per operand - same bound as the exact fp32 kernel,
-    and the difference between the two modes is at accumulation-noise level."""
+    """HL_CONV_BF16X3: fp32 products emulated with three bf16 planes per operand - same bound as the exact fp32 kernel (HL_CONV_FP32_DIRECT, which
+    is held to it here too), and the difference between the two modes is at accumulation-noise level.  Layers without the bf16x3 form keep k_conv
+    under the mode: the plan says which shape is which."""
     from humanliff_amd import _lib
+    kernel, split = conv_plan(_lib.HL_CONV_BF16X3, N, H, W, C, Cout, ks, stride, ups)
+    assert (kernel, split > 1) == _BF16X3_KERNEL[(N, C, H, W, Cout)], (kernel, split)
+    assert conv_plan(_lib.HL_CONV_FP32_DIRECT, N, H, W, C, Cout, ks, stride, ups)[0] in ("k_conv", "k_conv_dma")
     g = torch.Generator().manual_seed(N * 1000 + C + H + Cout)
     x = torch.randn((N, C, H, W), generator=g)
     w = torch.randn((Cout, C, ks, ks), generator=g) / (C * ks * ks) ** 0.5
     b = torch.randn((Cout,), generator=g)
     got = hip_conv(x, w, b, ks, stride, ups, mode=_lib.HL_CONV_BF16X3)
-    exact = hip_conv(x, w, b, ks, stride, ups, mode=_lib.HL_CONV_FP32)
+    exact = hip_conv(x, w, b, ks, stride, ups, mode=_lib.HL_CONV_FP32_DIRECT)
     xi = F.interpolate(x, scale_factor=2, mode="nearest") if ups else x
     want = F.conv2d(xi.double(), w.double(), b.double(), stride=stride, padding=ks // 2)
     e_bf3, e_f32 = (got.double() - want).abs().max().item(), (exact.double() - want).abs().max().item()
-    assert e_bf3 < 2e-5                      # the fp32 kernel's bound (test_conv_matches_torch)
+    assert e_f32 < 2e-5                      # the yardstick: the fp32 kernel's own bound (test_conv_matches_torch)
+    assert e_bf3 < 2e-5                      # the same bound
     assert e_bf3 < 4 * e_f32 + 1e-6          # and within a small factor of the exact kernel's error vs float64
+    assert (kernel == "k_conv_bf3") == (not torch.equal(got, exact))      # the emulation ran exactly where the plan says so
 
 
 def test_conv_winograd_upsample_matches_torch():
@@ -170,9 +190,15 @@ def test_conv_winograd_matches_torch(N, C, H, W, Cout, with_gn):
     (1, 384, 64, 64, 384, False, 0),    # W = 48 < 160: input channels split into slabs, summed by k_splitk_finish (the 64-pixel level at batch 1)
 ])
 def test_conv_winograd_f43_matches_torch(N, C, H, W, Cout, with_gn, ups):
-    """HL_CONV_FP32 takes Winograd F(4x4,3x3) with the points (0, +-3/4, +-3/2, inf) where it fills the chip - a quarter of the direct
-    multiplies, fp32 throughout; compared with float64 torch, with the F(2x2) kernel and with the direct kernel on the same inputs."""
+    """HL_CONV_FP32_MFMA (the default mode without the fp16x2 kernels, which have since taken most of these layers from it) takes Winograd
+    F(4x4,3x3) with the points (0, +-3/4, +-3/2, inf) where it fills the chip - a quarter of the direct multiplies, fp32 throughout; compared
+    with float64 torch, with the F(2x2) kernel and with the direct kernel on the same inputs.  The plan says which of the two F(4x4) kernels a
+    shape takes: k_conv_wino4w on the last three (the third one split into slabs), k_conv_wino4 on the seven before."""
     from humanliff_amd import _lib
+    kernel, slabs = conv_plan(_lib.HL_CONV_FP32_MFMA, N, H, W, C, Cout, 3, 1, ups, with_gn)
+    w4w = {(4, 32, 256, 256, 192): False, (4, 64, 64, 64, 384): False, (1, 384, 64, 64, 384): True}      # -> split into slabs?
+    want_kernel = ("k_conv_wino4w", w4w[(N, C, H, W, Cout)]) if (N, C, H, W, Cout) in w4w else ("k_conv_wino4", False)
+    assert (kernel, slabs > 1) == want_kernel, (kernel, slabs)
     g = torch.Generator().manual_seed(N * 1000 + C + H + Cout)
     x = torch.randn((N, C, H, W), generator=g)
     w = torch.randn((Cout, C, 3, 3), generator=g) / (C * 9) ** 0.5
@@ -187,7 +213,7 @@ def test_conv_winograd_f43_matches_torch(N, C, H, W, Cout, with_gn, ups):
         xin = hn * torch.sigmoid(hn)
     if ups:
         xin = F.interpolate(xin, scale_factor=2, mode="nearest")
-    got = hip_conv(x, w, b, 3, ups=ups, mode=_lib.HL_CONV_FP32, **kw)
+    got = hip_conv(x, w, b, 3, ups=ups, mode=_lib.HL_CONV_FP32_MFMA, **kw)
     f23 = hip_conv(x, w, b, 3, ups=ups, mode=_lib.HL_CONV_FP32_F23, **kw)
     direct = hip_conv(x, w, b, 3, ups=ups, mode=_lib.HL_CONV_FP32_DIRECT, **kw)
     want = F.conv2d(xin, w.double(), b.double(), padding=1)
