@@ -203,6 +203,8 @@ SIGNATURES = {
     "hl_view_ingest_table_words": (_sz, [_i, _i]),
     "hl_view_ingest_table": (_i, [_i, _i, _p]),
     "hl_view_ingest": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
+    "hl_view_ingest_layers": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
+    "hl_pose_body_margins": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _i, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _sz, C.c_float, C.c_float, _p]),
 }
 
 

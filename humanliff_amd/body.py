@@ -145,11 +145,12 @@ class BodyModel:
         return self._big
 
     # ---- posing ----------------------------------------------------------------------------------
-    def pose(self, poses, shapes, R=None, Th=None):
+    def pose(self, poses, shapes, R=None, Th=None, y_margin=0.05):
         """poses (F,3J) or (3J,), shapes (S,) or (F,S): device tensors.  R (3,3) or (F,3,3), Th (3,) or (F,3): host arrays (enqueue-only)
-        or device tensors (one read back here: the deform kernels take them from the host).  Returns a PosedBody of F frames."""
+        or device tensors (one read back here: the deform kernels take them from the host).  Returns a PosedBody of F frames.
+        `y_margin`: what world_bounds adds on y beyond the 0.05 of every axis - 0.05 for SynBody, 0.1 for TightCap (TightCap_dataset.py:165-168)."""
         self._need_device("BodyModel.pose")
-        return self._pose(poses, shapes, R, Th, big=self.big_pose())
+        return self._pose(poses, shapes, R, Th, big=self.big_pose(), y_margin=y_margin)
 
     def _dev(self, t, what):
         if not torch.is_tensor(t):
@@ -159,7 +160,7 @@ class BodyModel:
             raise RuntimeError(f"BodyModel.pose: `{what}` is a CPU tensor; there is no CPU path (move it to the model's device)")
         return t.detach().to(device=self.device, dtype=torch.float32)
 
-    def _pose(self, poses, shapes, R, Th, big):
+    def _pose(self, poses, shapes, R, Th, big, y_margin=0.05):
         self._need_device("BodyModel.pose")
         for name, t in (("poses", poses), ("shapes", shapes), ("R", R), ("Th", Th)):
             if torch.is_tensor(t) and not t.is_cuda:
@@ -195,11 +196,12 @@ class BodyModel:
             table = new(F, V, 36) if big is not None else None
             rows = new(F, V, 16) if big is None else None
             ws = new(L.hl_body_pose_workspace_bytes(J, F) // 4)
-            _lib.check(L.hl_body_pose(_lib.ptr(packed), _lib.ptr(self._parents_dev, torch.int32), V, J, self.Sp, S, F, _lib.ptr(poses),
-                                      _lib.ptr(shapes), S if shapes.shape[0] == F and F > 1 else 0, _lib.ptr(rt), 12 if n_rt > 1 else 0,
-                                      _lib.ptr(big.rows[0]) if big is not None else None, _lib.ptr(vertices), _lib.ptr(joints),
-                                      _lib.ptr(bounds), _lib.ptr(verts4), _lib.ptr(table), _lib.ptr(rows), _lib.ptr(ws), ws.numel() * 4,
-                                      _lib.stream_ptr(dev)), "hl_body_pose")
+            # (hl_body_pose with the margins of the bounds spelled out: 0.05f, 0.05f is what that call passes)
+            _lib.check(L.hl_pose_body_margins(_lib.ptr(packed), _lib.ptr(self._parents_dev, torch.int32), V, J, self.Sp, S, F, _lib.ptr(poses),
+                                              _lib.ptr(shapes), S if shapes.shape[0] == F and F > 1 else 0, _lib.ptr(rt), 12 if n_rt > 1 else 0,
+                                              _lib.ptr(big.rows[0]) if big is not None else None, _lib.ptr(vertices), _lib.ptr(joints),
+                                              _lib.ptr(bounds), _lib.ptr(verts4), _lib.ptr(table), _lib.ptr(rows), _lib.ptr(ws), ws.numel() * 4,
+                                              0.05, float(y_margin), _lib.stream_ptr(dev)), "hl_pose_body_margins")
         posed = PosedBody()
         posed.model, posed.big, posed.F = self, big, F
         posed.vertices, posed.joints, posed.world_bounds, posed.verts4, posed.table, posed.rows = vertices, joints, bounds, verts4, table, rows

@@ -17,7 +17,8 @@
 //   pose_off; 1], world = v_smpl R^T + Th, verts4 = (world - Th) R from the rounded world vertex, Rinv by cofactors, the table row.
 //   FC = 8 (kChunk) for a sequence - 24 accumulators, the features of a chunk are 6.6 KB of LDS for SMPL - and FC = 1 for one frame.
 // k_body_bounds: one workgroup per frame: min / max of the frame's vertices (thread t takes t, t + 256, ..., then the tree), - / +
-//   0.05f, y once more by 0.05f: two fp32 subtractions, as SynBodyView_datasets.py:174-179 does them.
+//   `margin`, y once more by `y_margin`: two fp32 subtractions, as SynBodyView_datasets.py:174-179 does them with 0.05f and 0.05f
+//   (hl_body_pose) and TightCap_dataset.py:165-168 of the reference with 0.05f and 0.1f (hl_pose_body_margins).
 #include "hl_reduce.h"
 
 #include <cmath>
@@ -279,7 +280,8 @@ __global__ __launch_bounds__(kThreads) void k_body_skin(PoseArgs a) {
     }
 }
 
-__global__ __launch_bounds__(kThreads) void k_body_bounds(const float *__restrict__ vertices, int V, float *__restrict__ bounds) {
+__global__ __launch_bounds__(kThreads) void k_body_bounds(const float *__restrict__ vertices, int V, float margin, float y_margin,
+                                                          float *__restrict__ bounds) {
     __shared__ float sh[kThreads];
     const float *p = vertices + (int64_t)blockIdx.x * V * 3;
     float lo[3], hi[3];
@@ -301,8 +303,8 @@ __global__ __launch_bounds__(kThreads) void k_body_bounds(const float *__restric
         float *o = bounds + (int64_t)blockIdx.x * 6;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            float a = lo[c] - 0.05f, b = hi[c] + 0.05f;
-            if (c == 1) a = a - 0.05f, b = b + 0.05f;
+            float a = lo[c] - margin, b = hi[c] + margin;
+            if (c == 1) a = a - y_margin, b = b + y_margin;
             o[c] = a, o[3 + c] = b;
         }
     }
@@ -352,6 +354,15 @@ size_t hl_body_pose_workspace_bytes(int J, int F) {
 int hl_body_pose(const float *packed, const int32_t *parents, int V, int J, int Sp, int S, int F, const float *poses, const float *shapes,
                  int shapes_stride, const float *rt, int rt_stride, const float *big, float *vertices, float *joints, float *bounds,
                  float *verts4, float *table, float *big_out, void *workspace, size_t workspace_bytes, void *stream) {
+    return hl_pose_body_margins(packed, parents, V, J, Sp, S, F, poses, shapes, shapes_stride, rt, rt_stride, big, vertices, joints, bounds, verts4,
+                                table, big_out, workspace, workspace_bytes, 0.05f, 0.05f, stream);
+}
+
+int hl_pose_body_margins(const float *packed, const int32_t *parents, int V, int J, int Sp, int S, int F, const float *poses, const float *shapes,
+                         int shapes_stride, const float *rt, int rt_stride, const float *big, float *vertices, float *joints, float *bounds,
+                         float *verts4, float *table, float *big_out, void *workspace, size_t workspace_bytes, float margin, float y_margin,
+                         void *stream) {
+    HL_REQUIRE(margin >= 0.f && y_margin >= 0.f, "hl_body_pose: the bounds' margins must not be negative (got %g, %g)", (double)margin, (double)y_margin);
     HL_REQUIRE(packed && parents && poses && shapes && rt, "hl_body_pose: NULL argument");
     HL_REQUIRE(sizes_ok(V, J, Sp) && J >= 2 && S >= 1 && S <= Sp && F >= 1,
                "hl_body_pose: bad sizes (V %d, J %d, Sp %d, S %d, F %d; V > 0, 2 <= J <= %d, 1 <= S <= Sp <= %d, F >= 1)", V, J, Sp, S, F, kMaxJ, kMaxS);
@@ -388,7 +399,7 @@ int hl_body_pose(const float *packed, const int32_t *parents, int V, int J, int 
         if (rc != HL_OK) return rc;
     }
     if (bounds) {
-        hipLaunchKernelGGL(k_body_bounds, dim3(F), dim3(kThreads), 0, st, vertices, V, bounds);
+        hipLaunchKernelGGL(k_body_bounds, dim3(F), dim3(kThreads), 0, st, vertices, V, margin, y_margin, bounds);
         rc = check_launch("k_body_bounds");
     }
     return rc;

@@ -8,7 +8,8 @@ reference, for the device-resident fitting path (contract: DESIGN.md 4i).
 The reference decodes, masks and resizes one image per __getitem__ call in a DataLoader worker (imageio + cv2, :266-278) and draws its rays
 there.  Here every view is decoded once (PIL, a bounded thread pool), uploaded as uint8 and turned into the store's float image and body
 mask by one launch per batch (humanliff_amd.view_ingest); rays are drawn on the device afterwards (if_nerf_data_utils.sample_ray_batch).
-SynBodyIndex and smpl_params are host code and need neither a GPU nor PIL.  smpl_type 'smplx' and the TightCap layout are not covered.
+SynBodyIndex and smpl_params are host code and need neither a GPU nor PIL.  smpl_type 'smplx' is not covered; the TightCap layout is
+TightCap_dataset.py's, which reuses the readers and helpers below.
 """
 import json
 import os
@@ -152,6 +153,20 @@ def load_view_store(index, body_model, image_scaling=1.0, device=None, items=Non
     body_model.pose of smpl_params (prepare_input :158-194).  The store also carries `dataset_index`, `pose_index` and `view_index`
     (host int64 arrays, one entry per view).  MemoryError before anything is decoded when the store would not fit the free device
     memory; ValueError for a file of another size than the first, and for image_scaling > 1."""
+    def ingest(recs, decoded, H, W, device):
+        img = torch.from_numpy(np.stack([d[rec[4]] for rec, d in zip(recs, decoded)])).to(device)
+        msk = torch.from_numpy(np.stack([d[rec[5]] for rec, d in zip(recs, decoded)])).to(device)
+        return view_ingest.ingest_views(img, msk, H, W)
+
+    return fill_view_store(index, body_model, image_scaling, device, items, decode_threads, source_bytes=4, y_margin=0.05,
+                           decode=lambda rec: {rec[4]: read_image(rec[4]), rec[5]: read_mask(rec[5])}, ingest=ingest)
+
+
+def fill_view_store(index, body_model, image_scaling, device, items, decode_threads, source_bytes, y_margin, decode, ingest):
+    """What the loaders of the two dataset layouts share.  `index.item(i)` gives (instance_idx, cloth_layer_index, pose_index, view_index,
+    img_path, ..., K, R, T) and `index.smpl_path`; `decode(rec)` -> {path: uint8 array} of the files the view names (called in the thread
+    pool); `ingest(recs, decoded, H, W, device)` -> (image (V, H, W, 3) float32, body (V, H, W) uint8) of one batch on the device;
+    `source_bytes`: uint8 bytes uploaded per source pixel; `y_margin`: BodyModel.pose's."""
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     if device.type != "cuda":
         raise RuntimeError("load_view_store needs a HIP device; humanliff_amd has no CPU path")
@@ -164,9 +179,9 @@ def load_view_store(index, body_model, image_scaling=1.0, device=None, items=Non
     H, W = scaled_size(Hs, Ws, image_scaling)
     view_ingest.check_sizes(Hs, Ws, H, W)
     V = len(records)
-    per_batch = max(1, min(V, UPLOAD_BYTES // (Hs * Ws * 4)))
+    per_batch = max(1, min(V, UPLOAD_BYTES // (Hs * Ws * source_bytes)))
     free = torch.cuda.mem_get_info(device)[0]
-    staging = per_batch * (Hs * Ws * 4 + H * W * 13)                  # a batch's uint8 source and its output before torch.cat
+    staging = per_batch * (Hs * Ws * source_bytes + H * W * 13)       # a batch's uint8 source and its output before torch.cat
     if store_bytes(V, H, W) + staging > free:
         fit = max(0, (free - staging) // store_bytes(1, H, W))
         raise MemoryError(f"load_view_store: {V} views of {H} x {W} need {store_bytes(V, H, W) + staging} bytes on {device}, "
@@ -176,25 +191,23 @@ def load_view_store(index, body_model, image_scaling=1.0, device=None, items=Non
     for inst, _, pose, *_ in records:
         if (inst, pose) not in bounds:
             p = smpl_params(index.smpl_path(inst), pose)
-            posed = body_model.pose(torch.from_numpy(p['poses']).to(device), torch.from_numpy(p['shapes'].reshape(-1)).to(device), p['R'], p['Th'])
+            posed = body_model.pose(torch.from_numpy(p['poses']).to(device), torch.from_numpy(p['shapes'].reshape(-1)).to(device), p['R'], p['Th'],
+                                    y_margin=y_margin)
             bounds[(inst, pose)] = posed.world_bounds[0]
     bounds = {k: b.double().cpu().numpy() for k, b in bounds.items()}
 
-    def decode(rec):
-        img, msk = read_image(rec[4]), read_mask(rec[5])
-        for path, a in ((rec[4], img), (rec[5], msk)):
+    def decode_checked(rec):
+        out = decode(rec)
+        for path, a in out.items():
             if a.shape[:2] != (Hs, Ws):
                 raise ValueError(f"{path} is {a.shape[0]} x {a.shape[1]}; the views of a store have one size and the first is {Hs} x {Ws}")
-        return img, msk
+        return out
 
     store = ViewStore(H, W, device)
     with ThreadPoolExecutor(max_workers=max(1, min(int(decode_threads), MAX_DECODE_THREADS))) as pool:
         for b0 in range(0, V, per_batch):
             recs = records[b0:b0 + per_batch]
-            decoded = list(pool.map(decode, recs))
-            img = torch.from_numpy(np.stack([d[0] for d in decoded])).to(device)
-            msk = torch.from_numpy(np.stack([d[1] for d in decoded])).to(device)
-            image, body = view_ingest.ingest_views(img, msk, H, W)
+            image, body = ingest(recs, list(pool.map(decode_checked, recs)), H, W, device)
             K = scaled_intrinsics(np.stack([r[6] for r in recs]), image_scaling)
             store.add(image, body, K, np.stack([r[7] for r in recs]), np.stack([r[8] for r in recs]),
                       np.stack([bounds[(r[0], r[2])] for r in recs]), [r[0] for r in recs], [r[1] for r in recs])

@@ -6,6 +6,11 @@ launch writes the float32 image and the body mask of every view of the batch.
 
     image, body = ingest_views(img_u8, msk_u8, H, W)      # (V, Hs, Ws, 3), (V, Hs, Ws) uint8 device tensors -> (V, H, W, 3) f32, (V, H, W) u8
 
+TightCap has one photograph and five masks per view and no image per cloth layer (recon_NeRF/lib/TightCap_dataset.py:233-298 of the
+reference); the same launch composes the layer's image and derives its mask first (contract: DESIGN.md 4j):
+
+    image, body = ingest_layered_views(img_u8, {'full': ..., 'person': ..., 'top': ..., 'bottom': ..., 'shoes': ...}, layers, H, W)
+
 The tap tables of the resize rule are built on the host (area_taps, nearest_taps: plain C++, callable without a GPU) and uploaded once per
 (Hs, Ws, H, W) and device.  There is no CPU path for the images.
 """
@@ -96,4 +101,62 @@ def ingest_views(img_u8, msk_u8, H, W):
         _lib.check(_lib.lib().hl_view_ingest(_lib.ptr(img_u8, torch.uint8), _lib.ptr(msk_u8, torch.uint8), V, Hs, Ws, H, W,
                                              _lib.ptr(xtab, torch.int32), _lib.ptr(ytab, torch.int32), _lib.ptr(image),
                                              _lib.ptr(body, torch.uint8), _lib.stream_ptr(dev)), "hl_view_ingest")
+    return image, body
+
+
+PLANES = ("full", "person", "top", "bottom", "shoes")
+# the planes a cloth layer's rule names besides the photograph (TightCap_dataset.py:233-298): a plane outside this set is never read
+LAYER_PLANES = (("full", "person", "top", "bottom", "shoes"), ("full", "person", "top", "shoes"), ("full", "person", "shoes"), ("full",))
+
+
+def planes_read(layers):
+    """The names of the planes a batch with these cloth layers reads, in PLANES order.  ValueError for a layer outside 0 .. 3."""
+    layers = [int(x) for x in layers]
+    bad = sorted({x for x in layers if not 0 <= x <= 3})
+    if bad:
+        raise ValueError(f"view ingest: cloth layers are 0 .. 3, got {bad}")
+    return tuple(n for n in PLANES if any(n in LAYER_PLANES[x] for x in layers))
+
+
+def ingest_layered_views(img_u8, masks, layers, H, W):
+    """TightCap's views: img_u8 (V, Hs, Ws, 3), the photographs; masks, a dict or 5-tuple of the (V, Hs, Ws) planes full,
+    person, top, bottom, shoes (None for one no view of the batch reads); layers, the V cloth layers as a host sequence.  All tensors
+    contiguous uint8 on the device.  -> image (V, H, W, 3) float32, the reduction of each view's composed layer image, and body (V, H, W)
+    uint8 of 0 / 1, the nearest pixel of the mask derived from it.  Enqueue-only on the current stream (the layers are uploaded here)."""
+    if isinstance(masks, dict):
+        unknown = sorted(set(masks) - set(PLANES))
+        if unknown:
+            raise ValueError(f"ingest_layered_views: unknown planes {unknown}; the planes are {PLANES}")
+        masks = tuple(masks.get(n) for n in PLANES)
+    masks = tuple(masks)
+    if len(masks) != 5:
+        raise ValueError(f"ingest_layered_views: masks must hold the five planes {PLANES} (None for one that is not read), got {len(masks)}")
+    given = [m for m in masks if m is not None]
+    if not (torch.is_tensor(img_u8) and img_u8.is_cuda and all(torch.is_tensor(m) and m.is_cuda for m in given)):
+        raise RuntimeError("ingest_layered_views needs device tensors; humanliff_amd has no CPU path")
+    if img_u8.dtype != torch.uint8 or any(m.dtype != torch.uint8 for m in given):
+        raise TypeError(f"ingest_layered_views: images and masks must be uint8, got {img_u8.dtype}, {[m.dtype for m in given]}")
+    if img_u8.dim() != 4 or img_u8.shape[3] != 3 or img_u8.shape[0] < 1 or any(tuple(m.shape) != tuple(img_u8.shape[:3]) for m in given):
+        raise ValueError(f"ingest_layered_views: images must be (V, Hs, Ws, 3) and every plane (V, Hs, Ws); got {tuple(img_u8.shape)}, "
+                         f"{[tuple(m.shape) for m in given]}")
+    V, Hs, Ws = (int(s) for s in img_u8.shape[:3])
+    layers = [int(x) for x in layers]
+    if len(layers) != V:
+        raise ValueError(f"ingest_layered_views: {len(layers)} layers for {V} views")
+    missing = [n for n in planes_read(layers) if masks[PLANES.index(n)] is None]
+    if missing:
+        raise ValueError(f"ingest_layered_views: the layers {sorted(set(layers))} read the planes {missing}, which are None")
+    Hs, Ws, H, W = check_sizes(Hs, Ws, H, W)
+    dev = img_u8.device
+    aligned = lambda t: t if t is None or (t.is_contiguous() and t.data_ptr() % 16 == 0) else t.contiguous().clone()  # noqa: E731
+    img_u8, masks = aligned(img_u8), [aligned(m) for m in masks]
+    d_layers = torch.tensor(layers, dtype=torch.int32).to(dev, non_blocking=True)
+    image = torch.empty((V, H, W, 3), dtype=torch.float32, device=dev)
+    body = torch.empty((V, H, W), dtype=torch.uint8, device=dev)
+    xtab, ytab = (None, None) if (H, W) == (Hs, Ws) else device_tables(Hs, Ws, H, W, dev)
+    with _lib.on(dev):
+        _lib.check(_lib.lib().hl_view_ingest_layers(_lib.ptr(img_u8, torch.uint8), *(_lib.ptr(m, torch.uint8) for m in masks),
+                                                    _lib.ptr(d_layers, torch.int32), V, Hs, Ws, H, W, _lib.ptr(xtab, torch.int32),
+                                                    _lib.ptr(ytab, torch.int32), _lib.ptr(image), _lib.ptr(body, torch.uint8),
+                                                    _lib.stream_ptr(dev)), "hl_view_ingest_layers")
     return image, body

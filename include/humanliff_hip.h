@@ -867,6 +867,13 @@ size_t hl_body_pose_workspace_bytes(int J, int F);
 int hl_body_pose(const float *packed, const int32_t *parents, int V, int J, int Sp, int S, int F, const float *poses, const float *shapes,
                  int shapes_stride, const float *rt, int rt_stride, const float *big, float *vertices, float *joints, float *bounds,
                  float *verts4, float *table, float *big_out, void *workspace, size_t workspace_bytes, void *stream);
+/* hl_body_pose with the margins of `bounds` as arguments: - / + margin on every axis, then y once more by y_margin (two fp32
+ * subtractions in that order; neither may be negative).  hl_body_pose is this call with 0.05f, 0.05f; the TightCap dataset pads with
+ * 0.05f, 0.1f (recon_NeRF/lib/TightCap_dataset.py:165-168 of the reference). */
+int hl_pose_body_margins(const float *packed, const int32_t *parents, int V, int J, int Sp, int S, int F, const float *poses, const float *shapes,
+                         int shapes_stride, const float *rt, int rt_stride, const float *big, float *vertices, float *joints, float *bounds,
+                         float *verts4, float *table, float *big_out, void *workspace, size_t workspace_bytes, float margin, float y_margin,
+                         void *stream);
 
 /* ---- raw dataset views -> ViewStore arrays (recon_NeRF/lib/SynBody_dataset.py:266-278: imread / 255, img[msk == 0] = 0,
  *      cv2.resize INTER_AREA of the image, INTER_NEAREST of the mask) ----
@@ -893,6 +900,19 @@ size_t hl_view_ingest_table_words(int src, int dst);
 int hl_view_ingest_table(int src, int dst, int32_t *h_table);
 int hl_view_ingest(const unsigned char *img_u8, const unsigned char *msk_u8, int V, int Hs, int Ws, int H, int W, const int32_t *xtab,
                    const int32_t *ytab, float *out_image, unsigned char *out_body, void *stream);
+/* hl_view_ingest_layers (enqueue-only; recon_NeRF/lib/TightCap_dataset.py:233-298 of the reference): hl_view_ingest for views
+ *   whose cloth layer is composed from one photograph img_u8 (V, Hs, Ws, 3) and five mask planes full, person, top, bottom, shoes, each
+ *   (V, Hs, Ws) uint8 and binary as "byte != 0"; layers (V) int32 on the device, values 0 .. 3 (others are clamped).  With
+ *   s = person + the garments the layer wears (0: top, bottom, shoes; 1: top, shoes; 2: shoes), the source pixel of a layer < 3 is, first
+ *   match: full == 0 -> 0;  s >= 2 -> the skin colour (0.607186f, 0.49289057f, 0.43795943f);  person == 0 and s == 1 -> 0;  otherwise
+ *   (float)u8 / 255.0f - and its source mask is "any channel != 0".  Layer 3: full ? (float)u8 / 255.0f : 0, mask = full.  out_image is
+ *   hl_view_ingest's reduction of that source (same tables, same order of sums), out_body the nearest pixel of that mask; for H == Hs and
+ *   W == Ws both are the composed source itself.  A plane a view's layer does not wear is never read for that view; person, top, bottom
+ *   and shoes may be NULL when no view of the batch reads them (a NULL plane that is read counts as all zero).  img_u8, the planes and the
+ *   outputs must be 16-byte aligned.  Limits as for hl_view_ingest.  No atomics; a view's bits do not depend on V. */
+int hl_view_ingest_layers(const unsigned char *img_u8, const unsigned char *full, const unsigned char *person, const unsigned char *top,
+                          const unsigned char *bottom, const unsigned char *shoes, const int32_t *layers, int V, int Hs, int Ws, int H, int W,
+                          const int32_t *xtab, const int32_t *ytab, float *out_image, unsigned char *out_body, void *stream);
 
 #ifdef __cplusplus
 }

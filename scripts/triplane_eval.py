@@ -12,6 +12,9 @@ optionally --test_layer_id); any other orbit needs --view_ids.  View id i is orb
 same view ids on a SynBody directory tree: the files are decoded, resized on the device (csrc/hl_view_ingest.hip) and held in a ViewStore,
 whose test_view gives the rays and the ground truth (recon_NeRF/lib/SynBody_dataset.py).
 
+--data tightcap does the same on a TightCap tree (recon_NeRF/lib/TightCap_dataset.py: the cloth layers are composed on the device from one
+photograph and five masks per view) with test_TightCap's held-out views (heldout_view_ids(tightcap=True)); --image_scaling defaults to 1.0 there.
+
 --views-npz loads real views: arrays ray_o_all, ray_d_all (N, R, 3), near_all, far_all (N, R), rgb_all (N, R, 3), mask_at_box_all (N, R),
 instance_idx, cloth_layer_index, pose_index, view_id (N), world_bounds (N, 2, 3) and optionally H, W; the N views must be grouped by
 instance_idx.
@@ -52,10 +55,10 @@ def parse():
     a.add_argument("--data_range", type=float, default=2.0)
     a.add_argument("--views-npz", dest="views_npz", type=str, default=None)
     a.add_argument("--seed", type=int, default=0)
-    a.add_argument("--data", choices=["synthetic", "synbody"], default="synthetic")
-    a.add_argument("--data_root", type=str, default=None, help="--data synbody: a subject's directory; human_list.txt lies beside it")
-    a.add_argument("--smpl_model", type=str, default=None, help="--data synbody: the SMPL asset (.pkl / .npz) load_body_model reads")
-    a.add_argument("--image_scaling", type=float, default=0.5)
+    a.add_argument("--data", choices=["synthetic", "synbody", "tightcap"], default="synthetic")
+    a.add_argument("--data_root", type=str, default=None, help="--data synbody / tightcap: a subject's directory; the human list lies beside it")
+    a.add_argument("--smpl_model", type=str, default=None, help="--data synbody / tightcap: the SMPL asset (.pkl / .npz) load_body_model reads")
+    a.add_argument("--image_scaling", type=float, default=None, help="default: 0.5 (synbody), 1.0 (tightcap)")
     a.add_argument("--poses_num", type=int, default=1)
     a.add_argument("--pose_start", type=int, default=0)
     a.add_argument("--pose_interval", type=int, default=5)
@@ -89,20 +92,26 @@ def synthetic_views(args, humans, dev):
 
 
 def synbody_views(args, humans, dev):
-    """The held-out views of a SynBody tree, read and resized on the device (recon_NeRF/lib/SynBody_dataset.py) and scored through
-    ViewStore.test_view.  View id i is view i % views_num of cloth layer i // views_num (with --layer_idx: of that layer), first pose."""
+    """The held-out views of a SynBody or TightCap tree, read and resized on the device (recon_NeRF/lib/SynBody_dataset.py,
+    TightCap_dataset.py) and scored through ViewStore.test_view.  View id i is view i % views_num of cloth layer i // views_num (with
+    --layer_idx: of that layer), first pose."""
     from humanliff_amd.body import load_body_model
-    from humanliff_amd.recon_NeRF.lib.SynBody_dataset import SynBodyIndex, load_view_store, store_test_views
+    tightcap = args.data == "tightcap"
+    if tightcap:
+        from humanliff_amd.recon_NeRF.lib.TightCap_dataset import TightCapIndex as Index, load_view_store, store_test_views
+    else:
+        from humanliff_amd.recon_NeRF.lib.SynBody_dataset import SynBodyIndex as Index, load_view_store, store_test_views
     if not args.data_root or not args.smpl_model:
-        raise SystemExit("--data synbody needs --data_root DIR and --smpl_model PATH")
-    ids = heldout_view_ids(args.views_num, args.test_layer_id, view_ids=args.view_ids)
-    index = SynBodyIndex(args.data_root, multi_person=True, num_instance=max(humans) + 1, pose_start=args.pose_start,
+        raise SystemExit(f"--data {args.data} needs --data_root DIR and --smpl_model PATH")
+    image_scaling = (1.0 if tightcap else 0.5) if args.image_scaling is None else args.image_scaling
+    ids = heldout_view_ids(args.views_num, args.test_layer_id, tightcap=tightcap, view_ids=args.view_ids)
+    index = Index(args.data_root, multi_person=True, num_instance=max(humans) + 1, pose_start=args.pose_start,
                          pose_interval=args.pose_interval, poses_num=args.poses_num, views_num=args.views_num, layer_idx=args.layer_idx)
     nv, per_layer = args.views_num, args.poses_num * args.views_num
     per_human = index.cloth_layer_num * per_layer
     layer_of = (lambda i: 0) if args.layer_idx is not None else (lambda i: (i // nv) % 4)
     items = [h * per_human + layer_of(i) * per_layer + i % nv for h in humans for i in ids]
-    store = load_view_store(index, load_body_model(args.smpl_model, dev), image_scaling=args.image_scaling, device=dev, items=items,
+    store = load_view_store(index, load_body_model(args.smpl_model, dev), image_scaling=image_scaling, device=dev, items=items,
                             decode_threads=args.decode_threads)
     return store_test_views(store, view_ids=[i for _ in humans for i in ids])
 
@@ -138,7 +147,7 @@ def main():
     if args.views_npz:
         views = npz_views(args.views_npz)
     else:
-        views = synbody_views(args, humans, dev) if args.data == "synbody" else synthetic_views(args, humans, dev)
+        views = synbody_views(args, humans, dev) if args.data in ("synbody", "tightcap") else synthetic_views(args, humans, dev)
     lpips_fn = None
     if args.lpips_weights:
         from humanliff_amd.lpips import LpipsVGG

@@ -15,6 +15,9 @@ With --ft_triplane_only it is run_nerf_batch_ft.py's flow (:348-360, 110-129): f
 every cloth layer, a one-subject tri-plane is fitted with the decoder of the run's checkpoint frozen - layer 0 starts from the checkpoint's
 first tri-plane, layer l from layer l - 1 of the subject's own file - and saved as {subject}_{n_iteration:06d}.tar.  (The learning rate
 follows FitLoop's schedule; the reference's separate 0.5 ^ (step / 500) decay of that script is not restated.)
+--data tightcap: the same for a TightCap tree (TightCap_human_list.txt beside the subjects; one photograph and five masks per view): every
+view's cloth layers are composed on the device (hl_view_ingest_layers; recon_NeRF/lib/TightCap_dataset.py).  --image_scaling and
+--views_num default to the reference's configs: 0.5 and 185 for synbody, 1.0 and 382 for tightcap.
 --tv_loss is accepted and ignored: FitLoop always computes both regularisers (a coefficient of 0 switches a term off).
 """
 import argparse
@@ -57,23 +60,27 @@ def parse():
     a.add_argument("--i_print", type=int, default=100)
     a.add_argument("--i_weights", type=int, default=10000)
     a.add_argument("--seed", type=int, default=0)
-    a.add_argument("--data", choices=["synthetic", "rendered", "synbody"], default="synthetic")
-    a.add_argument("--data_root", type=str, default=None, help="--data synbody: a subject's directory; human_list.txt lies beside it")
-    a.add_argument("--smpl_model", type=str, default=None, help="--data synbody: the SMPL asset (.pkl / .npz) load_body_model reads")
-    a.add_argument("--image_scaling", type=float, default=0.5)
-    a.add_argument("--views_num", type=int, default=185)
+    a.add_argument("--data", choices=["synthetic", "rendered", "synbody", "tightcap"], default="synthetic")
+    a.add_argument("--data_root", type=str, default=None, help="--data synbody / tightcap: a subject's directory; the human list lies beside it")
+    a.add_argument("--smpl_model", type=str, default=None, help="--data synbody / tightcap: the SMPL asset (.pkl / .npz) load_body_model reads")
+    a.add_argument("--image_scaling", type=float, default=None, help="default: 0.5 (synbody), 1.0 (tightcap)")
+    a.add_argument("--views_num", type=int, default=None, help="default: 185 (synbody), 382 (tightcap)")
     a.add_argument("--poses_num", type=int, default=1)
     a.add_argument("--pose_start", type=int, default=0)
     a.add_argument("--pose_interval", type=int, default=5)
     a.add_argument("--layer_idx", type=int, default=None)
-    a.add_argument("--single_person", action="store_true", help="--data synbody: only --data_root itself (multi_person=False)")
+    a.add_argument("--single_person", action="store_true", help="--data synbody / tightcap: only --data_root itself (multi_person=False)")
     a.add_argument("--start_idx", type=int, default=0, help="--ft_triplane_only: first subject of human_list.txt")
     a.add_argument("--end_idx", type=int, default=None)
     a.add_argument("--decode_threads", type=int, default=8)
     a.add_argument("--views", type=int, default=24, help="--data rendered: orbit views rendered from the hidden tri-plane")
     a.add_argument("--heldout", type=int, default=4, help="--data rendered: of which this many (evenly spaced) are only scored")
     a.add_argument("--image_size", type=int, default=128, help="--data rendered: side of the rendered views")
-    return a.parse_args()
+    args = a.parse_args()
+    tightcap = args.data == "tightcap"
+    args.image_scaling = (1.0 if tightcap else 0.5) if args.image_scaling is None else args.image_scaling
+    args.views_num = (382 if tightcap else 185) if args.views_num is None else args.views_num
+    return args
 
 
 def batches(args, dev):
@@ -141,9 +148,18 @@ def fit_rendered(args, model, dev, kw):
     score("after")
 
 
-def synbody_store(args, dev, body, data_root, multi_person, num_instance, layer_idx):
+def dataset_reader(args):
+    """(index class, load_view_store, name of the human list) of --data synbody / tightcap: the only things the two paths differ in."""
+    if args.data == "tightcap":
+        from humanliff_amd.recon_NeRF.lib.TightCap_dataset import TightCapIndex, load_view_store
+        return TightCapIndex, load_view_store, 'TightCap_human_list.txt'
     from humanliff_amd.recon_NeRF.lib.SynBody_dataset import SynBodyIndex, load_view_store
-    index = SynBodyIndex(data_root, multi_person=multi_person, num_instance=num_instance, pose_start=args.pose_start,
+    return SynBodyIndex, load_view_store, 'human_list.txt'
+
+
+def synbody_store(args, dev, body, data_root, multi_person, num_instance, layer_idx):
+    Index, load_view_store, _ = dataset_reader(args)
+    index = Index(data_root, multi_person=multi_person, num_instance=num_instance, pose_start=args.pose_start,
                          pose_interval=args.pose_interval, poses_num=args.poses_num, views_num=args.views_num, layer_idx=layer_idx)
     store = load_view_store(index, body, image_scaling=args.image_scaling, device=dev, decode_threads=args.decode_threads)
     print(f"loaded {len(store)} views of {store.H} x {store.W} from {data_root}"
@@ -170,7 +186,7 @@ def finetune_synbody(args, dev, body, kw):
             raise SystemExit(f"--ft_triplane_only needs the fitted decoder: no NNNNNN.tar checkpoint in {logdir} (fit without the flag first, or name one with --ft_path)")
         base_ckpt = os.path.join(logdir, runs[-1])
     root_dir = os.path.dirname(args.data_root)
-    with open(os.path.join(root_dir, 'human_list.txt')) as f:
+    with open(os.path.join(root_dir, dataset_reader(args)[2])) as f:
         names = [n.strip() for n in f.readlines()][args.start_idx:args.end_idx]
     kw = dict(kw, ft_triplane_only=True, expname=None)                       # (the hand-over below replaces FitLoop's own reload)
     for name in names:
@@ -203,7 +219,7 @@ def fit_synbody(args, model, dev, kw):
     from humanliff_amd.body import load_body_model
     from humanliff_amd.recon_NeRF.lib.if_nerf_data_utils import RayBatchLoader
     if not args.data_root or not args.smpl_model:
-        raise SystemExit("--data synbody needs --data_root DIR and --smpl_model PATH")
+        raise SystemExit(f"--data {args.data} needs --data_root DIR and --smpl_model PATH")
     body = load_body_model(args.smpl_model, dev)
     if args.ft_triplane_only:
         return finetune_synbody(args, dev, body, kw)
@@ -228,7 +244,7 @@ def main():
               ft_path=args.ft_path, no_reload=args.no_reload)
     if args.data == "rendered":
         return fit_rendered(args, model, dev, kw)
-    if args.data == "synbody":
+    if args.data in ("synbody", "tightcap"):
         return fit_synbody(args, model, dev, kw)
     FitLoop(model, batches(args, dev), **kw).run_loop()
 
