@@ -321,6 +321,7 @@ __device__ __forceinline__ void store_rows(i32x4 rs, unsigned voff, unsigned str
 
 // torch.linspace(0,1,N)[s] (CPU/CUDA kernels are symmetric about the midpoint)
 __device__ __forceinline__ float linspace01(int s, int N) {
+    if (N == 1) return 0.0f;       // torch.linspace(0, 1, 1) = [0]; the step below would be 1 / 0 and the depth NaN
     const float step = 1.0f / (float)(N - 1);
     return s < N / 2 ? step * (float)s : 1.0f - step * (float)(N - 1 - s);
 }
