@@ -26,6 +26,11 @@ HL_RENDER_WHITE_BKGD = 1
 HL_RENDER_NORMALIZE_DEPTH = 2
 HL_RENDER_REEVALUATE = 4
 HL_RENDER_CLAMP_DEPTH = 8
+HL_COMPOSITE_SERIAL_RAW = 1
+HL_COMPOSITE_WAVE_FWD = 2
+HL_COMPOSITE_SERIAL_EXACT = 3
+HL_COMPOSITE_WAVE_BWD = 4
+HL_COMPOSITE_SERIAL_BWD = 5
 
 
 class HipLibraryMissing(RuntimeError):
@@ -83,6 +88,8 @@ SIGNATURES = {
     "hl_render_importance_new": (_i, [_p, _p, _p, _p, _p, _p, _i64, _i, _i, _p, _p]),
     "hl_render_composite": (_i, [_p, _p, _p, _p, _p, _p, _i64, _i, _i, _u, _p, _p, _p, _p]),
     "hl_render_composite_noise": (_i, [_p, _p, _p, _p, _p, _p, _p, _i64, _i, _i, _u, _p, _p, _p, _p]),
+    "hl_render_composite_plan": (_i, [_i64, _i, _i, _i]),
+    "hl_render_composite_backward_plan": (_i, [_i, _i]),
     "hl_render_mlp_bwd_packed_bytes": (_sz, []),
     "hl_render_mlp_pack_bwd": (_i, [C.POINTER(RenderMlpParams), _p, _p]),
     "hl_render_train_rows": (None, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),

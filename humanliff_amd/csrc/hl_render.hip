@@ -3648,6 +3648,27 @@ int hl_render_importance_new(const float *records, const float *rays_d, const fl
     return hl::check_launch("k_importance<new>");
 }
 
+// Which kernel a compositing call launches: the entries below branch on these two functions and the plan queries return them, so a
+// test that pins a case to its kernel reads the dispatch itself.  The wave kernels hold both depth lists of a ray in LDS (CW_MAX / 2 each).
+static int composite_plan(int64_t n_rays, int n_samples, int n_importance, bool with_noise) {
+    if (!with_noise) return HL_COMPOSITE_SERIAL_RAW;
+    // fitting batches (training noise given, few rays): one wave per ray
+    return n_rays <= 65536 && n_samples <= CW_MAX / 2 && n_importance <= CW_MAX / 2 ? HL_COMPOSITE_WAVE_FWD : HL_COMPOSITE_SERIAL_EXACT;
+}
+static int composite_backward_plan(int n_samples, int n_importance) {
+    return n_samples <= CW_MAX / 2 && n_importance <= CW_MAX / 2 ? HL_COMPOSITE_WAVE_BWD : HL_COMPOSITE_SERIAL_BWD;
+}
+
+int hl_render_composite_plan(int64_t n_rays, int n_samples, int n_importance, int with_noise) {
+    HL_REQUIRE(n_rays > 0 && n_samples >= 1 && n_importance >= 1, "hl_render_composite_plan: bad sizes");
+    return composite_plan(n_rays, n_samples, n_importance, with_noise != 0);
+}
+
+int hl_render_composite_backward_plan(int n_samples, int n_importance) {
+    HL_REQUIRE(n_samples >= 1 && n_importance >= 1, "hl_render_composite_backward_plan: bad sizes");
+    return composite_backward_plan(n_samples, n_importance);
+}
+
 int hl_render_composite(const float *near, const float *far, const float *z_vals, const float *z_new, const float *rec_coarse,
                         const float *rec_new, int64_t n_rays, int n_samples, int n_importance, unsigned flags, float *rgb,
                         float *acc, float *depth, void *stream) {
@@ -3662,8 +3683,7 @@ int hl_render_composite_noise(const float *near, const float *far, const float *
     HL_REQUIRE(n_rays > 0 && n_samples >= 1 && n_importance >= 1, "hl_render_composite: bad sizes");
     CompArgs c{near, far, z_vals, z_new, (const float4 *)rec_coarse, (const float4 *)rec_new, n_rays, n_samples, n_importance,
                flags, rgb, acc, depth, noise};
-    // fitting batches (training noise given, few rays): one wave per ray
-    if (noise && n_rays <= 65536 && n_samples <= CW_MAX / 2 && n_importance <= CW_MAX / 2) {
+    if (composite_plan(n_rays, n_samples, n_importance, noise != nullptr) == HL_COMPOSITE_WAVE_FWD) {
         CompBwdArgs b{};
         b.c = c;
         hipLaunchKernelGGL(k_composite_wave<false>, dim3((unsigned)(tiles32(n_rays) * 8)), dim3(256), 0, (hipStream_t)stream, b);
@@ -3741,7 +3761,7 @@ int hl_render_composite_backward(const float *near, const float *far, const floa
     b.sT = (float *)scratch;
     b.sSrc = (int *)scratch + tiles32(n_rays) * 32 * (size_t)(n_samples + n_importance);
     b.del = del; b.del_stride = del_stride;
-    if (n_samples <= CW_MAX / 2 && n_importance <= CW_MAX / 2) {
+    if (composite_backward_plan(n_samples, n_importance) == HL_COMPOSITE_WAVE_BWD) {
         hipLaunchKernelGGL(k_composite_wave<true>, dim3((unsigned)(tiles32(n_rays) * 8)), dim3(256), 0, (hipStream_t)stream, b);
         return hl::check_launch("k_composite_wave<bwd>");
     }

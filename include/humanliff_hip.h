@@ -216,6 +216,16 @@ int hl_render_weight_grads(const float *del, int64_t del_stride, const float *ac
 int hl_render_composite_noise(const float *near, const float *far, const float *z_vals, const float *z_new, const float *rec_coarse,
                               const float *rec_new, const float *noise, int64_t n_rays, int n_samples, int n_importance,
                               unsigned flags, float *rgb, float *acc, float *depth, void *stream);
+/* The kernel a compositing call launches (host arithmetic, no HIP call; the entries take their branch from the same functions):
+ * hl_render_composite_plan for hl_render_composite (with_noise = 0) and hl_render_composite_noise (with_noise = whether `noise` is
+ * given), hl_render_composite_backward_plan for hl_render_composite_backward.  HL_ERR_INVALID for sizes the entries refuse. */
+#define HL_COMPOSITE_SERIAL_RAW 1   /* k_composite, a thread per ray, the raw exp2 / log2 / rcp forms of the inference paths */
+#define HL_COMPOSITE_WAVE_FWD 2     /* k_composite_wave<false>, a wave per ray: noise given, n_rays <= 65536, both sample counts <= 256 */
+#define HL_COMPOSITE_SERIAL_EXACT 3 /* k_composite with noise: the exact expf / log1pf forms the backward differentiates */
+#define HL_COMPOSITE_WAVE_BWD 4     /* k_composite_wave<true>: both sample counts <= 256 */
+#define HL_COMPOSITE_SERIAL_BWD 5   /* k_composite_bwd, a thread per ray */
+int hl_render_composite_plan(int64_t n_rays, int n_samples, int n_importance, int with_noise);
+int hl_render_composite_backward_plan(int n_samples, int n_importance);
 size_t hl_render_mlp_bwd_packed_bytes(void);
 int hl_render_mlp_pack_bwd(const hl_render_mlp_params *h_params, void *packed_bwd, void *stream);
 void hl_render_train_rows(int *act_rows, int *del_rows);
