@@ -166,6 +166,7 @@ SIGNATURES = {
     "hl_mt19937_uniform": (_i, [_p, _i, _p, C.c_int64, _p, _p]),
     "hl_debug_set_h16_min_blocks": (_i, [C.c_long]),
     "hl_debug_set_single_op_scale_source": (_i, [_i]),
+    "hl_debug_set_attention_tiling": (_i, [_i, _i]),
     "hl_debug_set_mt19937_piece": (_i, [C.c_int64]),
     "hl_smooth_workspace_bytes": (_sz, [_i, _i, _i]),
     "hl_smooth_prepare": (_i, [_p, _i, _i, _i, _i, C.c_double, _p, _p, _p, _sz, _p]),

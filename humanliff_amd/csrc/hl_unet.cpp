@@ -1310,6 +1310,7 @@ int hl_conv2d_nhwc_mode(int conv_mode, const float *in, int N, int H, int W, int
 
 int hl_debug_set_h16_min_blocks(long v) { hl::set_h16_min_blocks(v); return HL_OK; }
 int hl_debug_set_single_op_scale_source(int from_totals) { g_single_op_scale_from_totals = from_totals != 0; return HL_OK; }
+int hl_debug_set_attention_tiling(int query_tiles, int placement) { return hl::debug_set_attention_tiling(query_tiles, placement); }
 
 size_t hl_groupnorm_scratch_bytes(int N) { return hl::gn_scratch_floats(N) * sizeof(float); }
 

@@ -252,7 +252,7 @@ int groupnorm_coef(const View &x, const float *gamma, const float *beta, const f
 // GroupNorm forward of the training path)
 int gn_apply(const View &x, const float *coefA, const float *coefB, int act, float *y, hipStream_t st);
 
-// out[b][o] = bias[o] + sum_k act(in[b][k]) * W[o][k] (+ addrow[idx[b]][o]);  B <= 8
+// out[b][o] = bias[o] + sum_k act(in[b][k]) * W[o][k] (+ addrow[idx[b]][o]);  B <= 16; act is applied once per workgroup (inputs staged in LDS), weights streamed 16 bytes per lane
 int linear_small(const float *in, long in_pitch, int B, int K, const float *W, const float *bias, int O, int silu_in,
                  const float *addrow, const int64_t *idx, float *out, long out_pitch, hipStream_t st);
 // sinusoidal timestep embedding (nn.py:103-121); t is int64 (B,)
@@ -262,6 +262,7 @@ int timestep_embedding(const int64_t *t, const float *t_float, int B, int dim, f
 // h2: fp16x2 products where a kernel has them (the default conv mode's attention).  out_totals: optional zeroed conv_stats_floats(N, T) floats - the key-split kernels add the
 // sum x^2 of the output they store (the projection convolution's activation scale); *totals_emitted says whether the kernel that ran did
 int attention(const float *qkv, int N, int T, int C, int heads, float *out, hipStream_t st, int h2 = 0, float *out_totals = nullptr, int *totals_emitted = nullptr);
+int debug_set_attention_tiling(int query_tiles, int placement);                                // hl_debug_set_attention_tiling (test switch; 0 = the dispatch rule)
 size_t attention_backward_scratch_bytes(int N, int T, int C, int heads);                       // hl_attention_bwd.hip
 int attention_backward(const float *qkv, const float *out, const float *dout, int N, int T, int C, int heads, float *dqkv, void *scratch,
                        size_t scratch_bytes, hipStream_t st);

@@ -21,6 +21,7 @@
 
 #include "hl_reduce.h"
 #include "hl_stats.h"
+#include "hl_xcd_map.h"
 
 namespace hl {
 namespace {
@@ -2200,38 +2201,77 @@ __global__ __launch_bounds__(256) void k_tensor_absmax(const float *__restrict__
 }
 
 // ---------------------------------------------------------------------------------------------
-// small-batch linear: one wave per output row
+// small-batch linear: one wave per R output rows.  The (activated) inputs are staged in LDS once per workgroup, in chunks of KC columns,
+// so silu runs once per (b, k) and workgroup instead of once per output row; a lane streams 16 bytes of each of its R weight rows per
+// step (R independent loads in flight) against one LDS read of the inputs.  Rows past O are clamped for the loads and not stored.
 // ---------------------------------------------------------------------------------------------
-template <int MAXB>
+template <int MAXB, int R>
 __global__ __launch_bounds__(256) void k_linear_small(const float *__restrict__ in, long in_pitch, int B, int K,
                                                       const float *__restrict__ W, const float *__restrict__ bias, int O,
                                                       int silu_in, const float *__restrict__ addrow,
                                                       const int64_t *__restrict__ idx, float *__restrict__ out, long out_pitch) {
-    const int lane = threadIdx.x & 63;
-    const int o = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (o >= O) return;
-    float acc[MAXB];
+    constexpr int KC = 8192 / MAXB;       // columns per chunk: 32 KB of LDS; a multiple of 256, so chunks keep the 16-byte alignment of a row
+    __shared__ __attribute__((aligned(16))) float sIn[MAXB * KC];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int o0 = (blockIdx.x * 4 + (tid >> 6)) * R;
+    const bool vec = (K & 3) == 0 && (reinterpret_cast<uintptr_t>(W) & 15) == 0;      // 16-byte weight loads need aligned rows
+    const float *wrow[R];
 #pragma unroll
-    for (int b = 0; b < MAXB; ++b) acc[b] = 0.f;
-    for (int k = lane; k < K; k += 64) {
-        const float w = W[(long)o * K + k];
+    for (int r = 0; r < R; ++r) wrow[r] = W + (long)min(o0 + r, O - 1) * K;
+    float acc[R][MAXB];
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+        for (int b = 0; b < MAXB; ++b) acc[r][b] = 0.f;
+    for (int kc = 0; kc < K; kc += KC) {
+        const int kn = min(KC, K - kc), kn4 = (kn + 3) & ~3;       // (columns kn .. kn4 - 1 are staged as zeros)
+        if (kc) __syncthreads();
 #pragma unroll
         for (int b = 0; b < MAXB; ++b)
-            if (b < B) {
-                float v = in[(long)b * in_pitch + k];
-                if (silu_in) v = silu_f(v);
-                acc[b] = fmaf(v, w, acc[b]);
+            if (b < B)
+                for (int k = tid; k < kn4; k += 256) {
+                    float v = 0.f;
+                    if (k < kn) {
+                        v = in[(long)b * in_pitch + kc + k];
+                        if (silu_in) v = silu_f(v);
+                    }
+                    sIn[b * KC + k] = v;
+                }
+        __syncthreads();
+        for (int k = 4 * lane; k < kn; k += 256) {
+            f32x4 w[R];
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                if (vec) w[r] = *reinterpret_cast<const f32x4 *>(wrow[r] + kc + k);
+                else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) w[r][j] = k + j < kn ? wrow[r][kc + k + j] : 0.f;
+                }
             }
+#pragma unroll
+            for (int b = 0; b < MAXB; ++b)
+                if (b < B) {
+                    const f32x4 x = *reinterpret_cast<const f32x4 *>(sIn + b * KC + k);
+#pragma unroll
+                    for (int r = 0; r < R; ++r)
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) acc[r][b] = fmaf(x[j], w[r][j], acc[r][b]);
+                }
+        }
     }
 #pragma unroll
-    for (int b = 0; b < MAXB; ++b) {
-        float v = acc[b];
+    for (int r = 0; r < R; ++r) {
+        const int o = o0 + r;
 #pragma unroll
-        for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-        if (lane == 0 && b < B) {
-            v += bias ? bias[o] : 0.f;
-            if (addrow) v += addrow[(long)idx[b] * O + o];
-            out[(long)b * out_pitch + o] = v;
+        for (int b = 0; b < MAXB; ++b) {
+            float v = acc[r][b];
+#pragma unroll
+            for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
+            if (lane == 0 && b < B && o < O) {
+                v += bias ? bias[o] : 0.f;
+                if (addrow) v += addrow[(long)idx[b] * O + o];
+                out[(long)b * out_pitch + o] = v;
+            }
         }
     }
 }
@@ -2259,16 +2299,18 @@ __global__ void k_timestep_embedding(const int64_t *__restrict__ t, const float 
 // S^T accumulator itself after softmax - same register-resident trick as the render MLP)
 // ---------------------------------------------------------------------------------------------
 template <int CH, int WPB>
-__global__ __launch_bounds__(WPB * 64, 1) void k_attention(const float *__restrict__ qkv, int T, int C, int heads, float *__restrict__ out) {
+__global__ __launch_bounds__(WPB * 64, 1) void k_attention(const float *__restrict__ qkv, int T, int C, int heads, float *__restrict__ out, int place) {
     constexpr int CT = CH / 32;   // channel tiles of the output
     constexpr int KS = CH / 2;    // k-steps of the QK^T product
     constexpr int LDK = CH + 1;   // odd row stride: rows differ per lane in the A reads
     __shared__ float sK[32 * LDK];
     __shared__ __attribute__((aligned(16))) float sV[32 * CH];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5;
-    const int nh = blockIdx.y;  // n*heads + head
+    // 1-D grid, query block fastest; place: the query blocks of one (image, head) share an XCD's L2 for its K / V (hl_xcd_map.h)
+    int nh, qb;                 // n*heads + head, query block
+    xcd_group_item(blockIdx.x, gridDim.x, ((T + 31) / 32 + WPB - 1) / WPB, place != 0, nh, qb);
     const int n = nh / heads, head = nh % heads;
-    const int q0 = (blockIdx.x * WPB + wave) * 32;
+    const int q0 = (qb * WPB + wave) * 32;
     const float scale = 1.f / sqrtf(sqrtf((float)CH));
     const long pitch = 3L * C;
     const float *base = qkv + (long)n * T * pitch + (long)head * 3 * CH;
@@ -2376,33 +2418,45 @@ __device__ __forceinline__ f32x16 att_mma(const u32x4 a, const u32x4 b, const f3
 // products, fp32 accumulation; the convolutions' scheme): a k-step of the scores = two of the 8-channel groups (the lane half's 2 x 4 channels of K against the same channels
 // of Q, split once per query tile); a k-step of O^T = 8 of the lane half's 16 keys - the probabilities are the score accumulators split in place, V comes from the wave's LDS
 // tile as before (one dword per key and lane).  36 (CH = 96) / 72 (CH = 192) MFMAs of 32 cycles per key tile instead of 96 / 192 of 64.
-template <int CH, int KW, bool PF, bool H2>
+// QT (H2 only): query tiles per workgroup.  A wave keeps Q, O and the running max / sum of QT consecutive query tiles and multiplies each of them with the SAME K and V
+// planes: the K split, the V scale / store and the V read-back and split - none of which depend on the queries - are done once per key tile instead of once per query
+// tile.  Per query tile the key order, the running V scale and the order of the products are those of QT = 1, so the output has the same bits.  A tile past the end of the
+// sequence (odd tile count) loads clamped rows and stores nothing.
+// 1-D grid, query-tile group fastest; place: the workgroups of one (image, head) share an XCD's L2 for its K / V (hl_xcd_map.h)
+template <int CH, int KW, bool PF, bool H2, int QT = 1>
 __global__ __launch_bounds__(KW * 64, 1) void k_attention_ks(const float *__restrict__ qkv, int T, int C, int heads,
-                                                             float *__restrict__ out, float *__restrict__ out_tot, int N) {
+                                                             float *__restrict__ out, float *__restrict__ out_tot, int N, int place) {
+    static_assert(QT == 1 || H2, "several query tiles per wave: fp16x2 products only");
     constexpr int CT = CH / 32, NG = CH / 8, WLDS = CH * 33 + 64;
+    constexpr bool KLATE = QT > 1;   // the second tile's registers leave no room for a second K tile: the next K is loaded into kc itself once the scores are done with it
     extern __shared__ __attribute__((aligned(16))) float sh[];   // [KW][WLDS]: V tile (32 x CH), later O^T (CH x 33) + m,l
     const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     float *sV = sh + wave * WLDS;
-    const int nh = blockIdx.y, n = nh / heads, head = nh % heads;
-    const int q0 = blockIdx.x * 32;
+    int nh, qg;                 // n*heads + head, group of QT query tiles
+    xcd_group_item(blockIdx.x, gridDim.x, ((T + 31) / 32 + QT - 1) / QT, place != 0, nh, qg);
+    const int n = nh / heads, head = nh % heads;
+    const int q0 = qg * QT * 32;
     const float scale = 1.f / sqrtf(sqrtf((float)CH));
     const long pitch = 3L * C;
     const float *base = qkv + (long)n * T * pitch + (long)head * 3 * CH;
 
     // contraction order: MFMA (m, i) multiplies channel 8m + 4*half + i
-    const int qj = min(q0 + (lane & 31), T - 1);
-    f32x4 qreg[NG];
+    f32x4 qreg[NG];                                          // (not H2: the B operand itself; H2: only the input of the split)
+    u32x4 qp[QT][H2 ? NG / 2 : 1][2];                        // (H2) Q as two fp16 planes per k-step: channels of groups 2j, 2j + 1
 #pragma unroll
-    for (int m = 0; m < NG; ++m) {
-        qreg[m] = *reinterpret_cast<const f32x4 *>(base + (long)qj * pitch + 8 * m + 4 * half);
+    for (int t = 0; t < QT; ++t) {
+        const int qj = min(q0 + 32 * t + (lane & 31), T - 1);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) qreg[m][i] *= scale;
-    }
-    u32x4 qp[H2 ? NG / 2 : 1][2];                        // (H2) Q as two fp16 planes per k-step: channels of groups 2j, 2j + 1
-    if constexpr (H2) {
+        for (int m = 0; m < NG; ++m) {
+            qreg[m] = *reinterpret_cast<const f32x4 *>(base + (long)qj * pitch + 8 * m + 4 * half);
 #pragma unroll
-        for (int j = 0; j < NG / 2; ++j) att_split8(qreg[2 * j], qreg[2 * j + 1], 1.f, qp[j][0], qp[j][1]);
+            for (int i = 0; i < 4; ++i) qreg[m][i] *= scale;
+        }
+        if constexpr (H2) {
+#pragma unroll
+            for (int j = 0; j < NG / 2; ++j) att_split8(qreg[2 * j], qreg[2 * j + 1], 1.f, qp[t][j][0], qp[t][j][1]);
+        }
     }
     auto loadK = [&](int k0, f32x4(&kr)[NG]) {
         const int kk = min(k0 + (lane & 31), T - 1);
@@ -2443,12 +2497,17 @@ __global__ __launch_bounds__(KW * 64, 1) void k_attention_ks(const float *__rest
         }
     };
 
-    f32x16 o[CT];
+    f32x16 o[QT][CT];
+    float mrun[QT], lrun[QT];
 #pragma unroll
-    for (int c = 0; c < CT; ++c)
+    for (int t = 0; t < QT; ++t) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) o[c][r] = 0.f;
-    float mrun = -3.0e38f, lrun = 0.f;
+        for (int c = 0; c < CT; ++c)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) o[t][c][r] = 0.f;
+        mrun[t] = -3.0e38f;
+        lrun[t] = 0.f;
+    }
 
     f32x4 kc[NG], vn[NG], kn[NG];   // kn unused (and eliminated) without PF
     int k0 = wave * 32;
@@ -2456,55 +2515,77 @@ __global__ __launch_bounds__(KW * 64, 1) void k_attention_ks(const float *__rest
     for (; k0 < T; k0 += KW * 32) {
         storeV(vn);
         const int k1 = k0 + KW * 32;
-        if constexpr (PF) { if (k1 < T) { loadK(k1, kn); loadV(k1, vn); } }
-        f32x16 st;
+        if constexpr (PF) {
+            if (k1 < T) {
+                if constexpr (!KLATE) loadK(k1, kn);
+                loadV(k1, vn);
+            }
+        }
+        f32x16 st[QT];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) st[r] = 0.f;
+        for (int t = 0; t < QT; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) st[t][r] = 0.f;
         if constexpr (H2) {
 #pragma unroll
             for (int j = 0; j < NG / 2; ++j) {
                 u32x4 k0p, k1p;
                 att_split8(kc[2 * j], kc[2 * j + 1], scale, k0p, k1p);
-                st = att_mma(k1p, qp[j][0], st);           // smallest partial product first
-                st = att_mma(k0p, qp[j][1], st);
-                st = att_mma(k0p, qp[j][0], st);
+#pragma unroll
+                for (int t = 0; t < QT; ++t) {
+                    st[t] = att_mma(k1p, qp[t][j][0], st[t]);           // smallest partial product first
+                    st[t] = att_mma(k0p, qp[t][j][1], st[t]);
+                    st[t] = att_mma(k0p, qp[t][j][0], st[t]);
+                }
             }
+            if constexpr (PF && KLATE) { if (k1 < T) loadK(k1, kc); }
         } else {
 #pragma unroll
             for (int m = 0; m < NG; ++m)
 #pragma unroll
-                for (int i = 0; i < 4; ++i) st = __builtin_amdgcn_mfma_f32_32x32x2f32(kc[m][i] * scale, qreg[m][i], st, 0, 0, 0);
+                for (int i = 0; i < 4; ++i) st[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(kc[m][i] * scale, qreg[m][i], st[0], 0, 0, 0);
         }
-        // st[r] = score(key = (r&3)+8*(r>>2)+4*half, query = lane&31); mask keys beyond T
-        float mx = -3.0e38f;
+        // st[t][r] = score(key = (r&3)+8*(r>>2)+4*half, query = lane&31 of tile t); mask keys beyond T
+        float alpha[QT];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int key = k0 + (r & 3) + 8 * (r >> 2) + 4 * half;
-            if (key >= T) st[r] = -3.0e38f;
-            mx = fmaxf(mx, st[r]);
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        const float mnew = fmaxf(mrun, mx);
-        const float alpha = __expf(mrun - mnew);
-        float psum = 0.f;
+        for (int t = 0; t < QT; ++t) {
+            float mx = -3.0e38f;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            st[r] = __expf(st[r] - mnew);
-            psum += st[r];
+            for (int r = 0; r < 16; ++r) {
+                const int key = k0 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                if (key >= T) st[t][r] = -3.0e38f;
+                mx = fmaxf(mx, st[t][r]);
+            }
+            mx = fmaxf(mx, __shfl_xor(mx, 32));
+            const float mnew = fmaxf(mrun[t], mx);
+            alpha[t] = __expf(mrun[t] - mnew);
+            float psum = 0.f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                st[t][r] = __expf(st[t][r] - mnew);
+                psum += st[t][r];
+            }
+            psum += __shfl_xor(psum, 32);
+            lrun[t] = lrun[t] * alpha[t] + psum;
+            mrun[t] = mnew;
         }
-        psum += __shfl_xor(psum, 32);
-        lrun = lrun * alpha + psum;
-        mrun = mnew;
         if constexpr (H2) {
-            u32x4 pp[2][2];                                  // the probabilities of this lane half's keys st[8 jj .. 8 jj + 7] as two planes
+            u32x4 pp[QT][2][2];                              // the probabilities of this lane half's keys st[8 jj .. 8 jj + 7] as two planes
 #pragma unroll
-            for (int jj = 0; jj < 2; ++jj)
-                att_split8(f32x4{st[8 * jj], st[8 * jj + 1], st[8 * jj + 2], st[8 * jj + 3]}, f32x4{st[8 * jj + 4], st[8 * jj + 5], st[8 * jj + 6], st[8 * jj + 7]}, 1.f, pp[jj][0], pp[jj][1]);
-            const float alpha_o = alpha * vs_ratio;         // (O carries the V scale: both factors at once)
+            for (int t = 0; t < QT; ++t)
+#pragma unroll
+                for (int jj = 0; jj < 2; ++jj)
+                    att_split8(f32x4{st[t][8 * jj], st[t][8 * jj + 1], st[t][8 * jj + 2], st[t][8 * jj + 3]},
+                               f32x4{st[t][8 * jj + 4], st[t][8 * jj + 5], st[t][8 * jj + 6], st[t][8 * jj + 7]}, 1.f, pp[t][jj][0], pp[t][jj][1]);
 #pragma unroll
             for (int c = 0; c < CT; ++c) {
+                if constexpr (QT > 1) __builtin_amdgcn_sched_barrier(0);      // (keeps the V reads of later channel tiles from being hoisted: registers)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) o[c][r] *= alpha_o;
+                for (int t = 0; t < QT; ++t) {
+                    const float alpha_o = alpha[t] * vs_ratio;      // (O carries the V scale: both factors at once)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) o[t][c][r] *= alpha_o;
+                }
 #pragma unroll
                 for (int jj = 0; jj < 2; ++jj) {
                     f32x4 va, vb;                            // V of this lane's channel at the same eight keys, in the same order
@@ -2515,75 +2596,85 @@ __global__ __launch_bounds__(KW * 64, 1) void k_attention_ks(const float *__rest
                     }
                     u32x4 v0p, v1p;
                     att_split8(va, vb, 1.f, v0p, v1p);
-                    o[c] = att_mma(v1p, pp[jj][0], o[c]);
-                    o[c] = att_mma(v0p, pp[jj][1], o[c]);
-                    o[c] = att_mma(v0p, pp[jj][0], o[c]);
+#pragma unroll
+                    for (int t = 0; t < QT; ++t) {
+                        o[t][c] = att_mma(v1p, pp[t][jj][0], o[t][c]);
+                        o[t][c] = att_mma(v0p, pp[t][jj][1], o[t][c]);
+                        o[t][c] = att_mma(v0p, pp[t][jj][0], o[t][c]);
+                    }
                 }
             }
         } else {
 #pragma unroll
         for (int c = 0; c < CT; ++c) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) o[c][r] *= alpha;
+            for (int r = 0; r < 16; ++r) o[0][c][r] *= alpha[0];
 #pragma unroll
             for (int s = 0; s < 16; ++s) {
                 const int key = (s & 3) + 8 * (s >> 2) + 4 * half;  // the key this lane's st[s] belongs to
-                o[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(sV[key * CH + c * 32 + (lane & 31)], st[s], o[c], 0, 0, 0);
+                o[0][c] = __builtin_amdgcn_mfma_f32_32x32x2f32(sV[key * CH + c * 32 + (lane & 31)], st[0][s], o[0][c], 0, 0, 0);
             }
         }
         }
         if constexpr (PF) {
+            if constexpr (!KLATE) {
 #pragma unroll
-            for (int m = 0; m < NG; ++m) kc[m] = kn[m];
+                for (int m = 0; m < NG; ++m) kc[m] = kn[m];
+            }
         } else if (k1 < T) {
             loadK(k1, kc);
             loadV(k1, vn);
         }
     }
 
-    // merge the KW partials: O^T of every wave to its LDS region as [channel][33] (+ running max / sum per query)
-    __syncthreads();
+    // merge the KW partials, one query tile at a time: O^T of every wave to its LDS region as [channel][33] (+ running max / sum per query)
     const float vinv = (H2 && vs < 3.0e38f) ? 1.f / vs : 1.f;
 #pragma unroll
-    for (int c = 0; c < CT; ++c)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) sV[(c * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * 33 + (lane & 31)] = o[c][r] * vinv;
-    if (half == 0) {
-        sV[CH * 33 + lane] = mrun;
-        sV[CH * 33 + 32 + lane] = lrun;
-    }
-    __syncthreads();
-    float osq = 0.f;
-    for (int e = tid; e < 32 * CH; e += KW * 64) {
-        const int q = e / CH, c = e - q * CH;
-        float ms = -3.0e38f;
-#pragma unroll
-        for (int w = 0; w < KW; ++w) ms = fmaxf(ms, sh[w * WLDS + CH * 33 + q]);
-        float num = 0.f, den = 0.f;
-#pragma unroll
-        for (int w = 0; w < KW; ++w) {
-            const float f = __expf(sh[w * WLDS + CH * 33 + q] - ms);
-            num += sh[w * WLDS + c * 33 + q] * f;
-            den += sh[w * WLDS + CH * 33 + 32 + q] * f;
-        }
-        if (q0 + q < T) {
-            const float val = num / den;
-            out[((long)n * T + q0 + q) * C + head * CH + c] = val;
-            osq += val * val;
-        }
-    }
-    // sum x^2 of what this workgroup stored, into the fixed-point totals of the output (any "group": act_scale_totals adds all 32) - the projection convolution behind
-    // the attention reads its raw input's power-of-two scale from them (hl_stats.h), as every other raw-input convolution does from its producers' totals
-    if (out_tot) {
-        osq = wave_sum_f32(osq);
+    for (int t = 0; t < QT; ++t) {
+        const int qt0 = q0 + 32 * t;
+        if (qt0 >= T) break;                                 // (the missing tile of an odd tile count: the same for the whole workgroup)
         __syncthreads();
-        if (lane == 0) sh[wave] = osq;
-        __syncthreads();
-        if (tid == 0) {
-            float t = 0.f;
 #pragma unroll
-            for (int w = 0; w < KW; ++w) t += sh[w];
-            stat_add(out_tot, N, n, (int)(blockIdx.x & 31), (long)T, 0.f, t);
+        for (int c = 0; c < CT; ++c)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) sV[(c * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * 33 + (lane & 31)] = o[t][c][r] * vinv;
+        if (half == 0) {
+            sV[CH * 33 + lane] = mrun[t];
+            sV[CH * 33 + 32 + lane] = lrun[t];
+        }
+        __syncthreads();
+        float osq = 0.f;
+        for (int e = tid; e < 32 * CH; e += KW * 64) {
+            const int q = e / CH, c = e - q * CH;
+            float ms = -3.0e38f;
+#pragma unroll
+            for (int w = 0; w < KW; ++w) ms = fmaxf(ms, sh[w * WLDS + CH * 33 + q]);
+            float num = 0.f, den = 0.f;
+#pragma unroll
+            for (int w = 0; w < KW; ++w) {
+                const float f = __expf(sh[w * WLDS + CH * 33 + q] - ms);
+                num += sh[w * WLDS + c * 33 + q] * f;
+                den += sh[w * WLDS + CH * 33 + 32 + q] * f;
+            }
+            if (qt0 + q < T) {
+                const float val = num / den;
+                out[((long)n * T + qt0 + q) * C + head * CH + c] = val;
+                osq += val * val;
+            }
+        }
+        // sum x^2 of what this workgroup stored for the tile, into the fixed-point totals of the output (any "group": act_scale_totals adds all 32) - the projection
+        // convolution behind the attention reads its raw input's power-of-two scale from them (hl_stats.h), as every other raw-input convolution does from its producers' totals
+        if (out_tot) {
+            osq = wave_sum_f32(osq);
+            __syncthreads();
+            if (lane == 0) sh[wave] = osq;
+            __syncthreads();
+            if (tid == 0) {
+                float tot = 0.f;
+#pragma unroll
+                for (int w = 0; w < KW; ++w) tot += sh[w];
+                stat_add(out_tot, N, n, (int)((qg * QT + t) & 31), (long)T, 0.f, tot);
+            }
         }
     }
 }
@@ -3342,13 +3433,18 @@ int linear_small(const float *in, long in_pitch, int B, int K, const float *W, c
                  const float *addrow, const int64_t *idx, float *out, long out_pitch, hipStream_t st) {
     HL_REQUIRE(in && W && out && B >= 1, "linear_small: bad argument");
     HL_REQUIRE(B <= 16, "linear_small: batch %d > 16 (split the batch)", B);
-    dim3 grid((O + 3) / 4);
-    if (B <= 4)
-        hipLaunchKernelGGL(k_linear_small<4>, grid, dim3(256), 0, st, in, in_pitch, B, K, W, bias, O, silu_in, addrow, idx, out, out_pitch);
-    else if (B <= 8)
-        hipLaunchKernelGGL(k_linear_small<8>, grid, dim3(256), 0, st, in, in_pitch, B, K, W, bias, O, silu_in, addrow, idx, out, out_pitch);
-    else
-        hipLaunchKernelGGL(k_linear_small<16>, grid, dim3(256), 0, st, in, in_pitch, B, K, W, bias, O, silu_in, addrow, idx, out, out_pitch);
+    // four rows per wave where that still leaves a workgroup per CU (the one product of all emb_layers); the small time_embed products keep one row per wave
+#define HL_LIN(MAXB_)                                                                                                                                  \
+    do {                                                                                                                                               \
+        if (O >= 4096)                                                                                                                                 \
+            hipLaunchKernelGGL((k_linear_small<MAXB_, 4>), dim3((O + 15) / 16), dim3(256), 0, st, in, in_pitch, B, K, W, bias, O, silu_in, addrow, idx, out, out_pitch); \
+        else                                                                                                                                           \
+            hipLaunchKernelGGL((k_linear_small<MAXB_, 1>), dim3((O + 3) / 4), dim3(256), 0, st, in, in_pitch, B, K, W, bias, O, silu_in, addrow, idx, out, out_pitch);   \
+    } while (0)
+    if (B <= 4) HL_LIN(4);
+    else if (B <= 8) HL_LIN(8);
+    else HL_LIN(16);
+#undef HL_LIN
     return check_launch("k_linear_small");
 }
 
@@ -3358,8 +3454,20 @@ int timestep_embedding(const int64_t *t, const float *tf, int B, int dim, float 
     return check_launch("k_timestep_embedding");
 }
 
+// hl_debug_set_attention_tiling (test switch): query tiles per workgroup of the head-size-96 fp16x2 kernel (1, 2), XCD placement (1 off, 2 on); 0 = the dispatch rule
+static int g_att_query_tiles = 0, g_att_placement = 0;
+int debug_set_attention_tiling(int query_tiles, int placement) {
+    HL_REQUIRE(query_tiles >= 0 && query_tiles <= 2 && placement >= 0 && placement <= 2, "debug_set_attention_tiling: bad argument");
+    g_att_query_tiles = query_tiles;
+    g_att_placement = placement;
+    return HL_OK;
+}
+// a contiguous run of (image, head) groups per XCD from one workgroup per CU on; below that the launch is latency-bound and was measured faster in launch order
+static int att_place(long blocks) { return g_att_placement ? g_att_placement == 2 : blocks >= 256; }
+
 int attention(const float *qkv, int N, int T, int C, int heads, float *out, hipStream_t st, int h2, float *out_totals, int *totals_emitted) {
     HL_REQUIRE(qkv && out && heads > 0 && C % heads == 0, "attention: bad argument");
+    HL_REQUIRE((long)((T + 31) / 32) * N * heads < (1L << 31), "attention: too many query tiles");
     if (totals_emitted) *totals_emitted = 0;
     const int ch = C / heads;
     // 32 queries per wave; pick waves per workgroup so the grid has at least ~256 workgroups (K/V tiles are
@@ -3367,28 +3475,35 @@ int attention(const float *qkv, int N, int T, int C, int heads, float *out, hipS
     const int qtiles = (T + 31) / 32;
     int wpb = 4;
     while (wpb > 1 && (long)((qtiles + wpb - 1) / wpb) * N * heads < 256) wpb >>= 1;
-    dim3 grid((qtiles + wpb - 1) / wpb, N * heads);
-#define HL_ATT(CH_)                                                                                         \
+    dim3 grid((unsigned)((long)((qtiles + wpb - 1) / wpb) * N * heads));      // 1-D: the kernels place (image, head) runs on XCDs themselves
+    int place = att_place(grid.x);
+#define HL_ATT(CH_)                                                                                       \
     do {                                                                                                    \
-        if (wpb == 4) hipLaunchKernelGGL((k_attention<CH_, 4>), grid, dim3(256), 0, st, qkv, T, C, heads, out);      \
-        else if (wpb == 2) hipLaunchKernelGGL((k_attention<CH_, 2>), grid, dim3(128), 0, st, qkv, T, C, heads, out); \
-        else hipLaunchKernelGGL((k_attention<CH_, 1>), grid, dim3(64), 0, st, qkv, T, C, heads, out);                \
+        if (wpb == 4) hipLaunchKernelGGL((k_attention<CH_, 4>), grid, dim3(256), 0, st, qkv, T, C, heads, out, place);      \
+        else if (wpb == 2) hipLaunchKernelGGL((k_attention<CH_, 2>), grid, dim3(128), 0, st, qkv, T, C, heads, out, place); \
+        else hipLaunchKernelGGL((k_attention<CH_, 1>), grid, dim3(64), 0, st, qkv, T, C, heads, out, place);                \
     } while (0)
     // short sequences: split the keys over the 4 waves of a workgroup instead (one query tile per workgroup)
     // (with fp16x2 products the key-split kernel also takes the 1 024-token level of batches 8 ... 16: B = 8 49.4 -> 49.0 ms per forward)
     constexpr long ks_max = 1024, ks_max_h2 = 4097;
     if ((long)qtiles * N * heads < (h2 ? ks_max_h2 : ks_max) && (ch == 96 || ch == 192) && (3L * C) % 4 == 0) {
-        dim3 gks(qtiles, N * heads);
-        if (ch == 96 && h2)
-            hipLaunchKernelGGL((k_attention_ks<96, 4, true, true>), gks, dim3(256), (size_t)4 * (96 * 33 + 64) * sizeof(float), st, qkv, T, C, heads, out, out_totals, N);
+        dim3 gks((unsigned)((long)qtiles * N * heads));
+        // two query tiles per workgroup (the K / V preparation once for both) where that still leaves a workgroup per CU
+        const long pairs = (long)((qtiles + 1) / 2) * N * heads;
+        const bool qt2 = g_att_query_tiles ? g_att_query_tiles == 2 : pairs >= 256;
+        place = att_place(ch == 96 && h2 && qt2 ? pairs : (long)gks.x);
+        if (ch == 96 && h2 && qt2)
+            hipLaunchKernelGGL((k_attention_ks<96, 4, true, true, 2>), dim3((unsigned)pairs), dim3(256), (size_t)4 * (96 * 33 + 64) * sizeof(float), st, qkv, T, C, heads, out, out_totals, N, place);
+        else if (ch == 96 && h2)
+            hipLaunchKernelGGL((k_attention_ks<96, 4, true, true>), gks, dim3(256), (size_t)4 * (96 * 33 + 64) * sizeof(float), st, qkv, T, C, heads, out, out_totals, N, place);
         else if (ch == 96)
             hipLaunchKernelGGL((k_attention_ks<96, 4, true, false>), gks, dim3(256), (size_t)4 * (96 * 33 + 64) * sizeof(float), st, qkv, T, C,
-                               heads, out, out_totals, N);
+                               heads, out, out_totals, N, place);
         else if (h2)
-            hipLaunchKernelGGL((k_attention_ks<192, 4, false, true>), gks, dim3(256), (size_t)4 * (192 * 33 + 64) * sizeof(float), st, qkv, T, C, heads, out, out_totals, N);
+            hipLaunchKernelGGL((k_attention_ks<192, 4, false, true>), gks, dim3(256), (size_t)4 * (192 * 33 + 64) * sizeof(float), st, qkv, T, C, heads, out, out_totals, N, place);
         else
             hipLaunchKernelGGL((k_attention_ks<192, 4, false, false>), gks, dim3(256), (size_t)4 * (192 * 33 + 64) * sizeof(float), st, qkv, T,
-                               C, heads, out, out_totals, N);
+                               C, heads, out, out_totals, N, place);
         if (totals_emitted && out_totals) *totals_emitted = 1;
         return check_launch("k_attention_ks");
     }

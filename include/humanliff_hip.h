@@ -690,6 +690,10 @@ int hl_debug_set_h16_min_blocks(long v);
    0 (default): an exact abs-max pass over the input (tensor_absmax); 1: the fixed-point group totals (sum x^2) - what the producers' epilogues leave inside
    hl_unet_forward - formed here by one pass (tensor_totals), so that the network's scale source can be tested on single layers. */
 int hl_debug_set_single_op_scale_source(int from_totals);
+/* test switch of the attention's work distribution: query tiles per workgroup of the key-split fp16x2 kernel at head size 96 (1 or 2), and the placement of the
+   workgroups of one (image, head) on one XCD (1 off, 2 on); 0 (default) leaves either to the dispatch rule of hl::attention.  Every choice gives the same bits;
+   the tests run the small shapes on each. */
+int hl_debug_set_attention_tiling(int query_tiles, int placement);
 
 /* sample_pdf's uniforms on the device, bit for bit (replaces `u = torch.rand(...)` on the CPU generator + upload, NeRF/renderer.py:545):
  * continues the mt19937 stream of ATen's CPU generator from `state` (624 words, device) at position `pos` (words of the current block
