@@ -12,6 +12,7 @@
 #include <utility>
 #include <vector>
 
+#include "hl_stat_book.h"
 #include "hl_unet_kernels.h"
 #include <algorithm>
 
@@ -386,28 +387,38 @@ void build(Net &n) {
 }
 
 // ---- forward ------------------------------------------------------------------------------------
+// the affine of a GroupNorm in front of a convolution: arrays (cA, cB) or - no launch - the producers' group statistics (gn.gs0 set)
+struct Aff { float *cA = nullptr, *cB = nullptr; hl::GnSrc gn{}; };
+// everything about one convolution call beyond layer, input and output; the defaults are a bare stride-1 convolution that leaves statistics
+struct ConvOpt {
+    int stride = 1, ups = 0;
+    Aff af{};                                            // GroupNorm in front
+    int act = 0;                                         // SiLU behind the GroupNorm
+    const float *res = nullptr; long res_pitch = 0;      // out = conv + res
+    float *out2 = nullptr; long out2_pitch = 0;          // second store out2 = conv + res2 (the control tower's zero-convolution)
+    const float *res2 = nullptr; long res2_pitch = 0;
+    int nchw = 0;                                        // the network's output layout
+    bool stats = true;                                   // add the output's GroupNorm statistics (false: nobody normalises this store)
+    void residual(const View &v) { res = v.p; res_pitch = v.pitch; }
+};
+// a stream and the scratch its launches use.  act_ws: materialised GroupNorm(+SiLU) inputs (k_conv_dma path)
+struct Lane { hipStream_t st; float *gn_scratch, *splitk_ws, *act_ws; };
+
 struct Exec {
     Net &n;
     bool run;          // false: only size the workspace
     char *ws;
-    size_t off = 0;
-    hipStream_t st;
     int B, H, W;
+    size_t off = 0;
     float *emb_all = nullptr;
     const float *ctx = nullptr;    // cond_type='cross_attention': the context token (B, E)
-    float *gn_scratch = nullptr;
-    float *splitk_ws = nullptr;
-    float *gn_scratch2 = nullptr, *splitk_ws2 = nullptr;   // second set for the side stream
-    float *act_ws = nullptr, *act_ws2 = nullptr;           // materialised GroupNorm(+SiLU) inputs (k_conv_dma path)
-    size_t act_need = 0;                                   // floats, largest normalised conv input seen
+    Lane lanes[2]{};               // the caller's stream, and the side stream of the control tower
+    Lane *lane = &lanes[0];        // the one the walk enqueues on
+    size_t act_need = 0;           // floats, largest normalised conv input seen
     int rc = 0;
-    // GroupNorm statistics travel from the kernel that stores a tensor to the layer that normalises it (ConvArgs::stats): keyed by
-    // the address of channel 0 of the stored region, so a decoder "concat" finds its two producers at x.p and x.p + C0
-    // (buf = the group totals of the normalised view, viewC its channels, c0 / covered = the channel range this tensor fills of it)
-    struct StatReg { float *buf; int viewC, c0, covered; };
-    // the two halves of a decoder "concat" buffer are normalised as ONE view: their producers add into one statistics block (run pass only)
-    struct PartInfo { float *buf; int viewC, c0; };
-    std::unordered_map<const float *, PartInfo> part_reg;
+    // GroupNorm statistics travel from the kernel that stores a tensor to the layer that normalises it (ConvArgs::stats); the book says
+    // whose totals a consumer may read (hl_stat_book.h, run pass only)
+    hl::StatBook book;
     // the fixed-point totals live in one arena behind the activation scratch, zeroed by ONE memset at the start of the forward
     char *stat_base = nullptr;
     size_t stat_off = 0, stat_bytes = 0;
@@ -416,8 +427,14 @@ struct Exec {
         stat_off += (floats * sizeof(float) + 255) / 256 * 256;
         return p;
     }
-    std::unordered_map<const float *, StatReg> stat_reg;
-    bool want_stats = true;
+    // the block an output adds its statistics into: the shared one of a concat half (run pass), else a new one (every output of the sizing pass)
+    hl::StatBook::Block stat_block(const float *out, int Cout, long HW) {
+        return book.block_for(out, Cout, book.in_concat(out) ? nullptr : alloc_stat(hl::conv_stats_floats(B, HW)));
+    }
+    Exec(Net &n_, bool run_, char *ws_, hipStream_t st, int B_, int H_, int W_) : n(n_), run(run_), ws(ws_), B(B_), H(H_), W(W_) {
+        lanes[0].st = st;
+        lanes[1].st = n.side;
+    }
 
     float *alloc(size_t floats) {
         float *p = run ? reinterpret_cast<float *>(ws + off) : nullptr;
@@ -434,106 +451,82 @@ struct Exec {
     size_t span_begin() {
         if (!n.prof) return 0;
         const size_t a = n.next_event();
-        if (n.ev_pool[a]) hipEventRecord(n.ev_pool[a], st);
+        if (n.ev_pool[a]) hipEventRecord(n.ev_pool[a], lane->st);
         return a;
     }
     void span_end(int cat, size_t a, double flops, double exec = -1.0) {
         if (!n.prof) return;
         if (!n.err.empty() && !rc) rc = hl::fail(HL_ERR_RUNTIME, "hl_unet_forward: %s", n.err.c_str());
         const size_t b = n.next_event();
-        if (n.ev_pool[b]) hipEventRecord(n.ev_pool[b], st);
+        if (n.ev_pool[b]) hipEventRecord(n.ev_pool[b], lane->st);
         n.spans.push_back({cat, a, b, flops, exec < 0 ? flops : exec, {span_key[0], span_key[1], span_key[2], span_key[3], span_key[4]}, span_mid});
         span_key[0] = -1; span_mid = -1;
     }
     int span_key[5] = {-1, 0, 0, 0, 0};
     long span_mid = -1;
 
-    // the affine of a GroupNorm in front of a convolution: arrays (cA, cB) or - no launch - the producers' group statistics (gn.gs0 set)
-    struct Aff { float *cA = nullptr, *cB = nullptr; hl::GnSrc gn{}; bool on = false; };
-    const Aff none{};
-    void conv(const Conv &c, const View &in, const View &out, int stride, int ups, const Aff &af, int act,
-              const float *res, long res_pitch, float *out2 = nullptr, long out2_pitch = 0, const float *res2 = nullptr,
-              long res2_pitch = 0, int nchw = 0) {
-        const float *cA = af.cA, *cB = af.cB;
+    void conv(const Conv &c, const View &in, const View &out, const ConvOpt &o = {}) {
         if (!run) {   // sizing pass (pointers are null here): the largest conv input is also the largest normalised one
             const size_t need = (size_t)in.pixels() * c.Cin_pad;
             if (need > act_need) act_need = need;
         }
-        // room for the output statistics (same allocations in the sizing pass)
-        const bool st_ok = want_stats && !nchw;
-        // (sizing pass: every output gets its own block - an upper bound; run pass: the halves of a concat share the block made with the buffer)
-        PartInfo pi1{nullptr, c.Cout, 0}, pi2{nullptr, c.Cout, 0};
-        if (st_ok) {
-            auto f1 = run ? part_reg.find(out.p) : part_reg.end();
-            if (f1 != part_reg.end()) pi1 = f1->second; else pi1.buf = alloc_stat(hl::conv_stats_floats(B, (long)out.H * out.W));
-            if (out2_pitch != 0) {
-                auto f2 = run ? part_reg.find(out2) : part_reg.end();
-                if (f2 != part_reg.end()) pi2 = f2->second; else pi2.buf = alloc_stat(hl::conv_stats_floats(B, (long)out.H * out.W));
-            }
+        // where the output statistics go (same allocations in the sizing pass)
+        hl::StatBook::Block s1{nullptr, c.Cout, 0}, s2{nullptr, c.Cout, 0};
+        if (o.stats && !o.nchw) {
+            s1 = stat_block(out.p, c.Cout, (long)out.H * out.W);
+            if (o.out2_pitch != 0) s2 = stat_block(o.out2, c.Cout, (long)out.H * out.W);
         }
-        float *st1 = pi1.buf, *st2 = pi2.buf;
         if (!run) return;
         ConvArgs a{};
         a.in = in; a.in.C = c.Cin_pad;
         a.w = c.w.only(conv_forms(n.conv_mode, false, false)); a.mode = n.conv_mode;
-        a.bias = c.bias; a.Cout = c.Cout; a.ks = c.ks; a.stride = stride; a.ups = ups;
-        a.coefA = cA; a.coefB = cB; a.act = act; a.gn = af.gn;
-        a.out = out; a.res = res; a.res_pitch = res_pitch;
-        a.out2 = out2; a.out2_pitch = out2_pitch; a.res2 = res2; a.res2_pitch = res2_pitch; a.out_nchw = nchw;
-        a.splitk_ws = splitk_ws; a.splitk_ws_bytes = hl::conv_splitk_ws_bytes();
-        a.act_ws = act_ws; a.act_ws_bytes = act_need * sizeof(float);
-        a.stats = st1; a.stats2 = st2;
-        if (af.cA == nullptr && af.gn.gt == nullptr) a.in_stats = totals_of(in, false);     // (a raw input: the fp16x2 kernels scale it by a power of two from its sum x^2)
-        a.st_cg = pi1.viewC / 32; a.st_c0 = pi1.c0; a.st2_cg = pi2.viewC / 32; a.st2_c0 = pi2.c0;
+        a.bias = c.bias; a.Cout = c.Cout; a.ks = c.ks; a.stride = o.stride; a.ups = o.ups;
+        a.coefA = o.af.cA; a.coefB = o.af.cB; a.act = o.act; a.gn = o.af.gn;
+        a.out = out; a.res = o.res; a.res_pitch = o.res_pitch;
+        a.out2 = o.out2; a.out2_pitch = o.out2_pitch; a.res2 = o.res2; a.res2_pitch = o.res2_pitch; a.out_nchw = o.nchw;
+        a.splitk_ws = lane->splitk_ws; a.splitk_ws_bytes = hl::conv_splitk_ws_bytes();
+        a.act_ws = lane->act_ws; a.act_ws_bytes = act_need * sizeof(float);
+        a.stats = s1.buf; a.stats2 = s2.buf;
+        if (raw_input(o)) a.in_stats = book.totals_of(in.p, in.C, false);     // (the fp16x2 kernels scale a raw input by a power of two from its sum x^2)
+        a.st_cg = s1.viewC / 32; a.st_c0 = s1.c0; a.st2_cg = s2.viewC / 32; a.st2_c0 = s2.c0;
         const size_t e0 = span_begin();
         size_t emid = 0;
         if (n.prof) { emid = n.next_event(); a.ev_mid = n.ev_pool[emid]; }
         const hl::ConvPlan pl = hl::plan_conv(a);
-        ok(hl::conv2d(a, pl, st));
-        {   // developer audit (HL_AUDIT_SCALE=1, read once): fp16x2 launches whose raw input came without totals - their activation planes are unscaled (sx = 1)
-            static const int audit_ = [] { const char *e_ = getenv("HL_AUDIT_SCALE"); return e_ ? atoi(e_) : 0; }();
-            if (audit_ && pl.path == hl::ConvPath::Fp16x2 && af.cA == nullptr && af.gn.gt == nullptr && a.in_stats == nullptr)
-                fprintf(stderr, "[hl audit] fp16x2 convolution with an unscaled raw input: %dx%d px, %d -> %d channels, ks %d, stride %d\n", in.H, in.W, in.C, c.Cout, c.ks, stride);
-        }
-        if (n.prof && a.ev_mid && pl.pre != hl::ConvPrePass::None) span_mid = (long)emid;
-        {
-            int lvl = 0;
-            while (lvl < 7 && (out.H << lvl) < H) ++lvl;
-            n.census[hl::conv_census_row(pl.path)][lvl] += 1;
-            // (keyed like a rocprofv3 per-kernel, per-grid row: kernel family, level, Cout, kernel size - the input channel counts of a level share a row)
-            span_key[0] = (int)pl.path; span_key[1] = lvl; span_key[2] = ups ? 1 : 0; span_key[3] = c.Cout; span_key[4] = c.ks;
-        }
-        const double fl = 2.0 * (double)out.pixels() * c.Cout * c.Cin * c.ks * c.ks;
-        span_end(CAT_CONV, e0, fl, fl * hl::conv_issued_factor(pl.path) * (pl.kernel == hl::ConvKernel::H2sUp ? 4.0 / 9.0 : 1.0));   // (four of the nine taps)
+        ok(hl::conv2d(a, pl, lane->st));
+        note_conv(c, in, out, o, a, pl, e0, emid);
         // whoever stored the tensor last owns its statistics
         if (pl.stat_slots > 0) {
-            stat_reg[out.p] = {st1, pi1.viewC, pi1.c0, c.Cout};
-            if (out2) stat_reg[out2] = {st2, pi2.viewC, pi2.c0, c.Cout};
+            book.produced(out.p, s1, c.Cout);
+            if (o.out2) book.produced(o.out2, s2, c.Cout);
         } else {
-            stat_reg.erase(out.p);
-            if (out2) stat_reg.erase(out2);
+            book.stored_without_totals(out.p);
+            if (o.out2) book.stored_without_totals(o.out2);
         }
     }
-    // the group totals the producer(s) of x left if they cover exactly x's channels (both halves of a decoder "concat" when x is one), whatever view
-    // they were grouped for or - need_view_match - only those formed for exactly this view: complete when a consumer of x runs, since it is ordered
-    // behind every producer of x
-    const float *totals_of(const View &x, bool need_view_match) const {
-        auto it = stat_reg.find(x.p);
-        if (it == stat_reg.end() || it->second.c0 != 0 || (need_view_match && it->second.viewC != x.C)) return nullptr;
-        if (it->second.covered == x.C) return it->second.buf;
-        auto it2 = stat_reg.find(x.p + it->second.covered);
-        if (it2 != stat_reg.end() && it2->second.buf == it->second.buf && it2->second.c0 == it->second.covered &&
-            it->second.covered + it2->second.covered == x.C) return it->second.buf;
-        return nullptr;
+    static bool raw_input(const ConvOpt &o) { return o.af.cA == nullptr && o.af.gn.gt == nullptr; }
+    // what a launched convolution leaves outside the network: the developer audit line, the dispatch census, the profiling span
+    void note_conv(const Conv &c, const View &in, const View &out, const ConvOpt &o, const ConvArgs &a, const hl::ConvPlan &pl, size_t e0, size_t emid) {
+        // developer audit (HL_AUDIT_SCALE=1, read once): fp16x2 launches whose raw input came without totals - their activation planes are unscaled (sx = 1)
+        static const int audit_ = [] { const char *e_ = getenv("HL_AUDIT_SCALE"); return e_ ? atoi(e_) : 0; }();
+        if (audit_ && pl.path == hl::ConvPath::Fp16x2 && raw_input(o) && a.in_stats == nullptr)
+            fprintf(stderr, "[hl audit] fp16x2 convolution with an unscaled raw input: %dx%d px, %d -> %d channels, ks %d, stride %d\n", in.H, in.W, in.C, c.Cout, c.ks, o.stride);
+        if (n.prof && a.ev_mid && pl.pre != hl::ConvPrePass::None) span_mid = (long)emid;
+        int lvl = 0;
+        while (lvl < 7 && (out.H << lvl) < H) ++lvl;
+        n.census[hl::conv_census_row(pl.path)][lvl] += 1;
+        // (keyed like a rocprofv3 per-kernel, per-grid row: kernel family, level, Cout, kernel size - the input channel counts of a level share a row)
+        span_key[0] = (int)pl.path; span_key[1] = lvl; span_key[2] = o.ups ? 1 : 0; span_key[3] = c.Cout; span_key[4] = c.ks;
+        const double fl = 2.0 * (double)out.pixels() * c.Cout * c.Cin * c.ks * c.ks;
+        span_end(CAT_CONV, e0, fl, fl * hl::conv_issued_factor(pl.path) * (pl.kernel == hl::ConvKernel::H2sUp ? 4.0 / 9.0 : 1.0));   // (four of the nine taps)
     }
     // force_arrays: the caller needs cA / cB in memory (gn_apply_3d)
     Aff coef(const View &x, const Norm &g, const float *emb, bool force_arrays = false) {
         Aff af;
-        af.on = true;
         af.cA = alloc((size_t)B * x.C);
         af.cB = alloc((size_t)B * x.C);
         if (!run) return af;
-        const float *gt = totals_of(x, true);   // else one pass over the tensor
+        const float *gt = book.totals_of(x.p, x.C, true);   // else one pass over the tensor
         if (gt && !force_arrays && !n.prof) {
             // the consumer kernels form the coefficients themselves from the totals the producers left: no launch here
             af.cA = af.cB = nullptr;
@@ -542,106 +535,96 @@ struct Exec {
             return af;
         }
         const size_t e0 = span_begin();
-        if (gt) ok(hl::groupnorm_coef_stats(x, gt, g.gamma, g.beta, emb, n.emb_total, af.cA, af.cB, st, g.eps));
-        else ok(hl::groupnorm_coef(x, g.gamma, g.beta, emb, n.emb_total, af.cA, af.cB, gn_scratch, st, nullptr, g.eps));
+        if (gt) ok(hl::groupnorm_coef_stats(x, gt, g.gamma, g.beta, emb, n.emb_total, af.cA, af.cB, lane->st, g.eps));
+        else ok(hl::groupnorm_coef(x, g.gamma, g.beta, emb, n.emb_total, af.cA, af.cB, lane->gn_scratch, lane->st, nullptr, g.eps));
         span_end(CAT_GN, e0, 0.0);
         return af;
     }
     void res_block(const Res &r, const View &x, const View &dst) {
-        Aff a1 = coef(x, r.n1, nullptr), a2;
-        View h = plain(H / dst.H, r.Cout);
-        if (n.cfg.no_scale_shift) {
-            // use_scale_shift_norm=False (unet.py:216-218): h = h + emb_out[..., None, None]; h = out_layers(h).  The sum is materialised in
-            // place and its GroupNorm statistics come from a pass over the tensor (the producer's epilogue saw h without the embedding)
-            want_stats = false;
-            conv(r.c1, x, h, 1, 0, a1, 1, nullptr, 0);
-            want_stats = true;
-            if (run) ok(hl::add_rowvec(h, emb_all + r.emb_off, st, n.emb_total));
-            a2 = coef(h, r.n2, nullptr, r.aware);
-        } else {
-            conv(r.c1, x, h, 1, 0, a1, 1, nullptr, 0);
-            a2 = coef(h, r.n2, run ? emb_all + r.emb_off : nullptr, r.aware);
-        }
+        // use_scale_shift_norm=False (unet.py:216-218): h = h + emb_out[..., None, None]; h = out_layers(h).  The sum is materialised in
+        // place and its GroupNorm statistics come from a pass over the tensor (the producer's epilogue saw h without the embedding)
+        const bool noss = n.cfg.no_scale_shift;
+        ConvOpt o1, o2;
+        o1.af = coef(x, r.n1, nullptr); o1.act = 1; o1.stats = !noss;
+        View h = plain(H / dst.H, r.Cout), in2 = h;
+        conv(r.c1, x, h, o1);
+        if (noss && run) ok(hl::add_rowvec(h, emb_all + r.emb_off, lane->st, n.emb_total));
+        const Aff a2 = coef(h, r.n2, run && !noss ? emb_all + r.emb_off : nullptr, r.aware);
         if (r.aware) {
             // unet.py:208-214: every plane sees, next to its own normalised features, the other two planes averaged along the axis
             // it does not share with them; materialised (with the SiLU of out_layers) as a 3C-channel tensor for the convolution
-            View h3 = plain(H / dst.H, 3 * r.Cout);
+            in2 = plain(H / dst.H, 3 * r.Cout);
             float *sums = alloc((size_t)B * 3 * (h.H + h.W / 3) * r.Cout);
             if (run) {
                 const size_t e0 = span_begin();
-                ok(hl::gn_apply_3d(h, a2.cA, a2.cB, sums, h3.p, st));
+                ok(hl::gn_apply_3d(h, a2.cA, a2.cB, sums, in2.p, lane->st));
                 span_end(CAT_GN, e0, 0.0);
             }
-            if (r.has_skip) {
-                want_stats = false;
-                conv(r.skip, x, dst, 1, 0, none, 0, nullptr, 0);
-                want_stats = true;
-                conv(r.c2, h3, dst, 1, 0, none, 0, dst.p, dst.pitch);
-            } else {
-                conv(r.c2, h3, dst, 1, 0, none, 0, x.p, x.pitch);
-            }
-            return;
+        } else {
+            o2.af = a2; o2.act = 1;
         }
         if (r.has_skip) {
-            want_stats = false;          // dst is finished by c2 below
-            conv(r.skip, x, dst, 1, 0, none, 0, nullptr, 0);
-            want_stats = true;
-            conv(r.c2, h, dst, 1, 0, a2, 1, dst.p, dst.pitch);
-        } else {
-            conv(r.c2, h, dst, 1, 0, a2, 1, x.p, x.pitch);
+            ConvOpt sk;
+            sk.stats = false;            // dst is finished by c2 below
+            conv(r.skip, x, dst, sk);
         }
+        o2.residual(r.has_skip ? dst : x);
+        conv(r.c2, in2, dst, o2);
     }
     void attn_block(const Attn &a, const View &x, const View &dst) {
-        const Aff af = coef(x, a.norm, nullptr);
+        ConvOpt oq, op;
+        oq.af = coef(x, a.norm, nullptr);
+        oq.stats = false;                // qkv is not normalised
         View qkv = plain(H / x.H, 3 * a.C);
-        want_stats = false;              // qkv is not normalised
-        conv(a.qkv, x, qkv, 1, 0, af, 0, nullptr, 0);
-        want_stats = true;
+        conv(a.qkv, x, qkv, oq);
         View o = plain(H / x.H, a.C);
         // the attention's output is the RAW input of the projection convolution: the key-split kernels leave its sum x^2 like any other producer (hl_stats.h)
         float *ost = alloc_stat(hl::conv_stats_floats(B, (long)x.H * x.W));
         if (run) {
             const size_t e0 = span_begin();
             int emitted = 0;
-            ok(hl::attention(qkv.p, B, x.H * x.W, a.C, a.heads, o.p, st, n.conv_mode == HL_CONV_FP32, ost, &emitted));
-            if (emitted) stat_reg[o.p] = {ost, a.C, 0, a.C}; else stat_reg.erase(o.p);
+            ok(hl::attention(qkv.p, B, x.H * x.W, a.C, a.heads, o.p, lane->st, n.conv_mode == HL_CONV_FP32, ost, &emitted));
+            if (emitted) book.produced(o.p, {ost, a.C, 0}, a.C); else book.stored_without_totals(o.p);
             const double T = (double)x.H * x.W;
             span_end(CAT_ATTN, e0, 4.0 * B * T * T * a.C);
         }
-        conv(a.proj, o, dst, 1, 0, none, 0, x.p, x.pitch);
+        op.residual(x);
+        conv(a.proj, o, dst, op);
     }
     // SpatialTransformer (spatial_transformer.py:136-178, BasicTransformerBlock :115-134), depth 1, context = ONE token per image:
     //   h = proj_in(GroupNorm(x));  h += to_out(self-attention(LayerNorm1(h)));  h += to_out2(to_v2(context))  [softmax over a single key
     //   is 1, so norm2 / to_q / to_k of attn2 cannot act];  h += ff_out(GEGLU(ff_in(LayerNorm3(h))));  y = proj_out(h) + x
     void xf_block(const Xf &a, const View &x, const View &dst) {
         const int ds = H / x.H;
-        const Aff af = coef(x, a.norm, nullptr);
-        const bool ws_keep = want_stats;
-        want_stats = false;              // nothing in here feeds a GroupNorm
+        hipStream_t st = lane->st;
+        ConvOpt inner;
+        inner.stats = false;             // nothing in here feeds a GroupNorm: every call but proj_out
+        ConvOpt p_in = inner, p_out1 = inner, p_ff = inner, p_out;
+        p_in.af = coef(x, a.norm, nullptr);
         View h = plain(ds, a.C), ln = plain(ds, a.C), qkv = plain(ds, 3 * a.C), o = plain(ds, a.C), h1 = plain(ds, a.C);
         View ln3 = plain(ds, a.C), f8 = plain(ds, 8 * a.C), f4 = plain(ds, 4 * a.C), h2 = plain(ds, a.C);
         float *v2 = alloc((size_t)B * a.C), *r2 = alloc((size_t)B * a.C);
-        conv(a.proj_in, x, h, 1, 0, af, 0, nullptr, 0);
+        p_out1.residual(h); p_ff.residual(h1); p_out.residual(x);
+        conv(a.proj_in, x, h, p_in);
         if (run) ok(hl::layernorm(h, a.ln1_g, a.ln1_b, ln.p, st));
-        conv(a.qkv, ln, qkv, 1, 0, none, 0, nullptr, 0);
+        conv(a.qkv, ln, qkv, inner);
         if (run) {
             const size_t e0 = span_begin();
             ok(hl::attention(qkv.p, B, x.H * x.W, a.C, a.heads, o.p, st, n.conv_mode == HL_CONV_FP32));
             const double T = (double)x.H * x.W;
             span_end(CAT_ATTN, e0, 4.0 * B * T * T * a.C);
         }
-        conv(a.out1, o, h1, 1, 0, none, 0, h.p, h.pitch);
+        conv(a.out1, o, h1, p_out1);
         if (run) {
             ok(hl::linear_small(ctx, n.E, B, n.E, a.v2_w, nullptr, a.C, 0, nullptr, nullptr, v2, a.C, st));
             ok(hl::linear_small(v2, a.C, B, a.C, a.o2_w, a.o2_b, a.C, 0, nullptr, nullptr, r2, a.C, st));
             ok(hl::add_rowvec(h1, r2, st));
             ok(hl::layernorm(h1, a.ln3_g, a.ln3_b, ln3.p, st));
         }
-        conv(a.ff_in, ln3, f8, 1, 0, none, 0, nullptr, 0);
+        conv(a.ff_in, ln3, f8, inner);
         if (run) ok(hl::geglu(f8.p, f8.pixels(), 4 * a.C, f4.p, st));
-        conv(a.ff_out, f4, h2, 1, 0, none, 0, h1.p, h1.pitch);
-        want_stats = ws_keep;
-        conv(a.proj_out, h2, dst, 1, 0, none, 0, x.p, x.pitch);
+        conv(a.ff_out, f4, h2, p_ff);
+        conv(a.proj_out, h2, dst, p_out);
     }
     // run one TimestepEmbedSequential; the last layer writes into dst
     void block(const Block &b, View x, const View &dst) {
@@ -659,13 +642,14 @@ struct Exec {
                 default: Cout = n.convs[L.idx].Cout; ds_out = ds_in / 2; break;
             }
             View y = last ? dst : plain(ds_out, Cout);
+            ConvOpt o;
             switch (L.kind) {
-                case K_CONV: conv(n.convs[L.idx], x, y, 1, 0, none, 0, nullptr, 0); break;
+                case K_CONV: conv(n.convs[L.idx], x, y); break;
                 case K_RES: res_block(n.res[L.idx], x, y); break;
                 case K_ATTN: attn_block(n.attn[L.idx], x, y); break;
                 case K_XF: xf_block(n.xf[L.idx], x, y); break;
-                case K_DOWN: conv(n.convs[L.idx], x, y, 2, 0, none, 0, nullptr, 0); break;
-                case K_UP: conv(n.convs[L.idx], x, y, 1, 1, none, 0, nullptr, 0); break;
+                case K_DOWN: o.stride = 2; conv(n.convs[L.idx], x, y, o); break;
+                case K_UP: o.ups = 1; conv(n.convs[L.idx], x, y, o); break;
             }
             x = y;
         }
@@ -673,11 +657,12 @@ struct Exec {
 
     void forward(const float *x, const int64_t *t, const float *tf, const float *x_cond, const int64_t *y, float *out) {
         const hl_unet_cfg &c = n.cfg;
+        hipStream_t st = lane->st;     // the caller's stream: everything in here but the control tower
         if (run && stat_bytes) ok(hipMemsetAsync(stat_base, 0, stat_bytes, st) == hipSuccess ? 0 : hl::fail(HL_ERR_RUNTIME, "hl_unet_forward: memset of the statistics arena"));
-        gn_scratch = alloc(hl::gn_scratch_floats(B));
-        splitk_ws = alloc(hl::conv_splitk_ws_bytes() / sizeof(float));
-        gn_scratch2 = alloc(hl::gn_scratch_floats(B));
-        splitk_ws2 = alloc(hl::conv_splitk_ws_bytes() / sizeof(float));
+        for (Lane &l : lanes) {
+            l.gn_scratch = alloc(hl::gn_scratch_floats(B));
+            l.splitk_ws = alloc(hl::conv_splitk_ws_bytes() / sizeof(float));
+        }
         // embeddings (unet.py:564, 584-586) and all ResBlock emb_layers in one stacked product
         float *temb = alloc((size_t)B * c.model_channels), *e1 = alloc((size_t)B * n.E), *emb = alloc((size_t)B * n.E);
         emb_all = alloc((size_t)B * n.emb_total);
@@ -705,8 +690,10 @@ struct Exec {
                 ok(hl::prep_inputs(x_cond, nullptr, B, c.out_channels, H, W, ac.C, ac.p, nullptr, st));
             }
             View a1w = a1; a1w.C = 6;                                 // the conv writes 6 of the 16 (zeroed) channels
-            conv(n.ada1, ac, a1w, 2, 0, none, 0, nullptr, 0);
-            conv(n.ada2, a1, a2, 2, 0, none, 0, nullptr, 0);
+            ConvOpt down;
+            down.stride = 2;
+            conv(n.ada1, ac, a1w, down);
+            conv(n.ada2, a1, a2, down);
         }
         if (run) {
             const size_t e0 = span_begin();
@@ -722,8 +709,8 @@ struct Exec {
             else {
                 ok(hl::prep_inputs(x, c.controlnet ? x_cond : nullptr, B, c.in_channels, H, W, n.Cpad0, xin.p,
                                    c.controlnet ? xsum.p : nullptr, st, xin_tot, c.controlnet ? xsum_tot : nullptr));
-                stat_reg[xin.p] = {xin_tot, n.Cpad0, 0, n.Cpad0};
-                if (c.controlnet) stat_reg[xsum.p] = {xsum_tot, n.Cpad0, 0, n.Cpad0};
+                book.produced(xin.p, {xin_tot, n.Cpad0, 0}, n.Cpad0);
+                if (c.controlnet) book.produced(xsum.p, {xsum_tot, n.Cpad0, 0}, n.Cpad0);
             }
             span_end(CAT_OTHER, e0, 2.0 * B * ((double)n.E * c.model_channels + (double)n.E * n.E + (double)n.emb_total * n.E));
         }
@@ -738,26 +725,21 @@ struct Exec {
                 ch = n.out_blocks[j].Cout;
             }
         }
-        // one statistics block per concat view; its two halves (the decoder's running tensor | encoder skip + control residual) register as parts
+        // one statistics block per concat view, shared by its two halves (the decoder's running tensor | encoder skip + control residual)
         {
-            std::vector<float *> cat_st(nb);
-            for (size_t j = 0; j < nb; ++j) cat_st[j] = alloc_stat(hl::conv_stats_floats(B, (long)cat[j].H * cat[j].W));
-            if (run && c.controlnet) {
-                int ch = n.middle.Cout;
-                for (size_t j = 0; j < nb; ++j) {
-                    part_reg[cat[j].p] = {cat_st[j], cat[j].C, 0};
-                    part_reg[cat[j].p + ch] = {cat_st[j], cat[j].C, ch};
-                    ch = n.out_blocks[j].Cout;
-                }
+            int ch = n.middle.Cout;
+            for (size_t j = 0; j < nb; ++j) {
+                float *cat_st = alloc_stat(hl::conv_stats_floats(B, (long)cat[j].H * cat[j].W));
+                if (run && c.controlnet) book.concat_halves(cat[j].p, cat[j].C, ch, cat_st);
+                ch = n.out_blocks[j].Cout;
             }
         }
         auto first_part = [&](size_t j, int C) { View v = cat[j]; v.C = C; return v; };
         // main encoder + middle on the caller's stream; control encoder on the side stream (unet.py:588-602).
         // They are independent except that control block i's zero-conv adds the main encoder's hs[i].
         const bool fork = run && c.controlnet && n.overlap && !n.prof && n.side;
-        hipStream_t main_st = st;
         if (fork) {
-            hipEventRecord(n.ev_fork, main_st);
+            hipEventRecord(n.ev_fork, st);
             hipStreamWaitEvent(n.side, n.ev_fork, 0);
         }
         std::vector<View> hs(nb);
@@ -765,13 +747,13 @@ struct Exec {
         for (size_t i = 0; i < nb; ++i) {
             hs[i] = plain(n.in_blocks[i].ds_out, n.in_blocks[i].Cout);
             block(n.in_blocks[i], h, hs[i]);
-            if (fork) hipEventRecord(n.ev_block[i], main_st);
+            if (fork) hipEventRecord(n.ev_block[i], st);
             h = hs[i];
         }
         block(n.middle, h, first_part(0, n.middle.Cout));
         // control branch: zero-conv output feeds the next block AND (+ encoder skip) the decoder
         if (c.controlnet) {
-            if (fork) { st = n.side; std::swap(gn_scratch, gn_scratch2); std::swap(splitk_ws, splitk_ws2); std::swap(act_ws, act_ws2); }
+            if (fork) lane = &lanes[1];
             View hc = xsum;
             for (size_t i = 0; i < nb; ++i) {
                 View tmp = plain(n.cond_blocks[i].ds_out, n.cond_blocks[i].Cout);
@@ -780,14 +762,15 @@ struct Exec {
                 const size_t j = nb - 1 - i;
                 const int Ch = cat[j].C - hs[i].C;
                 if (fork) hipStreamWaitEvent(n.side, n.ev_block[i], 0);
-                conv(n.convs[n.proj_cond[i]], tmp, pj, 1, 0, none, 0, nullptr, 0,
-                     run ? cat[j].p + Ch : nullptr, cat[j].pitch, hs[i].p, hs[i].pitch);
+                ConvOpt zo;
+                zo.out2 = run ? cat[j].p + Ch : nullptr; zo.out2_pitch = cat[j].pitch; zo.res2 = hs[i].p; zo.res2_pitch = hs[i].pitch;
+                conv(n.convs[n.proj_cond[i]], tmp, pj, zo);
                 hc = pj;
             }
             if (fork) {
                 hipEventRecord(n.ev_join, n.side);
-                st = main_st; std::swap(gn_scratch, gn_scratch2); std::swap(splitk_ws, splitk_ws2); std::swap(act_ws, act_ws2);
-                hipStreamWaitEvent(main_st, n.ev_join, 0);
+                lane = &lanes[0];
+                hipStreamWaitEvent(st, n.ev_join, 0);
             }
         } else if (run) {
             for (size_t i = 0; i < nb; ++i) {
@@ -795,7 +778,7 @@ struct Exec {
                 const int Ch = cat[j].C - hs[i].C;
                 hipMemcpy2DAsync(cat[j].p + Ch, cat[j].pitch * sizeof(float), hs[i].p, hs[i].pitch * sizeof(float),
                                  (size_t)hs[i].C * sizeof(float), (size_t)hs[i].pixels(), hipMemcpyDeviceToDevice, st);
-                stat_reg.erase(cat[j].p + Ch);   // (the source's totals are grouped for its own norm, not for the concat: the decoder norm takes a pass over the tensor)
+                book.stored_without_totals(cat[j].p + Ch);   // (the source's totals are grouped for its own norm, not for the concat: the decoder norm takes a pass over the tensor)
             }
         }
         // decoder
@@ -805,17 +788,29 @@ struct Exec {
             block(n.out_blocks[j], cat[j], dst);
             last = dst;
         }
-        const Aff afo = coef(last, n.out_norm, nullptr);
+        ConvOpt oo;
+        oo.af = coef(last, n.out_norm, nullptr); oo.act = 1; oo.nchw = 1;
         View o; o.N = B; o.H = H; o.W = W; o.C = c.out_channels; o.pitch = c.out_channels; o.p = out;
-        if (c.aware3d) {   // unet.py:613-614: the planes go back to channels
-            o.p = alloc((size_t)o.pixels() * c.out_channels);
-            conv(n.out_conv, last, o, 1, 0, afo, 1, nullptr, 0, nullptr, 0, nullptr, 0, 1);
-            if (run) ok(hl::unroll_planes(o.p, B, c.out_channels, H, W / 3, out, st));
-            return;
-        }
-        conv(n.out_conv, last, o, 1, 0, afo, 1, nullptr, 0, nullptr, 0, nullptr, 0, 1);
+        if (c.aware3d) o.p = alloc((size_t)o.pixels() * c.out_channels);   // unet.py:613-614: the planes go back to channels
+        conv(n.out_conv, last, o, oo);
+        if (c.aware3d && run) ok(hl::unroll_planes(o.p, B, c.out_channels, H, W / 3, out, st));
     }
 };
+
+// The workspace from the sizing pass's results: | bump region (off) | act_ws of lane 0 | act_ws of lane 1 | statistics arena (stat_off) |, byte
+// offsets.  The arena starts on a 256-byte ADDRESS, so its offset depends on where the workspace lies (base; 0 in the size query).  The
+// total is what hl_unet_workspace_bytes has always returned; its 1024 holds the two round-ups wherever the workspace lies.
+struct WsLayout { size_t act_ws[2], stats, total; };
+int ws_layout(size_t off, size_t act_need, size_t stat_off, uintptr_t base, WsLayout *L) {
+    const size_t act = act_need * sizeof(float);
+    L->act_ws[0] = (off + 255) / 256 * 256;
+    L->act_ws[1] = L->act_ws[0] + act;
+    const size_t end = L->act_ws[1] + act;
+    L->stats = end + ((256 - ((base + end) & 255)) & 255);
+    L->total = off + 2 * act + stat_off + 1024;
+    HL_REQUIRE(L->stats + stat_off <= L->total, "hl_unet: the statistics arena ends %zu bytes behind the workspace", L->stats + stat_off - L->total);
+    return 0;
+}
 
 int validate(const hl_unet_cfg *c) {
     HL_REQUIRE(c, "unet: null cfg");
@@ -894,9 +889,10 @@ void hl_unet_destroy(void *handle) { delete static_cast<Net *>(handle); }
 size_t hl_unet_workspace_bytes(void *handle, int B, int H, int W) {
     if (!handle || B <= 0) return 0;
     Net &n = *static_cast<Net *>(handle);
-    Exec e{n, false, nullptr, 0, nullptr, B, H, n.cfg.aware3d ? 3 * W : W};
+    Exec e(n, false, nullptr, nullptr, B, H, n.cfg.aware3d ? 3 * W : W);
     e.forward(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-    return e.off + 2 * e.act_need * sizeof(float) + e.stat_off + 1024;
+    WsLayout L;
+    return ws_layout(e.off, e.act_need, e.stat_off, 0, &L) ? 0 : L.total;
 }
 
 int hl_unet_forward(void *handle, const float *x, const int64_t *t, const float *t_float, const float *x_cond,
@@ -911,14 +907,16 @@ int hl_unet_forward(void *handle, const float *x, const int64_t *t, const float 
                "hl_unet_forward: cond_type='AdaGN' / 'cross_attention' need x_cond and 256x256 inputs (Linear(64*64, ..))");
     HL_REQUIRE(n.cfg.num_classes == 0 || y, "hl_unet_forward: y is required for a class-conditional model");
     if (n.cfg.aware3d) W *= 3;                           // use_3d_aware: x is (B, 3*in_channels, H, W); the network runs on (B, in_channels, H, 3W)
-    Exec dry{n, false, nullptr, 0, nullptr, B, H, W};   // sizes only (host work, no launches)
+    Exec dry(n, false, nullptr, nullptr, B, H, W);   // sizes only (host work, no launches)
     dry.forward(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-    Exec e{n, true, static_cast<char *>(workspace), 0, (hipStream_t)stream, B, H, W};
+    char *const ws = static_cast<char *>(workspace);
+    WsLayout L;
+    const int lrc = ws_layout(dry.off, dry.act_need, dry.stat_off, reinterpret_cast<uintptr_t>(ws), &L);
+    if (lrc) return lrc;
+    Exec e(n, true, ws, (hipStream_t)stream, B, H, W);
     e.act_need = dry.act_need;
-    e.act_ws = reinterpret_cast<float *>(static_cast<char *>(workspace) + (dry.off + 255) / 256 * 256);
-    e.act_ws2 = e.act_ws + dry.act_need;
-    e.stat_base = reinterpret_cast<char *>(e.act_ws2 + dry.act_need);
-    e.stat_base += (256 - (reinterpret_cast<uintptr_t>(e.stat_base) & 255)) & 255;
+    for (int i = 0; i < 2; ++i) e.lanes[i].act_ws = reinterpret_cast<float *>(ws + L.act_ws[i]);
+    e.stat_base = ws + L.stats;
     e.stat_bytes = dry.stat_off;
     for (auto &row : n.census) for (auto &v : row) v = 0;
     e.forward(x, t, t_float, x_cond, y, out);
@@ -1137,10 +1135,10 @@ size_t hl_conv2d_scratch_bytes(int conv_mode, int N, int H, int W, int Cin, int 
 }
 
 // The plan conv2d_single makes for the same arguments, without a buffer (the plan queries; host arithmetic: no HIP call).  silu and
-// want_stats: what the call puts into ConvArgs::act and ::stats before it plans (hl_conv2d_nhwc_gn wants the statistics).  false:
+// with_stats: what the call puts into ConvArgs::act and ::stats before it plans (hl_conv2d_nhwc_gn wants the statistics).  false:
 // arguments no call accepts.
 static bool single_conv_query_plan(int mode, int tf, int N, int H, int W, int Cin, int Cout, int ks, int stride, int upsample, bool with_gn,
-                                   long out_pitch, hl::ConvPlan *pl, bool silu = false, bool want_stats = false) {
+                                   long out_pitch, hl::ConvPlan *pl, bool silu = false, bool with_stats = false) {
     if (single_conv_refusal(mode, N, H, W, Cin, Cout, ks, stride, upsample, with_gn, silu)) return false;
     const SingleConvRoom room = single_conv_room(mode, tf, N, H, W, Cin, Cout, ks, stride, upsample, with_gn);
     if (!room.total) return false;
@@ -1148,7 +1146,7 @@ static bool single_conv_query_plan(int mode, int tf, int N, int H, int W, int Ci
     ConvArgs a{};
     single_conv_plan_args(a, &at, mode, room.forms, N, H, W, Cin, Cout, ks, stride, upsample, with_gn, out_pitch);
     a.act = silu;
-    a.stats = want_stats ? &at : nullptr;
+    a.stats = with_stats ? &at : nullptr;
     *pl = hl::plan_conv(a);
     return true;
 }
@@ -1169,11 +1167,11 @@ static_assert((int)hl::ConvPrePass::None == HL_PRE_NONE && (int)hl::ConvPrePass:
 static_assert((int)hl::ConvStatsBy::None == HL_STATS_BY_NONE && (int)hl::ConvStatsBy::Epilogue == HL_STATS_BY_EPILOGUE &&
                   (int)hl::ConvStatsBy::Finish == HL_STATS_BY_FINISH,
               "humanliff_hip.h documents ConvStatsBy's numbers");
-int hl_conv2d_plan_ex(int conv_mode, int N, int H, int W, int Cin, int Cout, int ks, int stride, int upsample, int with_gn, int silu, int want_stats,
+int hl_conv2d_plan_ex(int conv_mode, int N, int H, int W, int Cin, int Cout, int ks, int stride, int upsample, int with_gn, int silu, int with_stats,
                       int *h_plan) {
     HL_REQUIRE(h_plan, "hl_conv2d_plan_ex: null argument");
     hl::ConvPlan pl;
-    HL_REQUIRE(single_conv_query_plan(conv_mode, 0, N, H, W, Cin, Cout, ks, stride, upsample, with_gn != 0, 0, &pl, silu != 0, want_stats != 0),
+    HL_REQUIRE(single_conv_query_plan(conv_mode, 0, N, H, W, Cin, Cout, ks, stride, upsample, with_gn != 0, 0, &pl, silu != 0, with_stats != 0),
                "hl_conv2d_plan_ex: bad argument (mode %d, N %d, H %d, W %d, Cin %d, Cout %d, ks %d, stride %d, upsample %d, with_gn %d, silu %d)", conv_mode, N,
                H, W, Cin, Cout, ks, stride, upsample, with_gn, silu);
     h_plan[HL_PLAN_KERNEL] = (int)pl.kernel; h_plan[HL_PLAN_SPLITS] = pl.splits; h_plan[HL_PLAN_CFG] = pl.cfg; h_plan[HL_PLAN_TILE8] = pl.tile8 ? 1 : 0;
