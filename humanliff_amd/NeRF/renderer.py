@@ -93,9 +93,10 @@ class Renderer(nn.Module):
     def load_body_model(self, path_or_dict, device=None):
         """What the reference's constructor does with assets/SMPL_NEUTRAL.pkl (renderer.py:41-45): SMPL_NEUTRAL = the SMPL_to_tensor
         dict on the device, faces = its 'f'.  Takes a path (.pkl / .npz), a dict, or a BodyModel; keeps the BodyModel, whose pose()
-        makes the tp_input of a posed frame (humanliff_amd/body.py)."""
-        from ..body import BodyModel, load_body_model
-        model = path_or_dict if isinstance(path_or_dict, BodyModel) else load_body_model(path_or_dict, device)
+        makes the tp_input of a posed frame (humanliff_amd/body.py).  A SmplxModel (body.load_smplx_model) is taken the same way: what
+        the reference does for smpl_type 'smplx' (renderer.py:46-49), every shape column of the file included."""
+        from ..body import BodyModel, SmplxModel, load_body_model
+        model = path_or_dict if isinstance(path_or_dict, (BodyModel, SmplxModel)) else load_body_model(path_or_dict, device)
         self.body_model = model
         self.SMPL_NEUTRAL = model.tensors
         self.faces = self.SMPL_NEUTRAL['f']

@@ -61,12 +61,23 @@ def get_rays(H, W, K, R, T, device=None):
     return ro.view(H, W, 3), rd.view(H, W, 3)
 
 
+BIG_GLOBAL_ORIENT = (-3.1416, 0.0, 0.0)          # this twin's big pose for smpl_type 'smplx' (:199)
+
+
 def prepare_input(body_model, params):
     """prepare_input (:141-182) for smpl_type='smpl' on the device: `params` holds 'poses' (1,72) or (F,72) and 'shapes' (device
     tensors), 'R' (3,3) and 'Th' (1,3) (host arrays, as prepare_smpl_params makes them) -> (world_bounds (2,3), vertices (V,3), params,
     joints (J,3)) as device float32 tensors, with a leading frame axis when poses has more than one row.  The PosedBody behind them
-    (tables for the renderer included) is body_model.pose(...) of the same arguments (humanliff_amd/body.py)."""
-    posed = body_model.pose(params['poses'], params['shapes'], params.get('R'), params.get('Th'))
+    (tables for the renderer included) is body_model.pose(...) of the same arguments (humanliff_amd/body.py).
+    A SmplxModel takes the SMPL-X params of prepare_smpl_params (:128-138: the smplx.npz keys, 'R', 'Th'); as the reference does (:158,
+    165-166) the model is run with a zero transl - this twin carries the translation in 'Th' - and 'poses' (the full pose) and 'shapes'
+    (betas || expression) are added to `params`."""
+    from .body import SmplxModel
+    if isinstance(body_model, SmplxModel):
+        posed = body_model.pose_dict(dict(params, transl=None), big_global_orient=BIG_GLOBAL_ORIENT)
+        params['poses'], params['shapes'] = posed.poses, posed.shapes
+    else:
+        posed = body_model.pose(params['poses'], params['shapes'], params.get('R'), params.get('Th'))
     if posed.F == 1:
         return posed.world_bounds[0], posed.vertices[0], params, posed.joints[0]
     return posed.world_bounds, posed.vertices, params, posed.joints

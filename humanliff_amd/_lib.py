@@ -213,6 +213,11 @@ SIGNATURES = {
     "hl_view_ingest": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     "hl_view_ingest_layers": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     "hl_pose_body_margins": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _i, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _sz, C.c_float, C.c_float, _p]),
+    "hl_smplx_packed_bytes": (_sz, [_i, _i, _i, _i]),
+    "hl_smplx_pack": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _i, _i, _p, _p]),
+    "hl_smplx_chunk_frames": (_i, []),
+    "hl_smplx_pose_workspace_bytes": (_sz, [_i, _i]),
+    "hl_smplx_pose": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _sz, C.c_float, C.c_float, _p]),
 }
 
 

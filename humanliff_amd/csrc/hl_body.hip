@@ -4,7 +4,7 @@
 // fp32 on the vector ALU, every sum in a fixed order, no float atomics; frames are independent, so a frame has the same bits alone or
 // inside a batch.  (-ffp-contract=off: a product and the sum it goes into are two roundings everywhere below.)
 //
-// k_body_transpose / k_body_regress (hl_body_pack, once per model): posedirs (V,3,P) -> (P,3,V), shapedirs -> (Sp,3,V), weights (V,J)
+// k_body_transpose (hl_body_kernels.h) / k_body_regress (hl_body_pack, once per model): posedirs (V,3,P) -> (P,3,V), shapedirs -> (Sp,3,V), weights (V,J)
 //   -> (J,V), v_template -> (3,V): a thread per vertex then reads neighbouring addresses in neighbouring lanes.  The joint regressor
 //   is applied to the template and to every shape direction once: (J,3) and (J,3,Sp).  One workgroup per output value; thread t adds
 //   the float64 products of vertices t, t + 256, ... in order, then the fixed tree of hl_reduce.h; the sum is rounded to fp32 once.
@@ -16,21 +16,16 @@
 //   index ascending.  Then per frame: shape_off (s ascending), T = sum_j w[v][j] A_j (j ascending), v_smpl = T [(v_t + shape_off) +
 //   pose_off; 1], world = v_smpl R^T + Th, verts4 = (world - Th) R from the rounded world vertex, Rinv by cofactors, the table row.
 //   FC = 8 (kChunk) for a sequence - 24 accumulators, the features of a chunk are 6.6 KB of LDS for SMPL - and FC = 1 for one frame.
-// k_body_bounds: one workgroup per frame: min / max of the frame's vertices (thread t takes t, t + 256, ..., then the tree), - / +
+// k_body_bounds (hl_body_kernels.h): one workgroup per frame: min / max of the frame's vertices (thread t takes t, t + 256, ..., then the tree), - / +
 //   `margin`, y once more by `y_margin`: two fp32 subtractions, as SynBodyView_datasets.py:174-179 does them with 0.05f and 0.05f
 //   (hl_body_pose) and TightCap_dataset.py:165-168 of the reference with 0.05f and 0.1f (hl_pose_body_margins).
-#include "hl_reduce.h"
-
-#include <cmath>
-#include <cstdint>
+#include "hl_body_kernels.h"
 
 namespace hl {
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int kChunk = 8;                   // frames per workgroup of the skinning pass
 constexpr int kMaxJ = 64, kMaxS = 16;
-static_assert(kThreads == kReduceThreads, "block_reduce reduces a workgroup of kReduceThreads");
 
 struct Packed {                             // offsets (floats) into the packed model
     int64_t pd, sd, wt, vt, jt, js, total;
@@ -46,18 +41,6 @@ inline Packed layout(int V, int J, int Sp) {
     p.js = p.jt + 3 * J;
     p.total = p.js + 3 * (int64_t)J * Sp;
     return p;
-}
-
-// out[(k C + c) V + v] = in[(v C + c) cols + k], k < K
-__global__ __launch_bounds__(kThreads) void k_body_transpose(const float *__restrict__ in, int V, int C, int cols, int K,
-                                                             float *__restrict__ out) {
-    const int64_t n = (int64_t)K * C * V;
-    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    if (i >= n) return;
-    const int v = (int)(i % V);
-    const int64_t kc = i / V;
-    const int c = (int)(kc % C), k = (int)(kc / C);
-    out[i] = in[((int64_t)v * C + c) * cols + k];
 }
 
 // workgroup o = (j 3 + c) (1 + Sp) + q: q = 0 the template, q >= 1 shape direction q - 1
@@ -276,36 +259,6 @@ __global__ __launch_bounds__(kThreads) void k_body_skin(PoseArgs a) {
             o[6] = make_float4(b0.w, b1.x, b1.y, b1.z);
             o[7] = make_float4(b1.w, b2.x, b2.y, b2.z);
             o[8] = make_float4(b2.w, 0.f, 0.f, 0.f);
-        }
-    }
-}
-
-__global__ __launch_bounds__(kThreads) void k_body_bounds(const float *__restrict__ vertices, int V, float margin, float y_margin,
-                                                          float *__restrict__ bounds) {
-    __shared__ float sh[kThreads];
-    const float *p = vertices + (int64_t)blockIdx.x * V * 3;
-    float lo[3], hi[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) lo[c] = INFINITY, hi[c] = -INFINITY;
-    for (int v = (int)threadIdx.x; v < V; v += kThreads)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float x = p[3 * (int64_t)v + c];
-            lo[c] = fminf(lo[c], x);
-            hi[c] = fmaxf(hi[c], x);
-        }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        lo[c] = block_reduce(lo[c], sh, Min());
-        hi[c] = block_reduce(hi[c], sh, Max());
-    }
-    if (threadIdx.x == 0) {
-        float *o = bounds + (int64_t)blockIdx.x * 6;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            float a = lo[c] - margin, b = hi[c] + margin;
-            if (c == 1) a = a - y_margin, b = b + y_margin;
-            o[c] = a, o[3 + c] = b;
         }
     }
 }

@@ -8,7 +8,8 @@ reference, for the device-resident fitting path (contract: DESIGN.md 4i).
 The reference decodes, masks and resizes one image per __getitem__ call in a DataLoader worker (imageio + cv2, :266-278) and draws its rays
 there.  Here every view is decoded once (PIL, a bounded thread pool), uploaded as uint8 and turned into the store's float image and body
 mask by one launch per batch (humanliff_amd.view_ingest); rays are drawn on the device afterwards (if_nerf_data_utils.sample_ray_batch).
-SynBodyIndex and smpl_params are host code and need neither a GPU nor PIL.  smpl_type 'smplx' is not covered; the TightCap layout is
+SynBodyIndex, smpl_params and smplx_params are host code and need neither a GPU nor PIL.  smpl_type 'smplx' (the reference's default,
+:44) reads <subject>/smplx.npz and poses a humanliff_amd.body.SmplxModel of the file's gender; the TightCap layout is
 TightCap_dataset.py's, which reuses the readers and helpers below.
 """
 import json
@@ -23,6 +24,7 @@ from .if_nerf_data_utils import ViewStore
 
 LAYER_DIRS = ('person', 'person-pants', 'person-pants-shirt', 'person-pants-shirt-shoes')          # cloth_layer_index 0 .. 3 (:253-264)
 SMPL_FILE = os.path.join('person-top-bottom-shoes', 'outputs_re_fitting', 'refit_smpl_2nd.npz')    # :283
+SMPLX_FILE = 'smplx.npz'                                                                            # :285
 MAX_DECODE_THREADS = 16
 UPLOAD_BYTES = 256 << 20                 # uint8 source bytes uploaded and ingested per batch
 
@@ -79,6 +81,9 @@ class SynBodyIndex:
     def smpl_path(self, instance_idx):
         return os.path.join(self.root_list[instance_idx], SMPL_FILE)
 
+    def smplx_path(self, instance_idx):
+        return os.path.join(self.root_list[instance_idx], SMPLX_FILE)                # :285
+
 
 def smpl_params(smpl_path, pose_index, smpl_type='smpl'):
     """prepare_smpl_params (:135-144) for smpl_type 'smpl': float32 numpy 'shapes' (betas), 'poses' (1, 72), 'R' = I and 'Th' = transl[0:1] -
@@ -93,6 +98,17 @@ def smpl_params(smpl_path, pose_index, smpl_type='smpl'):
     if poses.shape != (1, 72):
         raise ValueError(f"{smpl_path}: global_orient and body_pose of frame {pose_index} hold {poses.shape[1]} values, SMPL has 72")
     return {'shapes': f32(fitted['betas']), 'poses': poses, 'R': np.eye(3, dtype=np.float32), 'Th': f32(fitted['transl'][0:1])}
+
+
+def smplx_params(smplx_path, pose_index):
+    """prepare_smpl_params (:145-155) for smpl_type 'smplx' -> (params, gender): every key of the file's 'smplx' dict as a torch tensor,
+    'betas' whole and every other key [pose_index:pose_index + 1]; 'R' = I, 'Th' = zeros (1, 3) (float32 numpy); gender from 'meta'."""
+    with np.load(smplx_path, allow_pickle=True) as z:
+        fitted, gender = z['smplx'].item(), z['meta'].item()['gender']
+    params = {k: torch.from_numpy(np.asarray(v) if k == 'betas' else np.asarray(v)[pose_index:pose_index + 1]) for k, v in fitted.items()}
+    params['R'] = np.eye(3).astype(np.float32)
+    params['Th'] = np.zeros((1, 3)).astype(np.float32)
+    return params, gender
 
 
 def _pil():
@@ -147,26 +163,44 @@ def store_test_views(store, view_ids=None):
                "world_bounds": store.world_bounds[v:v + 1], "view_id": v if view_ids is None else int(view_ids[v]), "H": store.H, "W": store.W}
 
 
-def load_view_store(index, body_model, image_scaling=1.0, device=None, items=None, decode_threads=8):
+def load_view_store(index, body_model, image_scaling=1.0, device=None, items=None, decode_threads=8, smpl_type='smpl'):
     """Every dataset index in `items` (default: all of `index`) as one view of a prepared ViewStore on `device`, in that order: image
     and mask resized to int(Hs * image_scaling) x int(Ws * image_scaling) as :266-278 does, K[:2] scaled (:279), world bounds from
     body_model.pose of smpl_params (prepare_input :158-194).  The store also carries `dataset_index`, `pose_index` and `view_index`
     (host int64 arrays, one entry per view).  MemoryError before anything is decoded when the store would not fit the free device
-    memory; ValueError for a file of another size than the first, and for image_scaling > 1."""
+    memory; ValueError for a file of another size than the first, and for image_scaling > 1.
+    smpl_type 'smplx': `body_model` is a SmplxModel, or a dict of them keyed 'male' / 'female' / 'neutral' as the reference keeps them
+    (:84-99); the bounds come from SmplxModel.pose_dict of smplx_params (index.smplx_path), with the model of the file's gender - KeyError
+    naming the gender when the dict lacks it."""
+    if smpl_type not in ('smpl', 'smplx'):
+        raise ValueError(f"load_view_store: smpl_type {smpl_type!r}; 'smpl' or 'smplx'")
+
+    def smplx_bounds(inst, pose, device):
+        params, gender = smplx_params(index.smplx_path(inst), pose)
+        if isinstance(body_model, dict):
+            if gender not in body_model:
+                raise KeyError(f"load_view_store: {index.smplx_path(inst)} is of gender {gender!r}; body_model holds {sorted(body_model)}")
+            model = body_model[gender]
+        else:
+            model = body_model
+        return model.pose_dict({k: (v.to(device) if torch.is_tensor(v) else v) for k, v in params.items()}, y_margin=0.05).world_bounds[0]
+
     def ingest(recs, decoded, H, W, device):
         img = torch.from_numpy(np.stack([d[rec[4]] for rec, d in zip(recs, decoded)])).to(device)
         msk = torch.from_numpy(np.stack([d[rec[5]] for rec, d in zip(recs, decoded)])).to(device)
         return view_ingest.ingest_views(img, msk, H, W)
 
     return fill_view_store(index, body_model, image_scaling, device, items, decode_threads, source_bytes=4, y_margin=0.05,
-                           decode=lambda rec: {rec[4]: read_image(rec[4]), rec[5]: read_mask(rec[5])}, ingest=ingest)
+                           decode=lambda rec: {rec[4]: read_image(rec[4]), rec[5]: read_mask(rec[5])}, ingest=ingest,
+                           pose_bounds=smplx_bounds if smpl_type == 'smplx' else None)
 
 
-def fill_view_store(index, body_model, image_scaling, device, items, decode_threads, source_bytes, y_margin, decode, ingest):
+def fill_view_store(index, body_model, image_scaling, device, items, decode_threads, source_bytes, y_margin, decode, ingest, pose_bounds=None):
     """What the loaders of the two dataset layouts share.  `index.item(i)` gives (instance_idx, cloth_layer_index, pose_index, view_index,
     img_path, ..., K, R, T) and `index.smpl_path`; `decode(rec)` -> {path: uint8 array} of the files the view names (called in the thread
     pool); `ingest(recs, decoded, H, W, device)` -> (image (V, H, W, 3) float32, body (V, H, W) uint8) of one batch on the device;
-    `source_bytes`: uint8 bytes uploaded per source pixel; `y_margin`: BodyModel.pose's."""
+    `source_bytes`: uint8 bytes uploaded per source pixel; `y_margin`: BodyModel.pose's; `pose_bounds(inst, pose, device)` -> (2, 3)
+    device tensor: the world bounds of a posed subject where they do not come from body_model.pose of smpl_params."""
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     if device.type != "cuda":
         raise RuntimeError("load_view_store needs a HIP device; humanliff_amd has no CPU path")
@@ -189,7 +223,11 @@ def fill_view_store(index, body_model, image_scaling, device, items, decode_thre
     # world bounds: one posed body per (subject, pose)
     bounds = {}
     for inst, _, pose, *_ in records:
-        if (inst, pose) not in bounds:
+        if (inst, pose) in bounds:
+            continue
+        if pose_bounds is not None:
+            bounds[(inst, pose)] = pose_bounds(inst, pose, device)
+        else:
             p = smpl_params(index.smpl_path(inst), pose)
             posed = body_model.pose(torch.from_numpy(p['poses']).to(device), torch.from_numpy(p['shapes'].reshape(-1)).to(device), p['R'], p['Th'],
                                     y_margin=y_margin)

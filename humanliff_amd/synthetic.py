@@ -180,6 +180,34 @@ def smpl_like_model(n_vertices=6890, seed=21):
     }
 
 
+SMPLX_PARENTS = [-1, 0, 0, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 9, 9, 12, 13, 14, 16, 17, 18, 19, 15, 15, 15, 20, 25, 26, 20, 28, 29, 20, 31, 32, 20, 34, 35,
+                 20, 37, 38, 21, 40, 41, 21, 43, 44, 21, 46, 47, 21, 49, 50, 21, 52, 53]
+
+
+def smplx_like_model(n_vertices=10475, seed=23, shape_cols=400):
+    """A body model with the STRUCTURE of an SMPLX_{GENDER}.npz (the keys the reference's SMPLX reads for use_pca=False, landmarks
+    aside) and seeded random content: 55 joints on the SMPL-X kinematic tree, `shape_cols` shape columns (400 in the official files: 300
+    shape + 100 expression; 20 in the older ones), top-4 blend weights with exact zeros, non-zero hand means.  float32 tensors."""
+    g = _gen(seed)
+    V, J = n_vertices, 55
+    box = torch.tensor([0.9, 1.7, 0.4])
+    v_template = (torch.rand((V, 3), generator=g) - 0.5) * box
+    J_regressor = torch.softmax(torch.randn((J, V), generator=g) * 3.0, dim=1)
+    top = torch.topk(torch.randn((V, J), generator=g) * 2.5, 4, dim=1)
+    weights = torch.zeros((V, J)).scatter_(1, top.indices, torch.softmax(top.values, dim=1))
+    return {
+        "v_template": v_template,
+        "shapedirs": torch.randn((V, 3, shape_cols), generator=g) * 0.01,
+        "posedirs": torch.randn((V, 3, 9 * (J - 1)), generator=g) * 0.003,
+        "J_regressor": J_regressor,
+        "kintree_table": torch.tensor([SMPLX_PARENTS, list(range(J))], dtype=torch.long),
+        "weights": weights,
+        "f": torch.zeros((1, 3), dtype=torch.long),
+        "hands_meanl": torch.randn((45,), generator=g) * 0.2,
+        "hands_meanr": torch.randn((45,), generator=g) * 0.2,
+    }
+
+
 def _rodrigues1(v):
     a = torch.linalg.norm(v) + 1e-12
     k = v / a

@@ -889,6 +889,33 @@ int hl_pose_body_margins(const float *packed, const int32_t *parents, int V, int
                          float *verts4, float *table, float *big_out, void *workspace, size_t workspace_bytes, float margin, float y_margin,
                          void *stream);
 
+/* ---- posing an SMPL-X body: SMPLX.forward + lbs of the smplx package (recon_NeRF/smplx/body_models.py:1188-1242, smplx/lbs.py), the
+ *      dataset's R / Th and bounds (SynBody_dataset.py:182-192) and the renderer's per-vertex tables ----
+ * Contract: DESIGN.md 4k; csrc/hl_smplx.hip.  The conventions of hl_body_pose hold (fp32, fixed order, enqueue-only, nothing allocated).
+ * V vertices, 2 <= J <= 64 joints, P = 9 (J - 1), 1 <= S <= 32 coefficients (betas followed by expression), F >= 1 frames.
+ *   hl_smplx_pack (once per model): as hl_body_pack, with TWO sets of S shape directions taken from shapedirs (V,3,sd_cols):
+ *       set 1: columns [0, num_betas) followed by [expr_start, expr_start + num_expr) - shapes the body;
+ *       set 2: columns [0, S) - what the renderer's canonical-space tables use (NeRF/renderer.py:87, 364 of the reference).
+ *     With expr_start == num_betas the sets coincide and set 2 is not stored (two_sets = 0 below).  packed, as floats:
+ *       posedirs (P,3,V) | set 1 (S,3,V) | weights (J,V) | v_template (3,V) | J_regressor v_template (J,3) | J_regressor set 1 (J,3,S)
+ *       [ | set 2 (S,3,V) | J_regressor set 2 (J,3,S) ]      - hl_smplx_packed_bytes(V, J, S, two_sets) bytes.
+ *   hl_smplx_pose: poses (F,3J): the full pose, pose_mean added; coef (F,S); transl (F,3) or NULL, added to the skinned vertices and
+ *     joints before R / Th; rt, rt_stride, big, margins and the outputs as hl_pose_body_margins.  vertices, joints, bounds and verts4
+ *     come from set 1; the table's t, shape_off (and its big-pose rows, posed with zero coefficients) from set 2 and without transl;
+ *     Rinv and pose_off are common to both.  With table == NULL set 2 is not evaluated.
+ *     workspace: hl_smplx_pose_workspace_bytes(J, F) bytes; afterwards A (F,J,16) of set 1, the translation columns of set 2 (F,J,4),
+ *     the pose features (F,P).  Sizes outside the limits are refused before any launch: within them the skinning pass's staged frames
+ *     (hl_smplx_chunk_frames() of them) fit the default 64 KB of LDS. */
+size_t hl_smplx_packed_bytes(int V, int J, int S, int two_sets);
+int hl_smplx_pack(const float *v_template, const float *shapedirs, int sd_cols, int num_betas, int expr_start, int num_expr,
+                  const float *posedirs, const float *J_regressor, const float *weights, int V, int J, float *packed, void *stream);
+int hl_smplx_chunk_frames(void);
+size_t hl_smplx_pose_workspace_bytes(int J, int F);
+int hl_smplx_pose(const float *packed, const int32_t *parents, int V, int J, int S, int two_sets, int F, const float *poses, const float *coef,
+                  const float *transl, const float *rt, int rt_stride, const float *big, float *vertices, float *joints, float *bounds,
+                  float *verts4, float *table, float *big_out, void *workspace, size_t workspace_bytes, float margin, float y_margin,
+                  void *stream);
+
 /* ---- raw dataset views -> ViewStore arrays (recon_NeRF/lib/SynBody_dataset.py:266-278: imread / 255, img[msk == 0] = 0,
  *      cv2.resize INTER_AREA of the image, INTER_NEAREST of the mask) ----
  * Contract: DESIGN.md 4i; csrc/hl_view_ingest.hip.  The resize rule of one axis, src -> dst <= src, scale = src / dst in float64:

@@ -6,6 +6,9 @@ HIP events and host-inclusive time (wall clock around a synchronise) of
   (c) one canonical-space 128 x 128 view (64 + 64 samples) without prebuilt tables - a new pose per view (cache cleared) and the same
       pose again (cache hit, still fingerprinted) - and with them (tp_input['deform']).
 
+  (d) at SMPL-X size (10 475 vertices, 55 joints, a 400-column synthetic model): SmplxModel.pose for 1 frame and for 64 frames, and the
+      same rule - vertices, joints and bounds; no table - in fp32 torch ops on the device (NeRF/deform.py's generic functions, frame by frame).
+
     python scripts/body_pose_time.py [--reps 20] [--json out.json]
 """
 import argparse
@@ -39,6 +42,29 @@ def medians(fn, reps, before=None):
             dev_ms.append(start.elapsed_time(stop))
             host_ms.append((t1 - t0) * 1e3)
     return round(statistics.median(dev_ms), 4), round(statistics.median(host_ms), 4)
+
+
+def smplx_torch_rule(model, poses, coef, transl):
+    """SMPLX.forward + the dataset's bounds for every frame in torch ops on the model's device: poses (F,165) full poses, coef (F,20)."""
+    from humanliff_amd.NeRF import deform
+    t = model.tensors
+    sd = torch.cat([t["shapedirs"][..., :model.num_betas], t["shapedirs"][..., model.expr_start:model.expr_start + model.num_expr]], dim=-1)
+    m = dict(t, shapedirs=sd)
+    V = model.V
+    out = []
+    for f in range(poses.shape[0]):
+        A = deform.joint_transforms(m, poses[f], coef[f])
+        T = (t["weights"] @ A.reshape(-1, 16)).reshape(V, 4, 4)
+        v_shaped = t["v_template"] + sd @ coef[f]
+        vh = torch.cat([v_shaped + deform._pose_offsets(m, poses[f]), torch.ones((V, 1), device=poses.device)], dim=1)
+        v = torch.matmul(T, vh[:, :, None])[:, :3, 0] + transl[f]
+        rest = t["J_regressor"] @ v_shaped
+        joints = torch.matmul(A[:, :3, :3], rest[:, :, None])[:, :, 0] + A[:, :3, 3] + transl[f]
+        lo, hi = v.amin(dim=0) - 0.05, v.amax(dim=0) + 0.05
+        lo[1] -= 0.05
+        hi[1] += 0.05
+        out.append((v, joints, torch.stack([lo, hi])))
+    return out
 
 
 def main():
@@ -86,6 +112,22 @@ def main():
     out["c_view_128_same_pose_ms"] = dict(zip(("device", "host_inclusive"), medians(view(plain), a.reps)))
     out["c_view_128_prebuilt_ms"] = dict(zip(("device", "host_inclusive"), medians(view(tp), a.reps)))
     out["pose_1_frame_no_slower_than_deform_tables"] = out["b_pose_1_frame_ms"]["host_inclusive"] <= out["a_deform_tables_ms"]["host_inclusive"]
+
+    from humanliff_amd.body import load_smplx_model
+    xm = load_smplx_model(syn.smplx_like_model(10475, 23, 400), dev)
+    g = syn._gen(4)
+    parts = [(torch.randn((64, n), generator=g) * 0.25).to(dev) for n in (3, 63, 3, 3, 3, 45, 45)]
+    betas, expr, transl = [(torch.randn(s, generator=g) * 0.5).to(dev) for s in ((1, 10), (64, 10), (64, 3))]
+
+    def xpose(F):
+        go, bp, jaw, le, re, lh, rh = [p[:F] for p in parts]
+        return lambda: xm.pose(go, bp, betas, expr[:F], jaw, le, re, lh, rh, transl[:F])
+    first = xpose(64)()
+    out["smplx_V"] = 10475
+    for F in (1, 64):
+        out[f"d_smplx_pose_{F}_frame{'s' if F > 1 else ''}_ms"] = dict(zip(("device", "host_inclusive"), medians(xpose(F), a.reps)))
+        out[f"d_smplx_torch_ops_{F}_frame{'s' if F > 1 else ''}_ms"] = dict(zip(("device", "host_inclusive"), medians(
+            lambda: smplx_torch_rule(xm, first.poses[:F], first.shapes[:F], transl), a.reps)))
     print(json.dumps(out), flush=True)
     if a.json:
         with open(a.json, "w") as f:

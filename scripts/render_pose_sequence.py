@@ -4,9 +4,12 @@
 
     python scripts/render_pose_sequence.py --synthetic --out /tmp/seq [--frames 16] [--size 128] [--samples 64] [--fixed-camera]
     python scripts/render_pose_sequence.py --model assets/SMPL_NEUTRAL.pkl --poses poses.npz --planes planes.pt --mlp renderer.pt --out seq
+    python scripts/render_pose_sequence.py --smpl_type smplx --model assets/models/smplx [--gender female] --poses subject/smplx.npz ... --out seq
 
 --poses: an .npz with `poses` (F,72) and `shapes` (10,) or (F,10), optionally `R` (3,3) / (F,3,3) and `Th` (3,) / (F,3).
---planes: torch.save'd or .npy tri-planes (1,3,9,H,W) or (3,9,H,W); --mlp: the renderer's state dict.  --synthetic takes the seeded
+--planes: torch.save'd or .npy tri-planes (1,3,9,H,W) or (3,9,H,W); --mlp: the renderer's state dict.
+--smpl_type smplx: --model is an SMPLX_{GENDER}.npz or the directory of them, --poses a SynBody smplx.npz (its 'smplx' dict; --frames of
+its poses from the first on, the gender from its 'meta' unless --gender is given).  --synthetic takes the seeded
 stand-ins of humanliff_amd.synthetic for whatever is not given (the licensed body model is not shipped) and a swinging-limbs sequence.
 Frames are written as PNG (Pillow) or, without Pillow, as .npy; one JSON line of timings at the end.
 """
@@ -44,6 +47,8 @@ def load_array(path):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model")
+    ap.add_argument("--smpl_type", choices=["smpl", "smplx"], default="smpl")
+    ap.add_argument("--gender", default=None)
     ap.add_argument("--synthetic", action="store_true")
     ap.add_argument("--poses")
     ap.add_argument("--planes")
@@ -58,12 +63,27 @@ def main():
     from humanliff_amd import synthetic as syn
     from humanliff_amd.NeRF import Renderer
     from humanliff_amd.SynBodyView_datasets import camera_rays
-    from humanliff_amd.body import load_body_model
+    from humanliff_amd.body import load_body_model, load_smplx_model
     if not a.synthetic and not (a.model and a.poses and a.planes and a.mlp):
         ap.error("give --model, --poses, --planes and --mlp, or --synthetic for seeded stand-ins of what is missing")
     dev = torch.device("cuda:0")
-    model = load_body_model(a.model if a.model else syn.smpl_like_model(6890, 5), dev)
-    if a.poses:
+    smplx = a.smpl_type == "smplx"
+    if smplx:
+        fitted, gender = None, a.gender or "neutral"
+        if a.poses:
+            with np.load(a.poses, allow_pickle=True) as z:
+                fitted, gender = z["smplx"].item(), a.gender or z["meta"].item()["gender"]
+            fitted = {k: np.asarray(v, dtype=np.float32) if k == "betas" else np.asarray(v, dtype=np.float32)[:a.frames] for k, v in fitted.items()}
+        else:
+            body_pose = synthetic_sequence(a.frames)[:, 3:66]
+            fitted = {"global_orient": np.zeros((a.frames, 3), dtype=np.float32), "body_pose": body_pose, "betas": np.zeros((1, 10), dtype=np.float32),
+                      "expression": np.zeros((a.frames, 10), dtype=np.float32)}
+        model = load_smplx_model(a.model if a.model else syn.smplx_like_model(10475, 23), dev, gender=gender)
+    else:
+        model = load_body_model(a.model if a.model else syn.smpl_like_model(6890, 5), dev)
+    if smplx:
+        poses = shapes = R = Th = None
+    elif a.poses:
         z = np.load(a.poses)
         poses, shapes = z["poses"].astype(np.float32).reshape(-1, 72), z["shapes"].astype(np.float32)
         R, Th = (z["R"] if "R" in z.files else None), (z["Th"] if "Th" in z.files else None)
@@ -71,13 +91,16 @@ def main():
         poses, shapes, R, Th = synthetic_sequence(a.frames), np.zeros(10, dtype=np.float32), None, None
     planes = load_array(a.planes) if a.planes else syn.triplane(seed=11)
     planes = planes.reshape(1, 3, 9, *planes.shape[-2:]).to(dev)
-    r = Renderer(use_canonical_space=True, triplane_dim=planes.shape[-1], triplane_ch=27, test=True, body_model=model)
+    r = Renderer(use_canonical_space=True, triplane_dim=planes.shape[-1], triplane_ch=27, smpl_type=a.smpl_type, test=True, body_model=model)
     r.load_state_dict(torch.load(a.mlp, map_location="cpu") if a.mlp else syn.render_mlp_state(3), strict=False)
     r = r.to(dev)
 
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    posed = model.pose(torch.from_numpy(poses).to(dev), torch.from_numpy(shapes).to(dev), R, Th)      # every frame in one call
+    if smplx:
+        posed = model.pose_dict({k: torch.from_numpy(v) for k, v in fitted.items()})                   # every frame in one call
+    else:
+        posed = model.pose(torch.from_numpy(poses).to(dev), torch.from_numpy(shapes).to(dev), R, Th)
     bounds = posed.bounds_host()                                                                       # the one read-back of the sequence
     t1 = time.perf_counter()
     os.makedirs(a.out, exist_ok=True)

@@ -58,6 +58,9 @@ def parse():
     a.add_argument("--data", choices=["synthetic", "synbody", "tightcap"], default="synthetic")
     a.add_argument("--data_root", type=str, default=None, help="--data synbody / tightcap: a subject's directory; the human list lies beside it")
     a.add_argument("--smpl_model", type=str, default=None, help="--data synbody / tightcap: the SMPL asset (.pkl / .npz) load_body_model reads")
+    a.add_argument("--smpl_type", choices=["smpl", "smplx"], default="smpl",
+                   help="--data synbody: 'smplx' poses <subject>/smplx.npz with the SMPL-X models of --smplx_dir (the reference's default for SynBody)")
+    a.add_argument("--smplx_dir", type=str, default=None, help="--smpl_type smplx: the directory of SMPLX_{MALE,FEMALE,NEUTRAL}.npz")
     a.add_argument("--image_scaling", type=float, default=None, help="default: 0.5 (synbody), 1.0 (tightcap)")
     a.add_argument("--poses_num", type=int, default=1)
     a.add_argument("--pose_start", type=int, default=0)
@@ -95,13 +98,16 @@ def synbody_views(args, humans, dev):
     """The held-out views of a SynBody or TightCap tree, read and resized on the device (recon_NeRF/lib/SynBody_dataset.py,
     TightCap_dataset.py) and scored through ViewStore.test_view.  View id i is view i % views_num of cloth layer i // views_num (with
     --layer_idx: of that layer), first pose."""
-    from humanliff_amd.body import load_body_model
+    from humanliff_amd.body import load_body_model, load_smplx_models
     tightcap = args.data == "tightcap"
     if tightcap:
         from humanliff_amd.recon_NeRF.lib.TightCap_dataset import TightCapIndex as Index, load_view_store, store_test_views
     else:
         from humanliff_amd.recon_NeRF.lib.SynBody_dataset import SynBodyIndex as Index, load_view_store, store_test_views
-    if not args.data_root or not args.smpl_model:
+    smplx = args.smpl_type == "smplx"
+    if smplx and (tightcap or not args.data_root or not args.smplx_dir):
+        raise SystemExit("--smpl_type smplx is for --data synbody and needs --data_root DIR and --smplx_dir DIR")
+    if not smplx and (not args.data_root or not args.smpl_model):
         raise SystemExit(f"--data {args.data} needs --data_root DIR and --smpl_model PATH")
     image_scaling = (1.0 if tightcap else 0.5) if args.image_scaling is None else args.image_scaling
     ids = heldout_view_ids(args.views_num, args.test_layer_id, tightcap=tightcap, view_ids=args.view_ids)
@@ -111,8 +117,9 @@ def synbody_views(args, humans, dev):
     per_human = index.cloth_layer_num * per_layer
     layer_of = (lambda i: 0) if args.layer_idx is not None else (lambda i: (i // nv) % 4)
     items = [h * per_human + layer_of(i) * per_layer + i % nv for h in humans for i in ids]
-    store = load_view_store(index, load_body_model(args.smpl_model, dev), image_scaling=image_scaling, device=dev, items=items,
-                            decode_threads=args.decode_threads)
+    body = load_smplx_models(args.smplx_dir, dev) if smplx else load_body_model(args.smpl_model, dev)
+    store = load_view_store(index, body, image_scaling=image_scaling, device=dev, items=items, decode_threads=args.decode_threads,
+                            **({"smpl_type": "smplx"} if smplx else {}))
     return store_test_views(store, view_ids=[i for _ in humans for i in ids])
 
 

@@ -63,6 +63,9 @@ def parse():
     a.add_argument("--data", choices=["synthetic", "rendered", "synbody", "tightcap"], default="synthetic")
     a.add_argument("--data_root", type=str, default=None, help="--data synbody / tightcap: a subject's directory; the human list lies beside it")
     a.add_argument("--smpl_model", type=str, default=None, help="--data synbody / tightcap: the SMPL asset (.pkl / .npz) load_body_model reads")
+    a.add_argument("--smpl_type", choices=["smpl", "smplx"], default="smpl",
+                   help="--data synbody: 'smplx' poses <subject>/smplx.npz with the SMPL-X models of --smplx_dir (the reference's default for SynBody)")
+    a.add_argument("--smplx_dir", type=str, default=None, help="--smpl_type smplx: the directory of SMPLX_{MALE,FEMALE,NEUTRAL}.npz")
     a.add_argument("--image_scaling", type=float, default=None, help="default: 0.5 (synbody), 1.0 (tightcap)")
     a.add_argument("--views_num", type=int, default=None, help="default: 185 (synbody), 382 (tightcap)")
     a.add_argument("--poses_num", type=int, default=1)
@@ -161,7 +164,8 @@ def synbody_store(args, dev, body, data_root, multi_person, num_instance, layer_
     Index, load_view_store, _ = dataset_reader(args)
     index = Index(data_root, multi_person=multi_person, num_instance=num_instance, pose_start=args.pose_start,
                          pose_interval=args.pose_interval, poses_num=args.poses_num, views_num=args.views_num, layer_idx=layer_idx)
-    store = load_view_store(index, body, image_scaling=args.image_scaling, device=dev, decode_threads=args.decode_threads)
+    kw = {"smpl_type": "smplx"} if args.smpl_type == "smplx" else {}
+    store = load_view_store(index, body, image_scaling=args.image_scaling, device=dev, decode_threads=args.decode_threads, **kw)
     print(f"loaded {len(store)} views of {store.H} x {store.W} from {data_root}"
           f"{'' if layer_idx is None else f' (cloth layer {layer_idx})'}; class counts (body, background) of the first: "
           f"{store.class_counts()[0].tolist()}", flush=True)
@@ -216,11 +220,16 @@ def finetune_synbody(args, dev, body, kw):
 
 
 def fit_synbody(args, model, dev, kw):
-    from humanliff_amd.body import load_body_model
+    from humanliff_amd.body import load_body_model, load_smplx_models
     from humanliff_amd.recon_NeRF.lib.if_nerf_data_utils import RayBatchLoader
-    if not args.data_root or not args.smpl_model:
-        raise SystemExit(f"--data {args.data} needs --data_root DIR and --smpl_model PATH")
-    body = load_body_model(args.smpl_model, dev)
+    if args.smpl_type == "smplx":
+        if args.data != "synbody" or not args.data_root or not args.smplx_dir:
+            raise SystemExit("--smpl_type smplx is for --data synbody and needs --data_root DIR and --smplx_dir DIR")
+        body = load_smplx_models(args.smplx_dir, dev)
+    else:
+        if not args.data_root or not args.smpl_model:
+            raise SystemExit(f"--data {args.data} needs --data_root DIR and --smpl_model PATH")
+        body = load_body_model(args.smpl_model, dev)
     if args.ft_triplane_only:
         return finetune_synbody(args, dev, body, kw)
     store = synbody_store(args, dev, body, args.data_root, not args.single_person, 1 if args.single_person else args.num_instance, args.layer_idx)
