@@ -1,4 +1,4 @@
-"""The body model on the device: loading an SMPL-style asset and posing it with the hl_body_* kernels (csrc/hl_body.hip).
+"""The body model on the device: loading an SMPL-style asset and posing it with the hl_body_* / hl_smplx_* kernels (csrc/hl_body.hip).
 
 The reference poses the body in its dataset code with numpy (smpl/smpl_numpy.py, SynBodyView_datasets.py:141-194) and rebuilds the
 per-point deformation inputs with stock PyTorch ops.  Here one call poses a frame or a whole sequence: posed vertices, joints and
@@ -10,8 +10,8 @@ renderer handed `tp_input['deform']` runs no torch op chain and reads nothing ba
     posed = model.pose(poses, shapes, R, Th)          # (F, 72), (10,) or (F, 10), (3, 3) or (F, 3, 3), (3,) or (F, 3)
     out = renderer.render(posed.tp_input(f), ...)
 
-SMPL-X, which the reference's SynBody flows use by default, has a loader and kernels of its own (csrc/hl_smplx.hip) and
-returns the same PosedBody:
+SMPL-X, which the reference's SynBody flows use by default, has a loader of its own and runs the same kernels with its additions
+compiled in; it returns the same PosedBody:
 
     model = load_smplx_model("assets/models/smplx", "cuda", gender="female")
     posed = model.pose_dict(params)                   # the keys of <subject>/smplx.npz: global_orient, body_pose, betas, expression, ...
@@ -68,6 +68,22 @@ def _parents(kintree):
     return parents
 
 
+def _as_np(v):
+    return v.detach().cpu().numpy() if torch.is_tensor(v) else _dense(v)
+
+
+def _model_tensors(raw, device, posedirs_2d=False):
+    """SMPL_to_tensor on `device`: MODEL_KEYS as float32, the two index tables as long -> (tensors, parents).  `posedirs_2d`: a (3V,P)
+    posedirs, as the SMPL-X files store it, becomes (V,3,P)."""
+    tensors = {}
+    for k in MODEL_KEYS:
+        a = np.array(_as_np(raw[k])).astype(float)
+        if posedirs_2d and k == 'posedirs' and a.ndim == 2:
+            a = a.reshape(a.shape[0] // 3, 3, -1)
+        tensors[k] = torch.tensor(a, dtype=torch.long if k in ('kintree_table', 'f') else torch.float32, device=device)
+    return tensors, _parents(_as_np(raw['kintree_table']))
+
+
 def load_body_model(src, device=None):
     """src: a dict, an .npz or a pickle with the SMPL keys (J_regressor may be a scipy sparse matrix) -> BodyModel on `device`."""
     raw = _read(src)
@@ -75,54 +91,104 @@ def load_body_model(src, device=None):
         if k not in raw:
             raise KeyError(k)
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    as_np = lambda v: v.detach().cpu().numpy() if torch.is_tensor(v) else _dense(v)  # noqa: E731
-    tensors = {}
-    for k in MODEL_KEYS:                     # SMPL_to_tensor: float32, the two index tables as long
-        a = np.array(as_np(raw[k])).astype(float)
-        tensors[k] = torch.tensor(a, dtype=torch.long if k in ('kintree_table', 'f') else torch.float32, device=device)
-    return BodyModel(tensors, _parents(as_np(raw['kintree_table'])))
+    return BodyModel(*_model_tensors(raw, device))
 
 
-class BodyModel:
-    """`.tensors`: the fp32 device tensors under the SMPL_to_tensor keys (what Renderer.SMPL_NEUTRAL holds); `.parents`; the packed
-    buffers of hl_body_pack, made at the first pose() and kept."""
+class _DeviceModel:
+    """What BodyModel and SmplxModel share: the check of the model's arrays, the packed buffers (made at the first pose and kept), the
+    staging of a call's inputs and outputs, and the PosedBody.  A subclass names itself (`NAME`, `LABEL`), packs (`_pack_into`) and
+    hands `_run` the arguments of its pose entry point."""
 
     def __init__(self, tensors, parents):
         t = tensors
         V, J = t['weights'].shape
-        if not 2 <= J <= MAX_JOINTS:
-            raise ValueError(f"body model with {J} joints: the kernels take 2 .. {MAX_JOINTS}")
         if tuple(t['v_template'].shape) != (V, 3) or tuple(t['posedirs'].shape) != (V, 3, 9 * (J - 1)) or \
                 tuple(t['J_regressor'].shape) != (J, V) or tuple(t['shapedirs'].shape[:2]) != (V, 3) or len(parents) != J:
-            raise ValueError("body model: shapes do not fit together (v_template (V,3), shapedirs (V,3,S), posedirs (V,3,9(J-1)), "
+            raise ValueError(f"{self.LABEL}: shapes do not fit together (v_template (V,3), shapedirs (V,3,S), posedirs (V,3,9(J-1)), "
                              "J_regressor (J,V), weights (V,J), kintree_table (2,J))")
-        self.tensors = tensors
-        self.parents = list(parents)
+        self.tensors, self.parents = tensors, list(parents)
         self.V, self.J = int(V), int(J)
-        self.Sp = min(int(t['shapedirs'].shape[2]), MAX_SHAPES)
         self.device = t['v_template'].device
         self.packed = None
         self._parents_dev = None
-        self._big = None
 
-    # ---- packing ---------------------------------------------------------------------------------
-    def _need_device(self, what):
+    def _need_device(self):
         if self.device.type != "cuda":
-            raise RuntimeError(f"{what} needs the body model on a CUDA(HIP) device; there is no CPU path")
+            raise RuntimeError(f"{self.NAME}.pose needs the body model on a CUDA(HIP) device; there is no CPU path")
 
     def _pack(self):
         if self.packed is None:
-            self._need_device("BodyModel.pose")
-            L, t = _lib.lib(), self.tensors
-            c = {k: t[k].contiguous() for k in ('v_template', 'shapedirs', 'posedirs', 'J_regressor', 'weights')}
-            buf = torch.empty(L.hl_body_packed_bytes(self.V, self.J, self.Sp) // 4, dtype=torch.float32, device=self.device)
-            with _lib.on(self.device):
-                _lib.check(L.hl_body_pack(_lib.ptr(c['v_template']), _lib.ptr(c['shapedirs']), int(c['shapedirs'].shape[2]),
-                                          _lib.ptr(c['posedirs']), _lib.ptr(c['J_regressor']), _lib.ptr(c['weights']), self.V, self.J, self.Sp,
-                                          _lib.ptr(buf), _lib.stream_ptr(self.device)), "hl_body_pack")
+            self._need_device()
+            c = {k: self.tensors[k].contiguous() for k in ('v_template', 'shapedirs', 'posedirs', 'J_regressor', 'weights')}
+            packed = self._pack_into(_lib.lib(), c)
             self._parents_dev = torch.tensor(self.parents, dtype=torch.int32, device=self.device)
-            self.packed = buf
+            self.packed = packed
         return self.packed
+
+    def _dev(self, t, what):
+        if not torch.is_tensor(t):
+            return torch.as_tensor(np.asarray(t, dtype=np.float32)).to(self.device, non_blocking=True)
+        if not t.is_cuda:
+            raise RuntimeError(f"{self.NAME}.pose: `{what}` is a CPU tensor; there is no CPU path (move it to the model's device)")
+        return t.detach().to(device=self.device, dtype=torch.float32)
+
+    def _run(self, entry, model_args, ws_bytes, ws_joint_floats, F, poses, shapes, R, Th, big, y_margin):
+        """One call of the pose entry point `entry`: `model_args` are its arguments between J and rt, `ws_bytes` names its workspace
+        query; the workspace is A (F,J,16) | ... | the pose features (F,P), `ws_joint_floats` per joint before the features.  R, Th:
+        host arrays or tensors, one or F of each (None: I, 0).  Returns the PosedBody of the F frames."""
+        L, J, V, dev = _lib.lib(), self.J, self.V, self.device
+        host = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)  # noqa: E731
+        Rh = np.ascontiguousarray(host(np.eye(3) if R is None else R), dtype=np.float32).reshape(-1, 3, 3)
+        Thh = np.ascontiguousarray(host(np.zeros(3) if Th is None else Th), dtype=np.float32).reshape(-1, 3)
+        if Rh.shape[0] not in (1, F) or Thh.shape[0] not in (1, F):
+            raise ValueError(f"{self.NAME}.pose: R for {Rh.shape[0]} frames, Th for {Thh.shape[0]}, poses for {F}")
+        n_rt = max(Rh.shape[0], Thh.shape[0])
+        Rh = np.array(np.broadcast_to(Rh, (n_rt, 3, 3)), dtype=np.float32)
+        Thh = np.array(np.broadcast_to(Thh, (n_rt, 3)), dtype=np.float32)
+        rt_host = torch.empty((n_rt, 12), dtype=torch.float32, pin_memory=True)      # (pinned: the upload below only enqueues)
+        rt_host[:, :9] = torch.from_numpy(Rh.reshape(n_rt, 9))
+        rt_host[:, 9:] = torch.from_numpy(Thh)
+        packed = self._pack()
+        new = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)  # noqa: E731
+        with _lib.on(dev):
+            rt = rt_host.to(dev, non_blocking=True)
+            vertices, joints, bounds, verts4 = new(F, V, 3), new(F, J, 3), new(F, 2, 3), new(F, V, 4)
+            table = new(F, V, 36) if big is not None else None
+            rows = new(F, V, 16) if big is None else None
+            ws = new(getattr(L, ws_bytes)(J, F) // 4)
+            _lib.check(getattr(L, entry)(_lib.ptr(packed), _lib.ptr(self._parents_dev, torch.int32), V, J, *model_args, _lib.ptr(rt),
+                                         12 if n_rt > 1 else 0, _lib.ptr(big.rows[0]) if big is not None else None, _lib.ptr(vertices),
+                                         _lib.ptr(joints), _lib.ptr(bounds), _lib.ptr(verts4), _lib.ptr(table), _lib.ptr(rows), _lib.ptr(ws),
+                                         ws.numel() * 4, 0.05, float(y_margin), _lib.stream_ptr(dev)), entry)
+        posed = PosedBody()
+        posed.model, posed.big, posed.F = self, big, F
+        posed.vertices, posed.joints, posed.world_bounds, posed.verts4, posed.table, posed.rows = vertices, joints, bounds, verts4, table, rows
+        posed.A, posed.pose_features = ws[:F * J * 16].view(F, J, 4, 4), ws[F * J * ws_joint_floats:].view(F, 9 * (J - 1))
+        posed.R, posed.Th, posed.rt = Rh, Thh, rt
+        posed.poses, posed.shapes = poses, shapes
+        return posed
+
+
+class BodyModel(_DeviceModel):
+    """`.tensors`: the fp32 device tensors under the SMPL_to_tensor keys (what Renderer.SMPL_NEUTRAL holds); `.parents`; the packed
+    buffers of hl_body_pack, made at the first pose() and kept."""
+    NAME, LABEL = "BodyModel", "body model"
+
+    def __init__(self, tensors, parents):
+        J = tensors['weights'].shape[1]
+        if not 2 <= J <= MAX_JOINTS:
+            raise ValueError(f"body model with {J} joints: the kernels take 2 .. {MAX_JOINTS}")
+        super().__init__(tensors, parents)
+        self.Sp = min(int(tensors['shapedirs'].shape[2]), MAX_SHAPES)
+        self._big = None
+
+    def _pack_into(self, L, c):
+        buf = torch.empty(L.hl_body_packed_bytes(self.V, self.J, self.Sp) // 4, dtype=torch.float32, device=self.device)
+        with _lib.on(self.device):
+            _lib.check(L.hl_body_pack(_lib.ptr(c['v_template']), _lib.ptr(c['shapedirs']), int(c['shapedirs'].shape[2]),
+                                      _lib.ptr(c['posedirs']), _lib.ptr(c['J_regressor']), _lib.ptr(c['weights']), self.V, self.J, self.Sp,
+                                      _lib.ptr(buf), _lib.stream_ptr(self.device)), "hl_body_pack")
+        return buf
 
     # ---- the big pose ----------------------------------------------------------------------------
     def big_pose_params(self):
@@ -156,24 +222,15 @@ class BodyModel:
         """poses (F,3J) or (3J,), shapes (S,) or (F,S): device tensors.  R (3,3) or (F,3,3), Th (3,) or (F,3): host arrays (enqueue-only)
         or device tensors (one read back here: the deform kernels take them from the host).  Returns a PosedBody of F frames.
         `y_margin`: what world_bounds adds on y beyond the 0.05 of every axis - 0.05 for SynBody, 0.1 for TightCap (TightCap_dataset.py:165-168)."""
-        self._need_device("BodyModel.pose")
+        self._need_device()
         return self._pose(poses, shapes, R, Th, big=self.big_pose(), y_margin=y_margin)
 
-    def _dev(self, t, what):
-        if not torch.is_tensor(t):
-            t = torch.as_tensor(np.asarray(t, dtype=np.float32))
-            return t.to(self.device, non_blocking=True)
-        if not t.is_cuda:
-            raise RuntimeError(f"BodyModel.pose: `{what}` is a CPU tensor; there is no CPU path (move it to the model's device)")
-        return t.detach().to(device=self.device, dtype=torch.float32)
-
     def _pose(self, poses, shapes, R, Th, big, y_margin=0.05):
-        self._need_device("BodyModel.pose")
+        self._need_device()
         for name, t in (("poses", poses), ("shapes", shapes), ("R", R), ("Th", Th)):
             if torch.is_tensor(t) and not t.is_cuda:
                 raise RuntimeError(f"BodyModel.pose: `{name}` is a CPU tensor; there is no CPU path (move it to the model's device)")
-        L, J, V = _lib.lib(), self.J, self.V
-        poses = self._dev(poses, "poses").reshape(-1, 3 * J).contiguous()
+        poses = self._dev(poses, "poses").reshape(-1, 3 * self.J).contiguous()
         F = int(poses.shape[0])
         shapes = self._dev(shapes, "shapes")
         S = int(shapes.shape[-1])
@@ -182,40 +239,9 @@ class BodyModel:
         shapes = shapes.reshape(-1, S).contiguous()
         if shapes.shape[0] not in (1, F):
             raise ValueError(f"BodyModel.pose: shapes for {shapes.shape[0]} frames, poses for {F}")
-        host = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)  # noqa: E731
-        Rh = np.ascontiguousarray(host(np.eye(3) if R is None else R), dtype=np.float32).reshape(-1, 3, 3)
-        Thh = np.ascontiguousarray(host(np.zeros(3) if Th is None else Th), dtype=np.float32).reshape(-1, 3)
-        if Rh.shape[0] not in (1, F) or Thh.shape[0] not in (1, F):
-            raise ValueError(f"BodyModel.pose: R for {Rh.shape[0]} frames, Th for {Thh.shape[0]}, poses for {F}")
-        n_rt = max(Rh.shape[0], Thh.shape[0])
-        Rh = np.array(np.broadcast_to(Rh, (n_rt, 3, 3)), dtype=np.float32)
-        Thh = np.array(np.broadcast_to(Thh, (n_rt, 3)), dtype=np.float32)
-        rt_host = torch.empty((n_rt, 12), dtype=torch.float32, pin_memory=True)      # (pinned: the upload below only enqueues)
-        rt_host[:, :9] = torch.from_numpy(Rh.reshape(n_rt, 9))
-        rt_host[:, 9:] = torch.from_numpy(Thh)
-        packed = self._pack()
-        dev = self.device
-        new = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)  # noqa: E731
-        with _lib.on(dev):
-            rt = rt_host.to(dev, non_blocking=True)
-            vertices, joints, bounds = new(F, V, 3), new(F, J, 3), new(F, 2, 3)
-            verts4 = new(F, V, 4)
-            table = new(F, V, 36) if big is not None else None
-            rows = new(F, V, 16) if big is None else None
-            ws = new(L.hl_body_pose_workspace_bytes(J, F) // 4)
-            # (hl_body_pose with the margins of the bounds spelled out: 0.05f, 0.05f is what that call passes)
-            _lib.check(L.hl_pose_body_margins(_lib.ptr(packed), _lib.ptr(self._parents_dev, torch.int32), V, J, self.Sp, S, F, _lib.ptr(poses),
-                                              _lib.ptr(shapes), S if shapes.shape[0] == F and F > 1 else 0, _lib.ptr(rt), 12 if n_rt > 1 else 0,
-                                              _lib.ptr(big.rows[0]) if big is not None else None, _lib.ptr(vertices), _lib.ptr(joints),
-                                              _lib.ptr(bounds), _lib.ptr(verts4), _lib.ptr(table), _lib.ptr(rows), _lib.ptr(ws), ws.numel() * 4,
-                                              0.05, float(y_margin), _lib.stream_ptr(dev)), "hl_pose_body_margins")
-        posed = PosedBody()
-        posed.model, posed.big, posed.F = self, big, F
-        posed.vertices, posed.joints, posed.world_bounds, posed.verts4, posed.table, posed.rows = vertices, joints, bounds, verts4, table, rows
-        posed.A, posed.pose_features = ws[:F * J * 16].view(F, J, 4, 4), ws[F * J * 16:].view(F, 9 * (J - 1))
-        posed.R, posed.Th, posed.rt = Rh, Thh, rt
-        posed.poses, posed.shapes = poses, shapes
-        return posed
+        # (hl_body_pose with the margins of the bounds spelled out: 0.05f, 0.05f is what that call passes)
+        args = (self.Sp, S, F, _lib.ptr(poses), _lib.ptr(shapes), S if shapes.shape[0] == F and F > 1 else 0)
+        return self._run("hl_pose_body_margins", args, "hl_body_pose_workspace_bytes", 16, F, poses, shapes, R, Th, big, y_margin)
 
 
 class PosedBody:
@@ -270,13 +296,7 @@ def load_smplx_model(src, device=None, num_betas=10, num_expression_coeffs=10, f
         if k not in raw:
             raise KeyError(k)
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    as_np = lambda v: v.detach().cpu().numpy() if torch.is_tensor(v) else _dense(v)  # noqa: E731
-    tensors = {}
-    for k in MODEL_KEYS:
-        a = np.array(as_np(raw[k])).astype(float)
-        if k == 'posedirs' and a.ndim == 2:
-            a = a.reshape(a.shape[0] // 3, 3, -1)
-        tensors[k] = torch.tensor(a, dtype=torch.long if k in ('kintree_table', 'f') else torch.float32, device=device)
+    tensors, parents = _model_tensors(raw, device, posedirs_2d=True)
     cols = int(tensors['shapedirs'].shape[2])
     if cols < SHAPE_SPACE_DIM + EXPRESSION_SPACE_DIM:
         num_betas, e0, num_expr = min(int(num_betas), 10), 10, min(int(num_expression_coeffs), 10)
@@ -284,9 +304,9 @@ def load_smplx_model(src, device=None, num_betas=10, num_expression_coeffs=10, f
         num_betas, e0, num_expr = min(int(num_betas), SHAPE_SPACE_DIM), SHAPE_SPACE_DIM, min(int(num_expression_coeffs), EXPRESSION_SPACE_DIM)
     pose_mean = np.zeros(3 * sum(n for _, n in SMPLX_PARTS), dtype=np.float32)
     if not flat_hand_mean:
-        pose_mean[-90:-45] = np.asarray(as_np(raw['hands_meanl']), dtype=np.float32).reshape(-1)
-        pose_mean[-45:] = np.asarray(as_np(raw['hands_meanr']), dtype=np.float32).reshape(-1)
-    return SmplxModel(tensors, _parents(as_np(raw['kintree_table'])), num_betas, e0, num_expr, torch.from_numpy(pose_mean).to(device))
+        pose_mean[-90:-45] = np.asarray(_as_np(raw['hands_meanl']), dtype=np.float32).reshape(-1)
+        pose_mean[-45:] = np.asarray(_as_np(raw['hands_meanr']), dtype=np.float32).reshape(-1)
+    return SmplxModel(tensors, parents, num_betas, e0, num_expr, torch.from_numpy(pose_mean).to(device))
 
 
 def load_smplx_models(model_dir, device=None, genders=('male', 'female', 'neutral'), **kw):
@@ -298,52 +318,35 @@ def load_smplx_models(model_dir, device=None, genders=('male', 'female', 'neutra
     return found
 
 
-class SmplxModel:
-    """An SMPL-X body on the device (csrc/hl_smplx.hip).  `.tensors`: the fp32 device tensors under the SMPL_to_tensor keys,
+class SmplxModel(_DeviceModel):
+    """An SMPL-X body on the device (csrc/hl_body.hip).  `.tensors`: the fp32 device tensors under the SMPL_to_tensor keys,
     shapedirs with every column of the file (what Renderer.SMPL_NEUTRAL holds for smpl_type 'smplx'); `.parents`; `.num_betas`,
     `.expr_start`, `.num_expr`: the columns of shapedirs that shape the body; `.pose_mean` (165,)."""
+    NAME, LABEL = "SmplxModel", "SMPL-X model"
 
     def __init__(self, tensors, parents, num_betas, expr_start, num_expr, pose_mean):
-        t = tensors
-        V, J = t['weights'].shape
+        J = tensors['weights'].shape[1]
         if J != sum(n for _, n in SMPLX_PARTS):
             raise ValueError(f"SMPL-X model with {J} joints: the full pose has {sum(n for _, n in SMPLX_PARTS)}")
-        if tuple(t['v_template'].shape) != (V, 3) or tuple(t['posedirs'].shape) != (V, 3, 9 * (J - 1)) or \
-                tuple(t['J_regressor'].shape) != (J, V) or tuple(t['shapedirs'].shape[:2]) != (V, 3) or len(parents) != J:
-            raise ValueError("SMPL-X model: shapes do not fit together (v_template (V,3), shapedirs (V,3,S), posedirs (V,3,9(J-1)), "
-                             "J_regressor (J,V), weights (V,J), kintree_table (2,J))")
-        cols = int(t['shapedirs'].shape[2])
+        super().__init__(tensors, parents)
+        cols = int(tensors['shapedirs'].shape[2])
         S = num_betas + num_expr
         if not (1 <= S <= SMPLX_MAX_COEFFS and num_betas <= expr_start and expr_start + num_expr <= cols):
             raise ValueError(f"SMPL-X model: {num_betas} betas and {num_expr} expression coefficients from column {expr_start} of {cols}; "
                              f"the kernels take 1 .. {SMPLX_MAX_COEFFS} coefficients in all")
-        self.tensors, self.parents = tensors, list(parents)
-        self.V, self.J, self.S = int(V), int(J), int(S)
+        self.S = int(S)
         self.num_betas, self.expr_start, self.num_expr = int(num_betas), int(expr_start), int(num_expr)
         self.two_sets = int(num_expr > 0 and expr_start != num_betas)
         self.pose_mean = pose_mean
-        self.device = t['v_template'].device
-        self.packed = None
-        self._parents_dev = None
         self._big = {}
 
-    def _need_device(self, what):
-        if self.device.type != "cuda":
-            raise RuntimeError(f"{what} needs the body model on a CUDA(HIP) device; there is no CPU path")
-
-    def _pack(self):
-        if self.packed is None:
-            self._need_device("SmplxModel.pose")
-            L, t = _lib.lib(), self.tensors
-            c = {k: t[k].contiguous() for k in ('v_template', 'shapedirs', 'posedirs', 'J_regressor', 'weights')}
-            buf = torch.empty(L.hl_smplx_packed_bytes(self.V, self.J, self.S, self.two_sets) // 4, dtype=torch.float32, device=self.device)
-            with _lib.on(self.device):
-                _lib.check(L.hl_smplx_pack(_lib.ptr(c['v_template']), _lib.ptr(c['shapedirs']), int(c['shapedirs'].shape[2]), self.num_betas,
-                                           self.expr_start, self.num_expr, _lib.ptr(c['posedirs']), _lib.ptr(c['J_regressor']),
-                                           _lib.ptr(c['weights']), self.V, self.J, _lib.ptr(buf), _lib.stream_ptr(self.device)), "hl_smplx_pack")
-            self._parents_dev = torch.tensor(self.parents, dtype=torch.int32, device=self.device)
-            self.packed = buf
-        return self.packed
+    def _pack_into(self, L, c):
+        buf = torch.empty(L.hl_smplx_packed_bytes(self.V, self.J, self.S, self.two_sets) // 4, dtype=torch.float32, device=self.device)
+        with _lib.on(self.device):
+            _lib.check(L.hl_smplx_pack(_lib.ptr(c['v_template']), _lib.ptr(c['shapedirs']), int(c['shapedirs'].shape[2]), self.num_betas,
+                                       self.expr_start, self.num_expr, _lib.ptr(c['posedirs']), _lib.ptr(c['J_regressor']),
+                                       _lib.ptr(c['weights']), self.V, self.J, _lib.ptr(buf), _lib.stream_ptr(self.device)), "hl_smplx_pack")
+        return buf
 
     # ---- the big pose ----------------------------------------------------------------------------
     def big_pose_params(self, global_orient=None):
@@ -379,7 +382,7 @@ class SmplxModel:
         """SMPLX.forward for F frames: global_orient (F,3), body_pose (F,63), betas (nb,) / (1,nb) shared or (F,nb), expression (F,ne), the
         other parts (F,3) / (F,45) or None for zeros, transl (F,3) or None: device tensors (host arrays are uploaded).  R, Th: the dataset's
         world transform, as BodyModel.pose takes them.  `big_global_orient`: which big pose the tables' canonical columns come from."""
-        self._need_device("SmplxModel.pose")
+        self._need_device()
         parts = {'global_orient': global_orient, 'body_pose': body_pose, 'jaw_pose': jaw_pose, 'leye_pose': leye_pose, 'reye_pose': reye_pose,
                  'left_hand_pose': left_hand_pose, 'right_hand_pose': right_hand_pose}
         return self._pose(parts, betas, expression, transl, R, Th, big=self.big_pose(big_global_orient), y_margin=y_margin)
@@ -387,22 +390,15 @@ class SmplxModel:
     def pose_dict(self, d, R=None, Th=None, y_margin=0.05, big_global_orient=None):
         """pose() of a dict under the key names of a SynBody smplx.npz (missing parts are zeros; other keys are ignored).  Host tensors,
         as the dataset's prepare_smpl_params makes them, are uploaded."""
-        self._need_device("SmplxModel.pose")
+        self._need_device()
         d = {k: (v.to(self.device) if torch.is_tensor(v) and k not in ('R', 'Th') else v) for k, v in d.items()}
         return self.pose(d['global_orient'], d['body_pose'], d['betas'], d['expression'], d.get('jaw_pose'), d.get('leye_pose'), d.get('reye_pose'),
                          d.get('left_hand_pose'), d.get('right_hand_pose'), d.get('transl'), R if R is not None else d.get('R'),
                          Th if Th is not None else d.get('Th'), y_margin=y_margin, big_global_orient=big_global_orient)
 
-    def _dev(self, t, what):
-        if not torch.is_tensor(t):
-            return torch.as_tensor(np.asarray(t, dtype=np.float32)).to(self.device, non_blocking=True)
-        if not t.is_cuda:
-            raise RuntimeError(f"SmplxModel.pose: `{what}` is a CPU tensor; there is no CPU path (move it to the model's device)")
-        return t.detach().to(device=self.device, dtype=torch.float32)
-
     def _pose(self, parts, betas, expression, transl, R, Th, big, y_margin=0.05):
-        self._need_device("SmplxModel.pose")
-        L, J, V, S, dev = _lib.lib(), self.J, self.V, self.S, self.device
+        self._need_device()
+        dev = self.device
         go = self._dev(parts['global_orient'], 'global_orient').reshape(-1, 3)
         F = int(go.shape[0])
         cols = []
@@ -422,34 +418,7 @@ class SmplxModel:
             transl = self._dev(transl, 'transl').reshape(-1, 3).contiguous()
             if transl.shape[0] != F:
                 raise ValueError(f"SmplxModel.pose: transl for {transl.shape[0]} frames, poses for {F}")
-        host = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)  # noqa: E731
-        Rh = np.ascontiguousarray(host(np.eye(3) if R is None else R), dtype=np.float32).reshape(-1, 3, 3)
-        Thh = np.ascontiguousarray(host(np.zeros(3) if Th is None else Th), dtype=np.float32).reshape(-1, 3)
-        if Rh.shape[0] not in (1, F) or Thh.shape[0] not in (1, F):
-            raise ValueError(f"SmplxModel.pose: R for {Rh.shape[0]} frames, Th for {Thh.shape[0]}, poses for {F}")
-        n_rt = max(Rh.shape[0], Thh.shape[0])
-        Rh = np.array(np.broadcast_to(Rh, (n_rt, 3, 3)), dtype=np.float32)
-        Thh = np.array(np.broadcast_to(Thh, (n_rt, 3)), dtype=np.float32)
-        rt_host = torch.empty((n_rt, 12), dtype=torch.float32, pin_memory=True)
-        rt_host[:, :9] = torch.from_numpy(Rh.reshape(n_rt, 9))
-        rt_host[:, 9:] = torch.from_numpy(Thh)
-        packed = self._pack()
-        new = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)  # noqa: E731
-        with _lib.on(dev):
-            rt = rt_host.to(dev, non_blocking=True)
-            vertices, joints, bounds, verts4 = new(F, V, 3), new(F, J, 3), new(F, 2, 3), new(F, V, 4)
-            table = new(F, V, 36) if big is not None else None
-            rows = new(F, V, 16) if big is None else None
-            ws = new(L.hl_smplx_pose_workspace_bytes(J, F) // 4)
-            _lib.check(L.hl_smplx_pose(_lib.ptr(packed), _lib.ptr(self._parents_dev, torch.int32), V, J, S, self.two_sets, F, _lib.ptr(poses),
-                                       _lib.ptr(coef), _lib.ptr(transl), _lib.ptr(rt), 12 if n_rt > 1 else 0,
-                                       _lib.ptr(big.rows[0]) if big is not None else None, _lib.ptr(vertices), _lib.ptr(joints), _lib.ptr(bounds),
-                                       _lib.ptr(verts4), _lib.ptr(table), _lib.ptr(rows), _lib.ptr(ws), ws.numel() * 4, 0.05, float(y_margin),
-                                       _lib.stream_ptr(dev)), "hl_smplx_pose")
-        posed = PosedBody()
-        posed.model, posed.big, posed.F = self, big, F
-        posed.vertices, posed.joints, posed.world_bounds, posed.verts4, posed.table, posed.rows = vertices, joints, bounds, verts4, table, rows
-        posed.A, posed.pose_features = ws[:F * J * 16].view(F, J, 4, 4), ws[F * J * 20:].view(F, 9 * (J - 1))
-        posed.R, posed.Th, posed.rt = Rh, Thh, rt
-        posed.poses, posed.shapes, posed.transl = poses, coef, transl
+        args = (self.S, self.two_sets, F, _lib.ptr(poses), _lib.ptr(coef), _lib.ptr(transl))
+        posed = self._run("hl_smplx_pose", args, "hl_smplx_pose_workspace_bytes", 20, F, poses, coef, R, Th, big, y_margin)
+        posed.transl = transl
         return posed

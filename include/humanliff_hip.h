@@ -891,7 +891,7 @@ int hl_pose_body_margins(const float *packed, const int32_t *parents, int V, int
 
 /* ---- posing an SMPL-X body: SMPLX.forward + lbs of the smplx package (recon_NeRF/smplx/body_models.py:1188-1242, smplx/lbs.py), the
  *      dataset's R / Th and bounds (SynBody_dataset.py:182-192) and the renderer's per-vertex tables ----
- * Contract: DESIGN.md 4k; csrc/hl_smplx.hip.  The conventions of hl_body_pose hold (fp32, fixed order, enqueue-only, nothing allocated).
+ * Contract: DESIGN.md 4k; csrc/hl_body.hip (the X = true kernels).  The conventions of hl_body_pose hold (fp32, fixed order, enqueue-only, nothing allocated).
  * V vertices, 2 <= J <= 64 joints, P = 9 (J - 1), 1 <= S <= 32 coefficients (betas followed by expression), F >= 1 frames.
  *   hl_smplx_pack (once per model): as hl_body_pack, with TWO sets of S shape directions taken from shapedirs (V,3,sd_cols):
  *       set 1: columns [0, num_betas) followed by [expr_start, expr_start + num_expr) - shapes the body;

@@ -1,5 +1,5 @@
 """Float64 numpy restatement of posing an SMPL-X body, written from the formulas (Pavlakos et al., SMPL-X, 2019; Loper et al., SMPL,
-2015, eq. 2-10) with the conventions of the smplx package as the reference runs it - the truth the kernels of csrc/hl_smplx.hip and the
+2015, eq. 2-10) with the conventions of the smplx package as the reference runs it - the truth the kernels of csrc/hl_body.hip and the
 fp32 torch path are both measured against.
 
     full_pose = global | body 21 | jaw | leye | reye | left hand 15 | right hand 15, + pose_mean           (165 values)

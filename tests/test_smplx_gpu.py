@@ -1,4 +1,4 @@
-"""Posing an SMPL-X body on the device (csrc/hl_smplx.hip, humanliff_amd/body.py: SmplxModel), the renderer's hook for its tables and the
+"""Posing an SMPL-X body on the device (csrc/hl_body.hip, humanliff_amd/body.py: SmplxModel), the renderer's hook for its tables and the
 SynBody loader's smpl_type='smplx'.
 
 The truth is the reference's own float64 output (tests/golden/smplx.npz: smplx.body_models.SMPLX with dtype=torch.float64) or the float64
@@ -170,6 +170,49 @@ def test_small_shapes(dev, V, F, cols):
         one = pose(model, d, dev, *rt(f), f=f)
         for k in fields:
             assert torch.equal(getattr(posed, k)[f], getattr(one, k)[0]), f"{k}: frame {f} of the batch differs from the frame alone"
+
+
+# ---- the two entry points are one set of kernels ------------------------------------------------------------------------------
+class _BigRows:
+    """What _pose reads of a big-pose body: rows (1,V,16)."""
+
+    def __init__(self, rows):
+        self.rows = rows
+
+
+@pytest.mark.parametrize("V", [257, 300])
+@pytest.mark.parametrize("F", ["1", "chunk+1"])
+def test_smpl_and_smplx_entry_points_agree(dev, V, F):
+    """A 55-joint model with one direction set, a zero pose mean and no transl is the same rule through hl_pose_body_margins (the
+    X = false kernels) and hl_smplx_pose (X = true: t from the set-2 blend, which then copies A's last column): every output and both
+    workspace arrays are equal bit for bit, with big-pose rows written (big=None) and read (the table)."""
+    from humanliff_amd.body import load_body_model, load_smplx_model
+    F = 1 if F == "1" else _chunk() + 1
+    cpu = models(V, 3, 20, True, dev)[0]
+    smpl = load_body_model({k: cpu[k] for k in cpu if not k.startswith("hands_")}, dev)
+    smplx = load_smplx_model(cpu, dev, num_betas=10, num_expression_coeffs=6)
+    assert (smpl.J, smpl.Sp) == (55, 16) and (smplx.S, smplx.expr_start, smplx.two_sets) == (16, 10, 0) and not smplx.pose_mean.any()
+    g = syn._gen(4000 + 10 * V + F)
+    full = torch.randn((F, 165), generator=g) * 0.25
+    coef = torch.randn((F, 16), generator=g) * 0.5
+    if F > 1:
+        full[F // 2] = 0.0                                                      # an all-zero pose
+    Rs = torch.stack([syn._rodrigues1(torch.randn(3, generator=g) * 0.4) for _ in range(F)]).numpy()
+    Ths = (torch.randn((F, 3), generator=g) * 0.2).numpy()
+    parts, at = {}, 0
+    for k, n in sr.PARTS:
+        parts[k] = full[:, at:at + 3 * n].to(dev)
+        at += 3 * n
+    rows = _BigRows(torch.randn((1, V, 16), generator=g).to(dev))
+    for big in (None, rows):
+        a = smpl._pose(full.to(dev), coef.to(dev), Rs, Ths, big=big, y_margin=0.1)
+        b = smplx._pose(parts, coef[:, :10].to(dev), coef[:, 10:].to(dev), None, Rs, Ths, big=big, y_margin=0.1)
+        assert torch.equal(a.poses, b.poses) and torch.equal(a.shapes, b.shapes)
+        for k in ("vertices", "joints", "world_bounds", "verts4", "table", "rows", "A", "pose_features"):
+            x, y = getattr(a, k), getattr(b, k)
+            assert (x is None) == (y is None) == (k == ("table" if big is None else "rows")), k
+            if x is not None:
+                assert torch.isfinite(x).all() and torch.equal(x, y), f"{k} (big {'given' if big else 'None'}): the two entry points differ"
 
 
 # ---- the table: the renderer's rule, its two direction sets included ----------------------------------------------------------
