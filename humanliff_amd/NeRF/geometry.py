@@ -3,7 +3,8 @@
 The reference meshes a density lattice with mcubes.marching_cubes(mcubes.smooth(u), threshold) (NeRF/renderer.py:290-321,
 recon_NeRF/lib/renderer.py:304-348); Renderer.extract_geometry(..., mesher="hip") runs the same two steps through this module.
 The contract - signed distance, band, bounds, operator, stopping rule, corner rule, case table and ordering - is DESIGN.md
-"Mesh extraction".  CPU tensors raise: there is no host fallback.
+"Mesh extraction".  Beside the reference: the connected components of the solid side, the component filter and the vertex normals
+behind Renderer.extract_mesh ("Finishing the mesh" there).  CPU tensors raise: there is no host fallback.
 """
 import numpy as np
 import torch
@@ -115,6 +116,107 @@ def marching_cubes(volume, isovalue):
     return verts, tris
 
 
+def vertex_normals(volume, isovalue, vertices_index_coords, extent=None):
+    """Unit normals fp64 (V,3) of marching_cubes(volume, isovalue)'s vertices, in their order: the field's central-difference gradient
+    (one-sided at a volume face) interpolated along each vertex's lattice edge, divided per axis by `extent` (the world extent of the
+    lattice, default 1) and normalised.  +gradient points to the above side, so the normals point out of the body; a zero vector stays
+    zero.  The edges are taken from the volume's edge keys, not from the positions: `vertices_index_coords` must be that call's
+    vertices, and only its count is checked."""
+    v = _volume(volume, (torch.float64,), "vertex_normals")
+    L = _lib.lib()
+    dev = v.device
+    nx, ny, nz = (int(s) for s in v.shape)
+    nv = int(vertices_index_coords.shape[0])
+    if tuple(vertices_index_coords.shape) != (nv, 3):
+        raise ValueError(f"vertex_normals: vertices must be (V,3), got {tuple(vertices_index_coords.shape)}")
+    ext = None
+    if extent is not None:
+        ext = np.ascontiguousarray((extent.detach().cpu() if isinstance(extent, torch.Tensor) else extent), dtype=np.float64).reshape(3)
+    with _lib.on(dev):
+        st = _lib.stream_ptr(dev)
+        ws = _ws(L.hl_mc_workspace_bytes(nx, ny, nz), "vertex_normals", dev)
+        counts = torch.zeros(2, dtype=torch.int64, device=dev)
+        _lib.check(L.hl_mc_count(_dptr(v), nx, ny, nz, float(isovalue), _lib.ptr(counts), _dptr(ws), ws.numel(), st), "hl_mc_count")
+        have = int(counts[0].cpu())
+        if have != nv:
+            raise ValueError(f"vertex_normals: {nv} vertices given, the volume has {have} at this isovalue")
+        normals = torch.empty((nv, 3), dtype=torch.float64, device=dev)
+        keys = torch.empty(nv, dtype=torch.int32, device=dev)
+        _lib.check(L.hl_mc_vertex_normals(_dptr(v), nx, ny, nz, float(isovalue), ext.ctypes.data if ext is not None else None, nv,
+                                          _dptr(keys), _dptr(normals), _dptr(ws), ws.numel(), st), "hl_mc_vertex_normals")
+    return normals
+
+
+def label_components(volume, isovalue):
+    """26-connected components of the solid side `!(volume > isovalue)` of a device fp64 volume: (labels int32 (nx,ny,nz), sizes int64
+    (n,)).  Labels are 0 off the solid side and 1..n on it, numbered by the smallest C-order index of each component (the numbering
+    of scipy.ndimage.label with the full 3x3x3 structure); sizes[i] is the voxel count of label i+1."""
+    labels, sizes, _ = _label_components(volume, isovalue)
+    return labels, sizes
+
+
+def _label_components(volume, isovalue):
+    """label_components plus the number of link / flatten rounds the labelling ran."""
+    v = _volume(volume, (torch.float64,), "label_components")
+    L = _lib.lib()
+    dev = v.device
+    nx, ny, nz = (int(s) for s in v.shape)
+    with _lib.on(dev):
+        st = _lib.stream_ptr(dev)
+        ws = _ws(L.hl_cc_workspace_bytes(nx, ny, nz), "label_components", dev)
+        labels = torch.empty((nx, ny, nz), dtype=torch.int32, device=dev)
+        counts = torch.zeros(2, dtype=torch.int64, device=dev)
+        _lib.check(L.hl_cc_label(_dptr(v), nx, ny, nz, float(isovalue), _dptr(labels), _lib.ptr(counts), _dptr(ws), ws.numel(), st),
+                   "hl_cc_label")
+        n, rounds = (int(c) for c in counts.cpu())
+        sizes = torch.empty(n, dtype=torch.int64, device=dev)
+        _lib.check(L.hl_cc_sizes(_dptr(labels), nx * ny * nz, n, _lib.ptr(sizes) if n else None, st), "hl_cc_sizes")
+    return labels, sizes, rounds
+
+
+def select_components(sizes, keep):
+    """The labels (int64, ascending) that `keep` selects from `sizes`: "largest", an int k (the k largest; all when k exceeds their
+    number) or ("min_voxels", m).  Ties in size go to the lower label."""
+    n = int(sizes.numel())
+    if isinstance(keep, (tuple, list)):
+        if len(keep) != 2 or keep[0] != "min_voxels":
+            raise ValueError(f"keep_components: keep must be 'largest', an int or ('min_voxels', m), got {keep!r}")
+        return torch.nonzero(sizes >= int(keep[1])).reshape(-1) + 1
+    if keep == "largest":
+        keep = 1
+    if isinstance(keep, bool) or not isinstance(keep, int) or keep < 0:
+        raise ValueError(f"keep_components: keep must be 'largest', an int or ('min_voxels', m), got {keep!r}")
+    order = torch.sort(sizes, descending=True, stable=True).indices       # (stable: equal sizes stay in label order)
+    return torch.sort(order[:min(keep, n)]).values + 1
+
+
+def keep_components(volume, isovalue, keep, return_sizes=False):
+    """Drops solid components from a device fp64 volume: (filtered fp64 volume, kept labels int64).  Every voxel of a dropped component
+    gets iso + |v - iso| (the next double above iso where that is not above iso); every other voxel is copied bit for bit.  The
+    corners of a marching-cubes cell are pairwise 26-adjacent, so a rewritten value never meets a kept solid corner in a cell: the
+    mesh of the kept components does not change.  return_sizes: also the sizes of all components before filtering."""
+    v = _volume(volume, (torch.float64,), "keep_components")
+    labels, sizes = label_components(v, isovalue)
+    kept = select_components(sizes, keep)
+    out = filter_components(v, isovalue, labels, int(sizes.numel()), kept)
+    return (out, kept, sizes) if return_sizes else (out, kept)
+
+
+def filter_components(volume, isovalue, labels, n_labels, kept):
+    """The filter step of keep_components alone: `labels` as label_components returned them for this volume and isovalue, `kept` the
+    labels (int64, 1-based) that stay."""
+    v = _volume(volume, (torch.float64,), "filter_components")
+    if labels.dtype != torch.int32 or labels.shape != v.shape or labels.device != v.device:
+        raise ValueError("filter_components: labels must be the int32 device volume label_components returned")
+    mask = torch.zeros(max(n_labels, 1), dtype=torch.uint8, device=v.device)
+    mask[kept - 1] = 1
+    out = torch.empty_like(v)
+    with _lib.on(v.device):
+        _lib.check(_lib.lib().hl_cc_filter(_dptr(v), _dptr(labels.contiguous()), _dptr(mask), v.numel(), n_labels, float(isovalue), _dptr(out),
+                                           _lib.stream_ptr(v.device)), "hl_cc_filter")
+    return out
+
+
 def case_table():
     """The baked marching-cubes table: list over the 256 corner configurations of [(e0, e1, e2), ...] cube edges."""
     import ctypes as C
@@ -126,37 +228,67 @@ def case_table():
     return [[tuple(int(e) for e in tris[c, t]) for t in range(ntri[c])] for c in range(256)]
 
 
-def write_ply(path, vertices, triangles):
-    """Binary little-endian PLY: float64 vertices, one (uchar 3, int32 x3) list per face.  The reference writes its meshes with
-    trimesh, which this package does not depend on; any PLY reader loads this."""
-    v = np.ascontiguousarray(np.asarray(vertices.cpu() if isinstance(vertices, torch.Tensor) else vertices, dtype="<f8").reshape(-1, 3))
-    t = np.asarray(triangles.cpu() if isinstance(triangles, torch.Tensor) else triangles).reshape(-1, 3)
+def _host(a):
+    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+
+def write_ply(path, vertices, triangles, normals=None, colors=None):
+    """Binary little-endian PLY: float64 vertices, one (uchar 3, int32 x3) list per face.  With `normals` (V,3) and / or `colors`
+    (V,3) uint8 the vertex element also carries `float nx ny nz` and / or `uchar red green blue`; without them the file is what it
+    always was.  The reference writes its meshes with trimesh, which this package does not depend on; any PLY reader loads this."""
+    v = np.ascontiguousarray(np.asarray(_host(vertices), dtype="<f8").reshape(-1, 3))
+    t = _host(triangles).reshape(-1, 3)
     if len(v) and t.size and (t.min() < 0 or t.max() >= len(v)):
         raise ValueError("write_ply: triangle index out of range")
+    fields, props = [("p", "<f8", (3,))], "property double x\nproperty double y\nproperty double z\n"
+    if normals is not None:
+        fields.append(("n", "<f4", (3,)))
+        props += "property float nx\nproperty float ny\nproperty float nz\n"
+    if colors is not None:
+        fields.append(("c", "u1", (3,)))
+        props += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+    vert = np.empty(len(v), dtype=fields)
+    vert["p"] = v
+    for key, arr, what in (("n", normals, "normals"), ("c", colors, "colors")):
+        if arr is None:
+            continue
+        arr = _host(arr)
+        if arr.shape != (len(v), 3):
+            raise ValueError(f"write_ply: {what} must be (V,3) like the vertices, got {arr.shape}")
+        if key == "c" and arr.dtype != np.uint8:
+            raise TypeError(f"write_ply: colors must be uint8, got {arr.dtype}")
+        vert[key] = arr
     head = ("ply\nformat binary_little_endian 1.0\n"
-            f"element vertex {len(v)}\nproperty double x\nproperty double y\nproperty double z\n"
+            f"element vertex {len(v)}\n{props}"
             f"element face {len(t)}\nproperty list uchar int vertex_indices\nend_header\n").encode("ascii")
     face = np.empty(len(t), dtype=[("n", "u1"), ("i", "<i4", (3,))])
     face["n"] = 3
     face["i"] = t
     with open(path, "wb") as f:
         f.write(head)
-        f.write(v.tobytes())
+        f.write(vert.tobytes())
         f.write(face.tobytes())
 
 
 def read_ply(path):
-    """Reads back what write_ply wrote: (vertices float64 (V,3), triangles int64 (T,3))."""
+    """Reads back what write_ply wrote: (vertices float64 (V,3), triangles int64 (T,3)), followed by normals float32 (V,3) and / or
+    colors uint8 (V,3) when the file has them."""
     with open(path, "rb") as f:
         data = f.read()
     end = data.index(b"end_header\n") + len(b"end_header\n")
     head = data[:end].decode("ascii").split("\n")
     nv = int(next(h for h in head if h.startswith("element vertex")).split()[-1])
     nt = int(next(h for h in head if h.startswith("element face")).split()[-1])
-    v = np.frombuffer(data, dtype="<f8", count=nv * 3, offset=end).reshape(nv, 3)
-    face = np.frombuffer(data, dtype=[("n", "u1"), ("i", "<i4", (3,))], count=nt, offset=end + nv * 24)
+    fields = [("p", "<f8", (3,))]
+    if "property float nx" in head:
+        fields.append(("n", "<f4", (3,)))
+    if "property uchar red" in head:
+        fields.append(("c", "u1", (3,)))
+    vdt = np.dtype(fields)
+    vert = np.frombuffer(data, dtype=vdt, count=nv, offset=end)
+    face = np.frombuffer(data, dtype=[("n", "u1"), ("i", "<i4", (3,))], count=nt, offset=end + nv * vdt.itemsize)
     assert (face["n"] == 3).all()
-    return v.copy(), face["i"].astype(np.int64)
+    return (vert["p"].copy(), face["i"].astype(np.int64)) + tuple(vert[k].copy() for k in ("n", "c") if k in vdt.names)
 
 
 def _dptr(t):

@@ -517,6 +517,85 @@ class Renderer(nn.Module):
         verts = verts / (resolution - 1.0) * ext[None, :] + lo[None, :]
         return verts.cpu().numpy(), tris.cpu().numpy()
 
+    # ---- finishing the mesh: components, normals, colours (an extension beside the reference; DESIGN.md "Finishing the mesh") -----
+    def vertex_colors(self, tp_input, tri_planes, vertices_world, directions):
+        """Colours float32 (V,3) in [0,1] of this renderer's full MLP at `vertices_world` (V,3), seen along the unit view `directions`
+        (V,3) - the arithmetic of a ray's sample point: (canonical branch: deform_target2c, then) the tri-plane lookup, positional
+        encoding, both heads and the sigmoid on the colour.  Device tensors; rounded to float32 first."""
+        return self._vertex_colors(tp_input, tri_planes, vertices_world, directions)[0]
+
+    def _vertex_colors(self, tp_input, tri_planes, vertices_world, directions, want_u8=False):
+        assert tri_planes is not None and tri_planes.shape[0] == 1 and tri_planes.shape[1:3] == (3, 9)
+        dev = tri_planes.device
+        if not (torch.is_tensor(vertices_world) and vertices_world.is_cuda and torch.is_tensor(directions) and directions.is_cuda):
+            raise RuntimeError("vertex_colors needs device tensors (no CPU path)")
+        V = int(vertices_world.shape[0])
+        if tuple(vertices_world.shape) != (V, 3) or tuple(directions.shape) != (V, 3):
+            raise ValueError(f"vertex_colors: vertices and directions must both be (V,3), got {tuple(vertices_world.shape)} and "
+                             f"{tuple(directions.shape)}")
+        rgb = torch.empty((V, 3), dtype=torch.float32, device=dev)
+        rgb8 = torch.empty((V, 3), dtype=torch.uint8, device=dev) if want_u8 else None
+        if V == 0:
+            return rgb, rgb8
+        H, W = tri_planes.shape[-2:]
+        pts = vertices_world.detach().to(device=dev, dtype=torch.float32).contiguous()
+        dirs = directions.detach().to(device=dev, dtype=torch.float32).contiguous()
+        L = _lib.lib()
+        with _lib.on(dev):
+            st = _lib.stream_ptr()
+            if self.use_canonical_space:
+                verts4, table, Rh, Th = self._deform_tables(tp_input, dev)
+                bounds = tp_input['t_world_bounds']
+                can, cd = torch.empty_like(pts), torch.empty_like(dirs)
+                _lib.check(L.hl_deform_points(_lib.ptr(pts), _lib.ptr(dirs), Rh.ctypes.data, Th.ctypes.data, _lib.ptr(verts4), _lib.ptr(table),
+                                              int(verts4.shape[0]), V, _lib.ptr(can), _lib.ptr(cd), None, st), "hl_deform_points")
+                pts, dirs = can, cd
+            else:
+                bounds = tp_input['world_bounds']
+            bounds = bounds.reshape(-1, 2, 3)[0].to(device=dev, dtype=torch.float32).contiguous()
+            V32 = (V + 31) // 32 * 32
+            p4, d4, rec = (torch.empty((V32, 4), dtype=torch.float32, device=dev) for _ in range(3))
+            _lib.check(L.hl_mesh_pack_points(_lib.ptr(pts), _lib.ptr(dirs), V, _lib.ptr(p4), _lib.ptr(d4), st), "hl_mesh_pack_points")
+            packed, pp = self._packed_mlp(dev), self._packed_planes(tri_planes[0])
+            _lib.check(L.hl_render_eval_points(_lib.ptr(packed), _lib.ptr(pp), H, W, _lib.ptr(bounds), _lib.ptr(p4), _lib.ptr(d4), V, 1,
+                                               _lib.ptr(rec), st), "hl_render_eval_points")
+            _lib.check(L.hl_mesh_unpack_colors(_lib.ptr(rec), V, _lib.ptr(rgb), _lib.ptr(rgb8, torch.uint8), st), "hl_mesh_unpack_colors")
+        return rgb, rgb8
+
+    def extract_mesh(self, tp_input, tri_planes=None, resolution=512, threshold=0.0, components=None, normals=True, colors=True):
+        """The HIP mesh of extract_geometry(..., mesher="hip"), finished on the device.  Returns a dict of numpy arrays: `vertices` fp64
+        (V,3) world, `triangles` int64 (T,3) - the bits of extract_geometry when components is None - `normals` fp64 (V,3) unit,
+        outward (or None), `colors` uint8 (V,3) (or None): the MLP seen head-on, direction = -normal, and `component_sizes` int64:
+        the voxel counts of the 26-connected solid components of the smoothed field, before filtering.  components: None,
+        "largest", an int k or ("min_voxels", m) - which components to mesh (geometry.keep_components)."""
+        from . import geometry
+        out = {"vertices": np.zeros((0, 3), dtype=np.float64), "triangles": np.zeros((0, 3), dtype=np.int64),
+               "normals": np.zeros((0, 3), dtype=np.float64) if normals else None,
+               "colors": np.zeros((0, 3), dtype=np.uint8) if colors else None, "component_sizes": np.zeros(0, dtype=np.int64)}
+        u = Renderer.density_grid(self, tp_input, tri_planes, resolution)
+        try:
+            field = geometry.smooth(u)
+        except geometry.NoSignChange:        # nothing to mesh
+            return out
+        del u
+        if components is None:
+            sizes = geometry.label_components(field, threshold)[1]
+        else:
+            field, _, sizes = geometry.keep_components(field, threshold, components, return_sizes=True)
+        out["component_sizes"] = sizes.cpu().numpy()
+        verts, tris = geometry.marching_cubes(field, threshold)
+        b = tp_input['world_bounds'].reshape(-1, 2, 3)[0].detach().to(verts.device)
+        ext, lo = (b[1] - b[0]).double(), b[0].double()
+        nrm = geometry.vertex_normals(field, threshold, verts, ext) if (normals or colors) else None
+        del field
+        verts = verts / (resolution - 1.0) * ext[None, :] + lo[None, :]
+        out["vertices"], out["triangles"] = verts.cpu().numpy(), tris.cpu().numpy()
+        if normals:
+            out["normals"] = nrm.cpu().numpy()
+        if colors:
+            out["colors"] = self._vertex_colors(tp_input, tri_planes, verts, -nrm, want_u8=True)[1].cpu().numpy()
+        return out
+
 
 def render(chunk=1024 * 32, rays_o=None, rays_d=None, near=0., far=1., tri_planes=None, tp_input=None, renderer=None,
            n_samples=128, perturb=0., n_importance=0, white_bkgd=False):

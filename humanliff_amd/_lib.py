@@ -179,6 +179,13 @@ SIGNATURES = {
     "hl_mc_emit": (_i, [_p, _i, _i, _i, C.c_double, _p, _p, _p, _sz, _p]),
     "hl_mc_max_triangles": (_i, []),
     "hl_mc_case_table": (_i, [_p, _p]),
+    "hl_mc_vertex_normals": (_i, [_p, _i, _i, _i, C.c_double, _p, _i64, _p, _p, _p, _sz, _p]),
+    "hl_cc_workspace_bytes": (_sz, [_i, _i, _i]),
+    "hl_cc_label": (_i, [_p, _i, _i, _i, C.c_double, _p, _p, _p, _sz, _p]),
+    "hl_cc_sizes": (_i, [_p, _i64, _i64, _p, _p]),
+    "hl_cc_filter": (_i, [_p, _p, _p, _i64, _i64, C.c_double, _p, _p]),
+    "hl_mesh_pack_points": (_i, [_p, _p, _i64, _p, _p, _p]),
+    "hl_mesh_unpack_colors": (_i, [_p, _i64, _p, _p, _p]),
     "hl_adamw_chunks": (_i64, [C.POINTER(C.c_int64), _i]),
     "hl_adamw_table_bytes": (_sz, [_i, _i64]),
     "hl_adamw_table_pack": (_i, [_i, C.POINTER(C.c_int64), C.POINTER(C.c_void_p), _i, _p, _sz]),

@@ -3,6 +3,10 @@
 // Replaces the PyMCubes calls of the reference (human_diffusion/NeRF/renderer.py:290-321 and recon_NeRF/lib/renderer.py:304-348):
 //   mcubes.smooth(u)                -> hl_smooth_prepare / hl_smooth_band / hl_smooth_sweeps / hl_smooth_scatter
 //   mcubes.marching_cubes(u, iso)   -> hl_mc_count / hl_mc_emit
+// and, beside the reference (which stops at vertices and triangles), finishes the mesh behind Renderer.extract_mesh:
+//   components of the solid side    -> hl_cc_label / hl_cc_sizes / hl_cc_filter
+//   vertex normals                  -> hl_mc_vertex_normals
+//   vertex colours                  -> hl_mesh_pack_points / hl_mesh_unpack_colors around hl_render_eval_points
 // The contract (signed distance, band, bounds, operator, stopping rule, corner rule, case table, ordering) is in DESIGN.md
 // ("Mesh extraction"); tests/geometry_restatement.py states it again in numpy.  Everything is fp64, the file is built with
 // -ffp-contract=off, and every reduction is integer or fixed-order, so results are bit-reproducible run to run.
@@ -360,7 +364,217 @@ __global__ __launch_bounds__(TPB) void k_mc_emit(const double *__restrict__ v, i
     }
 }
 
+// ---- vertex normals: the field's gradient, interpolated along the vertex's lattice edge -------------------------------------
+// keys[j] = voxel * 3 + axis of vertex j, in hl_mc_emit's vertex order (voff as the scan left it)
+__global__ __launch_bounds__(TPB) void k_mc_keys(const unsigned char *__restrict__ code, const int *__restrict__ voff, long n, long n_verts,
+                                                 int *__restrict__ keys) {
+    const long i = (long)blockIdx.x * TPB + threadIdx.x;
+    if (i >= n) return;
+    const unsigned c = code[i] & 7u;
+    long j = voff[i];
+    for (int a = 0; a < 3; ++a) {
+        if (!(c & (1u << a))) continue;
+        if (j < n_verts) keys[j] = (int)(i * 3 + a);
+        ++j;
+    }
+}
+
+// central difference at lattice point p, one-sided at a volume face, 0 along an axis of one voxel
+__device__ inline void mc_gradient(const double *__restrict__ v, const int p[3], const int dim[3], const long step[3], double g[3]) {
+    const long i = p[0] * step[0] + p[1] * step[1] + p[2] * step[2];
+    for (int k = 0; k < 3; ++k) {
+        if (dim[k] < 2) g[k] = 0.0;
+        else if (p[k] == 0) g[k] = v[i + step[k]] - v[i];
+        else if (p[k] == dim[k] - 1) g[k] = v[i] - v[i - step[k]];
+        else g[k] = (v[i + step[k]] - v[i - step[k]]) * 0.5;
+    }
+}
+
+__global__ __launch_bounds__(TPB) void k_mc_normals(const double *__restrict__ v, int nx, int ny, int nz, double iso, double ex, double ey,
+                                                    double ez, const int *__restrict__ keys, long n_verts, double *__restrict__ normals) {
+    const long j = (long)blockIdx.x * TPB + threadIdx.x;
+    if (j >= n_verts) return;
+    const long n = (long)nx * ny * nz, nyz = (long)ny * nz;
+    const int key = keys[j];
+    const long i = key / 3;
+    const int a = key % 3;
+    const int dim[3] = {nx, ny, nz};
+    const long step[3] = {nyz, (long)nz, 1L};
+    const double ext[3] = {ex, ey, ez};
+    double out[3] = {0.0, 0.0, 0.0};
+    if (key >= 0 && i < n) {
+        int pa[3] = {(int)(i / nyz), (int)((i / nz) % ny), (int)(i % nz)};
+        if (pa[a] + 1 < dim[a]) {                  // (an edge that leaves the volume is never a key of this volume)
+            int pb[3] = {pa[0], pa[1], pa[2]};
+            pb[a] += 1;
+            const double fa = v[i], fb = v[i + step[a]];
+            const double t = (iso - fa) / (fb - fa);
+            double ga[3], gb[3];
+            mc_gradient(v, pa, dim, step, ga);
+            mc_gradient(v, pb, dim, step, gb);
+            double len2 = 0.0;
+            for (int k = 0; k < 3; ++k) {
+                out[k] = ((1.0 - t) * ga[k] + t * gb[k]) / ext[k];
+                len2 += out[k] * out[k];
+            }
+            const double len = sqrt(len2);
+            const bool ok = len > 0.0 && len < HUGE_VAL;      // zero stays zero; NaN / inf give zero, never NaN
+            for (int k = 0; k < 3; ++k) out[k] = ok ? out[k] / len : 0.0;
+        }
+    }
+    for (int k = 0; k < 3; ++k) normals[j * 3 + k] = out[k];
+}
+
+// ---- connected components of the solid side (26-connectivity) --------------------------------------------------------------
+// Union-find on parent[] (int32 voxel index): parent[i] = -1 off the solid side, and on it parent[i] <= i at all times; every
+// update is an integer atomicMin, so entries only decrease.  Every access another workgroup may race with is an agent-scope
+// atomic, and the host relaunches link + flatten until a round changes nothing (hl_cc_label).
+__device__ inline int cc_load(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// Root walk.  Invariant: parent[i] <= i on solid voxels and updates only decrease entries.  So whatever mix of old and new
+// parents the walk reads, each step goes to a strictly smaller index and it ends at a self-parent after at most i steps: it
+// never waits for another workgroup's write.
+__device__ inline int cc_find(const int *parent, int i) {
+    for (;;) {
+        const int p = cc_load(parent + i);
+        if (p >= i || p < 0) return i;
+        i = p;
+    }
+}
+
+// a + b strictly decreases with every iteration, so the loop ends on its own
+__device__ inline bool cc_unite(int *parent, int a, int b) {
+    bool changed = false;
+    a = cc_find(parent, a);
+    b = cc_find(parent, b);
+    while (a != b) {
+        if (a < b) { const int s = a; a = b; b = s; }
+        const int old = atomicMin(parent + a, b);        // (agent scope)
+        if (old > b) changed = true;
+        if (old == a) break;                             // a was a root and now hangs below b
+        a = old;                                         // a had the parent `old` already: old and b are one component too
+    }
+    return changed;
+}
+
+__global__ __launch_bounds__(TPB) void k_cc_init(const double *__restrict__ v, double iso, long n, int *__restrict__ parent) {
+    const long i = (long)blockIdx.x * TPB + threadIdx.x;
+    if (i < n) parent[i] = !(v[i] > iso) ? (int)i : -1;
+}
+
+__global__ __launch_bounds__(TPB) void k_cc_link(int *__restrict__ parent, int nx, int ny, int nz, int *__restrict__ changed) {
+    const long n = (long)nx * ny * nz;
+    const long i = (long)blockIdx.x * TPB + threadIdx.x;
+    if (i >= n) return;
+    if (cc_load(parent + i) < 0) return;
+    const long nyz = (long)ny * nz;
+    const int x = (int)(i / nyz), y = (int)((i / nz) % ny), z = (int)(i % nz);
+    bool any = false;
+    for (int k = 14; k < 27; ++k) {                      // the 13 neighbours behind i in C order
+        const int dx = k / 9 - 1, dy = (k / 3) % 3 - 1, dz = k % 3 - 1;
+        const int X = x + dx, Y = y + dy, Z = z + dz;
+        if (X < 0 || X >= nx || Y < 0 || Y >= ny || Z < 0 || Z >= nz) continue;
+        const long j = i + dx * nyz + dy * (long)nz + dz;
+        if (cc_load(parent + j) < 0) continue;
+        any |= cc_unite(parent, (int)i, (int)j);
+    }
+    if (any) atomicOr(changed, 1);
+}
+
+// pointer jumping: every solid voxel takes the root its walk ends at (an ancestor: the entry only decreases)
+__global__ __launch_bounds__(TPB) void k_cc_flatten(int *__restrict__ parent, long n) {
+    const long i = (long)blockIdx.x * TPB + threadIdx.x;
+    if (i >= n) return;
+    const int p = cc_load(parent + i);
+    if (p < 0 || p == (int)i) return;
+    const int r = cc_find(parent, p);
+    if (r != p) atomicMin(parent + i, r);
+}
+
+struct CcRootCount {
+    const int *parent;
+    __device__ unsigned long long operator()(long i) const { return (unsigned long long)(parent[i] == (int)i); }
+};
+struct CcRankOut {
+    int *rank;
+    __device__ void operator()(long i, unsigned long long prefix, unsigned long long) const { rank[i] = (int)(prefix & 0xffffffffull); }
+};
+
+__global__ __launch_bounds__(TPB) void k_cc_labels(const int *__restrict__ parent, const int *__restrict__ rank, long n, int *__restrict__ labels,
+                                                   int64_t *__restrict__ counts, int rounds) {
+    const long i = (long)blockIdx.x * TPB + threadIdx.x;
+    if (i == 0) counts[1] = rounds;
+    if (i >= n) return;
+    const int p = parent[i];
+    labels[i] = p < 0 ? 0 : rank[p] + 1;
+}
+
+__global__ __launch_bounds__(TPB) void k_cc_sizes(const int *__restrict__ labels, long n, long n_labels, unsigned long long *__restrict__ sizes) {
+    const long i = (long)blockIdx.x * TPB + threadIdx.x;
+    if (i >= n) return;
+    const int l = labels[i];
+    if (l > 0 && l <= n_labels) atomicAdd(sizes + (l - 1), 1ull);
+}
+
+// a voxel of a dropped component moves to the above side, mirrored about iso; everything else is copied
+__global__ __launch_bounds__(TPB) void k_cc_filter(const double *__restrict__ v, const int *__restrict__ labels, const unsigned char *__restrict__ keep,
+                                                   long n, long n_labels, double iso, double *__restrict__ out) {
+    const long i = (long)blockIdx.x * TPB + threadIdx.x;
+    if (i >= n) return;
+    const int l = labels[i];
+    double x = v[i];
+    if (l > 0 && l <= n_labels && !keep[l - 1]) {
+        x = iso + fabs(x - iso);
+        if (!(x > iso)) x = nextafter(iso, HUGE_VAL);
+    }
+    out[i] = x;
+}
+
+// ---- vertex colours: the hand-over to and from hl_render_eval_points -------------------------------------------------------
+// (V,3) points / directions -> float4 rows padded to a multiple of 32 (n_samples = 1: the tile-major layout is the plain array)
+__global__ __launch_bounds__(TPB) void k_mesh_pack(const float *__restrict__ pts, const float *__restrict__ dirs, long nv, long nv32,
+                                                   float4 *__restrict__ pts4, float4 *__restrict__ dirs4) {
+    const long j = (long)blockIdx.x * TPB + threadIdx.x;
+    if (j >= nv32) return;
+    float4 p = {0.f, 0.f, 0.f, 0.f}, d = {0.f, 0.f, 1.f, 0.f};
+    if (j < nv) {
+        p = make_float4(pts[j * 3], pts[j * 3 + 1], pts[j * 3 + 2], 0.f);
+        d = make_float4(dirs[j * 3], dirs[j * 3 + 1], dirs[j * 3 + 2], 0.f);
+    }
+    pts4[j] = p;
+    dirs4[j] = d;
+}
+
+// raw records (sigma, r, g, b) -> sigmoid colours, the compositing kernels' form of it; u8 = round(clip(c, 0, 1) * 255)
+__global__ __launch_bounds__(TPB) void k_mesh_colors(const float4 *__restrict__ rec, long nv, float *__restrict__ rgb, unsigned char *__restrict__ rgb8) {
+    const long j = (long)blockIdx.x * TPB + threadIdx.x;
+    if (j >= nv) return;
+    const float4 r = rec[j];
+    const float raw[3] = {r.y, r.z, r.w};
+    for (int k = 0; k < 3; ++k) {
+        const float c = __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-1.44269504088896341f * raw[k]));
+        rgb[j * 3 + k] = c;
+        if (rgb8) rgb8[j * 3 + k] = (unsigned char)rintf(fminf(fmaxf(c, 0.f), 1.f) * 255.f);
+    }
+}
+
 // workspace layouts
+struct CcWs {
+    int *parent, *rank;
+    unsigned long long *blocks;
+    int *changed;
+};
+CcWs cc_ws(void *ws, long n) {
+    char *p = (char *)ws;
+    CcWs w;
+    w.parent = (int *)p; p += n * 4;
+    w.rank = (int *)p; p += n * 4;
+    w.blocks = (unsigned long long *)p; p += scan_blocks(n) * 8;
+    w.changed = (int *)p;
+    return w;
+}
+constexpr int CC_MAX_ROUNDS = 40;      // pointer jumping: logarithmic in the longest chain, and a chain is shorter than 2^31
+
 struct SmoothWs {
     int *a, *b, *s, *t;
     unsigned long long *blocks;
@@ -499,6 +713,97 @@ extern "C" int hl_mc_emit(const double *vol, int nx, int ny, int nz, double iso,
                        n, (const unsigned long long *)w.blocks);
     hipLaunchKernelGGL(k_mc_emit, dim3(grid_of(n)), dim3(TPB), 0, st, vol, nx, ny, nz, iso, w.code, w.voff, w.toff, verts, tris);
     return hl::check_launch("hl_mc_emit");
+}
+
+extern "C" int hl_mc_vertex_normals(const double *vol, int nx, int ny, int nz, double iso, const double *h_ext, int64_t n_verts, int *keys,
+                                    double *normals, void *ws, size_t ws_bytes, void *stream) {
+    HL_REQUIRE(vol && ws, "hl_mc_vertex_normals: null argument");
+    HL_REQUIRE(volume_ok(nx, ny, nz), "hl_mc_vertex_normals: volume %d x %d x %d outside the supported sizes", nx, ny, nz);
+    HL_REQUIRE(ws_bytes >= hl_mc_workspace_bytes(nx, ny, nz), "hl_mc_vertex_normals: workspace too small");
+    const long n = (long)nx * ny * nz;
+    HL_REQUIRE(n_verts >= 0 && n_verts <= 3 * n, "hl_mc_vertex_normals: vertex count %lld", (long long)n_verts);
+    if (n_verts == 0) return HL_OK;
+    HL_REQUIRE(keys && normals, "hl_mc_vertex_normals: null argument");
+    const double ex = h_ext ? h_ext[0] : 1.0, ey = h_ext ? h_ext[1] : 1.0, ez = h_ext ? h_ext[2] : 1.0;
+    hipStream_t st = (hipStream_t)stream;
+    McWs w = mc_ws(ws, n);
+    hipLaunchKernelGGL((k_scan_down<McCount, McOut>), dim3((unsigned)scan_blocks(n)), dim3(TPB), 0, st, McCount{w.code}, McOut{w.voff, w.toff},
+                       n, (const unsigned long long *)w.blocks);
+    hipLaunchKernelGGL(k_mc_keys, dim3(grid_of(n)), dim3(TPB), 0, st, (const unsigned char *)w.code, (const int *)w.voff, n, (long)n_verts, keys);
+    hipLaunchKernelGGL(k_mc_normals, dim3(grid_of(n_verts)), dim3(TPB), 0, st, vol, nx, ny, nz, iso, ex, ey, ez, (const int *)keys, (long)n_verts,
+                       normals);
+    return hl::check_launch("hl_mc_vertex_normals");
+}
+
+extern "C" size_t hl_cc_workspace_bytes(int nx, int ny, int nz) {
+    if (!volume_ok(nx, ny, nz)) return 0;
+    const long n = (long)nx * ny * nz;
+    return (size_t)(n * 8 + scan_blocks(n) * 8 + 8);
+}
+
+extern "C" int hl_cc_label(const double *vol, int nx, int ny, int nz, double iso, int *labels, int64_t *counts, void *ws, size_t ws_bytes,
+                           void *stream) {
+    HL_REQUIRE(vol && labels && counts && ws, "hl_cc_label: null argument");
+    HL_REQUIRE(volume_ok(nx, ny, nz), "hl_cc_label: volume %d x %d x %d outside the supported sizes", nx, ny, nz);
+    HL_REQUIRE(ws_bytes >= hl_cc_workspace_bytes(nx, ny, nz), "hl_cc_label: workspace too small");
+    const long n = (long)nx * ny * nz;
+    hipStream_t st = (hipStream_t)stream;
+    CcWs w = cc_ws(ws, n);
+    hipLaunchKernelGGL(k_cc_init, dim3(grid_of(n)), dim3(TPB), 0, st, vol, iso, n, w.parent);
+    int rounds = 0;
+    for (;;) {
+        // one round: link, flatten, and the host reads whether anything moved (the pipeline's `counts` reads are of this kind)
+        if (rounds == CC_MAX_ROUNDS)
+            return hl::fail(HL_ERR_RUNTIME, "hl_cc_label: labels still changing after %d link / flatten rounds", CC_MAX_ROUNDS);
+        ++rounds;
+        HL_HIP(hipMemsetAsync(w.changed, 0, sizeof(int), st));
+        hipLaunchKernelGGL(k_cc_link, dim3(grid_of(n)), dim3(TPB), 0, st, w.parent, nx, ny, nz, w.changed);
+        hipLaunchKernelGGL(k_cc_flatten, dim3(grid_of(n)), dim3(TPB), 0, st, w.parent, n);
+        int changed = 0;
+        HL_HIP(hipMemcpyAsync(&changed, w.changed, sizeof(int), hipMemcpyDeviceToHost, st));
+        HL_HIP(hipStreamSynchronize(st));
+        if (!changed) break;
+    }
+    const long nbk = scan_blocks(n);
+    hipLaunchKernelGGL((k_scan_reduce<CcRootCount>), dim3((unsigned)nbk), dim3(TPB), 0, st, CcRootCount{w.parent}, n, w.blocks);
+    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(TPB), 0, st, w.blocks, nbk, counts);
+    hipLaunchKernelGGL((k_scan_down<CcRootCount, CcRankOut>), dim3((unsigned)nbk), dim3(TPB), 0, st, CcRootCount{w.parent}, CcRankOut{w.rank}, n,
+                       (const unsigned long long *)w.blocks);
+    hipLaunchKernelGGL(k_cc_labels, dim3(grid_of(n)), dim3(TPB), 0, st, (const int *)w.parent, (const int *)w.rank, n, labels, counts, rounds);
+    return hl::check_launch("hl_cc_label");
+}
+
+extern "C" int hl_cc_sizes(const int *labels, int64_t n_voxels, int64_t n_labels, int64_t *sizes, void *stream) {
+    HL_REQUIRE(labels && n_voxels > 0 && n_voxels < (1LL << 31) && n_labels >= 0, "hl_cc_sizes: bad argument");
+    if (n_labels == 0) return HL_OK;
+    HL_REQUIRE(sizes, "hl_cc_sizes: null argument");
+    hipStream_t st = (hipStream_t)stream;
+    HL_HIP(hipMemsetAsync(sizes, 0, (size_t)n_labels * 8, st));
+    hipLaunchKernelGGL(k_cc_sizes, dim3(grid_of(n_voxels)), dim3(TPB), 0, st, labels, (long)n_voxels, (long)n_labels, (unsigned long long *)sizes);
+    return hl::check_launch("hl_cc_sizes");
+}
+
+extern "C" int hl_cc_filter(const double *vol, const int *labels, const unsigned char *keep, int64_t n_voxels, int64_t n_labels, double iso,
+                            double *out, void *stream) {
+    HL_REQUIRE(vol && labels && out && n_voxels > 0 && n_voxels < (1LL << 31) && n_labels >= 0, "hl_cc_filter: bad argument");
+    HL_REQUIRE(keep || n_labels == 0, "hl_cc_filter: null argument");
+    hipLaunchKernelGGL(k_cc_filter, dim3(grid_of(n_voxels)), dim3(TPB), 0, (hipStream_t)stream, vol, labels, keep, (long)n_voxels, (long)n_labels, iso,
+                       out);
+    return hl::check_launch("hl_cc_filter");
+}
+
+extern "C" int hl_mesh_pack_points(const float *pts, const float *dirs, int64_t n_verts, float *pts4, float *dirs4, void *stream) {
+    HL_REQUIRE(pts && dirs && pts4 && dirs4 && n_verts > 0, "hl_mesh_pack_points: bad argument");
+    const long nv32 = (n_verts + 31) / 32 * 32;
+    hipLaunchKernelGGL(k_mesh_pack, dim3(grid_of(nv32)), dim3(TPB), 0, (hipStream_t)stream, pts, dirs, (long)n_verts, nv32, (float4 *)pts4,
+                       (float4 *)dirs4);
+    return hl::check_launch("hl_mesh_pack_points");
+}
+
+extern "C" int hl_mesh_unpack_colors(const float *records, int64_t n_verts, float *rgb, unsigned char *rgb8, void *stream) {
+    HL_REQUIRE(records && rgb && n_verts > 0, "hl_mesh_unpack_colors: bad argument");
+    hipLaunchKernelGGL(k_mesh_colors, dim3(grid_of(n_verts)), dim3(TPB), 0, (hipStream_t)stream, (const float4 *)records, (long)n_verts, rgb, rgb8);
+    return hl::check_launch("hl_mesh_unpack_colors");
 }
 
 extern "C" int hl_mc_max_triangles(void) { return HL_MC_MAX_TRI; }

@@ -40,3 +40,11 @@ class Renderer(_Renderer):
         """recon_NeRF/lib/renderer.py:304 (no tri_planes argument: the module's own, first subject of the batch); `mesher` as in
         NeRF.Renderer.extract_geometry."""
         return super().extract_geometry(tp_input, self._own_planes(tp_input)[:1], resolution, threshold, mesher=mesher)
+
+    def vertex_colors(self, tp_input, vertices_world, directions):
+        """NeRF.Renderer.vertex_colors on the module's own tri-planes."""
+        return super().vertex_colors(tp_input, self._own_planes(tp_input)[:1], vertices_world, directions)
+
+    def extract_mesh(self, tp_input, resolution=512, threshold=0.0, components=None, normals=True, colors=True):
+        """NeRF.Renderer.extract_mesh on the module's own tri-planes (first subject of the batch)."""
+        return super().extract_mesh(tp_input, self._own_planes(tp_input)[:1], resolution, threshold, components, normals, colors)

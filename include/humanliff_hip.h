@@ -736,6 +736,31 @@ int hl_mc_count(const double *vol, int nx, int ny, int nz, double iso, int64_t *
 int hl_mc_emit(const double *vol, int nx, int ny, int nz, double iso, double *verts, int64_t *tris, void *ws, size_t ws_bytes, void *stream);
 int hl_mc_max_triangles(void);
 int hl_mc_case_table(int8_t *h_tris, uint8_t *h_ntri);
+/* Finishing an extracted mesh (extensions beside the reference contract; DESIGN.md "Mesh extraction", "Finishing the mesh").
+ *   hl_mc_vertex_normals (ws as left by hl_mc_count at the same vol / iso): unit normals fp64 (n_verts,3) in hl_mc_emit's vertex
+ *     order.  Vertex on the lattice edge a -> b at t = (iso - f_a)/(f_b - f_a): n_idx = (1-t) g(a) + t g(b), g the central difference
+ *     (one-sided at a volume face), n = normalize(n_idx / ext); h_ext: 3 HOST doubles, the world extent per axis, or NULL (1,1,1).
+ *     A zero or non-finite vector gives (0,0,0).  keys: n_verts int32 of device scratch, left holding the edge keys voxel*3 + axis.
+ * Connected components of the solid side, solid = !(value > iso), 26-connectivity:
+ *   hl_cc_label: labels int32 (nx,ny,nz), 0 off the solid side, 1..n on it, numbered by the smallest linear index of each
+ *     component; counts[0] = n, counts[1] = link / flatten rounds run.  Relaunches until a round changes nothing and reads the
+ *     device flag in between, so it SYNCHRONISES the stream; HL_ERR_RUNTIME if 40 rounds do not settle it.
+ *   hl_cc_sizes: sizes[l-1] = voxels with label l (integer atomics).
+ *   hl_cc_filter: out = vol, except that a voxel whose label l has keep[l-1] == 0 gets iso + |v - iso|, or the next double above
+ *     iso where that is not above iso (out may be vol).
+ * Vertex colours through hl_render_eval_points with n_samples = 1:
+ *   hl_mesh_pack_points: (n_verts,3) fp32 points and directions -> float[4] rows, padded to a multiple of 32 rows.
+ *   hl_mesh_unpack_colors: its records -> rgb fp32 (n_verts,3) = sigmoid of the raw colour, rgb8 (or NULL) = round(clip(rgb,0,1)*255). */
+int hl_mc_vertex_normals(const double *vol, int nx, int ny, int nz, double iso, const double *h_ext, int64_t n_verts, int32_t *keys,
+                         double *normals, void *ws, size_t ws_bytes, void *stream);
+size_t hl_cc_workspace_bytes(int nx, int ny, int nz);
+int hl_cc_label(const double *vol, int nx, int ny, int nz, double iso, int32_t *labels, int64_t *counts, void *ws, size_t ws_bytes,
+                void *stream);
+int hl_cc_sizes(const int32_t *labels, int64_t n_voxels, int64_t n_labels, int64_t *sizes, void *stream);
+int hl_cc_filter(const double *vol, const int32_t *labels, const uint8_t *keep, int64_t n_voxels, int64_t n_labels, double iso, double *out,
+                 void *stream);
+int hl_mesh_pack_points(const float *pts, const float *dirs, int64_t n_verts, float *pts4, float *dirs4, void *stream);
+int hl_mesh_unpack_colors(const float *records, int64_t n_verts, float *rgb, uint8_t *rgb8, void *stream);
 
 /* ---- fused optimizer tail (train_util.TrainLoop.optimize_normal: _log_grad_norm, clip_grad_value_, AdamW, update_ema) -------------
  * Contract: DESIGN.md "Training loop".  fp32 tensors; the host packs a table once per parameter list and keeps it on the device.

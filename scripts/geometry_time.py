@@ -1,5 +1,6 @@
 """Times Renderer.extract_geometry(resolution=N, mesher="hip") by stage on the synthetic planes, and the numpy restatement of the
-same contract on the host (tests/geometry_restatement.py - a restatement, not PyMCubes).
+same contract on the host (tests/geometry_restatement.py - a restatement, not PyMCubes).  The stages that finish the mesh
+(Renderer.extract_mesh: labelling, filter, normals, colours) are timed in the same run, between HIP events.
 
     python scripts/geometry_time.py [--res 512] [--reps 3] [--json out.json]      # device
     python scripts/geometry_time.py --cpu 128 [--cpu-scipy-edt]                   # host restatement only
@@ -49,6 +50,17 @@ def timed(fn):
     return out, (time.perf_counter() - t) * 1e3
 
 
+def timed_events(fn):
+    """fn's span on the stream, between two HIP events (a host read inside fn, like the labelling's round flag, is inside the span)."""
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    a.record()
+    out = fn()
+    b.record()
+    b.synchronize()
+    return out, a.elapsed_time(b)
+
+
 def device(res, reps):
     from humanliff_amd.NeRF import geometry
     dev = torch.device("cuda:0")
@@ -62,11 +74,24 @@ def device(res, reps):
         (v, t), t_mc = timed(lambda: geometry.marching_cubes(sm, 0.0))
         _, t_all = timed(lambda: r.extract_geometry(tp, planes, resolution=res, mesher="hip"))
         t_sweep = (t_smooth - t_prep) / iters
+        # finishing the mesh
+        (labels, sizes, rounds), t_label = timed_events(lambda: geometry._label_components(sm, 0.0))
+        kept = geometry.select_components(sizes, "largest")
+        _, t_filter = timed_events(lambda: geometry.filter_components(sm, 0.0, labels, int(sizes.numel()), kept))
+        b = tp["world_bounds"].reshape(-1, 2, 3)[0]
+        ext, lo = (b[1] - b[0]).double(), b[0].double()
+        nrm, t_normals = timed_events(lambda: geometry.vertex_normals(sm, 0.0, v, ext))
+        vw = v / (res - 1.0) * ext[None, :] + lo[None, :]
+        _, t_colors = timed_events(lambda: r.vertex_colors(tp, planes, vw, -nrm))
+        _, t_mesh = timed(lambda: r.extract_mesh(tp, planes, resolution=res, components="largest"))
+        del labels, nrm, vw
         rows.append(dict(res=res, field_ms=round(t_field, 2), smooth_ms=round(t_smooth, 2), smooth_setup_ms=round(t_prep, 2),
                          sweeps=iters, sweep_ms=round(t_sweep, 4), band=nb,
                          sweep_GBps=round(SWEEP_BYTES * nb / (t_sweep * 1e-3) / 1e9, 1),
                          mc_ms=round(t_mc, 2), vertices=int(v.shape[0]), triangles=int(t.shape[0]),
-                         smooth_plus_mc_ms=round(t_smooth + t_mc, 2), extract_geometry_ms=round(t_all, 2)))
+                         smooth_plus_mc_ms=round(t_smooth + t_mc, 2), extract_geometry_ms=round(t_all, 2),
+                         label_ms=round(t_label, 2), label_rounds=rounds, components=int(sizes.numel()), filter_ms=round(t_filter, 2),
+                         normals_ms=round(t_normals, 2), colors_ms=round(t_colors, 2), extract_mesh_ms=round(t_mesh, 2)))
         del u, sm, v, t
         print(json.dumps(rows[-1]), flush=True)
     return rows

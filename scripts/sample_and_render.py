@@ -31,7 +31,12 @@ def main():
     ap.add_argument("--meshes", help="write one PLY mesh per subject and layer here (extract_geometry, mesher='hip'; "
                                      "triplane_sample_layered.py:201-207)")
     ap.add_argument("--mesh-res", type=int, default=512, help="density lattice resolution of the meshes (the reference's 512)")
+    ap.add_argument("--mesh-components", default="none", help="which solid components the meshes keep: largest, K (the K largest) or "
+                                                              "none (all of them: no filter)")
+    ap.add_argument("--mesh-attributes", action="store_true", help="write vertex normals and colours into the PLY files (extract_mesh)")
     args = ap.parse_args()
+    if args.mesh_components not in ("none", "largest") and not (args.mesh_components.isdigit() and int(args.mesh_components) > 0):
+        ap.error("--mesh-components: largest, a positive integer K or none")
     rank, world, dev = hd.init_distributed()
     cfg = dict(bench.F4, timestep_respacing=f"ddim{args.ddim}")
     model, diffusion = create_model_and_diffusion(**cfg)
@@ -78,10 +83,18 @@ def main():
             for sid in range(args.subjects):
                 for layer in range(args.layers):
                     planes = samples[sid, layer].to(dev).clamp(-1, 1).reshape(1, 3, 9, 256, 256)
-                    v, t = r.extract_geometry(tp, planes, resolution=args.mesh_res, threshold=0, mesher="hip")
                     path = os.path.join(args.meshes, f"subject{sid:03d}_layer{layer}.ply")
-                    write_ply(path, v, t)
-                    print(f"{path}: {len(v)} vertices, {len(t)} triangles")
+                    if args.mesh_components == "none" and not args.mesh_attributes:
+                        v, t = r.extract_geometry(tp, planes, resolution=args.mesh_res, threshold=0, mesher="hip")
+                        write_ply(path, v, t)
+                        print(f"{path}: {len(v)} vertices, {len(t)} triangles")
+                        continue
+                    keep = args.mesh_components if args.mesh_components == "largest" else int(args.mesh_components) if args.mesh_components != "none" else None
+                    m = r.extract_mesh(tp, planes, resolution=args.mesh_res, threshold=0, components=keep, normals=args.mesh_attributes,
+                                       colors=args.mesh_attributes)
+                    write_ply(path, m["vertices"], m["triangles"], normals=m["normals"], colors=m["colors"])
+                    print(f"{path}: {len(m['vertices'])} vertices, {len(m['triangles'])} triangles, {len(m['component_sizes'])} solid "
+                          f"components{' (kept: ' + args.mesh_components + ')' if args.mesh_components != 'none' else ''}")
 
 
 if __name__ == "__main__":
