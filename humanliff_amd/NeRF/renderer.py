@@ -596,6 +596,15 @@ class Renderer(nn.Module):
             out["colors"] = self._vertex_colors(tp_input, tri_planes, verts, -nrm, want_u8=True)[1].cpu().numpy()
         return out
 
+    def bind_mesh(self, mesh, posed, frame=0, neighbours=4):
+        """Tie the dict extract_mesh returns to the posed body it was extracted in (frame `frame` of `posed`, a PosedBody made with
+        forward_rows=True) -> animate.MeshBinding, whose repose(posed, frames) gives the mesh in any frames without another extraction;
+        `triangles` and `colors` ride along unchanged.  DESIGN.md "Animating the mesh"."""
+        from . import animate
+        binding = animate.bind_mesh(mesh["vertices"], posed, frame=frame, neighbours=neighbours, normals=mesh.get("normals"))
+        binding.triangles, binding.colors = mesh.get("triangles"), mesh.get("colors")
+        return binding
+
 
 def render(chunk=1024 * 32, rays_o=None, rays_d=None, near=0., far=1., tri_planes=None, tp_input=None, renderer=None,
            n_samples=128, perturb=0., n_importance=0, white_bkgd=False):

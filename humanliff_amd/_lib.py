@@ -225,6 +225,9 @@ SIGNATURES = {
     "hl_smplx_chunk_frames": (_i, []),
     "hl_smplx_pose_workspace_bytes": (_sz, [_i, _i]),
     "hl_smplx_pose": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _sz, C.c_float, C.c_float, _p]),
+    "hl_mesh_bind": (_i, [_p, _p, _i64, _p, _p, _i, _p, _p, _i, _p, _p, _p, _p, _p]),
+    "hl_mesh_repose_scratch_bytes": (_sz, [_i64, _i]),
+    "hl_mesh_repose": (_i, [_p, _p, _p, _p, _i64, _i, _p, _i, _i, _p, _i, _p, _p, _p, _p, C.c_float, C.c_float, _p, _sz, _p]),
 }
 
 

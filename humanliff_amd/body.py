@@ -132,10 +132,11 @@ class _DeviceModel:
             raise RuntimeError(f"{self.NAME}.pose: `{what}` is a CPU tensor; there is no CPU path (move it to the model's device)")
         return t.detach().to(device=self.device, dtype=torch.float32)
 
-    def _run(self, entry, model_args, ws_bytes, ws_joint_floats, F, poses, shapes, R, Th, big, y_margin):
+    def _run(self, entry, model_args, ws_bytes, ws_joint_floats, F, poses, shapes, R, Th, big, y_margin, forward_rows=False):
         """One call of the pose entry point `entry`: `model_args` are its arguments between J and rt, `ws_bytes` names its workspace
         query; the workspace is A (F,J,16) | ... | the pose features (F,P), `ws_joint_floats` per joint before the features.  R, Th:
-        host arrays or tensors, one or F of each (None: I, 0).  Returns the PosedBody of the F frames."""
+        host arrays or tensors, one or F of each (None: I, 0).  `forward_rows`: also write the (F,V,16) forward rows (what the big pose always
+        gets).  Returns the PosedBody of the F frames."""
         L, J, V, dev = _lib.lib(), self.J, self.V, self.device
         host = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)  # noqa: E731
         Rh = np.ascontiguousarray(host(np.eye(3) if R is None else R), dtype=np.float32).reshape(-1, 3, 3)
@@ -154,7 +155,7 @@ class _DeviceModel:
             rt = rt_host.to(dev, non_blocking=True)
             vertices, joints, bounds, verts4 = new(F, V, 3), new(F, J, 3), new(F, 2, 3), new(F, V, 4)
             table = new(F, V, 36) if big is not None else None
-            rows = new(F, V, 16) if big is None else None
+            rows = new(F, V, 16) if big is None or forward_rows else None
             ws = new(getattr(L, ws_bytes)(J, F) // 4)
             _lib.check(getattr(L, entry)(_lib.ptr(packed), _lib.ptr(self._parents_dev, torch.int32), V, J, *model_args, _lib.ptr(rt),
                                          12 if n_rt > 1 else 0, _lib.ptr(big.rows[0]) if big is not None else None, _lib.ptr(vertices),
@@ -218,14 +219,16 @@ class BodyModel(_DeviceModel):
         return self._big
 
     # ---- posing ----------------------------------------------------------------------------------
-    def pose(self, poses, shapes, R=None, Th=None, y_margin=0.05):
+    def pose(self, poses, shapes, R=None, Th=None, y_margin=0.05, forward_rows=False):
         """poses (F,3J) or (3J,), shapes (S,) or (F,S): device tensors.  R (3,3) or (F,3,3), Th (3,) or (F,3): host arrays (enqueue-only)
         or device tensors (one read back here: the deform kernels take them from the host).  Returns a PosedBody of F frames.
-        `y_margin`: what world_bounds adds on y beyond the 0.05 of every axis - 0.05 for SynBody, 0.1 for TightCap (TightCap_dataset.py:165-168)."""
+        `y_margin`: what world_bounds adds on y beyond the 0.05 of every axis - 0.05 for SynBody, 0.1 for TightCap (TightCap_dataset.py:165-168).
+        `forward_rows`: also keep `.rows` (F,V,16), the blended R[9] t[3] pose_off[3] pad[1] of every vertex, which NeRF/animate.py binds
+        an extracted mesh to and reposes it from."""
         self._need_device()
-        return self._pose(poses, shapes, R, Th, big=self.big_pose(), y_margin=y_margin)
+        return self._pose(poses, shapes, R, Th, big=self.big_pose(), y_margin=y_margin, forward_rows=forward_rows)
 
-    def _pose(self, poses, shapes, R, Th, big, y_margin=0.05):
+    def _pose(self, poses, shapes, R, Th, big, y_margin=0.05, forward_rows=False):
         self._need_device()
         for name, t in (("poses", poses), ("shapes", shapes), ("R", R), ("Th", Th)):
             if torch.is_tensor(t) and not t.is_cuda:
@@ -241,12 +244,13 @@ class BodyModel(_DeviceModel):
             raise ValueError(f"BodyModel.pose: shapes for {shapes.shape[0]} frames, poses for {F}")
         # (hl_body_pose with the margins of the bounds spelled out: 0.05f, 0.05f is what that call passes)
         args = (self.Sp, S, F, _lib.ptr(poses), _lib.ptr(shapes), S if shapes.shape[0] == F and F > 1 else 0)
-        return self._run("hl_pose_body_margins", args, "hl_body_pose_workspace_bytes", 16, F, poses, shapes, R, Th, big, y_margin)
+        return self._run("hl_pose_body_margins", args, "hl_body_pose_workspace_bytes", 16, F, poses, shapes, R, Th, big, y_margin, forward_rows)
 
 
 class PosedBody:
     """F posed frames.  Device tensors: vertices (F,V,3), joints (F,J,3), world_bounds (F,2,3), verts4 (F,V,4), table (F,V,36), A
-    (F,J,4,4), pose_features (F,9(J-1)), poses (F,3J), shapes (1 or F,S), rt (1 or F,12) = R | Th.  Host float32 arrays: R (1 or F,3,3), Th (1 or F,3)."""
+    (F,J,4,4), pose_features (F,9(J-1)), poses (F,3J), shapes (1 or F,S), rt (1 or F,12) = R | Th, rows (F,V,16) when posed with forward_rows=True
+    (None otherwise).  Host float32 arrays: R (1 or F,3,3), Th (1 or F,3)."""
 
     def _rt(self, f):
         return self.R[f if self.R.shape[0] > 1 else 0], self.Th[f if self.Th.shape[0] > 1 else 0]
@@ -378,25 +382,26 @@ class SmplxModel(_DeviceModel):
 
     # ---- posing ----------------------------------------------------------------------------------
     def pose(self, global_orient, body_pose, betas, expression, jaw_pose=None, leye_pose=None, reye_pose=None, left_hand_pose=None,
-             right_hand_pose=None, transl=None, R=None, Th=None, y_margin=0.05, big_global_orient=None):
+             right_hand_pose=None, transl=None, R=None, Th=None, y_margin=0.05, big_global_orient=None, forward_rows=False):
         """SMPLX.forward for F frames: global_orient (F,3), body_pose (F,63), betas (nb,) / (1,nb) shared or (F,nb), expression (F,ne), the
         other parts (F,3) / (F,45) or None for zeros, transl (F,3) or None: device tensors (host arrays are uploaded).  R, Th: the dataset's
-        world transform, as BodyModel.pose takes them.  `big_global_orient`: which big pose the tables' canonical columns come from."""
+        world transform, as BodyModel.pose takes them.  `big_global_orient`: which big pose the tables' canonical columns come from.
+        `forward_rows`: as BodyModel.pose (the rows are shape set 1's and, like every row, without transl)."""
         self._need_device()
         parts = {'global_orient': global_orient, 'body_pose': body_pose, 'jaw_pose': jaw_pose, 'leye_pose': leye_pose, 'reye_pose': reye_pose,
                  'left_hand_pose': left_hand_pose, 'right_hand_pose': right_hand_pose}
-        return self._pose(parts, betas, expression, transl, R, Th, big=self.big_pose(big_global_orient), y_margin=y_margin)
+        return self._pose(parts, betas, expression, transl, R, Th, big=self.big_pose(big_global_orient), y_margin=y_margin, forward_rows=forward_rows)
 
-    def pose_dict(self, d, R=None, Th=None, y_margin=0.05, big_global_orient=None):
+    def pose_dict(self, d, R=None, Th=None, y_margin=0.05, big_global_orient=None, forward_rows=False):
         """pose() of a dict under the key names of a SynBody smplx.npz (missing parts are zeros; other keys are ignored).  Host tensors,
         as the dataset's prepare_smpl_params makes them, are uploaded."""
         self._need_device()
         d = {k: (v.to(self.device) if torch.is_tensor(v) and k not in ('R', 'Th') else v) for k, v in d.items()}
         return self.pose(d['global_orient'], d['body_pose'], d['betas'], d['expression'], d.get('jaw_pose'), d.get('leye_pose'), d.get('reye_pose'),
                          d.get('left_hand_pose'), d.get('right_hand_pose'), d.get('transl'), R if R is not None else d.get('R'),
-                         Th if Th is not None else d.get('Th'), y_margin=y_margin, big_global_orient=big_global_orient)
+                         Th if Th is not None else d.get('Th'), y_margin=y_margin, big_global_orient=big_global_orient, forward_rows=forward_rows)
 
-    def _pose(self, parts, betas, expression, transl, R, Th, big, y_margin=0.05):
+    def _pose(self, parts, betas, expression, transl, R, Th, big, y_margin=0.05, forward_rows=False):
         self._need_device()
         dev = self.device
         go = self._dev(parts['global_orient'], 'global_orient').reshape(-1, 3)
@@ -419,6 +424,6 @@ class SmplxModel(_DeviceModel):
             if transl.shape[0] != F:
                 raise ValueError(f"SmplxModel.pose: transl for {transl.shape[0]} frames, poses for {F}")
         args = (self.S, self.two_sets, F, _lib.ptr(poses), _lib.ptr(coef), _lib.ptr(transl))
-        posed = self._run("hl_smplx_pose", args, "hl_smplx_pose_workspace_bytes", 20, F, poses, coef, R, Th, big, y_margin)
+        posed = self._run("hl_smplx_pose", args, "hl_smplx_pose_workspace_bytes", 20, F, poses, coef, R, Th, big, y_margin, forward_rows)
         posed.transl = transl
         return posed

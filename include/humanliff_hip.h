@@ -980,6 +980,30 @@ int hl_view_ingest_layers(const unsigned char *img_u8, const unsigned char *full
                           const unsigned char *bottom, const unsigned char *shoes, const int32_t *layers, int V, int Hs, int Ws, int H, int W,
                           const int32_t *xtab, const int32_t *ytab, float *out_image, unsigned char *out_body, void *stream);
 
+/* ---- animating an extracted mesh: bind its vertices to a posed body once, repose them for any frames (an extension beside the
+ *      reference) ----
+ * Contract: DESIGN.md "Animating the mesh"; csrc/hl_mesh_animate.hip.  Contiguous device arrays, enqueue-only on `stream`, nothing
+ * allocated, fp32 with every sum in a fixed order and no atomics: a frame has the same bits alone or inside a batch.  `rows` are the
+ * forward rows hl_body_pose / hl_smplx_pose write as big_out, (V,16) per frame: R[9] t[3] pose_off[3] pad[1]; `verts4` their verts4;
+ * `rt` 12 floats per frame, the row-major R and then Th.  N mesh vertices (N == 0: HL_OK, nothing launched), 1 <= K <= 8 neighbours,
+ * K <= V, V >= 1, F >= 1: other sizes are refused before any launch.  rows and verts4 must be 16-byte aligned.
+ *   hl_mesh_bind, against ONE frame (verts4 (V,4), rows (V,16), rt (12), transl (3) or NULL of that frame): for mesh vertex x (points (N,3), world) with
+ *     optional world normal n (normals (N,3) or NULL): q = (x - Th) R;  the K body vertices of smallest d = (dx dx + dy dy) + dz dz,
+ *     ordered by (d, index) ascending;  w_k = 1 / (d_k + 1e-8f) over their sum;  M = sum_k w_k R_k,  c = sum_k w_k (R_k po_k + t_k);
+ *     u = M^-1 ((q - transl) - c) (inverse by cofactors; verts4 holds transl, the rows do not);  m = normalize(M^T (n R)), zero for a zero or non-finite vector (and for normals == NULL).
+ *     -> ids int32 (N,K), weights (N,K), rest (N,3) = u, rest_normals (N,3) = m or NULL.
+ *   hl_mesh_repose, F frames (rows (F,V,16); rt with rt_stride 0 or 12; transl (F,3) or NULL - what hl_smplx_pose adds after skinning):
+ *     M_f, c_f as above from rows[f];  y = M_f u + c_f (+ transl[f]);  vertices (F,N,3) = R y + Th;  normals (F,N,3) or NULL =
+ *     R normalize(cof(M_f) m), the cofactor matrix (nothing is divided; zero stays zero; needs rest_normals);  bounds (F,2,3) or NULL =
+ *     min / max of the frame's vertices, - / + margin, y once more by y_margin (hl_pose_body_margins' arithmetic), through `scratch` of
+ *     hl_mesh_repose_scratch_bytes(N, F) bytes (not read when bounds is NULL). */
+int hl_mesh_bind(const float *points, const float *normals, int64_t N, const float *verts4, const float *rows, int V, const float *rt,
+                 const float *transl, int K, int32_t *ids, float *weights, float *rest, float *rest_normals, void *stream);
+size_t hl_mesh_repose_scratch_bytes(int64_t N, int F);
+int hl_mesh_repose(const int32_t *ids, const float *weights, const float *rest, const float *rest_normals, int64_t N, int K, const float *rows,
+                   int V, int F, const float *rt, int rt_stride, const float *transl, float *vertices, float *normals, float *bounds,
+                   float margin, float y_margin, void *scratch, size_t scratch_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,118 @@
+"""A mesh per frame of a motion without re-extracting: bind an extracted mesh to the body of the pose it was extracted in and repose
+it along a pose sequence on the device (humanliff_amd/NeRF/animate.py, csrc/hl_mesh_animate.hip; DESIGN.md "Animating the mesh").
+
+    python scripts/animate_mesh.py --synthetic --out /tmp/anim [--frames 16]
+    python scripts/animate_mesh.py --mesh subject.ply --model assets/SMPL_NEUTRAL.pkl --bind-pose extracted.npz --poses motion.npz --out anim
+    python scripts/animate_mesh.py --smpl_type smplx --model assets/models/smplx [--gender female] --mesh subject.ply \\
+        --bind-pose subject/smplx.npz --poses motion/smplx.npz --out anim
+
+--mesh: a PLY written by geometry.write_ply (vertices, triangles, optionally normals and colours).  --bind-pose: the pose the mesh was
+extracted in (its first frame is taken), --poses: the sequence; both in the format of scripts/render_pose_sequence.py - an .npz with
+`poses` (F,72), `shapes` and optionally `R`, `Th`, or for --smpl_type smplx a SynBody smplx.npz.  Writes <out>/frame_0000.ply, ...: the
+reposed vertices and normals, the triangles and the colours unchanged (they belong to the surface, not to the pose), `--chunk` frames
+per repose call so that the F x N output stays bounded.  --synthetic takes the seeded stand-ins of humanliff_amd.synthetic: the body
+model, a swinging-limbs sequence and, for the mesh, the body's own vertices pushed 1 cm off their centroid (no triangles).
+One JSON line of timings at the end.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "scripts"))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+
+def pose_file(model, path, smplx, frames=None):
+    """A pose file of render_pose_sequence.py's formats -> PosedBody with forward rows."""
+    if smplx:
+        with np.load(path, allow_pickle=True) as z:
+            fitted = z["smplx"].item()
+        fitted = {k: np.asarray(v, dtype=np.float32) if k == "betas" else np.asarray(v, dtype=np.float32)[:frames] for k, v in fitted.items()}
+        return model.pose_dict({k: torch.from_numpy(v) for k, v in fitted.items()}, forward_rows=True)
+    z = np.load(path)
+    poses, shapes = z["poses"].astype(np.float32).reshape(-1, 72)[:frames], z["shapes"].astype(np.float32)
+    if shapes.ndim == 2 and shapes.shape[0] > 1:
+        shapes = shapes[:frames]
+    dev = model.device
+    take = lambda k, n: (np.asarray(z[k])[:frames] if np.asarray(z[k]).ndim == n else z[k]) if k in z.files else None  # noqa: E731
+    return model.pose(torch.from_numpy(poses).to(dev), torch.from_numpy(shapes).to(dev), take("R", 3), take("Th", 2), forward_rows=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--mesh")
+    ap.add_argument("--model")
+    ap.add_argument("--smpl_type", choices=["smpl", "smplx"], default="smpl")
+    ap.add_argument("--gender", default=None)
+    ap.add_argument("--synthetic", action="store_true")
+    ap.add_argument("--bind-pose")
+    ap.add_argument("--poses")
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--frames", type=int, default=None)
+    ap.add_argument("--neighbours", type=int, default=4)
+    ap.add_argument("--chunk", type=int, default=16)
+    a = ap.parse_args()
+    from humanliff_amd import synthetic as syn
+    from humanliff_amd.NeRF import animate, geometry
+    from humanliff_amd.body import load_body_model, load_smplx_model
+    if not a.synthetic and not (a.mesh and a.model and a.bind_pose and a.poses):
+        ap.error("give --mesh, --model, --bind-pose and --poses, or --synthetic for seeded stand-ins")
+    dev = torch.device("cuda:0")
+    smplx = a.smpl_type == "smplx"
+    if a.synthetic:
+        from render_pose_sequence import synthetic_sequence
+        F = a.frames or 16
+        seq = synthetic_sequence(F)
+        if smplx:
+            model = load_smplx_model(a.model if a.model else syn.smplx_like_model(10475, 23), dev, gender=a.gender or "neutral")
+            z = lambda n: np.zeros((F, n), dtype=np.float32)  # noqa: E731
+            posed = model.pose_dict({"global_orient": z(3), "body_pose": seq[:, 3:66], "betas": np.zeros((1, 10), dtype=np.float32), "expression": z(10)},
+                                    forward_rows=True)
+        else:
+            model = load_body_model(a.model if a.model else syn.smpl_like_model(6890, 5), dev)
+            posed = model.pose(torch.from_numpy(seq).to(dev), torch.zeros(10, device=dev), forward_rows=True)
+        bind_posed = posed
+        body = posed.vertices[0].cpu().numpy().astype(np.float64)
+        off = body - body.mean(axis=0)
+        nrm = off / np.linalg.norm(off, axis=1, keepdims=True)
+        mesh = {"vertices": body + 0.01 * nrm, "triangles": np.zeros((0, 3), dtype=np.int64), "normals": nrm, "colors": None}
+    else:
+        if smplx and a.gender is None:
+            with np.load(a.bind_pose, allow_pickle=True) as z:
+                a.gender = z["meta"].item()["gender"]
+        model = load_smplx_model(a.model, dev, gender=a.gender or "neutral") if smplx else load_body_model(a.model, dev)
+        bind_posed = pose_file(model, a.bind_pose, smplx, 1)
+        posed = pose_file(model, a.poses, smplx, a.frames)
+        parts = geometry.read_ply(a.mesh)
+        mesh = {"vertices": parts[0], "triangles": parts[1], "normals": None, "colors": None}
+        for extra in parts[2:]:
+            mesh["colors" if extra.dtype == np.uint8 else "normals"] = extra
+    os.makedirs(a.out, exist_ok=True)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    binding = animate.bind_mesh(mesh["vertices"], bind_posed, frame=0, neighbours=a.neighbours, normals=mesh["normals"])
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    t_repose = 0.0
+    chunk = max(1, a.chunk)
+    for f0 in range(0, posed.F, chunk):
+        ta = time.perf_counter()
+        out = binding.repose(posed, frames=slice(f0, f0 + chunk), bounds=False)
+        verts = out["vertices"].cpu().numpy()                       # (the synchronise)
+        nrms = None if out["normals"] is None else out["normals"].cpu().numpy()
+        t_repose += time.perf_counter() - ta
+        for k in range(verts.shape[0]):
+            geometry.write_ply(os.path.join(a.out, f"frame_{f0 + k:04d}.ply"), verts[k], mesh["triangles"], None if nrms is None else nrms[k],
+                               mesh["colors"])
+    print(json.dumps({"frames": posed.F, "mesh_vertices": binding.N, "neighbours": binding.K, "bind_ms": round((t1 - t0) * 1e3, 3),
+                      "repose_and_read_back_ms_per_frame": round(t_repose * 1e3 / posed.F, 3), "out": a.out}))
+
+
+if __name__ == "__main__":
+    main()
