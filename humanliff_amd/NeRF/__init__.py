@@ -1,1 +1,2 @@
 from .renderer import Renderer, render, render_rays, render_view  # noqa: F401
+from .raster import rasterize  # noqa: F401

@@ -136,3 +136,17 @@ class MeshBinding:
                                         _lib.ptr(out["world_bounds"]), float(margin), float(y_margin), _lib.ptr(scratch),
                                         scratch.numel() * 4 if bounds else 0, _lib.stream_ptr(dev)), "hl_mesh_repose")
         return out
+
+    def rasterize(self, posed, H, W, K, R, T, frames=None, **kw):
+        """repose(posed, frames), then raster.rasterize with the binding's triangles and colours: the mesh in those frames as images
+        (rgb_map, acc_map, normal_map, depth_map, triangle_id, barycentrics, each (F,H,W,...)).  K, R, T: one camera for all frames or
+        one per frame; `kw`: rasterize's options (shade, white_bkgd, cull, znear, check_indices).  DESIGN.md "Rasterising the mesh"."""
+        from . import raster
+        if self.triangles is None or len(self.triangles) == 0:
+            raise ValueError("MeshBinding.rasterize: the binding carries no triangles (bind with Renderer.bind_mesh, or set `triangles`)")
+        moved = self.repose(posed, frames=frames, bounds=False)
+        dev = moved["vertices"].device
+        cached = getattr(self, "_triangles_i32", None)      # (triangles, its int32 device copy): converted once, not per call
+        if cached is None or cached[0] is not self.triangles or cached[1].device != dev:
+            cached = self._triangles_i32 = (self.triangles, raster.device_triangles(self.triangles, dev))
+        return raster.rasterize(moved["vertices"], cached[1], H, W, K, R, T, normals=moved["normals"], colors=self.colors, **kw)

@@ -31,6 +31,11 @@ HL_COMPOSITE_WAVE_FWD = 2
 HL_COMPOSITE_SERIAL_EXACT = 3
 HL_COMPOSITE_WAVE_BWD = 4
 HL_COMPOSITE_SERIAL_BWD = 5
+HL_RASTER_CAM_ROW = 30
+HL_RASTER_WHITE_BKGD = 1
+HL_RASTER_HEADLIGHT = 2
+HL_RASTER_CULL_BACK = 4
+HL_RASTER_CULL_FRONT = 8
 
 
 class HipLibraryMissing(RuntimeError):
@@ -228,6 +233,9 @@ SIGNATURES = {
     "hl_mesh_bind": (_i, [_p, _p, _i64, _p, _p, _i, _p, _p, _i, _p, _p, _p, _p, _p]),
     "hl_mesh_repose_scratch_bytes": (_sz, [_i64, _i]),
     "hl_mesh_repose": (_i, [_p, _p, _p, _p, _i64, _i, _p, _i, _i, _p, _i, _p, _p, _p, _p, C.c_float, C.c_float, _p, _sz, _p]),
+    "hl_mesh_raster_small_box": (_i, []),
+    "hl_mesh_raster_scratch_bytes": (_sz, [_i64, _i64, _i, _i, _i]),
+    "hl_mesh_raster": (_i, [_p, _i, _i64, _p, _i64, _p, _i, _p, _p, _i, _i, _i, _i, C.c_double, _u, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
 }
 
 

@@ -1004,6 +1004,38 @@ int hl_mesh_repose(const int32_t *ids, const float *weights, const float *rest, 
                    int V, int F, const float *rt, int rt_stride, const float *transl, float *vertices, float *normals, float *bounds,
                    float margin, float y_margin, void *scratch, size_t scratch_bytes, void *stream);
 
+/* ---- rasterising a mesh: z-buffer and shading (an extension beside the reference, which has no mesh renderer) ----
+ * Contract: DESIGN.md "Rasterising the mesh"; csrc/hl_mesh_raster.hip.  Contiguous device arrays, enqueue-only on `stream`, nothing
+ * allocated.  F images; vertices (vertex_frames,N,3) fp32 world with vertex_frames 1 (shared by all images) or F; triangles (T,3)
+ * int32; normals (normal_frames,N,3) or NULL (flat normals), normal_frames 1 or vertex_frames; colors uint8 (N,3) or NULL (0.7 grey).
+ * h_cams: a HOST float64 table, HL_RASTER_CAM_ROW values per camera: K (3,3), inv(K) (3,3), R (3,3) world->camera, T (3), row-major;
+ * cam_stride HL_RASTER_CAM_ROW (F cameras) or 0 (one camera for all images).  Its rows reach the device as launch arguments.
+ *   project: cam = (R v) + T, p = K cam, sx = p.x / p.z, sy = p.y / p.z in float64, snapped to 1/256 pixel; pixel centres are integer
+ *     coordinates as in hl_camera_rays.  A vertex is invalid when a coordinate is not finite, cam.z <= znear or |sx|, |sy| > 2^19.
+ *   cover: exact int64 edge functions with a one-sided rule on edges, fp32 perspective depth 1 / ((b0/z0 + b1/z1) + b2/z2), one
+ *     64-bit atomicMin of (depth bits << 32 | triangle) per covered pixel; triangles with an invalid vertex, zero area, a culled
+ *     winding or an index outside [0, N) are skipped - the last sets bit 0 of *status (device int32, cleared first; may be NULL).
+ *     No near-plane clipping.  Boxes of more than hl_mesh_raster_small_box() pixels are drawn by up to 16 waves each in a second launch.
+ *   resolve -> rgb_map (F,H,W,3), acc_map (F,H,W) 0 / 1, normal_map (F,H,W,3) world, depth_map (F,H,W) camera z (= the ray parameter of
+ *     hl_camera_rays' rays), triangle_id int32 (F,H,W) or NULL (-1: background), barycentrics (F,H,W,3) or NULL (perspective-correct
+ *     weights of the triangle's vertices 0, 1, 2).  Background: zeros, rgb 1 with HL_RASTER_WHITE_BKGD.  HL_RASTER_HEADLIGHT: rgb times
+ *     |n . r| with r the unit ray direction of the pixel.
+ * scratch: hl_mesh_raster_scratch_bytes(N, T, F, H, W) bytes, 16-byte aligned, in this order: camera rows F x 288 bytes; vertex records
+ *     F x N x 16 bytes {int32 X, int32 Y, float z, uint32 flags}; z-buffer F x H x W x 8 bytes (rounded up to 16); 16 bytes holding the
+ *     large list's uint64 counter; the large list, min(T F, 2^20) entries of 16 bytes {uint32 triangle, image, box pixels, 0}.  0 for refused sizes.
+ * Refused before any launch (HL_ERR_INVALID): N, T, F, H or W < 1, F > 65535, N, T or H W >= 2^31, bad frame counts, strides, flags, znear. */
+#define HL_RASTER_CAM_ROW 30
+#define HL_RASTER_WHITE_BKGD 1u
+#define HL_RASTER_HEADLIGHT 2u
+#define HL_RASTER_CULL_BACK 4u
+#define HL_RASTER_CULL_FRONT 8u
+int hl_mesh_raster_small_box(void);
+size_t hl_mesh_raster_scratch_bytes(int64_t N, int64_t T, int F, int H, int W);
+int hl_mesh_raster(const float *vertices, int vertex_frames, int64_t N, const int32_t *triangles, int64_t T, const float *normals, int normal_frames,
+                   const unsigned char *colors, const double *h_cams, int cam_stride, int F, int H, int W, double znear, unsigned flags,
+                   float *rgb_map, float *acc_map, float *normal_map, float *depth_map, int32_t *triangle_id, float *barycentrics, int32_t *status,
+                   void *scratch, size_t scratch_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
