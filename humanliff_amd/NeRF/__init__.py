@@ -1,2 +1,3 @@
 from .renderer import Renderer, render, render_rays, render_view  # noqa: F401
 from .raster import rasterize  # noqa: F401
+from .simplify import simplify_mesh  # noqa: F401

@@ -562,16 +562,23 @@ class Renderer(nn.Module):
             _lib.check(L.hl_mesh_unpack_colors(_lib.ptr(rec), V, _lib.ptr(rgb), _lib.ptr(rgb8, torch.uint8), st), "hl_mesh_unpack_colors")
         return rgb, rgb8
 
-    def extract_mesh(self, tp_input, tri_planes=None, resolution=512, threshold=0.0, components=None, normals=True, colors=True):
+    def extract_mesh(self, tp_input, tri_planes=None, resolution=512, threshold=0.0, components=None, normals=True, colors=True, simplify=None):
         """The HIP mesh of extract_geometry(..., mesher="hip"), finished on the device.  Returns a dict of numpy arrays: `vertices` fp64
         (V,3) world, `triangles` int64 (T,3) - the bits of extract_geometry when components is None - `normals` fp64 (V,3) unit,
         outward (or None), `colors` uint8 (V,3) (or None): the MLP seen head-on, direction = -normal, and `component_sizes` int64:
         the voxel counts of the 26-connected solid components of the smoothed field, before filtering.  components: None,
-        "largest", an int k or ("min_voxels", m) - which components to mesh (geometry.keep_components)."""
+        "largest", an int k or ("min_voxels", m) - which components to mesh (geometry.keep_components).  simplify: None, or the cell
+        size k >= 1 in voxels: the mesh then goes through simplify.simplify_mesh with cell = (k ext) / (resolution - 1) per axis and the
+        bounds' lower corner as origin - cells aligned with the marching-cubes lattice - and the dict gains `vertex_map` int64, the
+        simplified vertex of every marching-cubes vertex or -1 (DESIGN.md "Simplifying the mesh")."""
         from . import geometry
+        if simplify is not None and not (isinstance(simplify, (int, float)) and not isinstance(simplify, bool) and 1 <= simplify < float("inf")):
+            raise ValueError(f"extract_mesh: simplify must be None or a cell size >= 1 in voxels, got {simplify!r}")
         out = {"vertices": np.zeros((0, 3), dtype=np.float64), "triangles": np.zeros((0, 3), dtype=np.int64),
                "normals": np.zeros((0, 3), dtype=np.float64) if normals else None,
                "colors": np.zeros((0, 3), dtype=np.uint8) if colors else None, "component_sizes": np.zeros(0, dtype=np.int64)}
+        if simplify is not None:
+            out["vertex_map"] = np.zeros(0, dtype=np.int64)
         u = Renderer.density_grid(self, tp_input, tri_planes, resolution)
         try:
             field = geometry.smooth(u)
@@ -589,11 +596,18 @@ class Renderer(nn.Module):
         nrm = geometry.vertex_normals(field, threshold, verts, ext) if (normals or colors) else None
         del field
         verts = verts / (resolution - 1.0) * ext[None, :] + lo[None, :]
+        rgb8 = self._vertex_colors(tp_input, tri_planes, verts, -nrm, want_u8=True)[1] if colors else None
+        if simplify is not None and int(tris.shape[0]) > 0:
+            from .simplify import _simplify
+            small = _simplify(verts, tris, cell=(float(simplify) * ext.cpu().numpy()) / (resolution - 1), origin=lo.cpu().numpy(),
+                              normals=nrm if normals else None, colors=rgb8)[0]
+            verts, tris, nrm, rgb8 = small["vertices"], small["triangles"], small["normals"], small["colors"]
+            out["vertex_map"] = small["vertex_map"].cpu().numpy()
         out["vertices"], out["triangles"] = verts.cpu().numpy(), tris.cpu().numpy()
         if normals:
             out["normals"] = nrm.cpu().numpy()
         if colors:
-            out["colors"] = self._vertex_colors(tp_input, tri_planes, verts, -nrm, want_u8=True)[1].cpu().numpy()
+            out["colors"] = rgb8.cpu().numpy()
         return out
 
     def bind_mesh(self, mesh, posed, frame=0, neighbours=4):

@@ -36,6 +36,8 @@ HL_RASTER_WHITE_BKGD = 1
 HL_RASTER_HEADLIGHT = 2
 HL_RASTER_CULL_BACK = 4
 HL_RASTER_CULL_FRONT = 8
+HL_SIMPLIFY_BOUNDS_WORDS = 6 + 6 * 1024
+HL_SIMPLIFY_ACC_WORDS = 20
 
 
 class HipLibraryMissing(RuntimeError):
@@ -236,6 +238,10 @@ SIGNATURES = {
     "hl_mesh_raster_small_box": (_i, []),
     "hl_mesh_raster_scratch_bytes": (_sz, [_i64, _i64, _i, _i, _i]),
     "hl_mesh_raster": (_i, [_p, _i, _i64, _p, _i64, _p, _i, _p, _p, _i, _i, _i, _i, C.c_double, _u, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "hl_mesh_simplify_bounds": (_i, [_p, _i64, _p, _p, _p]),
+    "hl_mesh_simplify_scratch_bytes": (_sz, [_i64] * 5),
+    "hl_mesh_simplify_count": (_i, [_p, _i64, _i64, _p, _p, _i64, _i64, _i64, _p, _p, _p, _sz, _p]),
+    "hl_mesh_simplify_emit": (_i, [_p, _p, _p, _i64, _p, _i64, _p, _p, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
 }
 
 

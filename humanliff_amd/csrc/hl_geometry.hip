@@ -10,87 +10,22 @@
 // The contract (signed distance, band, bounds, operator, stopping rule, corner rule, case table, ordering) is in DESIGN.md
 // ("Mesh extraction"); tests/geometry_restatement.py states it again in numpy.  Everything is fp64, the file is built with
 // -ffp-contract=off, and every reduction is integer or fixed-order, so results are bit-reproducible run to run.
-#include "hl_reduce.h"
+#include "hl_scan.h"
 #include "hl_mc_table.h"
 
 namespace {
 
 constexpr int TPB = 256;
 static_assert(TPB == hl::kReduceThreads, "block_sum / strided_sum reduce a workgroup of kReduceThreads");
-constexpr int SCAN_ITEMS = 16;
-constexpr int SCAN_TILE = TPB * SCAN_ITEMS;
+static_assert(TPB == hl::kScanThreads, "the scan kernels (hl_scan.h: the exclusive scan of packed integer counts) run workgroups of kScanThreads");
 constexpr int INF32 = 0x3fffffff;            // "no feature on this line yet" in the int32 squared-distance buffers
 constexpr long long INF64 = 1LL << 40;       // the same inside the envelope arithmetic (squares of the lattice stay below 2^32)
 
-inline long scan_blocks(long n) { return (n + SCAN_TILE - 1) / SCAN_TILE; }
+using hl::k_scan_down;
+using hl::k_scan_reduce;
+using hl::k_scan_top;
+using hl::scan_blocks;
 inline unsigned grid_of(long n) { return (unsigned)((n + TPB - 1) / TPB); }
-
-// ---- exclusive scan of packed (low 32, high 32) integer counts; integer sums, so the order does not matter ----------------
-template <class F>
-__global__ __launch_bounds__(TPB) void k_scan_reduce(F f, long n, unsigned long long *__restrict__ block_sums) {
-    __shared__ unsigned long long red[TPB];
-    const long base = (long)blockIdx.x * SCAN_TILE;
-    unsigned long long s = 0;
-    for (int k = 0; k < SCAN_ITEMS; ++k) {
-        const long i = base + (long)k * TPB + threadIdx.x;
-        if (i < n) s += f(i);
-    }
-    s = hl::block_sum(s, red);
-    if (threadIdx.x == 0) block_sums[blockIdx.x] = s;
-}
-
-__device__ unsigned long long block_exclusive(unsigned long long v, unsigned long long *sh, unsigned long long *total) {
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int w = 1; w < TPB; w <<= 1) {            // Hillis-Steele inclusive scan
-        const unsigned long long add = (int)threadIdx.x >= w ? sh[threadIdx.x - w] : 0ull;
-        __syncthreads();
-        sh[threadIdx.x] += add;
-        __syncthreads();
-    }
-    const unsigned long long incl = sh[threadIdx.x];
-    if (total) *total = sh[TPB - 1];
-    __syncthreads();
-    return incl - v;
-}
-
-// one workgroup: block sums -> exclusive block offsets (in place); the grand total unpacked into counts[0] (low) / counts[1] (high)
-__global__ __launch_bounds__(TPB) void k_scan_top(unsigned long long *__restrict__ block_sums, long nblocks, int64_t *__restrict__ counts) {
-    __shared__ unsigned long long sh[TPB];
-    const long chunk = (nblocks + TPB - 1) / TPB;
-    const long b0 = (long)threadIdx.x * chunk;
-    const long b1 = b0 + chunk < nblocks ? b0 + chunk : nblocks;
-    unsigned long long s = 0;
-    for (long b = b0; b < b1; ++b) s += block_sums[b];
-    unsigned long long total;
-    unsigned long long run = block_exclusive(s, sh, &total);
-    for (long b = b0; b < b1; ++b) {
-        const unsigned long long v = block_sums[b];
-        block_sums[b] = run;
-        run += v;
-    }
-    if (threadIdx.x == 0) {
-        counts[0] = (int64_t)(total & 0xffffffffull);
-        counts[1] = (int64_t)(total >> 32);
-    }
-}
-
-template <class F, class O>
-__global__ __launch_bounds__(TPB) void k_scan_down(F f, O out, long n, const unsigned long long *__restrict__ block_off) {
-    __shared__ unsigned long long sh[TPB];
-    const long base = (long)blockIdx.x * SCAN_TILE + (long)threadIdx.x * SCAN_ITEMS;
-    unsigned long long s = 0;
-    for (int k = 0; k < SCAN_ITEMS; ++k)
-        if (base + k < n) s += f(base + k);
-    unsigned long long run = block_off[blockIdx.x] + block_exclusive(s, sh, nullptr);
-    for (int k = 0; k < SCAN_ITEMS; ++k) {
-        const long i = base + k;
-        if (i >= n) break;
-        const unsigned long long v = f(i);
-        out(i, run, v);
-        run += v;
-    }
-}
 
 // ---- exact squared Euclidean distance transform, one axis per pass (Meijster et al. 2000 lower envelope) ------------------
 // Source of the first pass: f = 0 on feature voxels (v > 0 equals `feature`), INF elsewhere; later passes read the int32 buffer.

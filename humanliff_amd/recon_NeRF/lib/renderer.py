@@ -45,6 +45,6 @@ class Renderer(_Renderer):
         """NeRF.Renderer.vertex_colors on the module's own tri-planes."""
         return super().vertex_colors(tp_input, self._own_planes(tp_input)[:1], vertices_world, directions)
 
-    def extract_mesh(self, tp_input, resolution=512, threshold=0.0, components=None, normals=True, colors=True):
+    def extract_mesh(self, tp_input, resolution=512, threshold=0.0, components=None, normals=True, colors=True, simplify=None):
         """NeRF.Renderer.extract_mesh on the module's own tri-planes (first subject of the batch)."""
-        return super().extract_mesh(tp_input, self._own_planes(tp_input)[:1], resolution, threshold, components, normals, colors)
+        return super().extract_mesh(tp_input, self._own_planes(tp_input)[:1], resolution, threshold, components, normals, colors, simplify)

@@ -1036,6 +1036,40 @@ int hl_mesh_raster(const float *vertices, int vertex_frames, int64_t N, const in
                    float *rgb_map, float *acc_map, float *normal_map, float *depth_map, int32_t *triangle_id, float *barycentrics, int32_t *status,
                    void *scratch, size_t scratch_bytes, void *stream);
 
+/* ---- simplifying a mesh: cell clustering with quadrics (an extension beside the reference, which meshes coarsely instead) ----
+ * Contract: DESIGN.md "Simplifying the mesh"; csrc/hl_mesh_simplify.hip.  Contiguous device arrays, enqueue-only on `stream`, nothing
+ * allocated.  vertices fp64 (N,3) world; triangles int32 (T,3); normals fp64 (N,3) or NULL; colors uint8 (N,3) or NULL.  h_cell, h_origin:
+ * 3 HOST doubles each.  Geometry is float64 in cell units q = (v - origin) / cell; a vertex with a non-finite coordinate or one below
+ * the origin belongs to no cell; every sum is an int64 in fixed point at 2^30 per unit, so results do not depend on scheduling.
+ *   hl_mesh_simplify_bounds: bounds[0..2] / [3..5] = componentwise min / max of the valid vertices (+inf / -inf when there is none);
+ *     h_origin may be NULL (every finite vertex is valid).  bounds: HL_SIMPLIFY_BOUNDS_WORDS device doubles (the rest holds partials).
+ *     The host takes origin = min when none is given and the extents g = floor((max - origin) / cell) + 1 per axis.
+ *   hl_mesh_simplify_count: marks the occupied cells of the g grid and ranks them; counts[0] = clusters.  *status (device int32) is
+ *     cleared first; bit 0: a vertex without a cell.  counts: 6 device int64, cleared first (the odd entries are the scans' high
+ *     halves and stay 0).
+ *   hl_mesh_simplify_emit (scratch as left by hl_mesh_simplify_count, `clusters` = its counts[0], at most 2^21): counts[2] = surviving
+ *     triangles T', counts[4] = output vertices V'.  out_vertices fp64, out_normals fp64 (unit or zero), out_colors uint8: (V',3), room
+ *     for `clusters` rows, in ascending cell-key order; out_triangles int64 (T',3), room for T rows, in input order, smallest index
+ *     first, orientation kept; vertex_map int64 (N): the output vertex of every input vertex, or -1.  A triangle with a vertex without
+ *     a cell or an index outside [0, N) (status bit 1; never dereferenced) is dropped, as is one with two corners in one cell and every
+ *     repetition of an oriented triple of cells after the one of smallest index.  Status bit 2: the duplicate table ran out of probes.
+ * scratch: hl_mesh_simplify_scratch_bytes(N, T, gx, gy, gz) bytes, 16-byte aligned; it begins with the cluster id of every vertex,
+ *     int32 (N) (-1: none), rounded up to 16 bytes, then the accumulators int64 (min(N, cells, 2^21), HL_SIMPLIFY_ACC_WORDS): count,
+ *     position x y z, normal x y z, colour r g b, quadric xx xy xz yy yz zz xd yd zd dd.  0 for refused sizes.
+ * Refused before any launch (HL_ERR_INVALID): N or T < 1 or >= 2^31, a cell that is not positive and finite, a non-finite origin, an
+ *     extent < 1, more than 2^31 cells, more than 2^21 clusters. */
+#define HL_SIMPLIFY_BOUNDS_BLOCKS 1024
+#define HL_SIMPLIFY_BOUNDS_WORDS (6 + 6 * HL_SIMPLIFY_BOUNDS_BLOCKS)
+#define HL_SIMPLIFY_ACC_WORDS 20
+int hl_mesh_simplify_bounds(const double *vertices, int64_t N, const double *h_origin, double *bounds, void *stream);
+size_t hl_mesh_simplify_scratch_bytes(int64_t N, int64_t T, int64_t gx, int64_t gy, int64_t gz);
+int hl_mesh_simplify_count(const double *vertices, int64_t N, int64_t T, const double *h_cell, const double *h_origin, int64_t gx, int64_t gy, int64_t gz,
+                           int64_t *counts, int32_t *status, void *scratch, size_t scratch_bytes, void *stream);
+int hl_mesh_simplify_emit(const double *vertices, const double *normals, const unsigned char *colors, int64_t N, const int32_t *triangles, int64_t T,
+                          const double *h_cell, const double *h_origin, int64_t gx, int64_t gy, int64_t gz, int64_t clusters, double *out_vertices,
+                          double *out_normals, unsigned char *out_colors, int64_t *out_triangles, int64_t *vertex_map, int64_t *counts, int32_t *status,
+                          void *scratch, size_t scratch_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,8 @@ One JSON line of timings at the end.
 --images DIR also rasterises every frame (humanliff_amd/NeRF/raster.py; DESIGN.md "Rasterising the mesh") and writes
 DIR/frame_0000.png, ...: headlight-shaded colours on white.  The camera is --camera cam.npz (`K`, `R`, `T` - one camera or one per frame
 - and `H`, `W`) or --turntable N: N cameras of --res pixels on a circle around the first frame's bounds, frame f seen from camera f mod N.
+--simplify CELL first clusters the mesh on a grid of CELL world units (humanliff_amd/NeRF/simplify.py; DESIGN.md "Simplifying the
+mesh"): the binding, every reposed frame and every PLY then carry the smaller mesh.
 The mesh needs triangles; with --synthetic and --images the stand-in is an ellipsoid of the body's proportions around the body's centroid
 (triangulated, with normals and colours) instead of the offset vertices.  The JSON line then carries the raster timings too.
 """
@@ -99,7 +101,10 @@ def main():
     ap.add_argument("--camera")
     ap.add_argument("--turntable", type=int, default=0)
     ap.add_argument("--res", type=int, default=256)
+    ap.add_argument("--simplify", type=float, default=None, metavar="CELL")
     a = ap.parse_args()
+    if a.simplify is not None and not a.simplify > 0:
+        ap.error("--simplify CELL: a positive cell size in world units")
     if a.images and bool(a.camera) == bool(a.turntable > 0):
         ap.error("--images needs exactly one of --camera cam.npz and --turntable N")
     from humanliff_amd import synthetic as syn
@@ -140,6 +145,14 @@ def main():
         for extra in parts[2:]:
             mesh["colors" if extra.dtype == np.uint8 else "normals"] = extra
     os.makedirs(a.out, exist_ok=True)
+    simplified = None
+    if a.simplify is not None:
+        if len(mesh["triangles"]) == 0:
+            ap.error("--simplify needs a mesh with triangles (with --synthetic: add --images for the ellipsoid stand-in)")
+        from humanliff_amd.NeRF.simplify import simplify_mesh
+        before = (len(mesh["vertices"]), len(mesh["triangles"]))
+        mesh = simplify_mesh(mesh, cell=a.simplify)
+        simplified = {"cell": a.simplify, "vertices": [before[0], len(mesh["vertices"])], "triangles": [before[1], len(mesh["triangles"])]}
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     binding = animate.bind_mesh(mesh["vertices"], bind_posed, frame=0, neighbours=a.neighbours, normals=mesh["normals"])
@@ -195,6 +208,8 @@ def main():
     if a.images:
         line.update(images=a.images, image_size=[Hi, Wi], triangles=int(len(mesh["triangles"])),
                     raster_and_read_back_ms_per_frame=round(t_raster * 1e3 / posed.F, 3))
+    if simplified:
+        line.update(simplify=simplified)
     print(json.dumps(line))
 
 

@@ -34,7 +34,11 @@ def main():
     ap.add_argument("--mesh-components", default="none", help="which solid components the meshes keep: largest, K (the K largest) or "
                                                               "none (all of them: no filter)")
     ap.add_argument("--mesh-attributes", action="store_true", help="write vertex normals and colours into the PLY files (extract_mesh)")
+    ap.add_argument("--mesh-simplify", type=float, default=None, metavar="K",
+                    help="cluster the meshes on cells of K >= 1 lattice voxels before writing them (extract_mesh(..., simplify=K))")
     args = ap.parse_args()
+    if args.mesh_simplify is not None and not args.mesh_simplify >= 1:
+        ap.error("--mesh-simplify: a cell size of at least 1 voxel")
     if args.mesh_components not in ("none", "largest") and not (args.mesh_components.isdigit() and int(args.mesh_components) > 0):
         ap.error("--mesh-components: largest, a positive integer K or none")
     rank, world, dev = hd.init_distributed()
@@ -84,17 +88,19 @@ def main():
                 for layer in range(args.layers):
                     planes = samples[sid, layer].to(dev).clamp(-1, 1).reshape(1, 3, 9, 256, 256)
                     path = os.path.join(args.meshes, f"subject{sid:03d}_layer{layer}.ply")
-                    if args.mesh_components == "none" and not args.mesh_attributes:
+                    if args.mesh_components == "none" and not args.mesh_attributes and args.mesh_simplify is None:
                         v, t = r.extract_geometry(tp, planes, resolution=args.mesh_res, threshold=0, mesher="hip")
                         write_ply(path, v, t)
                         print(f"{path}: {len(v)} vertices, {len(t)} triangles")
                         continue
                     keep = args.mesh_components if args.mesh_components == "largest" else int(args.mesh_components) if args.mesh_components != "none" else None
                     m = r.extract_mesh(tp, planes, resolution=args.mesh_res, threshold=0, components=keep, normals=args.mesh_attributes,
-                                       colors=args.mesh_attributes)
+                                       colors=args.mesh_attributes, simplify=args.mesh_simplify)
                     write_ply(path, m["vertices"], m["triangles"], normals=m["normals"], colors=m["colors"])
                     print(f"{path}: {len(m['vertices'])} vertices, {len(m['triangles'])} triangles, {len(m['component_sizes'])} solid "
                           f"components{' (kept: ' + args.mesh_components + ')' if args.mesh_components != 'none' else ''}")
+                    if args.mesh_simplify is not None:
+                        print(f"{path}: simplified from {len(m['vertex_map'])} marching-cubes vertices (cells of {args.mesh_simplify:g} voxels)")
 
 
 if __name__ == "__main__":
