@@ -309,6 +309,10 @@ __global__ __launch_bounds__(256, 1) void k_conv_h16(const ConvK p) {
 // two-plane activation image; weight ring two k-steps deep; the epilogue exchange in two channel halves of 128 slots x 96 channels (50 KB).
 // Round 7: the 4 waves split N only (1 x 4), each owns all 128 pixels x 48 channels as 8 x 3 tiles of v_mfma_f32_16x16x32_f16 - a weight fragment
 // feeds 8 tiles instead of 2, which halves the weight bytes per FLOP (2048-workgroup launch at B = 4: 525 -> 479 us, profiles/r07_h2s_16x16x32_ab.md).
+// The chunk loop is straight-line code: the staging mode (raw / affine / affine + SiLU / two-plane image) is a template parameter of the body with one
+// entry point per mode (k_conv_h2s = affine + SiLU, k_conv_h2s_aff, k_conv_h2s_raw, k_conv_h2s_planes), the activation descriptor is built from
+// readfirstlane'd values so that no patch load sits in a waterfall loop, and a staged unit is eight slices behind the eight MFMA rows of its k-step with
+// its coefficient quads read a row ahead (headline 25.63 -> 25.20 ms per step, outputs bit for bit the same: profiles/h2s_straight_loop_ab.md).
 // k_conv_h2s_ph: the same body for the Upsample layers, four 2x2-tap phases of the source instead of nine taps of the upsampled image (256 px, B = 4: 463 -> 231 us,
 // profiles/upsample_phases_ab.md).
 // ---------------------------------------------------------------------------------------------------------------------------------------------
@@ -454,9 +458,18 @@ __device__ __forceinline__ float wave_uniform(float v) { return __builtin_bit_ca
 // the same mathematics.  A workgroup = the 8x16 source positions of ONE phase (tile index & 3: the four phases of a tile are neighbours in the grid, so
 // they run on one XCD and share the patch in L2), its 128 pixels stored at (2i + py, 2j + px); patch = the 9x17 source pixels from (i0 - 1 + py,
 // j0 - 1 + px) in the same [plane][10x18] layout, tap (a, b) = row mf + a, aoff[b]; a chunk of 32 channels is 4 k-steps.
+//
+// How the staging treats its input is a template parameter (H2sIn; the launchers pick the instantiation from ConvK::in16, cA / gn and act): the
+// unrolled chunk holds no branch on a launch constant, so it is ONE basic block (apart from per-lane exec masks) that the scheduler can order as a
+// whole.  A staged unit is cut into eight slices, one behind each MFMA row of its k-step - the affine, the 8 + 8 transcendentals of the SiLU two
+// values at a time, the splits, the two ds_write_b128 - and the unit's coefficient quads are read from the table with the
+// fragments of row 6 of the k-step before, a row ahead of the slice that needs them.
+enum H2sIn : int { H2S_RAW = 0, H2S_AFF = 1, H2S_AFF_SILU = 2, H2S_PLANES = 3 };   // fp32 x sx | x A + B | silu(x A + B) | the two-plane 16-bit image, as it is
 #if __HIP_DEVICE_COMPILE__
-template <bool PH>
+template <bool PH, int MODE>
 __device__ __forceinline__ void conv_h2s_body(const ConvK &p) {
+    static_assert(!PH || MODE == H2S_RAW, "an Upsample convolution follows a raw tensor");
+    constexpr bool IN16 = MODE == H2S_PLANES, AFF = MODE == H2S_AFF || MODE == H2S_AFF_SILU, ACT = MODE == H2S_AFF_SILU;
     constexpr unsigned OOB = 0x80000000u;
     constexpr int PW = PH ? H16_PW - 1 : H16_PW, PR = PH ? H2S_PH - 1 : H2S_PH;   // patch columns / rows
     constexpr int NU = PR * PW * 4, NUT = (NU + 255) / 256;       // staging units (pixel, 8-channel group): 720 (PH: 612) -> 3 per thread
@@ -476,16 +489,20 @@ __device__ __forceinline__ void conv_h2s_body(const ConvK &p) {
     const int img = tl / (bw * bh), brem = tl - img * (bw * bh);
     const int y0 = (brem / bw) * 8, x0 = (brem - (brem / bw) * bw) * 16;
     const int nch = p.Cin >> 5;
-    const unsigned pitch4 = (unsigned)p.in_pitch * (p.in16 ? 2u : 4u);
+    const unsigned pitch4 = (unsigned)p.in_pitch * (IN16 ? 2u : 4u);
     const unsigned plane_b = (unsigned)((long)p.N * p.Hin * p.Win * p.in_pitch * 2);
+    // The activation descriptor from values the compiler can PROVE wave-uniform (readfirstlane of the base's halves and of the byte count): left to
+    // itself it kept two descriptor words in VGPRs and wrapped each of the 12 patch loads in a waterfall loop (readfirstlane x 4, compare, saveexec,
+    // load, branch), which serialised the six loads behind every chunk's barrier and cost two registers.
+    const unsigned long in_u = (unsigned long)p.in;
+    const unsigned long in_s = ((unsigned long)(unsigned)__builtin_amdgcn_readfirstlane((int)(in_u >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)in_u);
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)p.in, (short)0, (int)((long)p.N * p.Hin * p.Win * pitch4 * (p.in16 == 2 ? 2 : 1)), 0x00020000);
+        (void *)in_s, (short)0, __builtin_amdgcn_readfirstlane((int)((long)p.N * p.Hin * p.Win * pitch4 * (IN16 ? 2 : 1))), 0x00020000);
     const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc(
         (void *)p.wf, (short)0, (int)((long)(PH ? 4 : 1) * p.n_nblocks * nch * NS * 24576), 0x00020000);
 
     // GroupNorm affine (+ SiLU) of the INPUT applied while staging (ConvK::cA / cB arrays, or ConvK::gn: coefficients formed here from the producers' group
     // totals): no pre-pass over the tensor.  The table sits behind the stages; padding pixels are zero AFTER the activation (the convolution pads the activated tensor).
-    const bool aff = !PH && (p.cA != nullptr || p.gn.gt != nullptr);      // (an Upsample convolution follows a raw tensor)
     float *sA = reinterpret_cast<float *>(lds + H2S_LDS), *sB = sA + p.Cin;
     float sx = 1.f, kq = -1.44269504088896341f;                    // power-of-two scale of the staged activations (hl_stats.h), -log2(e) / sx
     unsigned sv[NUT], sl[NUT];
@@ -496,38 +513,61 @@ __device__ __forceinline__ void conv_h2s_body(const ConvK &p) {
         const int y = y0 - 1 + phy + py, x = x0 - 1 + phx + px;
         const bool ok = u < NU && y >= 0 && y < Ht && x >= 0 && x < Wt;
         const int ys = !PH && p.ups ? y >> 1 : y, xs = !PH && p.ups ? x >> 1 : x;
-        sv[j] = ok ? (unsigned)((img * p.Hin + ys) * p.Win + xs) * pitch4 + grp * (p.in16 ? 16 : 32) : OOB;
+        sv[j] = ok ? (unsigned)((img * p.Hin + ys) * p.Win + xs) * pitch4 + grp * (IN16 ? 16 : 32) : OOB;
         sl[j] = u < NU ? (unsigned)((py * H16_LP + px) * 64 + ((grp ^ ((px >> 2) & 3)) << 4)) : (unsigned)(2 * H2S_STG + (tid & 63) * 16);
     }
     u32x4 ar[NUT][2];
     auto a_load = [&](int chunk) {
 #pragma unroll
         for (int j = 0; j < NUT; ++j) {
-            const int so = chunk * (p.in16 ? 64 : 128);
+            const int so = chunk * (IN16 ? 64 : 128);
             ar[j][0] = __builtin_amdgcn_raw_buffer_load_b128(rsA, sv[j], so, 0);
-            ar[j][1] = __builtin_amdgcn_raw_buffer_load_b128(rsA, sv[j] == OOB ? OOB : sv[j] + (p.in16 ? plane_b : 16u), so, 0);
+            ar[j][1] = __builtin_amdgcn_raw_buffer_load_b128(rsA, sv[j] == OOB ? OOB : sv[j] + (IN16 ? plane_b : 16u), so, 0);
         }
     };
-    auto a_store = [&](int stage, int j, int chunk) {
-        u32x4 h0 = ar[j][0], h1 = ar[j][1];
-        if (!p.in16) {
-            f32x4 v0 = __builtin_bit_cast(f32x4, ar[j][0]), v1 = __builtin_bit_cast(f32x4, ar[j][1]);
-            if (aff) {
-                const int cb = chunk * 32 + (tid & 3) * 8;           // this unit's eight channels (the group is tid & 3 for every unit of the thread)
-                v0 = v0 * *reinterpret_cast<const f32x4 *>(sA + cb) + *reinterpret_cast<const f32x4 *>(sB + cb);
-                v1 = v1 * *reinterpret_cast<const f32x4 *>(sA + cb + 4) + *reinterpret_cast<const f32x4 *>(sB + cb + 4);
-                if (p.act) {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) { v0[i] = h2s_silu(v0[i], kq); v1[i] = h2s_silu(v1[i], kq); }
-                }
-                if (sv[j] == OOB) { v0 = f32x4{0.f, 0.f, 0.f, 0.f}; v1 = v0; }
-            } else { v0 = v0 * sx; v1 = v1 * sx; }
-            const H2Pair q0 = split_h2(v0[0], v0[1]), q1 = split_h2(v0[2], v0[3]), q2 = split_h2(v1[0], v1[1]), q3 = split_h2(v1[2], v1[3]);
-            h0 = u32x4{q0.p0, q1.p0, q2.p0, q3.p0}; h1 = u32x4{q0.p1, q1.p1, q2.p1, q3.p1};
+    // the thread's coefficient quads of a chunk: A and B of channels cb .. cb + 3 and cb + 4 .. cb + 7, cb = 32 chunk + 8 (tid & 3) - the 8-channel group is
+    // tid & 3 for every unit of the thread, so the prologue reads them once for its three units; in the loop they are read again for every unit, since held
+    // over the three staging k-steps their 16 registers spill (24 bytes of scratch)
+    f32x4 cf[4];
+    auto c_read = [&](int chunk) {
+        if constexpr (AFF) {
+            const int cb = chunk * 32 + (tid & 3) * 8;
+            cf[0] = *reinterpret_cast<const f32x4 *>(sA + cb); cf[1] = *reinterpret_cast<const f32x4 *>(sB + cb);
+            cf[2] = *reinterpret_cast<const f32x4 *>(sA + cb + 4); cf[3] = *reinterpret_cast<const f32x4 *>(sB + cb + 4);
         }
-        char *dst = lds + (sl[j] >= 2u * H2S_STG ? 0 : stage * H2S_STG) + sl[j];
-        *reinterpret_cast<u32x4 *>(dst) = h0;
-        if (sl[j] < 2u * H2S_STG) *reinterpret_cast<u32x4 *>(dst + H2S_PLANE) = h1;
+    };
+    // Slice SL of staging unit j; the unit lives in ar[j] from slice to slice.  0: the affine (or the scale sx); 1 - 4: SiLU of two values each (2 + 2
+    // transcendentals); 5, 6: padding to zero and the split of four values into their planes, left where the values were (p0, p1 of a pair side by side);
+    // 7: the planes gathered and written.  All eight in order are the unit's staging; the arithmetic of a value does not depend on the cut.
+    auto a_slice = [&](auto sl_, int stage, int j) {
+        constexpr int SL = decltype(sl_)::value;
+        if constexpr (!IN16 && SL < 7) {
+            f32x4 v0 = __builtin_bit_cast(f32x4, ar[j][0]), v1 = __builtin_bit_cast(f32x4, ar[j][1]);
+            if constexpr (SL == 0) {
+                if constexpr (AFF) {
+                    v0 = v0 * cf[0] + cf[1];
+                    v1 = v1 * cf[2] + cf[3];
+                } else { v0 = v0 * sx; v1 = v1 * sx; }
+            } else if constexpr (SL <= 4) {
+                if constexpr (ACT) { v0[SL - 1] = h2s_silu(v0[SL - 1], kq); v1[SL - 1] = h2s_silu(v1[SL - 1], kq); }
+            } else {
+                f32x4 &v = SL == 5 ? v0 : v1;
+                if constexpr (AFF) { if (sv[j] == OOB) v = f32x4{0.f, 0.f, 0.f, 0.f}; }
+                const H2Pair qa = split_h2(v[0], v[1]), qb = split_h2(v[2], v[3]);
+                v = __builtin_bit_cast(f32x4, u32x4{qa.p0, qa.p1, qb.p0, qb.p1});
+            }
+            ar[j][0] = __builtin_bit_cast(u32x4, v0); ar[j][1] = __builtin_bit_cast(u32x4, v1);
+        }
+        if constexpr (SL == 7) {
+            const u32x4 h0 = IN16 ? ar[j][0] : u32x4{ar[j][0][0], ar[j][0][2], ar[j][1][0], ar[j][1][2]};
+            const u32x4 h1 = IN16 ? ar[j][1] : u32x4{ar[j][0][1], ar[j][0][3], ar[j][1][1], ar[j][1][3]};
+            char *dst = lds + (sl[j] >= 2u * H2S_STG ? 0 : stage * H2S_STG) + sl[j];
+            *reinterpret_cast<u32x4 *>(dst) = h0;
+            if (sl[j] < 2u * H2S_STG) *reinterpret_cast<u32x4 *>(dst + H2S_PLANE) = h1;
+        }
+    };
+    auto a_store = [&](int stage, int j) {      // a whole unit at once (the prologue)
+        [&]<int... SL>(std::integer_sequence<int, SL...>) { (a_slice(std::integral_constant<int, SL>{}, stage, j), ...); }(std::make_integer_sequence<int, 8>{});
     };
     // ---- 16x16x32 operands.  Lane L of an A / B fragment holds k-group kg = L >> 4: the chunk's 8-channel group h2s_kgrp(kg) (groups 0, 2, 1, 3).
     // A fragment (mf, tap) = tile row mf, pixel x = h2s_px(L & 15) of row L & 15: one ds_read_b128 per plane from the swizzled patch.  With the
@@ -566,20 +606,23 @@ __device__ __forceinline__ void conv_h2s_body(const ConvK &p) {
     a_load(c0);
     w_load(0, c0, 0);
     w_load(1, c0, 1);
-    if (aff) {   // (the first patch and weights are on their way)
+    if constexpr (AFF) {   // (the first patch and weights are on their way; arrays or producer totals: a run-time choice of the prologue alone)
         if (p.cA) {
             for (int c = tid; c < p.Cin; c += 256) { sA[c] = p.cA[(long)img * p.Cin + c]; sB[c] = p.cB[(long)img * p.Cin + c]; }
             __syncthreads();
         } else sx = wave_uniform(coef_to_lds<true>(nullptr, nullptr, p.gn, p.N, img, sA, sB, sB + p.Cin, tid, 256));      // (ends with a barrier)
-    } else if (p.xs_max && !p.in16) sx = wave_uniform(pow2_scale_for_bound(p.xs_max[img]));
-    else if (p.xs_gt && !p.in16) sx = wave_uniform(act_scale_totals(p.xs_gt, p.N, img, p.xs_hw));
+    } else if constexpr (!IN16) {
+        if (p.xs_max) sx = wave_uniform(pow2_scale_for_bound(p.xs_max[img]));
+        else if (p.xs_gt) sx = wave_uniform(act_scale_totals(p.xs_gt, p.N, img, p.xs_hw));
+    }
     const float rsx = 1.f / sx;
     kq *= rsx;
+    c_read(c0);
 #pragma unroll
-    for (int j = 0; j < NUT; ++j) a_store(0, j, c0);
+    for (int j = 0; j < NUT; ++j) a_store(0, j);
     __syncthreads();
 
-    u32x4 af[2][2];                                                // [buffer][plane]: fragment row mf + 1 is read while the MFMAs of row mf run
+    u32x4 af[2][2];                                               // [buffer][plane]: fragment row mf + 1 is read while the MFMAs of row mf run
     auto a_read = [&](const char *st, int tap, int mf, u32x4 (&dst)[2]) {
 #pragma unroll
         for (int pl = 0; pl < 2; ++pl)
@@ -595,6 +638,9 @@ __device__ __forceinline__ void conv_h2s_body(const ConvK &p) {
             constexpr int S = decltype(s_)::value, M = decltype(m_)::value, rs = S & 1, cur = M & 1;
             if constexpr (M + 1 < 8) a_read(st, S, M + 1, af[cur ^ 1]);
             else if constexpr (S + 1 < NS) a_read(st, S + 1, 0, af[cur ^ 1]);
+            // the coefficients of a unit travel with the fragments of row 6 of the k-step before its own: a whole row ahead of slice 0, which needs them
+            // (once per chunk would hold 16 registers over three k-steps, which the kernel does not have: 24 bytes of scratch)
+            if constexpr (S >= ST0 - 1 && S + 1 < NS && M == 6) c_read(ccn);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int pr = 0; pr < 3; ++pr)                              // smallest partial product first: h1 w0, h0 w1, h0 w0 into every tile
@@ -602,6 +648,9 @@ __device__ __forceinline__ void conv_h2s_body(const ConvK &p) {
                 for (int f = 0; f < 3; ++f)
                     acc[M][f] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, af[cur][pr == 0 ? 1 : 0]),
                                                                         __builtin_bit_cast(f16x8, ring[rs][pr == 1 ? 1 : 0][f]), acc[M][f], 0, 0, 0);
+            // slice M of the step's staging unit shares the row's stretch with its nine MFMAs (18 with the slice in front of them: the scheduler is free
+            // between the two fences, and the MFMAs do not depend on the slice)
+            if constexpr (S >= ST0) a_slice(m_, (c - c0 + 1) & 1, S - ST0);
             __builtin_amdgcn_sched_barrier(0);
         };
         auto kstep = [&](auto s_) {
@@ -610,7 +659,6 @@ __device__ __forceinline__ void conv_h2s_body(const ConvK &p) {
             // two steps ahead, each into its own slot parity: of 9 steps per chunk, steps 7 and 8 fetch the next chunk's steps 1 and 0; of 4 (an even
             // count keeps the parity across chunks), steps 2 and 3 fetch its steps 0 and 1
             w_load(rs, S + 2 < NS ? cc : ccn, S + 2 < NS ? S + 2 : (PH ? S + 2 - NS : 8 - S));
-            if constexpr (S >= ST0 && S < ST0 + NUT) a_store((c - c0 + 1) & 1, S - ST0, ccn);
             __builtin_amdgcn_sched_barrier(0);
         };
         [&]<int... S>(std::integer_sequence<int, S...>) { (kstep(std::integral_constant<int, S>{}), ...); }(std::make_integer_sequence<int, NS>{});
@@ -630,17 +678,21 @@ __device__ __forceinline__ void conv_h2s_body(const ConvK &p) {
 }
 #endif
 
-// (two plain entry points over the one body: a kernel trace and the compiled metadata keep the name k_conv_h2s for the nine-tap kernel)
-__global__ __launch_bounds__(256, 2) void k_conv_h2s(const ConvK p) {
+// (plain entry points over the one body: a kernel trace and the compiled metadata keep the name k_conv_h2s for the nine-tap kernel in the staging
+// mode the production forward launches most, GroupNorm affine + SiLU; the other modes carry a suffix)
 #if __HIP_DEVICE_COMPILE__
-    conv_h2s_body<false>(p);
+#define H2S_ENTRY(name, PH, MODE) \
+    __global__ __launch_bounds__(256, 2) void name(const ConvK p) { conv_h2s_body<PH, MODE>(p); }
+#else
+#define H2S_ENTRY(name, PH, MODE) \
+    __global__ __launch_bounds__(256, 2) void name(const ConvK p) {}
 #endif
-}
-__global__ __launch_bounds__(256, 2) void k_conv_h2s_ph(const ConvK p) {
-#if __HIP_DEVICE_COMPILE__
-    conv_h2s_body<true>(p);
-#endif
-}
+H2S_ENTRY(k_conv_h2s, false, H2S_AFF_SILU)
+H2S_ENTRY(k_conv_h2s_aff, false, H2S_AFF)
+H2S_ENTRY(k_conv_h2s_raw, false, H2S_RAW)
+H2S_ENTRY(k_conv_h2s_planes, false, H2S_PLANES)
+H2S_ENTRY(k_conv_h2s_ph, true, H2S_RAW)
+#undef H2S_ENTRY
 
 // k_conv1_h16: the 1x1 convolutions (skip / qkv / proj) in the same arithmetic.  A workgroup = 256 consecutive pixels x 192 output channels,
 // the same 2x2 wave split, weight ring and epilogue; K in chunks of 96 input channels = six k-steps: the chunk's [256 px][96 ch] slab is fetched
@@ -888,8 +940,13 @@ constexpr int H2_PITCH = 112;
 constexpr int H2S1_PLANE = 128 * H2_PITCH, H2S1_STAGE = 2 * H2S1_PLANE;          // 14 KB per plane, 28 KB per stage
 constexpr int H2S1_LDS = 2 * H2S1_STAGE > 128 * H2S_EP * 4 ? 2 * H2S1_STAGE : 128 * H2S_EP * 4;
 
-__global__ __launch_bounds__(256, 2) void k_conv1_h2s(const ConvK p) {
+// The staging mode is a template parameter here too (H2sIn: raw, affine, affine + SiLU - the launcher refuses a 16-bit image): a chunk is one basic block,
+// and a unit's coefficient quads are read with the A fragments of its k-step, in front of the step's 18 MFMAs, which the scheduler mixes the staging into.
 #if __HIP_DEVICE_COMPILE__
+template <int MODE>
+__device__ __forceinline__ void conv1_h2s_body(const ConvK &p) {
+    static_assert(MODE != H2S_PLANES, "k_conv1_h2s stages fp32");
+    constexpr bool AFF = MODE == H2S_AFF || MODE == H2S_AFF_SILU, ACT = MODE == H2S_AFF_SILU;
     constexpr int NUT = 3;                                         // staging units per thread: 128 px x 6 groups of 8 channels / 256 threads
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -908,7 +965,6 @@ __global__ __launch_bounds__(256, 2) void k_conv1_h2s(const ConvK p) {
     const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc(
         (void *)p.wf, (short)0, (int)((long)p.n_nblocks * nch * 3 * 12288), 0x00020000);
     // GroupNorm affine (+ SiLU) of the input applied while staging, as in k_conv_h2s (ConvK::cA / cB arrays or ConvK::gn); a tile = 128 pixels of ONE image
-    const bool aff = p.cA != nullptr || p.gn.gt != nullptr;
     float *sA = reinterpret_cast<float *>(lds + H2S1_LDS), *sB = sA + p.Cin;
     const int img = (int)(m0 / ((long)p.Hout * p.Wout));
     float sx = 1.f, kq = -1.44269504088896341f;                    // power-of-two scale of the staged activations (hl_stats.h), -log2(e) / sx
@@ -929,13 +985,20 @@ __global__ __launch_bounds__(256, 2) void k_conv1_h2s(const ConvK p) {
             ar[j][1] = __builtin_amdgcn_raw_buffer_load_b128(rsA, sv[j] + 16, chunk * 192, 0);
         }
     };
-    auto a_store = [&](int stage, int j, int chunk) {
-        f32x4 v0 = __builtin_bit_cast(f32x4, ar[j][0]), v1 = __builtin_bit_cast(f32x4, ar[j][1]);
-        if (aff) {
+    f32x4 cf[4];                                                    // unit j's coefficient quads: A, B of channels cb .. cb + 3 and cb + 4 .. cb + 7
+    auto c_read = [&](int j, int chunk) {
+        if constexpr (AFF) {
             const int cb = chunk * 48 + sg[j];
-            v0 = v0 * *reinterpret_cast<const f32x4 *>(sA + cb) + *reinterpret_cast<const f32x4 *>(sB + cb);
-            v1 = v1 * *reinterpret_cast<const f32x4 *>(sA + cb + 4) + *reinterpret_cast<const f32x4 *>(sB + cb + 4);
-            if (p.act) {
+            cf[0] = *reinterpret_cast<const f32x4 *>(sA + cb); cf[1] = *reinterpret_cast<const f32x4 *>(sB + cb);
+            cf[2] = *reinterpret_cast<const f32x4 *>(sA + cb + 4); cf[3] = *reinterpret_cast<const f32x4 *>(sB + cb + 4);
+        }
+    };
+    auto a_store = [&](int stage, int j) {
+        f32x4 v0 = __builtin_bit_cast(f32x4, ar[j][0]), v1 = __builtin_bit_cast(f32x4, ar[j][1]);
+        if constexpr (AFF) {
+            v0 = v0 * cf[0] + cf[1];
+            v1 = v1 * cf[2] + cf[3];
+            if constexpr (ACT) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) { v0[i] = h2s_silu(v0[i], kq); v1[i] = h2s_silu(v1[i], kq); }
             }
@@ -969,17 +1032,17 @@ __global__ __launch_bounds__(256, 2) void k_conv1_h2s(const ConvK p) {
     a_load(c0);
 #pragma unroll
     for (int s = 0; s < 3; ++s) w_load(s, c0 * 3 + s);
-    if (aff) {   // (the first slab and weights are on their way)
+    if constexpr (AFF) {   // (the first slab and weights are on their way; arrays or producer totals: a run-time choice of the prologue alone)
         if (p.cA) {
             for (int c = tid; c < p.Cin; c += 256) { sA[c] = p.cA[(long)img * p.Cin + c]; sB[c] = p.cB[(long)img * p.Cin + c]; }
             __syncthreads();
         } else sx = wave_uniform(coef_to_lds<true>(nullptr, nullptr, p.gn, p.N, img, sA, sB, sB + p.Cin, tid, 256));      // (ends with a barrier)
-    } else if (p.xs_max && !p.in16) sx = wave_uniform(pow2_scale_for_bound(p.xs_max[img]));
-    else if (p.xs_gt && !p.in16) sx = wave_uniform(act_scale_totals(p.xs_gt, p.N, img, p.xs_hw));
+    } else if (p.xs_max) sx = wave_uniform(pow2_scale_for_bound(p.xs_max[img]));
+    else if (p.xs_gt) sx = wave_uniform(act_scale_totals(p.xs_gt, p.N, img, p.xs_hw));
     const float rsx = 1.f / sx;
     kq *= rsx;
 #pragma unroll
-    for (int j = 0; j < NUT; ++j) a_store(0, j, c0);
+    for (int j = 0; j < NUT; ++j) { c_read(j, c0); a_store(0, j); }
     __syncthreads();
     u32x4 af[2][2];                                                 // [plane][fragment mf] of the current k-step (the partner wave of the SIMD covers the LDS latency)
     for (int c = c0; c < c1; ++c) {
@@ -992,6 +1055,7 @@ __global__ __launch_bounds__(256, 2) void k_conv1_h2s(const ConvK p) {
                 for (int pl = 0; pl < 2; ++pl)
 #pragma unroll
                     for (int mf = 0; mf < 2; ++mf) af[pl][mf] = *reinterpret_cast<const u32x4 *>(st + pl * H2S1_PLANE + aoff[mf] + S * 32);
+                c_read(S, cn);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int nf = 0; nf < 3; ++nf)
@@ -1002,15 +1066,25 @@ __global__ __launch_bounds__(256, 2) void k_conv1_h2s(const ConvK p) {
                         acc[mf][nf] = mma<true>(af[0][mf], ring[S][0][nf], acc[mf][nf]);
                     }
                 w_load(S, c * 3 + S + 3);
-                a_store((c - c0 + 1) & 1, S, cn);
+                a_store((c - c0 + 1) & 1, S);
                 __builtin_amdgcn_sched_barrier(0);
             }(), ...);
         }(std::make_integer_sequence<int, 3>{});
         __syncthreads();
     }
     h2s_epilogue(p, lds, h2s_scatter_2x2(acc, lane, wm, wn), tid, nb * 192, (long)tb, rsx, [&](int pc) { return m0 + pc; });
-#endif
 }
+#define H2S1_ENTRY(name, MODE) \
+    __global__ __launch_bounds__(256, 2) void name(const ConvK p) { conv1_h2s_body<MODE>(p); }
+#else
+#define H2S1_ENTRY(name, MODE) \
+    __global__ __launch_bounds__(256, 2) void name(const ConvK p) {}
+#endif
+// (k_conv1_h2s is the raw mode: the ResBlock skips, proj_out and the zero convolutions, most of the production forward's 1x1 launches; qkv is k_conv1_h2s_aff)
+H2S1_ENTRY(k_conv1_h2s, H2S_RAW)
+H2S1_ENTRY(k_conv1_h2s_aff, H2S_AFF)
+H2S1_ENTRY(k_conv1_h2s_aff_silu, H2S_AFF_SILU)
+#undef H2S1_ENTRY
 
 // Scale of the fp16x2 weight planes (round 6).  fp16 has a 5-bit exponent: unscaled, the low plane w1 = w - fp16(w) of a weight below 2^-3 falls under
 // fp16's smallest normal (2^-14) and is rounded on the 2^-24 subnormal grid - at |w| ~ 5e-3 (the production net's own 1536 -> 768 layers at initialisation)
@@ -1282,8 +1356,15 @@ int conv3_h2s_launch(const ConvK &p, hipStream_t st, int splits) {
     constexpr int LDS_MAX = H2S_LDS + (2 * 4096 + COEF_SCR_FLOATS) * 4;         // + the coefficient table of a fused GroupNorm (<= 4096 input channels)
     const bool aff = p.cA != nullptr || p.gn.gt != nullptr;
     HL_REQUIRE(!aff || (p.Cin <= 4096 && !p.in16 && !p.ups), "k_conv_h2s: fused GroupNorm needs a raw fp32 input of <= 4096 channels");
+    HL_REQUIRE(p.in16 == 0 || p.in16 == 2, "k_conv_h2s: a 16-bit input is the two-plane image");
+    HL_REQUIRE(aff || !p.act, "k_conv_h2s: SiLU without the GroupNorm affine");
     const size_t lds_bytes = (size_t)H2S_LDS + (aff ? (size_t)(2 * p.Cin + COEF_SCR_FLOATS) * 4 : 0);
-    return launch_lds<k_conv_h2s>("k_conv_h2s", LDS_MAX, dim3((unsigned)(p.n_mtiles * p.n_nblocks), 1, (unsigned)splits), dim3(256), lds_bytes, st, p);
+    const dim3 grid((unsigned)(p.n_mtiles * p.n_nblocks), 1, (unsigned)splits);
+    // the staging mode is the kernel's template parameter: one instantiation per mode, picked from the fields the kernel used to branch on
+    if (p.in16) return launch_lds<k_conv_h2s_planes>("k_conv_h2s_planes", LDS_MAX, grid, dim3(256), lds_bytes, st, p);
+    if (!aff) return launch_lds<k_conv_h2s_raw>("k_conv_h2s_raw", LDS_MAX, grid, dim3(256), lds_bytes, st, p);
+    if (!p.act) return launch_lds<k_conv_h2s_aff>("k_conv_h2s_aff", LDS_MAX, grid, dim3(256), lds_bytes, st, p);
+    return launch_lds<k_conv_h2s>("k_conv_h2s", LDS_MAX, grid, dim3(256), lds_bytes, st, p);
 }
 
 // the 3x3 / stride-2 layers: p.n_mtiles = output pixels / 128
@@ -1300,8 +1381,12 @@ int conv1_h2s_launch(const ConvK &p, hipStream_t st, int splits) {
     constexpr int LDS_MAX = H2S1_LDS + (2 * 4096 + COEF_SCR_FLOATS) * 4;        // + the coefficient table of a fused GroupNorm (<= 4096 input channels)
     const bool aff = p.cA != nullptr || p.gn.gt != nullptr;
     HL_REQUIRE(!aff || (p.Cin <= 4096 && ((long)p.Hout * p.Wout) % 128 == 0), "k_conv1_h2s: fused GroupNorm needs <= 4096 input channels and whole tiles per image");
+    HL_REQUIRE(aff || !p.act, "k_conv1_h2s: SiLU without the GroupNorm affine");
     const size_t lds_bytes = (size_t)H2S1_LDS + (aff ? (size_t)(2 * p.Cin + COEF_SCR_FLOATS) * 4 : 0);
-    return launch_lds<k_conv1_h2s>("k_conv1_h2s", LDS_MAX, dim3((unsigned)(p.n_mtiles * p.n_nblocks), 1, (unsigned)splits), dim3(256), lds_bytes, st, p);
+    const dim3 grid((unsigned)(p.n_mtiles * p.n_nblocks), 1, (unsigned)splits);
+    if (!aff) return launch_lds<k_conv1_h2s>("k_conv1_h2s", LDS_MAX, grid, dim3(256), lds_bytes, st, p);
+    if (!p.act) return launch_lds<k_conv1_h2s_aff>("k_conv1_h2s_aff", LDS_MAX, grid, dim3(256), lds_bytes, st, p);
+    return launch_lds<k_conv1_h2s_aff_silu>("k_conv1_h2s_aff_silu", LDS_MAX, grid, dim3(256), lds_bytes, st, p);
 }
 
 size_t conv_h16_lds_bytes() { return (size_t)2 * H1_STAGE; }   // 104 KB: the two 1x1 stages (the epilogue exchange needs 98 KB, the 3x3 patch stages 45 KB)
