@@ -38,6 +38,10 @@ HL_RASTER_CULL_BACK = 4
 HL_RASTER_CULL_FRONT = 8
 HL_SIMPLIFY_BOUNDS_WORDS = 6 + 6 * 1024
 HL_SIMPLIFY_ACC_WORDS = 20
+HL_DISTANCE_WIDE_CELLS = 4096
+HL_DISTANCE_MAX_WIDE = 65536
+HL_DISTANCE_REDUCE_FIELDS = 16
+HL_DISTANCE_REDUCE_WORDS = 16 + 16 * 1024
 
 
 class HipLibraryMissing(RuntimeError):
@@ -242,6 +246,14 @@ SIGNATURES = {
     "hl_mesh_simplify_scratch_bytes": (_sz, [_i64] * 5),
     "hl_mesh_simplify_count": (_i, [_p, _i64, _i64, _p, _p, _i64, _i64, _i64, _p, _p, _p, _sz, _p]),
     "hl_mesh_simplify_emit": (_i, [_p, _p, _p, _i64, _p, _i64, _p, _p, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "hl_mesh_distance_scratch_bytes": (_sz, [_i64] * 4),
+    "hl_mesh_distance_areas": (_i, [_p, _i64, _p, _i64, _p, C.c_double, _p, _p, _p, _sz, _p]),
+    "hl_mesh_distance_count": (_i, [_p, _i64, _p, _i64, _p, C.c_double, _i64, _i64, _i64, _p, _p, _p, _sz, _p]),
+    "hl_mesh_distance_fill": (_i, [_i64, _p, C.c_double, _i64, _i64, _i64, _p, _i64, _p, _sz, _p]),
+    "hl_mesh_distance_query": (_i, [_p, _p, _i64, _i64, _p, C.c_double, _i64, _i64, _i64, _p, _i64, _i64, C.c_double, _p, _p, _p, _p, _p, _p, _p, _p, _sz,
+                                    _p]),
+    "hl_mesh_distance_sample": (_i, [_p, _i64, _p, _i64, _p, _p, _i64, _i64, C.c_uint64, _p, _p, _p, _p, _p]),
+    "hl_mesh_distance_reduce": (_i, [_p, _p, _p, _i64, _p, _i, _p, _p]),
 }
 
 

@@ -1070,6 +1070,54 @@ int hl_mesh_simplify_emit(const double *vertices, const double *normals, const u
                           double *out_normals, unsigned char *out_colors, int64_t *out_triangles, int64_t *vertex_map, int64_t *counts, int32_t *status,
                           void *scratch, size_t scratch_bytes, void *stream);
 
+/* ---- measuring mesh distance: the exact closest triangle, surface samples, score sums (an extension beside the reference) ----
+ * Contract: DESIGN.md "Measuring mesh distance"; csrc/hl_mesh_distance.hip.  Contiguous device arrays, enqueue-only on `stream`, nothing
+ * allocated.  vertices fp64 (N,3) world; triangles int32 (T,3); h_origin: 3 HOST doubles, the lower corner of the mesh's bounds
+ * (hl_mesh_simplify_bounds); h: the side of the cubic cells; gx gy gz = floor((max - origin) / h) + 1 per axis.  All geometry is float64
+ * relative to the origin.  A triangle with an index outside [0, N) (status bit 0; never dereferenced) or a non-finite corner (bit 1) is
+ * dropped; a query with a non-finite coordinate (bit 2) gets sqdist NaN and triangle -1.
+ *   hl_mesh_distance_areas: prefix[i] = sum over j < i of a_j, a_j = llrint((|cross(b - a, c - a)| / 2) / unit), 0 for a dropped triangle;
+ *     counts[0] | counts[1] << 32 = the total (2 device int64).  blocks: device scratch of ((T + 4095) / 4096) * 8 bytes.
+ *   hl_mesh_distance_count: gathers the triangle records, counts the references of every cell and scans them: counts[0] | counts[1] << 32 =
+ *     references in all, counts[2] = wide triangles (a box of more than HL_DISTANCE_WIDE_CELLS cells: kept in a list every query tests, in
+ *     index order), counts[3] = valid triangles.  counts: 4 device int64, *status a device int32, both cleared first.
+ *   hl_mesh_distance_fill (scratch as left by the count stage, n_refs = its reference total, at most 2^31): refs int32 (n_refs), caller-owned.
+ *   hl_mesh_distance_query (n_wide = counts[2], at most HL_DISTANCE_MAX_WIDE; max_distance +inf for none): per query sqdist, distance =
+ *     sqrt(sqdist), triangle int32, barycentric (Q,3), point (Q,3) world, and with normals (Q,3) normal_dot (Q) (both or neither).  A query
+ *     farther than max_distance gets +inf and -1.  *status is or-ed into, not cleared.
+ *   hl_mesh_distance_sample (prefix and total from the areas stage, total >= 1): sample s of S lies in the triangle that holds position
+ *     floor((s + 0.5) / S * total) of the prefix, at the barycentrics of the R2 sequence's term seed * 2^32 + s + 1.
+ *   hl_mesh_distance_reduce: out[0..15] = sum of distance, sum of sqdist, sum of the finite normal_dot, their count, max distance, count of
+ *     finite distances, two spare, then the counts of distance <= threshold[k]; non-finite distances count nowhere.  out:
+ *     HL_DISTANCE_REDUCE_WORDS device doubles (the rest holds partials); h_thresholds: HOST doubles.  Fixed order: the same bits every run.
+ * scratch: hl_mesh_distance_scratch_bytes(T, gx, gy, gz) bytes, 16-byte aligned, every part rounded up to 16 bytes: the records, fp64
+ *     (T, HL_DISTANCE_RECORD_WORDS): a b c relative to the origin and a zero; the flags int32 (T): 0 dropped, 1 registered, 2 wide; the cell
+ *     starts uint32 (cells + 1); the fill cursors uint32 (cells); the wide list int32 (HL_DISTANCE_MAX_WIDE); the scans' block sums.  0 for
+ *     refused sizes.
+ * Refused before any launch (HL_ERR_INVALID): N, T, Q or S < 1 or >= 2^31, a cell that is not positive and finite, a non-finite origin, an
+ *     extent < 1, more than 2^27 cells, more than 2^31 references, more than HL_DISTANCE_MAX_WIDE wide triangles, more than 8 thresholds. */
+#define HL_DISTANCE_WIDE_CELLS 4096
+#define HL_DISTANCE_MAX_WIDE 65536
+#define HL_DISTANCE_RECORD_WORDS 10
+#define HL_DISTANCE_REDUCE_BLOCKS 1024
+#define HL_DISTANCE_REDUCE_FIELDS 16
+#define HL_DISTANCE_REDUCE_WORDS (HL_DISTANCE_REDUCE_FIELDS + HL_DISTANCE_REDUCE_FIELDS * HL_DISTANCE_REDUCE_BLOCKS)
+size_t hl_mesh_distance_scratch_bytes(int64_t T, int64_t gx, int64_t gy, int64_t gz);
+int hl_mesh_distance_areas(const double *vertices, int64_t N, const int32_t *triangles, int64_t T, const double *h_origin, double unit, int64_t *prefix,
+                           int64_t *counts, void *blocks, size_t blocks_bytes, void *stream);
+int hl_mesh_distance_count(const double *vertices, int64_t N, const int32_t *triangles, int64_t T, const double *h_origin, double h, int64_t gx, int64_t gy,
+                           int64_t gz, int64_t *counts, int32_t *status, void *scratch, size_t scratch_bytes, void *stream);
+int hl_mesh_distance_fill(int64_t T, const double *h_origin, double h, int64_t gx, int64_t gy, int64_t gz, int32_t *refs, int64_t n_refs, void *scratch,
+                          size_t scratch_bytes, void *stream);
+int hl_mesh_distance_query(const double *points, const double *normals, int64_t Q, int64_t T, const double *h_origin, double h, int64_t gx, int64_t gy,
+                           int64_t gz, const int32_t *refs, int64_t n_refs, int64_t n_wide, double max_distance, double *sqdist, double *distance,
+                           int32_t *triangle, double *barycentric, double *point, double *normal_dot, int32_t *status, const void *scratch,
+                           size_t scratch_bytes, void *stream);
+int hl_mesh_distance_sample(const double *vertices, int64_t N, const int32_t *triangles, int64_t T, const double *h_origin, const int64_t *prefix,
+                            int64_t total, int64_t S, uint64_t seed, double *points, int64_t *triangle, double *barycentric, double *normals, void *stream);
+int hl_mesh_distance_reduce(const double *distance, const double *sqdist, const double *normal_dot, int64_t Q, const double *h_thresholds, int n_thresholds,
+                            double *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

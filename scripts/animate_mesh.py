@@ -18,7 +18,9 @@ One JSON line of timings at the end.
 DIR/frame_0000.png, ...: headlight-shaded colours on white.  The camera is --camera cam.npz (`K`, `R`, `T` - one camera or one per frame
 - and `H`, `W`) or --turntable N: N cameras of --res pixels on a circle around the first frame's bounds, frame f seen from camera f mod N.
 --simplify CELL first clusters the mesh on a grid of CELL world units (humanliff_amd/NeRF/simplify.py; DESIGN.md "Simplifying the
-mesh"): the binding, every reposed frame and every PLY then carry the smaller mesh.
+mesh"): the binding, every reposed frame and every PLY then carry the smaller mesh.  --simplify-report [SAMPLES] adds to the JSON line how
+far the smaller mesh is from the full one, in cells: mesh_distance over the vertices and SAMPLES (default 100 000) surface samples per side
+(humanliff_amd/NeRF/distance.py; DESIGN.md "Measuring mesh distance").
 The mesh needs triangles; with --synthetic and --images the stand-in is an ellipsoid of the body's proportions around the body's centroid
 (triangulated, with normals and colours) instead of the offset vertices.  The JSON line then carries the raster timings too.
 """
@@ -102,7 +104,10 @@ def main():
     ap.add_argument("--turntable", type=int, default=0)
     ap.add_argument("--res", type=int, default=256)
     ap.add_argument("--simplify", type=float, default=None, metavar="CELL")
+    ap.add_argument("--simplify-report", type=int, nargs="?", const=100000, default=0, metavar="SAMPLES")
     a = ap.parse_args()
+    if a.simplify_report and a.simplify is None:
+        ap.error("--simplify-report needs --simplify CELL")
     if a.simplify is not None and not a.simplify > 0:
         ap.error("--simplify CELL: a positive cell size in world units")
     if a.images and bool(a.camera) == bool(a.turntable > 0):
@@ -151,8 +156,17 @@ def main():
             ap.error("--simplify needs a mesh with triangles (with --synthetic: add --images for the ellipsoid stand-in)")
         from humanliff_amd.NeRF.simplify import simplify_mesh
         before = (len(mesh["vertices"]), len(mesh["triangles"]))
-        mesh = simplify_mesh(mesh, cell=a.simplify)
+        full, mesh = mesh, simplify_mesh(mesh, cell=a.simplify)
         simplified = {"cell": a.simplify, "vertices": [before[0], len(mesh["vertices"])], "triangles": [before[1], len(mesh["triangles"])]}
+        if a.simplify_report:
+            if len(mesh["triangles"]) == 0:
+                ap.error("--simplify-report: the simplified mesh has no triangles (the mesh lies inside one cell)")
+            from humanliff_amd.NeRF.distance import mesh_distance
+            score = mesh_distance(full, mesh, samples=a.simplify_report, thresholds=(0.25 * a.simplify, 0.5 * a.simplify))
+            in_cells = lambda s: {k: round(s[k] / a.simplify, 5) for k in ("mean", "rms", "max")}  # noqa: E731
+            simplified["distance_in_cells"] = {"samples": a.simplify_report, "full_to_simplified": in_cells(score["a_to_b"]),
+                                               "simplified_to_full": in_cells(score["b_to_a"]), "chamfer": round(score["chamfer"] / a.simplify, 5),
+                                               "hausdorff": round(score["hausdorff"] / a.simplify, 5), "fscore_at_quarter_and_half_cell": score["fscore"]}
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     binding = animate.bind_mesh(mesh["vertices"], bind_posed, frame=0, neighbours=a.neighbours, normals=mesh["normals"])
