@@ -83,6 +83,8 @@ SIGNATURES = {
     "hl_planes_packed_bytes": (_sz, [_i, _i]),
     "hl_planes_pack": (_i, [_p, _i, _i, _p, _p]),
     "hl_render_workspace_bytes": (_sz, [_i64, _i, _i]),
+    "hl_render_workspace_new_depths_offset": (_sz, [_i64, _i, _i]),
+    "hl_render_importance_plan": (_i, [_i64]),
     "hl_render_rays": (_i, [_p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i64, _i, _i, _u, _p, _p, _p, _p, _p]),
     "hl_render_rays_u_event": (_i, [_p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i, _i, _u, _p, _p, _p, _p, _p]),
     "hl_render_coarse": (_i, [_p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _i64, _i, _p, _p]),

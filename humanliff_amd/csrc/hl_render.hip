@@ -3507,6 +3507,15 @@ size_t hl_render_workspace_bytes(int64_t n_rays, int n_samples, int n_importance
     return render_workspace(nullptr, n_rays, n_samples, n_importance, Schedule::EvalOnce).bytes;
 }
 
+size_t hl_render_workspace_new_depths_offset(int64_t n_rays, int n_samples, int n_importance) {
+    return (size_t)(uintptr_t)render_workspace(nullptr, n_rays, n_samples, n_importance, Schedule::EvalOnce).zn;   // (base = null: the pointer is the offset)
+}
+
+int hl_render_importance_plan(int64_t n_rays) {
+    HL_REQUIRE(n_rays > 0, "hl_render_importance_plan: bad sizes");
+    return imp_rays_per_wave(n_rays);
+}
+
 static inline int mlp_mode_of(unsigned flags) {   // 0 fp32 MFMA, 1 fp16 operands (opt-in), 2 bf16x3 split products, 3 fp16x2 products
     return (flags & HL_RENDER_MLP_FP16) ? 1 : ((flags & HL_RENDER_MLP_FP16X2) ? 3 : ((flags & HL_RENDER_MLP_BF16X3) ? 2 : 0));
 }

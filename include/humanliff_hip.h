@@ -91,6 +91,9 @@ int hl_planes_pack(const float *planes, int H, int W, void *packed, void *stream
                                         coarse + new samples in depth order as it goes (renderer.py:172-231, 252-253); bit-identical images */
 
 size_t hl_render_workspace_bytes(int64_t n_rays, int n_samples, int n_importance);
+/* Byte offset, inside that workspace, of the sorted new depths of the evaluate-once schedules (tile-major [ceil(R/32)][n_importance][32],
+ * behind the raw records of the coarse and the new points); 0 where the workspace holds nothing (no rays, n_importance <= 0).  Host arithmetic. */
+size_t hl_render_workspace_new_depths_offset(int64_t n_rays, int n_samples, int n_importance);
 
 /* Replaces Renderer.render (human_diffusion/NeRF/renderer.py:234-281,
  * recon_NeRF/lib/renderer.py:244-291) together with the per-chunk body of
@@ -145,6 +148,10 @@ int hl_render_eval_products(const void *mlp_packed, const void *planes_packed, i
                             int n_samples, unsigned flags, float *records_out, void *stream);
 int hl_render_importance_new(const float *records, const float *rays_d, const float *near, const float *far, const float *z_vals,
                              const float *u, int64_t n_rays, int n_samples, int n_importance, float *z_new_out, void *stream);
+/* Rays a wave of k_importance walks one after the other in a call of hl_render_importance / hl_render_importance_new with n_rays rays (host
+ * arithmetic; both entries launch with the same function): 8 = one workgroup per 32-ray tile, from 1024 tiles; 4 from 512 tiles, 2 from 256,
+ * 1 below (the tile is spread over 2, 4, 8 workgroups).  HL_ERR_INVALID for n_rays <= 0. */
+int hl_render_importance_plan(int64_t n_rays);
 int hl_render_composite(const float *near, const float *far, const float *z_vals /* coarse rows or NULL */, const float *z_new,
                         const float *rec_coarse, const float *rec_new, int64_t n_rays, int n_samples, int n_importance,
                         unsigned flags, float *rgb, float *acc, float *depth, void *stream);
