@@ -16,10 +16,10 @@ stored rest position: reposing with other betas moves the joints with the new sh
 
 There is no CPU path: binding and reposing need device tensors and the HIP library.
 """
-import numpy as np
 import torch
 
 from .. import _lib
+from . import mesh
 
 MAX_NEIGHBOURS = 8
 
@@ -30,17 +30,13 @@ def _rows_of(posed, what):
     return posed.rows
 
 
-def _points(a, what, dev):
-    """(N,3) numpy array or tensor of any float dtype -> contiguous fp32 on `dev`."""
-    if torch.is_tensor(a):
-        if not a.is_cuda:
-            raise RuntimeError(f"{what} is a CPU tensor; there is no CPU path (pass a numpy array or a device tensor)")
-        t = a.detach().to(device=dev, dtype=torch.float32)
-    else:
-        t = torch.as_tensor(np.ascontiguousarray(np.asarray(a), dtype=np.float32)).to(dev)
+def _points(what, a, dev):
+    """(N,3) numpy array or device tensor of any dtype -> contiguous fp32 on `dev`."""
+    mesh.refuse_cpu_tensor("bind_mesh", what, a)
+    t = mesh.to_device(a, torch.float32, dev)
     if t.ndim != 2 or t.shape[1] != 3:
-        raise ValueError(f"{what} must be (N,3), got {tuple(t.shape)}")
-    return t.contiguous()
+        raise ValueError(f"bind_mesh: `{what}` must be (N,3), got {tuple(t.shape)}")
+    return t
 
 
 def bind_mesh(vertices, posed, frame=0, neighbours=4, normals=None):
@@ -58,8 +54,8 @@ def bind_mesh(vertices, posed, frame=0, neighbours=4, normals=None):
     if not rows.is_cuda:
         raise RuntimeError("bind_mesh needs the posed body on a CUDA(HIP) device; there is no CPU path")
     dev = rows.device
-    pts = _points(vertices, "bind_mesh: `vertices`", dev)
-    nrm = None if normals is None else _points(normals, "bind_mesh: `normals`", dev)
+    pts = _points("vertices", vertices, dev)
+    nrm = None if normals is None else _points("normals", normals, dev)
     N = int(pts.shape[0])
     if nrm is not None and int(nrm.shape[0]) != N:
         raise ValueError(f"bind_mesh: {N} vertices, {int(nrm.shape[0])} normals")
@@ -148,5 +144,5 @@ class MeshBinding:
         dev = moved["vertices"].device
         cached = getattr(self, "_triangles_i32", None)      # (triangles, its int32 device copy): converted once, not per call
         if cached is None or cached[0] is not self.triangles or cached[1].device != dev:
-            cached = self._triangles_i32 = (self.triangles, raster.device_triangles(self.triangles, dev))
+            cached = self._triangles_i32 = (self.triangles, mesh.device_triangles(self.triangles, dev))
         return raster.rasterize(moved["vertices"], cached[1], H, W, K, R, T, normals=moved["normals"], colors=self.colors, **kw)

@@ -21,57 +21,15 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .raster import device_triangles
-from .simplify import _device, _is_float, _is_int, grid_extents
+from . import mesh
 
 MAX_CELLS = 1 << 27
 DEFAULT_CELLS = 1 << 24
 MAX_REFS = 1 << 31
 MAX_THRESHOLDS = 8
 STATUS_INDEX, STATUS_CORNER, STATUS_QUERY = 1, 2, 4
+_dp = mesh.dptr
 REDUCE_FIELDS = ("sum_distance", "sum_sqdist", "sum_normal_dot", "count_normal_dot", "max", "count")
-
-
-def _mesh_arrays(who, mesh_or_vertices, triangles):
-    """A mesh dict or (vertices, triangles) -> (vertices, triangles, the dict's normals or None), shapes and dtypes checked."""
-    normals = None
-    if isinstance(mesh_or_vertices, dict):
-        if triangles is not None:
-            raise ValueError(f"{who}: pass a mesh dict or (vertices, triangles), not both")
-        mesh = mesh_or_vertices
-        if "vertices" not in mesh or "triangles" not in mesh:
-            raise ValueError(f"{who}: a mesh dict needs `vertices` and `triangles`")
-        vertices, triangles, normals = mesh["vertices"], mesh["triangles"], mesh.get("normals")
-    else:
-        vertices = mesh_or_vertices
-        if triangles is None:
-            raise ValueError(f"{who}: `triangles` is missing")
-    for what, a in (("vertices", vertices), ("triangles", triangles)):
-        if torch.is_tensor(a) and not a.is_cuda:
-            raise RuntimeError(f"{who}: `{what}` is a CPU tensor; there is no CPU path (pass a numpy array or a device tensor)")
-    vertices, triangles = (a if torch.is_tensor(a) else np.asarray(a) for a in (vertices, triangles))
-    vshape, tshape = tuple(vertices.shape), tuple(triangles.shape)
-    if len(vshape) != 2 or vshape[1] != 3 or not _is_float(vertices):
-        raise ValueError(f"{who}: `vertices` must be float (N,3), got {vertices.dtype} {vshape}")
-    if len(tshape) != 2 or tshape[1] != 3 or not _is_int(triangles):
-        raise ValueError(f"{who}: `triangles` must be integer (T,3), got {triangles.dtype} {tshape}")
-    N, T = vshape[0], tshape[0]
-    if not (1 <= N < 1 << 31 and 1 <= T < 1 << 31):
-        raise ValueError(f"{who}: {N} vertices and {T} triangles (each 1 .. 2^31 - 1)")
-    return vertices, triangles, normals
-
-
-def _points(who, what, a, rows=None):
-    """Query points or normals: float (Q,3), numpy or device tensor."""
-    if torch.is_tensor(a) and not a.is_cuda:
-        raise RuntimeError(f"{who}: `{what}` is a CPU tensor; there is no CPU path (pass a numpy array or a device tensor)")
-    a = a if torch.is_tensor(a) else np.asarray(a)
-    shape = tuple(a.shape)
-    if len(shape) != 2 or shape[1] != 3 or not _is_float(a) or (rows is not None and shape[0] != rows):
-        raise ValueError(f"{who}: `{what}` must be float ({'Q' if rows is None else rows},3), got {a.dtype} {shape}")
-    if shape[0] >= 1 << 31:
-        raise ValueError(f"{who}: {shape[0]} rows in `{what}` (at most 2^31 - 1)")
-    return a
 
 
 def _positive(who, what, x, allow_inf=False):
@@ -99,24 +57,15 @@ def _validate(points, mesh_or_vertices, triangles=None, normals=None, cell=None,
     """Everything point_mesh_distance and mesh_distance can refuse without a device -> (points or None, vertices, triangles,
     normals or None, cell or None, max_distance or None, thresholds)."""
     who = "point_mesh_distance"
-    vertices, triangles, _ = _mesh_arrays(who, mesh_or_vertices, triangles)
+    vertices, triangles = mesh.mesh_arrays(who, mesh_or_vertices, triangles)[:2]
     if points is not None:
-        points = _points(who, "points", points)
+        points = mesh.float_rows(who, "points", points)
     if normals is not None:
         if points is None:
             raise ValueError(f"{who}: `normals` without `points`")
-        normals = _points(who, "normals", normals, rows=int(points.shape[0]))
+        normals = mesh.float_rows(who, "normals", normals, rows=int(points.shape[0]))
     return (points, vertices, triangles, normals, _positive(who, "cell", cell), _positive(who, "max_distance", max_distance, allow_inf=True),
             _thresholds("mesh_distance", thresholds))
-
-
-def _need_device(who):
-    if not torch.cuda.is_available():
-        raise RuntimeError(f"{who} needs a CUDA(HIP) device; there is no CPU path")
-
-
-def _dp(t):
-    return _lib.ptr(t, None if t is None else t.dtype)
 
 
 def default_cell(area, T, longest, lo, hi):
@@ -140,13 +89,7 @@ class MeshIndex:
         self.device, self.vertices, self.triangles = dev, verts, tri
         self.origin, self.lo, self.hi, self.cell = origin, lo, hi, float(cell)
         N, T = int(verts.shape[0]), int(tri.shape[0])
-        q = (hi - origin) / self.cell
-        if not np.isfinite(q).all() or (q >= MAX_CELLS).any():
-            raise ValueError(f"build_index: the grid of cell {self.cell} over the mesh holds more than 2^27 cells; pass a larger `cell`")
-        _, g = grid_extents(lo, hi, np.full(3, self.cell), origin)
-        gx, gy, gz = (int(x) for x in g)
-        if gx * gy * gz > MAX_CELLS:
-            raise ValueError(f"build_index: a grid of {[gx, gy, gz]} cells holds more than 2^27; pass a larger `cell`")
+        gx, gy, gz = (int(x) for x in mesh.grid_extents(lo, hi, self.cell, origin, MAX_CELLS, "build_index")[1])
         self.extents = (gx, gy, gz)
         L = _lib.lib()
         need = int(L.hl_mesh_distance_scratch_bytes(T, gx, gy, gz))
@@ -160,8 +103,7 @@ class MeshIndex:
             st = _lib.stream_ptr(dev)
             _lib.check(L.hl_mesh_distance_count(_dp(verts), N, _dp(tri), T, origin.ctypes.data, self.cell, gx, gy, gz, _dp(counts), _dp(status),
                                                 _dp(self.scratch), need, st), "hl_mesh_distance_count")
-            w = words.cpu()
-            refs, wide, valid, flags = int(w[0]) | (int(w[1]) << 32), int(w[2]), int(w[3]), int(w[4:].view(torch.int32)[0])
+            (refs, _, wide, valid), flags = mesh.read_counts(words, 4, joined=(0,))
             self.info = {"N": N, "T": T, "valid": valid, "wide": wide, "references": refs, "extents": self.extents, "status": flags}
             if check and flags & STATUS_INDEX:
                 raise ValueError(f"build_index: `triangles` holds an index outside [0, {N}) (check=False drops such triangles)")
@@ -182,10 +124,10 @@ class MeshIndex:
         """points (Q,3), normals (Q,3) or None: numpy arrays or device tensors of any float dtype -> the dict point_mesh_distance
         returns."""
         who = "MeshIndex.query"
-        points = _points(who, "points", points)
+        points = mesh.float_rows(who, "points", points)
         Q = int(points.shape[0])
         if normals is not None:
-            normals = _points(who, "normals", normals, rows=Q)
+            normals = mesh.float_rows(who, "normals", normals, rows=Q)
         max_distance = _positive(who, "max_distance", max_distance, allow_inf=True)
         dev = self.device
         f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)  # noqa: E731
@@ -196,8 +138,8 @@ class MeshIndex:
         if Q == 0:
             out["triangle"] = torch.empty(0, dtype=torch.int64, device=dev)
             return out
-        pts = _device(points, torch.float64, dev)
-        nrm = None if normals is None else _device(normals, torch.float64, dev)
+        pts = mesh.to_device(points, torch.float64, dev)
+        nrm = None if normals is None else mesh.to_device(normals, torch.float64, dev)
         tri = torch.empty(Q, dtype=torch.int32, device=dev)
         status = out["status"]
         gx, gy, gz = self.extents
@@ -214,15 +156,11 @@ class MeshIndex:
 
 
 def _bounds(verts):
-    """Device vertices -> (lo, hi) float64 (3,) of the finite ones, by the simplifier's bounds pass."""
-    dev = verts.device
-    bounds = torch.empty(_lib.HL_SIMPLIFY_BOUNDS_WORDS, dtype=torch.float64, device=dev)
-    with _lib.on(dev):
-        _lib.check(_lib.lib().hl_mesh_simplify_bounds(_dp(verts), int(verts.shape[0]), None, _dp(bounds), _lib.stream_ptr(dev)), "hl_mesh_simplify_bounds")
-    b = bounds[:6].cpu().numpy()
-    if not np.isfinite(b).all():
+    """Device vertices -> (lo, hi) float64 (3,) of the finite ones."""
+    b = mesh.finite_bounds(verts)
+    if b is None:
         raise ValueError("mesh distance: no vertex of the mesh is finite")
-    return np.ascontiguousarray(b[:3]), np.ascontiguousarray(b[3:])
+    return b
 
 
 class _Areas:
@@ -244,16 +182,17 @@ class _Areas:
         with _lib.on(dev):
             _lib.check(_lib.lib().hl_mesh_distance_areas(_dp(verts), N, _dp(tri), T, lo.ctypes.data, self.unit, _dp(self.prefix), _dp(counts), _dp(blocks),
                                                          nb * 8, _lib.stream_ptr(dev)), "hl_mesh_distance_areas")
-        c = counts.cpu()
-        self.total = int(c[0]) | (int(c[1]) << 32)
+        self.total = mesh.read_counts(counts, 2, joined=(0,))[0][0]
         self.area = self.total * self.unit
 
 
 def _device_mesh(who, mesh_or_vertices, triangles):
-    vertices, triangles, normals = _mesh_arrays(who, mesh_or_vertices, triangles)
-    _need_device(who)
-    dev = next((a.device for a in (vertices, triangles) if torch.is_tensor(a)), torch.device("cuda", torch.cuda.current_device()))
-    return _device(vertices, torch.float64, dev), device_triangles(triangles, dev), normals
+    """-> (vertices fp64, triangles int32 on the device, the dict's `normals` as given or None)."""
+    vertices, triangles = mesh.mesh_arrays(who, mesh_or_vertices, triangles)[:2]
+    mesh.need_device(who)
+    dev = mesh.device_of(vertices, triangles)
+    normals = mesh_or_vertices.get("normals") if isinstance(mesh_or_vertices, dict) else None
+    return mesh.to_device(vertices, torch.float64, dev), mesh.device_triangles(triangles, dev), normals
 
 
 def build_index(mesh_or_vertices, triangles=None, *, cell=None, check=True):
@@ -339,10 +278,10 @@ def _side_queries(verts, tri, normals, samples, seed):
     """One mesh's queries: its vertices, then `samples` surface samples -> (points, normals or None).  Without vertex normals the
     vertices' rows of the normals are zero, which gives them no normal_dot."""
     if samples == 0:
-        return verts, None if normals is None else _device(normals, torch.float64, verts.device)
+        return verts, None if normals is None else mesh.to_device(normals, torch.float64, verts.device)
     lo, hi = _bounds(verts)
     smp = _sample(verts, tri, lo, _Areas(verts, tri, lo, hi), samples, seed)
-    vn = torch.zeros_like(verts) if normals is None else _device(normals, torch.float64, verts.device)
+    vn = torch.zeros_like(verts) if normals is None else mesh.to_device(normals, torch.float64, verts.device)
     return torch.cat([verts, smp["points"]]), torch.cat([vn, smp["normals"]])
 
 
@@ -365,7 +304,7 @@ def mesh_distance(a, b, *, samples=0, seed=0, thresholds=(), cell=None, check=Tr
         m = m if isinstance(m, dict) else {"vertices": m[0], "triangles": m[1]}
         verts, tri, normals = _device_mesh("mesh_distance", m, None)
         if normals is not None:
-            normals = _points("mesh_distance", "normals", normals, rows=int(verts.shape[0]))
+            normals = mesh.float_rows("mesh_distance", "normals", normals, rows=int(verts.shape[0]))
         sides.append((verts, tri, normals))
     out = {}
     for name, (src, dst) in (("a_to_b", (0, 1)), ("b_to_a", (1, 0))):

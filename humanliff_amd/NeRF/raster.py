@@ -18,26 +18,13 @@ import numpy as np
 import torch
 
 from .. import _lib
+from . import mesh
+from .mesh import device_triangles  # noqa: F401  (callers convert their triangles once with raster.device_triangles)
 
 SHADES = ("colors", "headlight")
 CULLS = (None, "back", "front")
 MAX_IMAGES = 65535
 CAM_ROW_BYTES = 288          # a camera row inside the scratch (36 float64)
-
-
-def _device_floats(a, what, dev):
-    """(N,3) or (F,N,3) numpy array or device tensor of any float dtype -> contiguous fp32 (F,N,3) on `dev` (animate._points' rule)."""
-    if torch.is_tensor(a):
-        if not a.is_cuda:
-            raise RuntimeError(f"{what} is a CPU tensor; there is no CPU path (pass a numpy array or a device tensor)")
-        t = a.detach().to(device=dev, dtype=torch.float32)
-    else:
-        t = torch.as_tensor(np.ascontiguousarray(np.asarray(a), dtype=np.float32))
-    if t.ndim == 2:
-        t = t[None]
-    if t.ndim != 3 or t.shape[2] != 3:
-        raise ValueError(f"{what} must be (N,3) or (F,N,3), got {tuple(a.shape)}")
-    return t if dev is None else t.to(dev).contiguous()
 
 
 def _cameras(K, R, T):
@@ -67,17 +54,6 @@ def _cameras(K, R, T):
     return table
 
 
-def device_triangles(triangles, dev):
-    """(T,3) of any integer dtype, numpy array or device tensor -> contiguous int32 on `dev`.  An index that does not fit int32 is out of
-    range whatever N is: it becomes -1, which the cover stage skips and flags.  An int32 device tensor passes through untouched, so a
-    caller that rasterises the same triangles again and again converts them once with this and hands the result in."""
-    tri = (triangles.detach() if torch.is_tensor(triangles) else torch.as_tensor(np.ascontiguousarray(triangles).astype(np.int64))).to(device=dev)
-    if tri.dtype != torch.int32:
-        tri = tri.to(torch.int64)
-        tri = torch.where((tri < 0) | (tri >= 1 << 31), torch.full_like(tri, -1), tri).to(torch.int32)
-    return tri.contiguous()
-
-
 def rasterize(vertices, triangles, H, W, K, R, T, normals=None, colors=None, shade="colors", white_bkgd=False, cull=None, znear=1e-3,
               check_indices=True):
     """vertices (N,3) | (F,N,3), triangles (T,3) of any integer dtype, normals (N,3) | (1,N,3) | (F,N,3) or None (flat normals, turned
@@ -104,25 +80,8 @@ def _rasterize(vertices, triangles, H, W, K, R, T, normals=None, colors=None, sh
         raise ValueError(f"rasterize: cull must be one of {CULLS}, got {cull!r}")
     if not (float(znear) > 0 and np.isfinite(float(znear))):
         raise ValueError(f"rasterize: znear must be positive and finite, got {znear}")
-    for what, a in (("vertices", vertices), ("triangles", triangles), ("normals", normals), ("colors", colors)):
-        if torch.is_tensor(a) and not a.is_cuda:
-            raise RuntimeError(f"rasterize: `{what}` is a CPU tensor; there is no CPU path (pass a numpy array or a device tensor)")
-    vertices, triangles = (a if torch.is_tensor(a) else np.asarray(a) for a in (vertices, triangles))
-    normals, colors = (a if a is None or torch.is_tensor(a) else np.asarray(a) for a in (normals, colors))
-    tshape, tdt = tuple(triangles.shape), triangles.dtype
-    if len(tshape) != 2 or tshape[1] != 3:
-        raise ValueError(f"rasterize: `triangles` must be (T,3), got {tshape}")
-    if (tdt.is_floating_point or tdt == torch.bool) if torch.is_tensor(triangles) else not np.issubdtype(tdt, np.integer):
-        raise ValueError(f"rasterize: `triangles` must have an integer dtype, got {tdt}")
-    Tn = int(tshape[0])
-    if not 1 <= Tn < 1 << 31:
-        raise ValueError(f"rasterize: {Tn} triangles (1 .. 2^31 - 1)")
-    vshape = tuple(vertices.shape)
-    if len(vshape) not in (2, 3) or vshape[-1] != 3:
-        raise ValueError(f"rasterize: `vertices` must be (N,3) or (F,N,3), got {vshape}")
-    Fv, N = (1, vshape[0]) if len(vshape) == 2 else vshape[:2]
-    if N < 1 or Fv < 1:
-        raise ValueError(f"rasterize: `vertices` {vshape} holds no vertex")
+    vertices, triangles, normals, colors, N, Tn = mesh.mesh_arrays("rasterize", vertices, triangles, normals, colors, frames=True, any_dtype=True)
+    Fv = 1 if len(vertices.shape) == 2 else int(vertices.shape[0])
     table = _cameras(K, R, T)
     C = table.shape[0]
     if not (Fv == C or Fv == 1 or C == 1):
@@ -130,21 +89,12 @@ def _rasterize(vertices, triangles, H, W, K, R, T, normals=None, colors=None, sh
     F = max(Fv, C)
     if F > MAX_IMAGES:
         raise ValueError(f"rasterize: {F} images in one call (at most {MAX_IMAGES})")
-    if normals is not None:
-        nshape = tuple(normals.shape)
-        if len(nshape) not in (2, 3) or nshape[-1] != 3 or nshape[-2] != N or (len(nshape) == 3 and nshape[0] not in (1, Fv)):
-            raise ValueError(f"rasterize: `normals` must be ({N},3), (1,{N},3) or ({Fv},{N},3), got {nshape}")
-    if colors is not None:
-        is_u8 = colors.dtype == torch.uint8 if torch.is_tensor(colors) else colors.dtype == np.uint8
-        if tuple(colors.shape) != (N, 3) or not is_u8:
-            raise ValueError(f"rasterize: `colors` must be uint8 ({N},3), got {colors.dtype} {tuple(colors.shape)}")
-    if not torch.cuda.is_available():
-        raise RuntimeError("rasterize needs a CUDA(HIP) device; there is no CPU path")
-    dev = next((a.device for a in (vertices, triangles, normals, colors) if torch.is_tensor(a)), torch.device("cuda", torch.cuda.current_device()))
-    verts = _device_floats(vertices, "rasterize: `vertices`", dev)
-    nrm = None if normals is None else _device_floats(normals, "rasterize: `normals`", dev)
+    mesh.need_device("rasterize")
+    dev = mesh.device_of(vertices, triangles, normals, colors)
+    verts = mesh.to_device(vertices, torch.float32, dev).view(Fv, N, 3)
+    nrm = None if normals is None else mesh.to_device(normals, torch.float32, dev).view(-1, N, 3)
     tri = device_triangles(triangles, dev)
-    col = None if colors is None else (colors.detach() if torch.is_tensor(colors) else torch.as_tensor(np.ascontiguousarray(colors))).to(dev).contiguous()
+    col = None if colors is None else mesh.to_device(colors, torch.uint8, dev)
     flags = (_lib.HL_RASTER_WHITE_BKGD if white_bkgd else 0) | (_lib.HL_RASTER_HEADLIGHT if shade == "headlight" else 0) | \
         {None: 0, "back": _lib.HL_RASTER_CULL_BACK, "front": _lib.HL_RASTER_CULL_FRONT}[cull]
     if alloc is None:

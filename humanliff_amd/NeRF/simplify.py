@@ -18,26 +18,12 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .raster import device_triangles
+from . import mesh
 
 MAX_CELLS = 1 << 31
 MAX_CLUSTERS = 1 << 21
 ACC_FIELDS = ("count", "px", "py", "pz", "nx", "ny", "nz", "r", "g", "b", "xx", "xy", "xz", "yy", "yz", "zz", "xd", "yd", "zd", "dd")
 STATUS_VERTEX, STATUS_INDEX, STATUS_TABLE = 1, 2, 4
-
-
-def _shape_dtype(a):
-    return tuple(a.shape), a.dtype
-
-
-def _is_float(a):
-    return a.dtype.is_floating_point if torch.is_tensor(a) else np.issubdtype(a.dtype, np.floating)
-
-
-def _is_int(a):
-    if torch.is_tensor(a):
-        return not (a.dtype.is_floating_point or a.dtype.is_complex or a.dtype == torch.bool)
-    return np.issubdtype(a.dtype, np.integer)
 
 
 def _three(x, what):
@@ -55,52 +41,9 @@ def _three(x, what):
     return np.ascontiguousarray(v)
 
 
-def grid_extents(lo, hi, cell, origin):
-    """Valid vertices between `lo` and `hi` (float64 (3,)) -> (origin, extents g int64 (3,)): origin = lo when none is given,
-    g = floor((hi - origin) / cell) + 1 per axis - the arithmetic of the kernels, which is monotone in the coordinate, so no vertex
-    lies past the extents.  ValueError for a grid of more than 2^31 cells."""
-    origin = lo.copy() if origin is None else origin
-    q = (hi - origin) / cell
-    if not np.isfinite(q).all() or (q >= MAX_CELLS).any():
-        raise ValueError(f"simplify_mesh: the grid of cell {cell.tolist()} over the vertices holds more than 2^31 cells; use a larger cell")
-    g = np.floor(q).astype(np.int64) + 1
-    if int(g[0]) * int(g[1]) * int(g[2]) > MAX_CELLS:
-        raise ValueError(f"simplify_mesh: a grid of {g.tolist()} cells holds more than 2^31; use a larger cell")
-    return origin, g
-
-
 def _validate(mesh_or_vertices, triangles, cell, origin, normals, colors):
     """Everything that can be refused without a device -> (vertices, triangles, normals, colors, cell (3,), origin (3,) | None)."""
-    if isinstance(mesh_or_vertices, dict):
-        if triangles is not None:
-            raise ValueError("simplify_mesh: pass a mesh dict or (vertices, triangles), not both")
-        mesh = mesh_or_vertices
-        if "vertices" not in mesh or "triangles" not in mesh:
-            raise ValueError("simplify_mesh: a mesh dict needs `vertices` and `triangles`")
-        vertices, triangles = mesh["vertices"], mesh["triangles"]
-        normals = mesh.get("normals") if normals is None else normals
-        colors = mesh.get("colors") if colors is None else colors
-    else:
-        vertices = mesh_or_vertices
-        if triangles is None:
-            raise ValueError("simplify_mesh: `triangles` is missing")
-    for what, a in (("vertices", vertices), ("triangles", triangles), ("normals", normals), ("colors", colors)):
-        if torch.is_tensor(a) and not a.is_cuda:
-            raise RuntimeError(f"simplify_mesh: `{what}` is a CPU tensor; there is no CPU path (pass a numpy array or a device tensor)")
-    vertices, triangles = (a if torch.is_tensor(a) else np.asarray(a) for a in (vertices, triangles))
-    normals, colors = (a if a is None or torch.is_tensor(a) else np.asarray(a) for a in (normals, colors))
-    vshape, tshape = tuple(vertices.shape), tuple(triangles.shape)
-    if len(vshape) != 2 or vshape[1] != 3 or not _is_float(vertices):
-        raise ValueError(f"simplify_mesh: `vertices` must be float (N,3), got {vertices.dtype} {vshape}")
-    if len(tshape) != 2 or tshape[1] != 3 or not _is_int(triangles):
-        raise ValueError(f"simplify_mesh: `triangles` must be integer (T,3), got {triangles.dtype} {tshape}")
-    N, T = vshape[0], tshape[0]
-    if not (1 <= N < 1 << 31 and 1 <= T < 1 << 31):
-        raise ValueError(f"simplify_mesh: {N} vertices and {T} triangles (each 1 .. 2^31 - 1)")
-    if normals is not None and (tuple(normals.shape) != (N, 3) or not _is_float(normals)):
-        raise ValueError(f"simplify_mesh: `normals` must be float ({N},3), got {normals.dtype} {tuple(normals.shape)}")
-    if colors is not None and (tuple(colors.shape) != (N, 3) or colors.dtype not in (torch.uint8, np.uint8)):
-        raise ValueError(f"simplify_mesh: `colors` must be uint8 ({N},3), got {colors.dtype} {tuple(colors.shape)}")
+    vertices, triangles, normals, colors, _, _ = mesh.mesh_arrays("simplify_mesh", mesh_or_vertices, triangles, normals, colors, dict_extras=True)
     cell = _three(cell, "cell")
     if not (np.isfinite(cell).all() and (cell > 0).all()):
         raise ValueError(f"simplify_mesh: `cell` must be positive and finite, got {cell.tolist()}")
@@ -115,13 +58,8 @@ def _validate(mesh_or_vertices, triangles, cell, origin, normals, colors):
         if origin is not None:
             ok &= (v >= origin[None]).all(axis=1)
         if ok.any():
-            grid_extents(v[ok].min(axis=0), v[ok].max(axis=0), cell, origin)
+            mesh.grid_extents(v[ok].min(axis=0), v[ok].max(axis=0), cell, origin, MAX_CELLS, "simplify_mesh")
     return vertices, triangles, normals, colors, cell, origin
-
-
-def _device(a, dtype, dev):
-    t = a.detach() if torch.is_tensor(a) else torch.as_tensor(np.ascontiguousarray(a))
-    return t.to(device=dev, dtype=dtype).contiguous()
 
 
 def simplify_mesh(mesh_or_vertices, triangles=None, *, cell, origin=None, normals=None, colors=None, check=True):
@@ -143,18 +81,17 @@ def _simplify(mesh_or_vertices, triangles=None, *, cell, origin=None, normals=No
     N, T, clusters, extents, status).  `alloc(shape, dtype)`, default torch.empty on the device, provides the five outputs at their
     upper bounds and then the scratch, in that order."""
     vertices, triangles, normals, colors, cell, origin = _validate(mesh_or_vertices, triangles, cell, origin, normals, colors)
-    if not torch.cuda.is_available():
-        raise RuntimeError("simplify_mesh needs a CUDA(HIP) device; there is no CPU path")
-    dev = next((a.device for a in (vertices, triangles, normals, colors) if torch.is_tensor(a)), torch.device("cuda", torch.cuda.current_device()))
+    mesh.need_device("simplify_mesh")
+    dev = mesh.device_of(vertices, triangles, normals, colors)
     N, T = int(vertices.shape[0]), int(triangles.shape[0])
-    verts = _device(vertices, torch.float64, dev)
-    nrm = None if normals is None else _device(normals, torch.float64, dev)
-    col = None if colors is None else _device(colors, torch.uint8, dev)
-    tri = device_triangles(triangles, dev)
+    verts = mesh.to_device(vertices, torch.float64, dev)
+    nrm = None if normals is None else mesh.to_device(normals, torch.float64, dev)
+    col = None if colors is None else mesh.to_device(colors, torch.uint8, dev)
+    tri = mesh.device_triangles(triangles, dev)
     if alloc is None:
         alloc = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)  # noqa: E731
     L = _lib.lib()
-    dp = lambda t: _lib.ptr(t, None if t is None else t.dtype)  # noqa: E731
+    dp = mesh.dptr
     info = {"N": N, "T": T, "clusters": 0, "extents": None, "status": 0}
 
     def result(v, t, n, c, vmap, org):
@@ -167,15 +104,13 @@ def _simplify(mesh_or_vertices, triangles=None, *, cell, origin=None, normals=No
 
     with _lib.on(dev):
         st = _lib.stream_ptr(dev)
-        bounds = torch.empty(_lib.HL_SIMPLIFY_BOUNDS_WORDS, dtype=torch.float64, device=dev)
-        _lib.check(L.hl_mesh_simplify_bounds(dp(verts), N, None if origin is None else origin.ctypes.data, dp(bounds), st), "hl_mesh_simplify_bounds")
-        b = bounds[:6].cpu().numpy()
-        if not np.isfinite(b).all():                 # no vertex has a cell
+        b = mesh.finite_bounds(verts, origin)
+        if b is None:                                # no vertex has a cell
             if check:
                 raise ValueError("simplify_mesh: no vertex is finite and at or above `origin`")
             info["status"] = STATUS_VERTEX
             return empty(np.zeros(3) if origin is None else origin), None, info
-        origin, g = grid_extents(b[:3], b[3:], cell, origin)
+        origin, g = mesh.grid_extents(*b, cell, origin, MAX_CELLS, "simplify_mesh")
         gx, gy, gz = (int(x) for x in g)
         info["extents"] = (gx, gy, gz)
         need = int(L.hl_mesh_simplify_scratch_bytes(N, T, gx, gy, gz))
@@ -201,8 +136,7 @@ def _simplify(mesh_or_vertices, triangles=None, *, cell, origin=None, normals=No
         _lib.check(L.hl_mesh_simplify_emit(dp(verts), dp(nrm), dp(col), N, dp(tri), T, cell.ctypes.data, origin.ctypes.data, gx, gy, gz, clusters,
                                            dp(out_v), dp(out_n), dp(out_c), dp(out_t), dp(vmap), dp(counts), dp(status), dp(scratch), need, st),
                    "hl_mesh_simplify_emit")
-        w = words.cpu()
-        n_tri, n_vert, flags = int(w[2]), int(w[4]), int(w[6:].view(torch.int32)[0])
+        (_, _, n_tri, _, n_vert, _), flags = mesh.read_counts(words, 6)
     info["status"] = flags
     if flags & STATUS_TABLE:
         raise RuntimeError("simplify_mesh: the duplicate table ran out of probes")       # (half empty by construction: cannot happen)

@@ -22,8 +22,6 @@ constexpr int INF32 = 0x3fffffff;            // "no feature on this line yet" in
 constexpr long long INF64 = 1LL << 40;       // the same inside the envelope arithmetic (squares of the lattice stay below 2^32)
 
 using hl::k_scan_down;
-using hl::k_scan_reduce;
-using hl::k_scan_top;
 using hl::scan_blocks;
 inline unsigned grid_of(long n) { return (unsigned)((n + TPB - 1) / TPB); }
 
@@ -563,10 +561,7 @@ extern "C" int hl_smooth_prepare(const void *vol, int is_fp64, int nx, int ny, i
     const int rc = is_fp64 ? signed_distance((const double *)vol, nx, ny, nz, d_out, w.a, w.b, w.s, w.t, st)
                            : signed_distance((const float *)vol, nx, ny, nz, d_out, w.a, w.b, w.s, w.t, st);
     if (rc) return rc;
-    const long nbk = scan_blocks(n);
-    hipLaunchKernelGGL((k_scan_reduce<BandCount>), dim3((unsigned)nbk), dim3(TPB), 0, st, BandCount{d_out, band_radius}, n, w.blocks);
-    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(TPB), 0, st, w.blocks, nbk, counts);
-    return hl::check_launch("hl_smooth_prepare");
+    return hl::scan_total(BandCount{d_out, band_radius}, n, w.blocks, counts, st, "hl_smooth_prepare");
 }
 
 extern "C" int hl_smooth_band(const double *d, int nx, int ny, int nz, double band_radius, int64_t nb, int *lin, int *nbr, double *x,
@@ -631,9 +626,7 @@ extern "C" int hl_mc_count(const double *vol, int nx, int ny, int nz, double iso
     hipStream_t st = (hipStream_t)stream;
     McWs w = mc_ws(ws, n);
     hipLaunchKernelGGL(k_mc_classify, dim3(grid_of(n)), dim3(TPB), 0, st, vol, nx, ny, nz, iso, w.code);
-    hipLaunchKernelGGL((k_scan_reduce<McCount>), dim3((unsigned)scan_blocks(n)), dim3(TPB), 0, st, McCount{w.code}, n, w.blocks);
-    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(TPB), 0, st, w.blocks, scan_blocks(n), counts);
-    return hl::check_launch("hl_mc_count");
+    return hl::scan_total(McCount{w.code}, n, w.blocks, counts, st, "hl_mc_count");
 }
 
 extern "C" int hl_mc_emit(const double *vol, int nx, int ny, int nz, double iso, double *verts, int64_t *tris, void *ws, size_t ws_bytes,
@@ -699,11 +692,8 @@ extern "C" int hl_cc_label(const double *vol, int nx, int ny, int nz, double iso
         HL_HIP(hipStreamSynchronize(st));
         if (!changed) break;
     }
-    const long nbk = scan_blocks(n);
-    hipLaunchKernelGGL((k_scan_reduce<CcRootCount>), dim3((unsigned)nbk), dim3(TPB), 0, st, CcRootCount{w.parent}, n, w.blocks);
-    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(TPB), 0, st, w.blocks, nbk, counts);
-    hipLaunchKernelGGL((k_scan_down<CcRootCount, CcRankOut>), dim3((unsigned)nbk), dim3(TPB), 0, st, CcRootCount{w.parent}, CcRankOut{w.rank}, n,
-                       (const unsigned long long *)w.blocks);
+    const int rc = hl::scan_exclusive(CcRootCount{w.parent}, CcRankOut{w.rank}, n, w.blocks, counts, st, "hl_cc_label: scan");
+    if (rc != HL_OK) return rc;
     hipLaunchKernelGGL(k_cc_labels, dim3(grid_of(n)), dim3(TPB), 0, st, (const int *)w.parent, (const int *)w.rank, n, labels, counts, rounds);
     return hl::check_launch("hl_cc_label");
 }

@@ -21,6 +21,7 @@
 //   reduces its 256 world vertices to one min / max box per frame (the tree of hl_reduce.h) and writes it to the scratch.
 // k_mesh_bounds: one workgroup per frame folds the boxes of that frame's workgroups (thread t takes t, t + 256, ..., then the tree) and
 //   applies the margins with the body's two subtractions.  Min and max are exact in any order.
+#include "hl_mesh.h"
 #include "hl_reduce.h"
 
 #include <cmath>
@@ -29,7 +30,7 @@
 namespace hl {
 namespace {
 
-constexpr int kThreads = 256;
+constexpr int kThreads = kMeshThreads;
 static_assert(kThreads == kReduceThreads, "block_reduce reduces a workgroup of kReduceThreads");
 constexpr int kTile = 2048;                 // body vertices per LDS tile (32 KB)
 constexpr int kMaxK = 8;
@@ -285,8 +286,6 @@ __global__ __launch_bounds__(kThreads) void k_mesh_bounds(const float *__restric
         }
     }
 }
-
-inline int64_t blocks_of(int64_t N) { return (N + kThreads - 1) / kThreads; }
 
 // the sizes both entry points refuse; N == 0 is not among them
 #define HL_MESH_SIZES(name, N, V, K)                                                                                               \

@@ -26,6 +26,7 @@
 //   k_dist_sample:  a thread per sample: stratified position in the area prefix, binary search, R2 barycentrics.
 // hl_mesh_distance_reduce
 //   k_dist_reduce / k_dist_reduce_finish: per-workgroup partials by the fixed tree, then strided_sum in one workgroup.
+#include "hl_mesh.h"
 #include "hl_scan.h"
 
 #include <cmath>
@@ -34,7 +35,8 @@
 namespace hl {
 namespace {
 
-constexpr int kThreads = kScanThreads;
+constexpr int kThreads = kMeshThreads;
+static_assert(kThreads == kScanThreads, "the scans and reductions run workgroups of kThreads");
 constexpr int64_t kMaxCells = (int64_t)1 << 27;
 constexpr int64_t kMaxRefs = (int64_t)1 << 31;
 constexpr int64_t kWideCells = HL_DISTANCE_WIDE_CELLS;
@@ -46,17 +48,6 @@ constexpr int kMaxThresholds = 8;
 constexpr double kInf = (double)INFINITY;
 constexpr double kSlack = 9.5367431640625e-07;                // 2^-20 of a cell
 enum { kStatusIndex = 1, kStatusCorner = 2, kStatusQuery = 4 };
-
-inline size_t up16(size_t b) { return (b + 15) / 16 * 16; }
-inline int64_t blocks_of(int64_t n) { return (n + kThreads - 1) / kThreads; }
-inline bool count_ok(int64_t n) { return n >= 1 && n <= 0x7fffffff; }
-
-inline int64_t cells_of(int64_t gx, int64_t gy, int64_t gz) {
-    if (gx < 1 || gy < 1 || gz < 1 || gx > kMaxCells || gy > kMaxCells || gz > kMaxCells) return 0;
-    if (gx * gy > kMaxCells) return 0;              // (<= 2^54)
-    if (gx * gy * gz > kMaxCells) return 0;         // (<= 2^54)
-    return gx * gy * gz;
-}
 
 struct Layout {                                     // the scratch, in this order; every part a multiple of 16 bytes
     size_t rec, flag, start, cursor, wide, blocks, total;
@@ -80,8 +71,6 @@ struct Grid {
     int g[3];                                       // each <= 2^27
 };
 
-inline bool finite_host(double x) { return fabs(x) < kInf; }
-
 inline Grid grid_of(const double *origin, double h, int64_t gx, int64_t gy, int64_t gz) {
     Grid gr;
     for (int a = 0; a < 3; ++a) gr.origin[a] = origin[a];
@@ -98,7 +87,6 @@ __device__ __forceinline__ V3 sub(const V3 &a, const V3 &b) { return {a.x - b.x,
 __device__ __forceinline__ double dot(const V3 &a, const V3 &b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
 __device__ __forceinline__ V3 cross(const V3 &a, const V3 &b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
 __device__ __forceinline__ bool finite(double x) { return fabs(x) < kInf; }      // (false for NaN)
-__device__ __forceinline__ bool finite3(const V3 &v) { return finite(v.x) && finite(v.y) && finite(v.z); }
 
 struct Closest {
     double d2;
@@ -158,15 +146,14 @@ struct MeshIn {
 
 // the corners of triangle t relative to the origin; 0: valid, otherwise the status bit (an index outside [0, N) is never dereferenced)
 __device__ __forceinline__ int load_corners(const MeshIn &m, int64_t t, V3 (&p)[3]) {
-    const int *tp = m.triangles + t * 3;
-    const int iv[3] = {tp[0], tp[1], tp[2]};
-    if (!(iv[0] >= 0 && iv[1] >= 0 && iv[2] >= 0 && iv[0] < m.N && iv[1] < m.N && iv[2] < m.N)) return kStatusIndex;
+    int iv[3];
+    if (!load_indices(m.triangles, t, m.N, iv)) return kStatusIndex;
     bool ok = true;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         const double *vp = m.vertices + (int64_t)iv[k] * 3;
         const V3 v = {vp[0], vp[1], vp[2]};
-        ok = ok && finite3(v);
+        ok = ok && finite3(v.x, v.y, v.z);
         p[k] = {v.x - m.origin[0], v.y - m.origin[1], v.z - m.origin[2]};
     }
     return ok ? 0 : kStatusCorner;
@@ -337,7 +324,7 @@ __global__ __launch_bounds__(kThreads) void k_dist_query(const QueryArgs q) {
     const Grid &gr = q.gr;
     const V3 w = {q.points[i * 3], q.points[i * 3 + 1], q.points[i * 3 + 2]};
     const double nan = __builtin_nan("");
-    if (!finite3(w)) {
+    if (!finite3(w.x, w.y, w.z)) {
         q.sqdist[i] = nan, q.distance[i] = nan, q.triangle[i] = -1;
 #pragma unroll
         for (int k = 0; k < 3; ++k) q.bary[i * 3 + k] = nan, q.point[i * 3 + k] = nan;
@@ -394,7 +381,7 @@ __global__ __launch_bounds__(kThreads) void k_dist_query(const QueryArgs q) {
         const V3 nq = {q.normals[i * 3], q.normals[i * 3 + 1], q.normals[i * 3 + 2]};
         const V3 n = cross(sub(t[1], t[0]), sub(t[2], t[0]));
         const double len = sqrt(dot(n, n));
-        const bool ok = len > 0.0 && finite(len) && finite3(nq) && !(nq.x == 0.0 && nq.y == 0.0 && nq.z == 0.0);
+        const bool ok = len > 0.0 && finite(len) && finite3(nq.x, nq.y, nq.z) && !(nq.x == 0.0 && nq.y == 0.0 && nq.z == 0.0);
         const V3 u = {n.x / len, n.y / len, n.z / len};
         q.normal_dot[i] = ok ? dot(nq, u) : nan;
     }
@@ -500,8 +487,6 @@ inline MeshIn mesh_of(const double *vertices, int64_t N, const int32_t *triangle
     return m;
 }
 
-inline bool origin_ok(const double *o) { return o && finite_host(o[0]) && finite_host(o[1]) && finite_host(o[2]); }
-
 }  // namespace
 }  // namespace hl
 
@@ -510,7 +495,7 @@ using namespace hl;
 extern "C" {
 
 size_t hl_mesh_distance_scratch_bytes(int64_t T, int64_t gx, int64_t gy, int64_t gz) {
-    const int64_t cells = cells_of(gx, gy, gz);
+    const int64_t cells = cells_of(gx, gy, gz, kMaxCells);
     return count_ok(T) && cells ? layout_of(T, cells).total : 0;
 }
 
@@ -520,26 +505,22 @@ int hl_mesh_distance_areas(const double *vertices, int64_t N, const int32_t *tri
     HL_REQUIRE(origin_ok(h_origin), "hl_mesh_distance_areas: the origin must be finite");
     HL_REQUIRE(unit > 0.0 && finite_host(unit), "hl_mesh_distance_areas: the area unit must be positive and finite");
     HL_REQUIRE(vertices && triangles && prefix && counts && blocks, "hl_mesh_distance_areas: NULL argument");
-    const long nb = scan_blocks(T);
-    HL_REQUIRE(blocks_bytes >= (size_t)nb * 8, "hl_mesh_distance_areas: block sums too small (%zu bytes, need %zu)", blocks_bytes, (size_t)nb * 8);
+    HL_REQUIRE(blocks_bytes >= (size_t)scan_blocks(T) * 8, "hl_mesh_distance_areas: block sums too small (%zu bytes, need %zu)", blocks_bytes,
+               (size_t)scan_blocks(T) * 8);
     const hipStream_t st = (hipStream_t)stream;
     const MeshIn m = mesh_of(vertices, N, triangles, T, h_origin);
     unsigned long long *pre = reinterpret_cast<unsigned long long *>(prefix), *bl = static_cast<unsigned long long *>(blocks);
     hipLaunchKernelGGL(k_dist_area, dim3((unsigned)blocks_of(T)), dim3(kThreads), 0, st, m, unit, pre);
     int rc = check_launch("k_dist_area");
     if (rc != HL_OK) return rc;
-    hipLaunchKernelGGL((k_scan_reduce<AreaIn>), dim3((unsigned)nb), dim3(kThreads), 0, st, AreaIn{pre}, (long)T, bl);
-    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(kThreads), 0, st, bl, nb, counts);
-    hipLaunchKernelGGL((k_scan_down<AreaIn, AreaOut>), dim3((unsigned)nb), dim3(kThreads), 0, st, AreaIn{pre}, AreaOut{pre}, (long)T,
-                       (const unsigned long long *)bl);
-    return check_launch("hl_mesh_distance_areas: scan");
+    return scan_exclusive(AreaIn{pre}, AreaOut{pre}, (long)T, bl, counts, st, "hl_mesh_distance_areas: scan");
 }
 
 int hl_mesh_distance_count(const double *vertices, int64_t N, const int32_t *triangles, int64_t T, const double *h_origin, double h, int64_t gx, int64_t gy,
                            int64_t gz, int64_t *counts, int32_t *status, void *scratch, size_t scratch_bytes, void *stream) {
     HL_REQUIRE(count_ok(N) && count_ok(T), "hl_mesh_distance_count: bad sizes (N %lld, T %lld; both 1 .. 2^31 - 1)", (long long)N, (long long)T);
     HL_REQUIRE(origin_ok(h_origin) && h > 0.0 && finite_host(h), "hl_mesh_distance_count: the cell must be positive and finite, the origin finite");
-    const int64_t cells = cells_of(gx, gy, gz);
+    const int64_t cells = cells_of(gx, gy, gz, kMaxCells);
     HL_REQUIRE(cells, "hl_mesh_distance_count: a grid of %lld x %lld x %lld cells (each >= 1, at most 2^27 in all: pass a larger cell)", (long long)gx,
                (long long)gy, (long long)gz);
     HL_REQUIRE(vertices && triangles && counts && status && scratch, "hl_mesh_distance_count: NULL argument");
@@ -560,26 +541,16 @@ int hl_mesh_distance_count(const double *vertices, int64_t N, const int32_t *tri
     hipLaunchKernelGGL(k_dist_records, dim3((unsigned)blocks_of(T)), dim3(kThreads), 0, st, m, gr, rec, flag, start, status);
     int rc = check_launch("k_dist_records");
     if (rc != HL_OK) return rc;
-    const long nbc = scan_blocks(cells + 1);
-    hipLaunchKernelGGL((k_scan_reduce<CellIn>), dim3((unsigned)nbc), dim3(kThreads), 0, st, CellIn{start}, (long)(cells + 1), bl);
-    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(kThreads), 0, st, bl, nbc, counts);
-    hipLaunchKernelGGL((k_scan_down<CellIn, CellOut>), dim3((unsigned)nbc), dim3(kThreads), 0, st, CellIn{start}, CellOut{start}, (long)(cells + 1),
-                       (const unsigned long long *)bl);
-    rc = check_launch("hl_mesh_distance_count: cell scan");
+    rc = scan_exclusive(CellIn{start}, CellOut{start}, (long)(cells + 1), bl, counts, st, "hl_mesh_distance_count: cell scan");
     if (rc != HL_OK) return rc;
-    const long nbt = scan_blocks(T);
-    hipLaunchKernelGGL((k_scan_reduce<FlagIn>), dim3((unsigned)nbt), dim3(kThreads), 0, st, FlagIn{flag}, (long)T, bl);
-    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(kThreads), 0, st, bl, nbt, counts + 2);
-    hipLaunchKernelGGL((k_scan_down<FlagIn, WideOut>), dim3((unsigned)nbt), dim3(kThreads), 0, st, FlagIn{flag}, WideOut{wide}, (long)T,
-                       (const unsigned long long *)bl);
-    return check_launch("hl_mesh_distance_count: triangle scan");
+    return scan_exclusive(FlagIn{flag}, WideOut{wide}, (long)T, bl, counts + 2, st, "hl_mesh_distance_count: triangle scan");
 }
 
 int hl_mesh_distance_fill(int64_t T, const double *h_origin, double h, int64_t gx, int64_t gy, int64_t gz, int32_t *refs, int64_t n_refs, void *scratch,
                           size_t scratch_bytes, void *stream) {
     HL_REQUIRE(count_ok(T), "hl_mesh_distance_fill: bad triangle count %lld (1 .. 2^31 - 1)", (long long)T);
     HL_REQUIRE(origin_ok(h_origin) && h > 0.0 && finite_host(h), "hl_mesh_distance_fill: the cell must be positive and finite, the origin finite");
-    const int64_t cells = cells_of(gx, gy, gz);
+    const int64_t cells = cells_of(gx, gy, gz, kMaxCells);
     HL_REQUIRE(cells, "hl_mesh_distance_fill: a grid of %lld x %lld x %lld cells (each >= 1, at most 2^27 in all: pass a larger cell)", (long long)gx,
                (long long)gy, (long long)gz);
     HL_REQUIRE(n_refs >= 0 && n_refs <= kMaxRefs, "hl_mesh_distance_fill: %lld references, at most 2^31 (pass a larger cell)", (long long)n_refs);
@@ -603,7 +574,7 @@ int hl_mesh_distance_query(const double *points, const double *normals, int64_t 
                            size_t scratch_bytes, void *stream) {
     HL_REQUIRE(count_ok(Q) && count_ok(T), "hl_mesh_distance_query: bad sizes (Q %lld, T %lld; both 1 .. 2^31 - 1)", (long long)Q, (long long)T);
     HL_REQUIRE(origin_ok(h_origin) && h > 0.0 && finite_host(h), "hl_mesh_distance_query: the cell must be positive and finite, the origin finite");
-    const int64_t cells = cells_of(gx, gy, gz);
+    const int64_t cells = cells_of(gx, gy, gz, kMaxCells);
     HL_REQUIRE(cells, "hl_mesh_distance_query: a grid of %lld x %lld x %lld cells (each >= 1, at most 2^27 in all: pass a larger cell)", (long long)gx,
                (long long)gy, (long long)gz);
     HL_REQUIRE(n_refs >= 0 && n_refs <= kMaxRefs, "hl_mesh_distance_query: %lld references, at most 2^31 (pass a larger cell)", (long long)n_refs);

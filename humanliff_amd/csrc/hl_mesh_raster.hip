@@ -29,7 +29,7 @@
 //   drawn by 16 waves and a wave whose slice starts past the box's end moves on after reading the entry's 16 bytes.
 // k_raster_resolve: a thread per pixel: winner's triangle reloaded, exact E_i recomputed, w_i = (b_i / z_i) * depth with depth the
 //   key's high word (depth_map is exactly what won), attributes (w0 a0 + w1 a1) + w2 a2.
-#include "hl_common.h"
+#include "hl_mesh.h"
 
 #include <cmath>
 #include <cstdint>
@@ -39,7 +39,7 @@
 namespace hl {
 namespace {
 
-constexpr int kThreads = 256;
+constexpr int kThreads = kMeshThreads;
 constexpr int kWave = 64;
 constexpr int kCamsPerLaunch = 8;
 constexpr int kMaxImages = 65535;                 // grid.y
@@ -74,8 +74,6 @@ struct Layout {                                   // the scratch, in this order;
     size_t cams, recs, zbuf, counter, list, total;
     int64_t capacity;
 };
-
-inline size_t up16(size_t b) { return (b + 15) / 16 * 16; }
 
 inline Layout layout_of(int64_t N, int64_t T, int F, int H, int W) {
     Layout l;
@@ -221,21 +219,15 @@ struct CoverArgs {
     int *status;                                  // or NULL
 };
 
-__device__ __forceinline__ bool load_triangle(const CoverArgs &a, int64_t t, int &i0, int &i1, int &i2) {
-    const int *tp = a.triangles + t * 3;
-    i0 = tp[0], i1 = tp[1], i2 = tp[2];
-    return i0 >= 0 && i1 >= 0 && i2 >= 0 && i0 < a.N && i1 < a.N && i2 < a.N;
-}
-
 __global__ __launch_bounds__(kThreads) void k_raster_cover(const CoverArgs a) {
     const int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     const int64_t img = blockIdx.y;
     Setup s;
     bool draw = false;
     if (t < a.T) {
-        int i0, i1, i2;
-        if (load_triangle(a, t, i0, i1, i2))
-            draw = setup_triangle(a.recs + img * a.N, i0, i1, i2, a.cull, a.H, a.W, s);
+        int iv[3];
+        if (load_indices(a.triangles, t, a.N, iv))
+            draw = setup_triangle(a.recs + img * a.N, iv[0], iv[1], iv[2], a.cull, a.H, a.W, s);
         else if (a.status)
             atomicOr(a.status, 1);
     }
@@ -276,9 +268,10 @@ __global__ __launch_bounds__(kThreads) void k_raster_cover_large(const CoverArgs
         const int64_t t = le.tri, img = le.img;
         if (le.pixels <= first) continue;
         if (t >= a.T || img >= a.F) continue;              // (entries come from k_raster_cover; never index outside whatever they hold)
-        int i0, i1, i2;
+        int iv[3];
         Setup s;
-        if (!load_triangle(a, t, i0, i1, i2) || !setup_triangle(a.recs + img * a.N, i0, i1, i2, a.cull, a.H, a.W, s)) continue;
+        if (!load_indices(a.triangles, t, a.N, iv)) continue;
+        if (!setup_triangle(a.recs + img * a.N, iv[0], iv[1], iv[2], a.cull, a.H, a.W, s)) continue;
         unsigned long long *zimg = a.zbuf + img * a.H * a.W;
         const int bw = s.x1 - s.x0 + 1;
         const int64_t n = (int64_t)bw * (s.y1 - s.y0 + 1);
@@ -319,10 +312,10 @@ __global__ __launch_bounds__(kThreads) void k_raster_resolve(const ResolveArgs a
     float rgb[3], nrm[3] = {0.f, 0.f, 0.f}, w[3] = {0.f, 0.f, 0.f}, depth = 0.f, acc = 0.f;
     int id = -1;
     rgb[0] = rgb[1] = rgb[2] = a.white ? 1.f : 0.f;
-    int i0, i1, i2;
+    int ti[3];                                    // the triangle's own order
     Setup s;
-    if (key != kEmpty && t < a.c.T && load_triangle(a.c, t, i0, i1, i2) &&
-        setup_triangle(a.c.recs + img * a.c.N, i0, i1, i2, a.c.cull, a.c.H, a.c.W, s)) {
+    if (key != kEmpty && t < a.c.T && load_indices(a.c.triangles, t, a.c.N, ti) &&
+        setup_triangle(a.c.recs + img * a.c.N, ti[0], ti[1], ti[2], a.c.cull, a.c.H, a.c.W, s)) {
         int64_t E[3];
         edge_functions(s, px, py, E);
         float q[3];
@@ -331,7 +324,7 @@ __global__ __launch_bounds__(kThreads) void k_raster_resolve(const ResolveArgs a
         acc = 1.f, id = (int)t;
 #pragma unroll
         for (int i = 0; i < 3; ++i) w[i] = q[i] * depth;
-        const int iv[3] = {i0, s.swapped ? i2 : i1, s.swapped ? i1 : i2};      // the drawing order
+        const int iv[3] = {ti[0], s.swapped ? ti[2] : ti[1], s.swapped ? ti[1] : ti[2]};      // the drawing order
         const RasterCam &cam = a.cams[a.cam_frames == 1 ? 0 : img];
         if (a.normals) {
             const float *nb = a.normals + (a.normal_frames == 1 ? 0 : img) * a.c.N * 3;
@@ -341,7 +334,7 @@ __global__ __launch_bounds__(kThreads) void k_raster_resolve(const ResolveArgs a
         } else {
             // the flat normal of the triangle in its own order, turned towards the camera
             const float *vb = a.vertices + (a.vertex_frames == 1 ? 0 : img) * a.c.N * 3;
-            const float *v0 = vb + (int64_t)i0 * 3, *v1 = vb + (int64_t)i1 * 3, *v2 = vb + (int64_t)i2 * 3;
+            const float *v0 = vb + (int64_t)ti[0] * 3, *v1 = vb + (int64_t)ti[1] * 3, *v2 = vb + (int64_t)ti[2] * 3;
             const float e1[3] = {v1[0] - v0[0], v1[1] - v0[1], v1[2] - v0[2]}, e2[3] = {v2[0] - v0[0], v2[1] - v0[1], v2[2] - v0[2]};
             nrm[0] = e1[1] * e2[2] - e1[2] * e2[1], nrm[1] = e1[2] * e2[0] - e1[0] * e2[2], nrm[2] = e1[0] * e2[1] - e1[1] * e2[0];
             const float d[3] = {v0[0] - (float)cam.o[0], v0[1] - (float)cam.o[1], v0[2] - (float)cam.o[2]};
@@ -387,10 +380,8 @@ __global__ __launch_bounds__(kThreads) void k_raster_resolve(const ResolveArgs a
     }
 }
 
-inline int64_t blocks_of(int64_t n) { return (n + kThreads - 1) / kThreads; }
-
 inline bool sizes_ok(int64_t N, int64_t T, int F, int H, int W) {
-    return N >= 1 && N <= 0x7fffffff && T >= 1 && T <= 0x7fffffff && F >= 1 && F <= kMaxImages && H >= 1 && W >= 1 && (int64_t)H * W <= 0x7fffffff;
+    return count_ok(N) && count_ok(T) && F >= 1 && F <= kMaxImages && H >= 1 && W >= 1 && (int64_t)H * W <= 0x7fffffff;
 }
 
 }  // namespace

@@ -23,6 +23,7 @@
 //   k_simplify_used:   a triangle survives when it is its key's smallest index; survivors flag their three clusters.
 //   scan over the clusters -> new vertex index;  k_simplify_solve: a thread per surviving cluster, the representative by Cramer's rule;
 //   scan over the triangles -> k_simplify_triangles writes the survivors in input order, renumbered;  k_simplify_vertex_map.
+#include "hl_mesh.h"
 #include "hl_scan.h"
 
 #include <cmath>
@@ -31,7 +32,8 @@
 namespace hl {
 namespace {
 
-constexpr int kThreads = kScanThreads;
+constexpr int kThreads = kMeshThreads;
+static_assert(kThreads == kScanThreads, "the scans and reductions run workgroups of kThreads");
 constexpr int kBoundsBlocks = HL_SIMPLIFY_BOUNDS_BLOCKS;
 constexpr int kAccWords = HL_SIMPLIFY_ACC_WORDS;    // count, position x y z, normal x y z, colour r g b, quadric xx xy xz yy yz zz xd yd zd dd
 constexpr int64_t kMaxCells = (int64_t)1 << 31;
@@ -47,23 +49,10 @@ struct Grid {
     int has_origin;
 };
 
-inline size_t up16(size_t b) { return (b + 15) / 16 * 16; }
-inline int64_t blocks_of(int64_t n) { return (n + kThreads - 1) / kThreads; }
-
-inline bool sizes_ok(int64_t N, int64_t T) { return N >= 1 && N <= 0x7fffffff && T >= 1 && T <= 0x7fffffff; }
-
-// extents -> number of cells, 0 when an extent is below 1 or the grid holds more than 2^31 cells (checked without overflow)
-inline int64_t cells_of(int64_t gx, int64_t gy, int64_t gz) {
-    if (gx < 1 || gy < 1 || gz < 1 || gx > kMaxCells || gy > kMaxCells || gz > kMaxCells) return 0;
-    if (gx * gy > kMaxCells) return 0;              // (<= 2^62)
-    if (gx * gy * gz > kMaxCells) return 0;         // (<= 2^62)
-    return gx * gy * gz;
-}
-
 inline bool grid_ok(const double *cell, const double *origin) {
     for (int a = 0; a < 3; ++a) {
-        if (!(cell[a] > 0.0 && cell[a] < (double)INFINITY)) return false;
-        if (origin && !(fabs(origin[a]) < (double)INFINITY)) return false;
+        if (!(cell[a] > 0.0 && finite_host(cell[a]))) return false;
+        if (origin && !finite_host(origin[a])) return false;
     }
     return true;
 }
@@ -98,12 +87,8 @@ inline Layout layout_of(int64_t N, int64_t T, int64_t cells) {
 }
 
 // ---- bounds ---------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool finite3(const double (&v)[3]) {
-    return fabs(v[0]) < (double)INFINITY && fabs(v[1]) < (double)INFINITY && fabs(v[2]) < (double)INFINITY;      // (false for NaN)
-}
-
 __device__ __forceinline__ bool vertex_valid(const Grid &gr, const double (&v)[3]) {
-    return finite3(v) && (!gr.has_origin || (v[0] >= gr.origin[0] && v[1] >= gr.origin[1] && v[2] >= gr.origin[2]));
+    return finite3(v[0], v[1], v[2]) && (!gr.has_origin || (v[0] >= gr.origin[0] && v[1] >= gr.origin[1] && v[2] >= gr.origin[2]));
 }
 
 // partial (blocks, 6): min x y z, max x y z of the block's valid vertices (+inf / -inf where it has none)
@@ -139,7 +124,7 @@ __global__ __launch_bounds__(kThreads) void k_simplify_bounds_finish(const doubl
 // q = (v - origin) / cell and ci = floor(q) per axis; false: the vertex belongs to no cell
 __device__ __forceinline__ bool cell_of(const Grid &gr, const double *__restrict__ vp, double (&q)[3], int64_t (&ci)[3]) {
     const double v[3] = {vp[0], vp[1], vp[2]};
-    bool ok = finite3(v);
+    bool ok = finite3(v[0], v[1], v[2]);
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         q[a] = (v[a] - gr.origin[a]) / gr.cell[a];
@@ -229,19 +214,12 @@ __global__ __launch_bounds__(kThreads) void k_simplify_members(const MeshIn m, c
     }
 }
 
-// the triangle's indices, validated; false: an index outside [0, N) (never dereferenced)
-__device__ __forceinline__ bool load_triangle(const MeshIn &m, int64_t t, int (&iv)[3]) {
-    const int *tp = m.triangles + t * 3;
-    iv[0] = tp[0], iv[1] = tp[1], iv[2] = tp[2];
-    return iv[0] >= 0 && iv[1] >= 0 && iv[2] >= 0 && iv[0] < m.N && iv[1] < m.N && iv[2] < m.N;
-}
-
 __global__ __launch_bounds__(kThreads) void k_simplify_quadrics(const MeshIn m, const Grid gr, const int *__restrict__ vid, int64_t *__restrict__ acc,
                                                                 int *__restrict__ status) {
     const int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     if (t >= m.T) return;
     int iv[3];
-    if (!load_triangle(m, t, iv)) {
+    if (!load_indices(m.triangles, t, m.N, iv)) {
         atomicOr(status, kStatusIndex);
         return;
     }
@@ -282,7 +260,7 @@ __global__ __launch_bounds__(kThreads) void k_simplify_quadrics(const MeshIn m, 
 // two equal ids)
 __device__ __forceinline__ bool triangle_ids(const MeshIn &m, const int *__restrict__ vid, int64_t t, int (&c)[3]) {
     int iv[3];
-    if (!load_triangle(m, t, iv)) return false;
+    if (!load_indices(m.triangles, t, m.N, iv)) return false;
     const int a = vid[iv[0]], b = vid[iv[1]], d = vid[iv[2]];
     if (a < 0 || b < 0 || d < 0 || a == b || b == d || a == d) return false;
     if (a < b && a < d)
@@ -446,9 +424,8 @@ using namespace hl;
 extern "C" {
 
 int hl_mesh_simplify_bounds(const double *vertices, int64_t N, const double *h_origin, double *bounds, void *stream) {
-    HL_REQUIRE(N >= 1 && N <= 0x7fffffff, "hl_mesh_simplify_bounds: bad vertex count %lld (1 .. 2^31 - 1)", (long long)N);
-    HL_REQUIRE(!h_origin || (fabs(h_origin[0]) < (double)INFINITY && fabs(h_origin[1]) < (double)INFINITY && fabs(h_origin[2]) < (double)INFINITY),
-               "hl_mesh_simplify_bounds: the origin must be finite");
+    HL_REQUIRE(count_ok(N), "hl_mesh_simplify_bounds: bad vertex count %lld (1 .. 2^31 - 1)", (long long)N);
+    HL_REQUIRE(!h_origin || origin_ok(h_origin), "hl_mesh_simplify_bounds: the origin must be finite");
     HL_REQUIRE(vertices && bounds, "hl_mesh_simplify_bounds: NULL argument");
     const double one[3] = {1.0, 1.0, 1.0};
     const Grid gr = grid_of(one, h_origin, 1, 1, 1);
@@ -462,15 +439,15 @@ int hl_mesh_simplify_bounds(const double *vertices, int64_t N, const double *h_o
 }
 
 size_t hl_mesh_simplify_scratch_bytes(int64_t N, int64_t T, int64_t gx, int64_t gy, int64_t gz) {
-    const int64_t cells = cells_of(gx, gy, gz);
-    return sizes_ok(N, T) && cells ? layout_of(N, T, cells).total : 0;
+    const int64_t cells = cells_of(gx, gy, gz, kMaxCells);
+    return count_ok(N) && count_ok(T) && cells ? layout_of(N, T, cells).total : 0;
 }
 
 int hl_mesh_simplify_count(const double *vertices, int64_t N, int64_t T, const double *h_cell, const double *h_origin, int64_t gx, int64_t gy, int64_t gz,
                            int64_t *counts, int32_t *status, void *scratch, size_t scratch_bytes, void *stream) {
-    HL_REQUIRE(sizes_ok(N, T), "hl_mesh_simplify_count: bad sizes (N %lld, T %lld; both 1 .. 2^31 - 1)", (long long)N, (long long)T);
+    HL_REQUIRE(count_ok(N) && count_ok(T), "hl_mesh_simplify_count: bad sizes (N %lld, T %lld; both 1 .. 2^31 - 1)", (long long)N, (long long)T);
     HL_REQUIRE(h_cell && h_origin && grid_ok(h_cell, h_origin), "hl_mesh_simplify_count: the cell must be positive and finite, the origin finite");
-    const int64_t cells = cells_of(gx, gy, gz);
+    const int64_t cells = cells_of(gx, gy, gz, kMaxCells);
     HL_REQUIRE(cells, "hl_mesh_simplify_count: a grid of %lld x %lld x %lld cells (each >= 1, at most 2^31 in all: use a larger cell)", (long long)gx,
                (long long)gy, (long long)gz);
     HL_REQUIRE(vertices && counts && status && scratch, "hl_mesh_simplify_count: NULL argument");
@@ -489,21 +466,16 @@ int hl_mesh_simplify_count(const double *vertices, int64_t N, int64_t T, const d
     hipLaunchKernelGGL(k_simplify_mark, dim3((unsigned)blocks_of(N)), dim3(kThreads), 0, st, vertices, N, gr, bitmap, vkey, status);
     int rc = check_launch("k_simplify_mark");
     if (rc != HL_OK) return rc;
-    const long nb = scan_blocks(l.words);
-    hipLaunchKernelGGL((k_scan_reduce<PopCount>), dim3((unsigned)nb), dim3(kThreads), 0, st, PopCount{bitmap}, (long)l.words, blocks);
-    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(kThreads), 0, st, blocks, nb, counts);
-    hipLaunchKernelGGL((k_scan_down<PopCount, RankOut>), dim3((unsigned)nb), dim3(kThreads), 0, st, PopCount{bitmap}, RankOut{rank}, (long)l.words,
-                       (const unsigned long long *)blocks);
-    return check_launch("hl_mesh_simplify_count: scan");
+    return scan_exclusive(PopCount{bitmap}, RankOut{rank}, (long)l.words, blocks, counts, st, "hl_mesh_simplify_count: scan");
 }
 
 int hl_mesh_simplify_emit(const double *vertices, const double *normals, const unsigned char *colors, int64_t N, const int32_t *triangles, int64_t T,
                           const double *h_cell, const double *h_origin, int64_t gx, int64_t gy, int64_t gz, int64_t clusters, double *out_vertices,
                           double *out_normals, unsigned char *out_colors, int64_t *out_triangles, int64_t *vertex_map, int64_t *counts, int32_t *status,
                           void *scratch, size_t scratch_bytes, void *stream) {
-    HL_REQUIRE(sizes_ok(N, T), "hl_mesh_simplify_emit: bad sizes (N %lld, T %lld; both 1 .. 2^31 - 1)", (long long)N, (long long)T);
+    HL_REQUIRE(count_ok(N) && count_ok(T), "hl_mesh_simplify_emit: bad sizes (N %lld, T %lld; both 1 .. 2^31 - 1)", (long long)N, (long long)T);
     HL_REQUIRE(h_cell && h_origin && grid_ok(h_cell, h_origin), "hl_mesh_simplify_emit: the cell must be positive and finite, the origin finite");
-    const int64_t cells = cells_of(gx, gy, gz);
+    const int64_t cells = cells_of(gx, gy, gz, kMaxCells);
     HL_REQUIRE(cells, "hl_mesh_simplify_emit: a grid of %lld x %lld x %lld cells (each >= 1, at most 2^31 in all: use a larger cell)", (long long)gx,
                (long long)gy, (long long)gz);
     HL_REQUIRE(clusters <= kMaxClusters, "hl_mesh_simplify_emit: %lld clusters, at most 2^21 (use a larger cell)", (long long)clusters);
@@ -552,12 +524,7 @@ int hl_mesh_simplify_emit(const double *vertices, const double *normals, const u
     if (rc != HL_OK) return rc;
 
     // surviving clusters -> new vertex indices (counts[4]), then their representatives
-    const long nbc = scan_blocks(clusters);
-    hipLaunchKernelGGL((k_scan_reduce<UsedCount>), dim3((unsigned)nbc), bt, 0, st, UsedCount{used}, (long)clusters, blocks);
-    hipLaunchKernelGGL(k_scan_top, dim3(1), bt, 0, st, blocks, nbc, counts + 4);
-    hipLaunchKernelGGL((k_scan_down<UsedCount, NewIndexOut>), dim3((unsigned)nbc), bt, 0, st, UsedCount{used}, NewIndexOut{newidx}, (long)clusters,
-                       (const unsigned long long *)blocks);
-    rc = check_launch("hl_mesh_simplify_emit: cluster scan");
+    rc = scan_exclusive(UsedCount{used}, NewIndexOut{newidx}, (long)clusters, blocks, counts + 4, st, "hl_mesh_simplify_emit: cluster scan");
     if (rc != HL_OK) return rc;
     SolveArgs sa;
     sa.acc = acc, sa.ckey = ckey, sa.newidx = newidx, sa.clusters = clusters, sa.gr = gr, sa.vertices = out_vertices, sa.normals = out_normals,
@@ -567,13 +534,8 @@ int hl_mesh_simplify_emit(const double *vertices, const double *normals, const u
     if (rc != HL_OK) return rc;
 
     // surviving triangles, in input order (counts[2])
-    const long nbt = scan_blocks(T);
-    const SurvivorCount sc{slot_of, tb.min_tri};
-    hipLaunchKernelGGL((k_scan_reduce<SurvivorCount>), dim3((unsigned)nbt), bt, 0, st, sc, (long)T, blocks);
-    hipLaunchKernelGGL(k_scan_top, dim3(1), bt, 0, st, blocks, nbt, counts + 2);
-    hipLaunchKernelGGL((k_scan_down<SurvivorCount, TriangleOut>), dim3((unsigned)nbt), bt, 0, st, sc, TriangleOut{m, vid, newidx, out_triangles}, (long)T,
-                       (const unsigned long long *)blocks);
-    rc = check_launch("hl_mesh_simplify_emit: triangle scan");
+    rc = scan_exclusive(SurvivorCount{slot_of, tb.min_tri}, TriangleOut{m, vid, newidx, out_triangles}, (long)T, blocks, counts + 2, st,
+                        "hl_mesh_simplify_emit: triangle scan");
     if (rc != HL_OK) return rc;
     hipLaunchKernelGGL(k_simplify_vertex_map, gn, bt, 0, st, (const int *)vid, (const int *)newidx, N, vertex_map);
     return check_launch("k_simplify_vertex_map");

@@ -1,10 +1,13 @@
 // The three-kernel exclusive scan of the mesh path (hl_geometry.hip: band, marching-cubes and component offsets; hl_mesh_simplify.hip:
-// cluster ids, surviving triangles, surviving vertices).  The values are packed (low 32, high 32) integer counts and every sum is an
-// integer sum, so the result does not depend on any order.
+// cluster ids, surviving triangles, surviving vertices; hl_mesh_distance.hip: triangle areas, cell starts, wide triangles).  The values
+// are packed (low 32, high 32) integer counts and every sum is an integer sum, so the result does not depend on any order.
 //
 //   k_scan_reduce: a workgroup per tile of kScanTile values -> the tile's sum.
 //   k_scan_top:    one workgroup: tile sums -> exclusive tile offsets (in place); the grand total unpacked into counts[0] (low) / [1] (high).
 //   k_scan_down:   a workgroup per tile, kScanItems consecutive values per thread: out(i, exclusive prefix of i, value of i).
+//
+//   scan_exclusive: the three on a stream, then check_launch(what); `blocks` holds scan_blocks(n) words.
+//   scan_total:     reduce and top alone: only the total, in counts[0] / [1].
 //
 // F is a functor `unsigned long long operator()(long i)`, O a functor `void operator()(long i, unsigned long long run, unsigned long long v)`.
 // The kernels have internal linkage: every file that includes this header gets its own.
@@ -86,6 +89,23 @@ __global__ __launch_bounds__(kScanThreads) void k_scan_down(F f, O out, long n, 
         out(i, run, v);
         run += v;
     }
+}
+
+template <class F>
+int scan_total(F f, long n, unsigned long long *blocks, int64_t *counts, hipStream_t st, const char *what) {
+    const long nb = scan_blocks(n);
+    hipLaunchKernelGGL((k_scan_reduce<F>), dim3((unsigned)nb), dim3(kScanThreads), 0, st, f, n, blocks);
+    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(kScanThreads), 0, st, blocks, nb, counts);
+    return check_launch(what);
+}
+
+template <class F, class O>
+int scan_exclusive(F f, O out, long n, unsigned long long *blocks, int64_t *counts, hipStream_t st, const char *what) {
+    const long nb = scan_blocks(n);
+    hipLaunchKernelGGL((k_scan_reduce<F>), dim3((unsigned)nb), dim3(kScanThreads), 0, st, f, n, blocks);
+    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(kScanThreads), 0, st, blocks, nb, counts);
+    hipLaunchKernelGGL((k_scan_down<F, O>), dim3((unsigned)nb), dim3(kScanThreads), 0, st, f, out, n, (const unsigned long long *)blocks);
+    return check_launch(what);
 }
 
 }  // namespace

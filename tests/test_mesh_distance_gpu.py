@@ -275,6 +275,36 @@ def test_sampler(dev, mesh):
         sample_surface(v, 16, np.asarray([[0, 0, 1], [2, 2, 2]]))
 
 
+def _regular_sheet(T):
+    """The first T triangles of an n x n sheet of quads over the xy plane with a smooth bump in z, n the smallest with 2 n^2 >= T."""
+    n = int(np.ceil(np.sqrt(T / 2.0)))
+    i, j = np.meshgrid(np.arange(n + 1), np.arange(n + 1), indexing="ij")
+    x, y = i.reshape(-1).astype(np.float64), j.reshape(-1).astype(np.float64)
+    v = np.stack([x, y, 0.25 * n * np.sin(x / n * 2.0) * np.cos(y / n * 3.0)], axis=1) * SPACING
+    a, b = (k.reshape(-1) for k in np.meshgrid(np.arange(n), np.arange(n), indexing="ij"))
+    at = lambda p, q: p * (n + 1) + q  # noqa: E731
+    quads = np.stack([at(a, b), at(a + 1, b), at(a + 1, b + 1), at(a, b), at(a + 1, b + 1), at(a, b + 1)], axis=1)
+    return v, quads.reshape(-1, 3)[:T].astype(np.int64)
+
+
+@pytest.mark.parametrize("T", [1, 4095, 4096, 4097, 4096 * 256 + 1])
+def test_area_prefix_at_the_scan_tile_edges(dev, T):
+    """Every exclusive scan of the mesh path goes through scan_exclusive (hl_scan.h): a tile is 256 x 16 = 4096 values, and from
+    4096 x 256 + 1 values on a thread of k_scan_top owns more than one tile sum.  The area prefix and total are integer sums: equal."""
+    from humanliff_amd.NeRF import distance as ds
+    v, t = _regular_sheet(T)
+    assert len(t) == T
+    verts, tri, _ = ds._device_mesh("test", v, t)
+    lo, hi = ds._bounds(verts)
+    ar = ds._Areas(verts, tri, lo, hi)
+    a, P, total, u = md.areas(md.target(v, t))
+    prefix = ar.prefix.cpu().numpy()
+    print(f"area prefix, T {T}: total {ar.total} against {total}, {int((prefix != P).sum())} of {T} prefix words differ; areas {a.min()} .. {a.max()}")
+    assert ar.unit == u and a.min() > 0
+    assert prefix.dtype == np.int64 and np.array_equal(prefix, P)
+    assert ar.total == total and ar.area == total * u
+
+
 def test_scores(dev):
     from humanliff_amd.NeRF import distance as ds
     va, ta, na = md.ellipsoid(24, 32)
