@@ -70,6 +70,15 @@ class LpipsParams(C.Structure):
     _fields_ = [("conv_w", C.c_void_p * 13), ("conv_b", C.c_void_p * 13), ("lin", C.c_void_p * 5), ("shift", C.c_float * 3), ("scale", C.c_float * 3)]
 
 
+HL_FID_LAYERS = 94
+HL_FID_DIMS = 2048
+HL_FID_STATE_BYTES = HL_FID_DIMS * HL_FID_DIMS * 8 + HL_FID_DIMS * 8
+
+
+class FidParams(C.Structure):
+    _fields_ = [("conv_w", C.c_void_p * HL_FID_LAYERS), ("conv_b", C.c_void_p * HL_FID_LAYERS)]
+
+
 _lib = None
 
 _p, _i, _i64, _u, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_uint, C.c_size_t
@@ -256,6 +265,12 @@ SIGNATURES = {
                                     _p]),
     "hl_mesh_distance_sample": (_i, [_p, _i64, _p, _i64, _p, _p, _i64, _i64, C.c_uint64, _p, _p, _p, _p, _p]),
     "hl_mesh_distance_reduce": (_i, [_p, _p, _p, _i64, _p, _i, _p, _p]),
+    "hl_fid_layer": (_i, [_i, C.c_char_p, _i, C.POINTER(C.c_int)]),
+    "hl_fid_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "hl_fid_block_shape": (_i, [_i, _i, _i, _i, _i, C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "hl_fid_features": (_i, [C.POINTER(FidParams), _p, _i, _i, _i, _i, _i, _p, _p, _sz, _p]),
+    "hl_fid_moments_update": (_i, [_p, _p, _i, _p]),
+    "hl_fid_moments_finalize": (_i, [_p, _i64, _p, _p, _p]),
 }
 
 

@@ -1125,6 +1125,40 @@ int hl_mesh_distance_sample(const double *vertices, int64_t N, const int32_t *tr
 int hl_mesh_distance_reduce(const double *distance, const double *sqdist, const double *normal_dot, int64_t Q, const double *h_thresholds, int n_thresholds,
                             double *out, void *stream);
 
+/* ---- FID: pytorch-fid's InceptionV3 pool3 features and the float64 moments of a feature set ----
+ * Contract: DESIGN.md 4l "FID"; csrc/hl_fid.hip.  Contiguous fp32 images, enqueue-only on `stream`, caller-owned workspace and state,
+ * exact fp32 products, no atomics: the same bits every run, and an image's features do not depend on the batch it is in.  The
+ * architecture has not been checked against pytorch-fid's own weights.
+ *   hl_fid_layer: row i of the layer table (the HL_FID_LAYERS BasicConv2d in the order the forward runs them): its state-dict name
+ *     ("Mixed_5b.branch1x1"; at most 39 characters) and desc[8] = Cin, Cout, kH, kW, sH, sW, pH, pW.
+ *   params: per layer, BatchNorm (eps 1e-3) folded in by the caller: conv_w[l] packed as (kH kW, ceil(Cin / 16), CoutP, 16) - tap, chunk of
+ *     16 input channels, output channel, channel within the chunk - with CoutP = Cout rounded up to 32 and zeros in all padding; conv_b[l]
+ *     (Cout).  16-byte aligned.
+ *   hl_fid_features: in (N, 3, h, w) in [0, 1], only read.  resize: bilinear to 299 x 299 (align_corners = False, no antialiasing);
+ *     normalize: 2 x - 1.  The four block outputs stay in the workspace as NHWC tensors (N, h_k, w_k, C_k), C_k = 64, 192, 768, 2048 (the
+ *     last one 1 x 1: the pool3 features), at the offsets hl_fid_block_shape gives for (N, h, w, resize); out (N, 2048), if not NULL,
+ *     receives the pool3 features as well.
+ *   1 <= N <= 4096; h, w <= 16384, and >= 75 without resize; workspace: hl_fid_workspace_bytes(N, h, w, resize) (0: bad shape).
+ *   Moments: state = HL_FID_STATE_BYTES, zeroed by the caller before the first update: S (2048, 2048) float64, of which the 64 x 64
+ *     tiles on and above the diagonal are kept, then s (2048) float64.  hl_fid_moments_update adds the n rows of features (n, 2048)
+ *     strictly in order: s[i] += x[i], S[i][j] += x[i] x[j], the product and the sum rounded separately - so the state does not depend
+ *     on how the images were split into updates.  The caller keeps the count.  hl_fid_moments_finalize(count >= 2): mu = s / count,
+ *     sigma[i][j] = (S[i][j] - (count mu[i]) mu[j]) / (count - 1) for i <= j, each operation rounded separately, mirrored below the diagonal. */
+#define HL_FID_LAYERS 94
+#define HL_FID_DIMS 2048
+#define HL_FID_STATE_BYTES ((size_t)HL_FID_DIMS * HL_FID_DIMS * 8 + (size_t)HL_FID_DIMS * 8)
+typedef struct hl_fid_params {
+    const float *conv_w[HL_FID_LAYERS];
+    const float *conv_b[HL_FID_LAYERS];
+} hl_fid_params;
+int hl_fid_layer(int i, char *name, int name_bytes, int *desc);
+size_t hl_fid_workspace_bytes(int N, int h, int w, int resize);
+int hl_fid_block_shape(int N, int h, int w, int resize, int k, size_t *offset_bytes, int *hk, int *wk, int *channels);
+int hl_fid_features(const hl_fid_params *params, const float *in, int N, int h, int w, int resize, int normalize, float *out, void *workspace,
+                    size_t workspace_bytes, void *stream);
+int hl_fid_moments_update(void *state, const float *features, int n, void *stream);
+int hl_fid_moments_finalize(const void *state, int64_t count, double *mu, double *sigma, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
