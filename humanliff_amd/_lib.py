@@ -271,6 +271,12 @@ SIGNATURES = {
     "hl_fid_features": (_i, [C.POINTER(FidParams), _p, _i, _i, _i, _i, _i, _p, _p, _sz, _p]),
     "hl_fid_moments_update": (_i, [_p, _p, _i, _p]),
     "hl_fid_moments_finalize": (_i, [_p, _i64, _p, _p, _p]),
+    "hl_feat_workspace_bytes": (_sz, [_i, _i64, _i64, _i64, _i64, _i]),
+    "hl_feat_split": (_i, [_i64, _i64, _i]),
+    "hl_feat_pairwise": (_i, [_p, _i64, _p, _i64, _i64, _i, _p, _p, _sz, _p]),
+    "hl_feat_kid": (_i, [_p, _i64, _p, _i64, _i64, _p, _p, _i64, _i64, _p, _p, _sz, _p]),
+    "hl_feat_knn_radii": (_i, [_p, _i64, _i64, _i, _i, _p, _p, _sz, _p]),
+    "hl_feat_manifold": (_i, [_p, _i64, _p, _i64, _i64, _p, _p, _i, _p, _p, _p, _p, _sz, _p]),
 }
 
 

@@ -1159,6 +1159,39 @@ int hl_fid_features(const hl_fid_params *params, const float *in, int N, int h, 
 int hl_fid_moments_update(void *state, const float *features, int n, void *stream);
 int hl_fid_moments_finalize(const void *state, int64_t count, double *mu, double *sigma, void *stream);
 
+/* ---- Feature metrics: KID, k-NN radii and the precision / recall manifold pass on two feature sets, pairwise in float64 ----
+ * Contract: DESIGN.md 4m "Feature metrics"; csrc/hl_feature_metrics.hip.  x (N, D), y (M, D) row-major fp32, any N, M, D >= 1, only read;
+ * enqueue-only on `stream`, caller-owned workspace of hl_feat_workspace_bytes(op, N, M, S, m, split) bytes (0: bad sizes), 16-byte aligned.
+ *   g(a, b) = sum_k (double)a_k (double)b_k, added for k = 0 .. D - 1 in that order, one rounding per k (the fp32 product is exact): a
+ *     function of the two rows' contents alone, symmetric bit for bit, the same bits every run.  d2(a, b) = max(0, (g(a,a) + g(b,b)) - 2 g(a,b)),
+ *     each operation rounded separately: exactly 0 for bit-equal rows.
+ *   hl_feat_pairwise: out (N, M) float64 = g (HL_FEAT_GRAM) or d2 (HL_FEAT_D2).
+ *   hl_feat_kid: x_index, y_index (S, m) int32 rows of x and of y (an index outside its set counts as a row of zeros; the caller checks).
+ *     k(a, b) = (g(a,b) / D + 1)^3, each operation rounded separately.  Per subset: sxx = sum_{i != j} k(x_i, x_j), syy likewise, sxy =
+ *     sum_{i, j} k(x_i, y_j) (i, j positions in the subset), as 64 x 64 tile partials in the workspace added in the fixed order of
+ *     hl_reduce.h; out[s] = sxx / (m (m - 1)) + syy / (m (m - 1)) - 2 sxy / m^2.  2 <= m <= min(N, M), 1 <= S <= 65535.
+ *   hl_feat_knn_radii: r2[i] = the k-th smallest d2(x_i, x_j) over j != i (by position: a duplicate row stays, at 0).  1 <= k <=
+ *     HL_FEAT_MAX_K, k < N.  The columns are cut into `split` chunks (<= 0: the library's rule, hl_feat_split) whose k-lists a second
+ *     kernel merges; the result does not depend on the split.
+ *   hl_feat_manifold: hits_fake[j] = #{i : d2(r_i, f_j) <= r2_real[i]} (M) int32, hits_real[i] = #{j : d2(r_i, f_j) <= r2_fake[j]} (N) int32,
+ *     nearest_real[i] = min_j d2(r_i, f_j) (N) float64; all three are initialised here.  `split` as above. */
+#define HL_FEAT_MAX_K 8
+#define HL_FEAT_GRAM 0
+#define HL_FEAT_D2 1
+#define HL_FEAT_OP_PAIRWISE 0
+#define HL_FEAT_OP_KID 1
+#define HL_FEAT_OP_KNN 2
+#define HL_FEAT_OP_MANIFOLD 3
+size_t hl_feat_workspace_bytes(int op, int64_t N, int64_t M, int64_t S, int64_t m, int split);
+int hl_feat_split(int64_t rows, int64_t cols, int split);
+int hl_feat_pairwise(const float *x, int64_t N, const float *y, int64_t M, int64_t D, int kind, double *out, void *workspace, size_t workspace_bytes,
+                     void *stream);
+int hl_feat_kid(const float *x, int64_t N, const float *y, int64_t M, int64_t D, const int32_t *x_index, const int32_t *y_index, int64_t S, int64_t m,
+                double *out, void *workspace, size_t workspace_bytes, void *stream);
+int hl_feat_knn_radii(const float *x, int64_t N, int64_t D, int k, int split, double *r2, void *workspace, size_t workspace_bytes, void *stream);
+int hl_feat_manifold(const float *real, int64_t N, const float *fake, int64_t M, int64_t D, const double *r2_real, const double *r2_fake, int split,
+                     int32_t *hits_fake, int32_t *hits_real, double *nearest_real, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -36,25 +36,29 @@ def main():
     ap.add_argument("--mesh-attributes", action="store_true", help="write vertex normals and colours into the PLY files (extract_mesh)")
     ap.add_argument("--mesh-simplify", type=float, default=None, metavar="K",
                     help="cluster the meshes on cells of K >= 1 lattice voxels before writing them (extract_mesh(..., simplify=K))")
-    ap.add_argument("--fid-weights", help="a saved state dict of pytorch-fid's InceptionV3 (INTEGRATION.md): with --fid-stats, every rendered "
-                                          "view goes through InceptionFID into FidStatistics as it is produced - no PNG round trip")
+    ap.add_argument("--fid-weights", help="a saved state dict of pytorch-fid's InceptionV3 (INTEGRATION.md): with --fid-stats and / or "
+                                          "--fid-features, every rendered view goes through a FeatureCollector (InceptionFID, 64 views a "
+                                          "call) as it is produced - no PNG round trip")
     ap.add_argument("--fid-stats", metavar="OUT.npz", help="write the mean and covariance of the views' pool3 features here (pytorch-fid's "
                                                            "--save-stats layout; scripts/triplane_fid.py scores two such files)")
+    ap.add_argument("--fid-features", metavar="OUT.npy", help="write the views' pool3 features (n, 2048) float32 here (scripts/triplane_fid.py "
+                                                              "--kid --prc scores two such files)")
     args = ap.parse_args()
-    if bool(args.fid_weights) != bool(args.fid_stats):
-        ap.error("--fid-weights and --fid-stats go together")
+    if bool(args.fid_weights) != bool(args.fid_stats or args.fid_features):
+        ap.error("--fid-weights goes together with --fid-stats and / or --fid-features")
     if args.mesh_simplify is not None and not args.mesh_simplify >= 1:
         ap.error("--mesh-simplify: a cell size of at least 1 voxel")
     if args.mesh_components not in ("none", "largest") and not (args.mesh_components.isdigit() and int(args.mesh_components) > 0):
         ap.error("--mesh-components: largest, a positive integer K or none")
     rank, world, dev = hd.init_distributed()
-    fid_model = fid_stats = None
-    if args.fid_stats:
+    fid_views = None
+    if args.fid_stats or args.fid_features:
         if world != 1:
-            ap.error("--fid-stats: the statistics take the views in order on one device; run it with one rank")
+            ap.error("--fid-stats / --fid-features: the views are taken in order on one device; run it with one rank")
+        from humanliff_amd.feature_metrics import FeatureCollector
         from humanliff_amd.fid import FidStatistics, InceptionFID
-        fid_model = InceptionFID.from_state_dict(torch.load(args.fid_weights, map_location="cpu"), dev)
-        fid_stats = FidStatistics(dev)
+        fid_views = FeatureCollector(InceptionFID.from_state_dict(torch.load(args.fid_weights, map_location="cpu"), dev), batch=64,
+                                     stats=FidStatistics(dev) if args.fid_stats else None, keep=bool(args.fid_features))
     cfg = dict(bench.F4, timestep_respacing=f"ddim{args.ddim}")
     model, diffusion = create_model_and_diffusion(**cfg)
     keys = [(k, tuple(v.shape)) for k, v in model.state_dict().items()]
@@ -80,8 +84,8 @@ def main():
         K, c2w, cam = syn.orbit_camera(v, args.views, H, W)
         R = c2w.T.copy(); T = (-R @ cam).reshape(3, 1)
         rgb = render_view(H, W, K, R, T, planes, tp, r, n_samples=128, n_importance=128)[0]
-        if fid_stats is not None:                                                 # enqueue-only: nothing is read back per view
-            fid_stats.update(fid_model(rgb.detach().float().clamp(0, 1).permute(2, 0, 1)[None]))
+        if fid_views is not None:                                                 # enqueue-only: nothing is read back per view
+            fid_views.add(rgb.detach().float().clamp(0, 1).permute(2, 0, 1).contiguous())
         return rgb
 
     torch.cuda.synchronize(); t0 = time.perf_counter()
@@ -97,9 +101,15 @@ def main():
         print(f"ranks {world}: {args.subjects} subjects x {args.layers} layers x DDIM-{args.ddim} ({steps} denoise steps) + "
               f"{args.subjects * args.views} views {H}x{W} ({rays / 1e6:.1f} Mrays) + gathers in {t2 - t0:.2f} s; "
               f"samples {tuple(samples.shape)} images {tuple(images.shape)} {images.dtype} mean {float(images.float().mean()):.4f}")
-        if fid_stats is not None:
-            fid_stats.save(args.fid_stats)
-            print(f"{args.fid_stats}: mean and covariance of the pool3 features of {fid_stats.count} views")
+        if fid_views is not None:
+            fid_views.flush()
+            if args.fid_stats:
+                fid_views.stats.save(args.fid_stats)
+                print(f"{args.fid_stats}: mean and covariance of the pool3 features of {fid_views.stats.count} views")
+            if args.fid_features:
+                with open(args.fid_features, "wb") as f:
+                    np.save(f, fid_views.features().cpu().numpy())
+                print(f"{args.fid_features}: pool3 features of {fid_views.count} views")
         if args.meshes:
             from humanliff_amd.NeRF.geometry import write_ply
             os.makedirs(args.meshes, exist_ok=True)
